@@ -6,17 +6,25 @@ Workload of the JSON line (config.workload): BASELINE configs[1] -- per GPU ONE 
 + stage 2, through the C ABI's device-resident entry) over `--seconds` of capture already resident in HBM.  With N GPUs the
 streams shard stream-major over the ranks (boondock-airband_amd/shard.py: independent dongles, weak scaling, no data-path
 collective) and the decimated audio + batch flags of every rank are gathered to rank 0 over RCCL inside the timed region.
-With N > 1 the same line also carries `config5`: BASELINE configs[4] (64 streams x 32 mixed channels per GPU, fft 512)
-measured with the full gather, with the open-batches-only gather and without the gather.
+A plain run measures only that line: set-up, warm-up, the timed steps, the result.  `--full` adds what takes runs of its
+own: `cpu_baseline` (below) and, with N > 1, `config5`: BASELINE configs[4] (64 streams x 32 mixed channels per GPU, fft
+512) measured with the full gather, with the open-batches-only gather and without the gather.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W --full
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller after the timed region: DIR/audio.npy (the
+decimated audio [streams][channels][samples]) and DIR/flags.npy (the batch flags [streams][channels][batches], as
+float32), those of every rank on rank 0 when the audio is gathered.  The capture is generated from fixed seeds, so two
+runs with the same arguments see the same input.  Above 64 MB in all, audio.npy holds a fixed, seeded sample of the
+(stream, channel) rows and DIR/audio_rows.npy their flat indices.
 
 Prints ONE JSON line on rank 0.  `roofline`: the kernel with the largest time per step, from HIP events the library records
 on its launch streams around each kernel; `achieved` = SURVEY 8(d) algorithmic bytes per sample x the samples one launch
 covers / that kernel's mean launch duration (`frac_path`: the same bytes / the step's wall time; `alu_frac`: algorithmic
-flops / step time / 157.3 TFLOP/s fp32 vector).  `cpu_baseline` is the CPU oracle (a port of the reference path,
+flops / step time / 157.3 TFLOP/s fp32 vector).  `cpu_baseline` (--full) is the CPU oracle (a port of the reference path,
 oracle/airband_oracle.c) timed on one host core over a bounded sample of the same workload.
 """
 import argparse
@@ -36,6 +44,7 @@ PMC_PROFILES = {"config2": "r03_pmc.csv", "config3": "r03_config3_pmc.csv", "con
 SAMPLE_RATE = 2560000
 WAVE_BATCH = 2000
 AGC_EXTRA = 100
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
 HOP = SAMPLE_RATE // 16000  # complex samples per output sample
 
 WORKLOADS = {
@@ -92,8 +101,9 @@ def workload_shape(pkg, workload, streams, seconds):
     return centre, chans, streams or 64, 9, seconds or 2.0  # config4 / config5
 
 
-def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, local_rank):
-    """Times `steps` steps of one workload.  gather_mode: None | "full" | "open" (open batches only)."""
+def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, local_rank, dump=False):
+    """Times `steps` steps of one workload.  gather_mode: None | "full" | "open" (open batches only).  dump: return the
+    outputs of the last timed step (res["outputs"], rank 0)."""
     import torch
     import torch.distributed as dist
     from boondock_airband_amd import shard
@@ -139,6 +149,8 @@ def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, l
     d_axcs = [torch.empty((nstreams, nch, nbat), dtype=torch.uint8, device="cuda") for _ in range(nbuf)]
     gath = shard.AudioGather((nstreams, nch, nsteps), nbat, torch.device("cuda", local_rank), dst=0) if gathering else None
     outs = [None] * nbuf
+    gathered = [None] * nbuf  # what the last gather of each buffer delivered (rank 0)
+    last = [None]  # the buffer of the newest step
     if gathering and rank == 0:
         outs = [([torch.empty(sh, dtype=torch.float32, device="cuda") for sh in gath.shapes],
                  [torch.empty((sh[0], sh[1], nbat), dtype=torch.uint8, device="cuda") for sh in gath.shapes]) for _ in range(nbuf)]
@@ -168,6 +180,7 @@ def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, l
     def step(timed):
         b = nstep[0] % nbuf
         nstep[0] += 1
+        last[0] = b
         if pending[b] is not None:
             # The gather of three steps ago still reads this buffer.  With MI_OPT_EARLY_INPUT the library may write a call's
             # audio before the stream reaches the call, so a stream-side wait is not enough: the host waits.
@@ -187,7 +200,7 @@ def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, l
     def drain():
         for b in range(nbuf):
             if pending[b] is not None:
-                pending[b].wait()
+                gathered[b] = pending[b].wait()
                 pending[b] = None
 
     for _ in range(warmup):
@@ -215,6 +228,12 @@ def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, l
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    outputs = None
+    if dump and rank == 0 and steps > 0:
+        b = last[0]
+        audio, flags = (torch.cat(gathered[b][0]), torch.cat(gathered[b][1])) if gathered[b] is not None else (d_wos[b], d_axcs[b])
+        outputs = {"audio": audio.cpu().numpy(), "flags": flags.cpu().numpy().astype("float32")}
+
     samples_per_step_per_gpu = nsteps * HOP * nstreams
     value = samples_per_step_per_gpu * steps * world / dt / 1e6  # MS/s, whole job
     path = h.last_path()[0]
@@ -224,8 +243,23 @@ def run_workload(pkg, args, workload, steps, warmup, gather_mode, rank, world, l
     h.close()
     res = {"value": value, "ms_per_step": dt / steps * 1e3, "nch": nch, "n_iq": n_iq, "nstreams": nstreams, "fft_log": fft_log, "nbat": nbat,
            "samples_per_step_per_gpu": samples_per_step_per_gpu, "kms": kms, "path": path, "gathering": gathering, "dev": dev,
-           "centre": centre, "chans": chans}
+           "centre": centre, "chans": chans, "outputs": outputs}
     return res
+
+
+def dump_outputs(path, outputs):
+    """DIR/<name>.npy of the last timed step (float32), at most DUMP_LIMIT bytes: beyond that a fixed, seeded sample of the audio rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    audio, flags = outputs["audio"], outputs["flags"]
+    rows = audio.reshape(-1, audio.shape[-1])
+    budget = (DUMP_LIMIT - flags.nbytes) // rows[0].nbytes
+    if rows.shape[0] > budget:
+        keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], budget - 1, replace=False))  # (one row's bytes for the indices)
+        np.save(os.path.join(path, "audio_rows.npy"), keep.astype(np.float64))
+        audio = rows[keep]
+    np.save(os.path.join(path, "audio.npy"), audio)
+    np.save(os.path.join(path, "flags.npy"), flags)
 
 
 def kernel_table(res):
@@ -308,16 +342,20 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=0.0, help="capture length per stream per step (HBM-resident); 0 = the workload's default")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="length of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="length of the CPU-baseline sample of --full (0 = skip)")
     ap.add_argument("--noise-only", action="store_true", help="diagnostic: no carriers in the synthetic capture (squelch never opens)")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL gather of audio to rank 0 (N>1)")
     ap.add_argument("--open-only", action="store_true", help="gather only the batches whose squelch flag is not NO_SIGNAL")
-    ap.add_argument("--no-config5", action="store_true", help="N>1: do not add the config5 measurements to the line")
+    ap.add_argument("--no-config5", action="store_true", help="N>1 with --full: do not add the config5 measurements to the line")
     ap.add_argument("--diag", action="store_true", help="print the time-parallel path's per-channel counters to stderr")
     ap.add_argument("--no-overlap", action="store_true", help="do not let consecutive steps overlap (MI_OPT_EARLY_INPUT off)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="config2",
                     help="config2 = BASELINE configs[1], the bench line (default); the others are extra measurements, not the driver's line")
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU for the many-stream workloads (default 64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (1 GPU) and config5 (N > 1); a plain run times the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the audio and batch flags of the last timed step to DIR/*.npy (float32, <= 64 MB)")
     args = ap.parse_args()
 
     import torch
@@ -337,10 +375,10 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
 
     gather_mode = None if (args.no_gather or not dist.is_initialized()) else ("open" if args.open_only else "full")
-    res = run_workload(pkg, args, args.workload, args.steps, args.warmup, gather_mode, rank, world, local_rank)
+    res = run_workload(pkg, args, args.workload, args.steps, args.warmup, gather_mode, rank, world, local_rank, dump=args.dump_outputs is not None)
 
     extra = {}
-    if (world > 1 or os.environ.get("BENCH_FORCE_CONFIG5") == "1") and not args.no_config5 and args.workload == "config2":
+    if args.full and (world > 1 or os.environ.get("BENCH_FORCE_CONFIG5") == "1") and not args.no_config5 and args.workload == "config2":
         # BASELINE configs[4] on the same ranks: short runs, outside the timed region of the line's own metric
         saved = (args.streams, args.seconds)
         args.streams, args.seconds = 0, 0.0
@@ -355,6 +393,8 @@ def main():
         args.streams, args.seconds = saved
 
     if rank == 0:
+        if res["outputs"] is not None:
+            dump_outputs(args.dump_outputs, res["outputs"])
         kernels = kernel_table(res)
         # HBM traffic per launch from the committed PMC passes of this same command (rocprofv3 cannot run inside the bench):
         # only quoted when the launch geometry is the one that was profiled (default --seconds, default chunking).
@@ -397,7 +437,7 @@ def main():
         }
         if extra:
             out["config5"] = extra
-        if world == 1 and args.cpu_seconds > 0 and args.workload == "config2":
+        if args.full and world == 1 and args.cpu_seconds > 0 and args.workload == "config2":
             out["cpu_baseline"] = cpu_baseline(pkg, res["dev"], res["centre"], res["chans"], args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -1,5 +1,6 @@
 """Seeded inputs for the component fixtures (shared by tests/golden/gen_golden.py, which runs them through
 the compiled reference, and by the tests, which run them through the oracle)."""
+import hashlib
 import math
 
 import numpy as np
@@ -103,3 +104,34 @@ FILTER_CASES = {
     "lp2500": dict(kind="lowpass", freq=2500.0, seed=44, n=4000),
     "lp4000": dict(kind="lowpass", freq=4000.0, seed=45, n=4000),
 }
+
+
+def digest(a):
+    """sha256 of an array's bytes, as 32 uint8: how tests/golden/ref_sweeps.npz keeps long reference outputs bit-exact but small."""
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+SQUELCH_SWEEP_SEEDS = range(6)
+
+
+def squelch_sweep(seed):
+    """One random squelch sweep: (raw, the keyword sets of squelch_run it is run with)."""
+    rng = np.random.default_rng(100 + seed)
+    n = 50000
+    raw = make_raw(dict(kind="bursts", seed=200 + seed, n=n))
+    filt = (raw * rng.uniform(0.4, 1.1, n)).astype(np.float32)
+    audio = make_audio(dict(seed=seed, n=n, tone=float(rng.choice([67.0, 100.0, 151.4]))))
+    return raw, (dict(), dict(filt=filt), dict(audio=audio, ctcss_freq=100.0), dict(filt=filt, audio=audio, ctcss_freq=151.4),
+                 dict(manual_level=float(rng.uniform(0.3, 1.0))), dict(snr_db=float(rng.uniform(0.5, 15.0)), filt=filt))
+
+
+TONE_BANK_WINDOWS = ((8000, 400), (16000, 6400))
+
+
+def tone_bank_inputs(tones):
+    """(tone, rate, window, audio) for every standard tone and both detector windows: the tone plus seeded noise."""
+    rng = np.random.default_rng(7)
+    for t in tones:
+        for rate, win in TONE_BANK_WINDOWS:
+            n = win * 2 + 10
+            yield float(t), rate, win, (0.2 * det_sin(float(t) / rate, n) + 0.05 * rng.normal(size=n)).astype(np.float32)

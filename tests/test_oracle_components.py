@@ -1,7 +1,8 @@
 """Pins the oracle's Squelch / CTCSS / NotchFilter / LowpassFilter restatements:
   - against the committed fixtures generated from the REFERENCE's own compiled sources
     (tests/golden/components_ref.npz, made by tests/golden/gen_golden.py), everywhere;
-  - against the live reference build oracle/_ref when it is present (this container).
+  - over longer random sweeps and every standard tone, against the reference's answers recorded in
+    tests/golden/ref_sweeps.npz (same generator), everywhere.
 Bit-exact: flags, squelch level, noise floor, signal level, counters, filter outputs."""
 import os
 
@@ -9,7 +10,8 @@ import numpy as np
 import pytest
 
 import libs
-from golden_inputs import CTCSS_CASES, FILTER_CASES, SQUELCH_CASES, make_audio, make_filtered, make_raw
+from golden_inputs import (CTCSS_CASES, FILTER_CASES, SQUELCH_CASES, SQUELCH_SWEEP_SEEDS, digest, make_audio, make_filtered, make_raw,
+                           squelch_sweep, tone_bank_inputs)
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "components_ref.npz"))
 
@@ -75,51 +77,45 @@ def test_tone_generator_matches_reference_fixture():
     assert np.array_equal(bits(libs.oracle().tone_run(8000, 79.7, 0.2, 4000)), bits(GOLD["tone_79_7"]))
 
 
-# ---------- live comparison with the compiled reference (only where oracle/_ref can exist) ----------
+# ---------- the longer sweeps, against the reference's recorded answers (tests/golden/ref_sweeps.npz) ----------
 
-needs_ref = pytest.mark.skipif(not libs.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
+SWEEPS = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_sweeps.npz"))
 
 
-@needs_ref
-@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("seed", SQUELCH_SWEEP_SEEDS)
 def test_squelch_random_vs_live_reference(seed):
-    rng = np.random.default_rng(100 + seed)
-    n = 50000
-    case = dict(kind="bursts", seed=200 + seed, n=n)
-    raw = make_raw(case)
-    filt = (raw * rng.uniform(0.4, 1.1, n)).astype(np.float32)
-    audio = make_audio(dict(seed=seed, n=n, tone=float(rng.choice([67.0, 100.0, 151.4]))))
-    o, r = libs.oracle(), libs.ref()
-    for kw in (dict(), dict(filt=filt), dict(audio=audio, ctcss_freq=100.0), dict(filt=filt, audio=audio, ctcss_freq=151.4),
-               dict(manual_level=float(rng.uniform(0.3, 1.0))), dict(snr_db=float(rng.uniform(0.5, 15.0)), filt=filt)):
-        a, b = o.squelch_run(raw, **kw), r.squelch_run(raw, **kw)
+    """Random bursts under every squelch mode; the compiled reference's outputs were recorded as digests by gen_golden.py."""
+    raw, kws = squelch_sweep(seed)
+    o = libs.oracle()
+    for i, kw in enumerate(kws):
+        a = o.squelch_run(raw, **kw)
         for key in ("flags", "level", "noise", "signal"):
-            assert np.array_equal(bits(a[key]), bits(b[key])), (seed, list(kw), key)
-        assert a["final"].astuple() == b["final"].astuple()
+            assert np.array_equal(digest(bits(a[key])), SWEEPS[f"sw{seed}_{i}_{key}"]), (seed, list(kw), key)
+        f = a["final"]
+        assert [f.open_count, f.flappy_count, f.ctcss_count, f.no_ctcss_count] == list(SWEEPS[f"sw{seed}_{i}_final_counts"]), (seed, list(kw))
+        assert np.array_equal(bits(np.array([f.noise_level, f.signal_level, f.squelch_level], np.float32)),
+                              bits(SWEEPS[f"sw{seed}_{i}_final_levels"])), (seed, list(kw))
 
 
-@needs_ref
 def test_every_standard_tone_bank_vs_live_reference():
     """Detector-bank construction (dedupe by coefficient, +-5 Hz exclusion) for every standard tone."""
-    o, r = libs.oracle(), libs.ref()
-    rng = np.random.default_rng(7)
-    tones = np.zeros(64, np.float32)
-    import ctypes as C
-    reflib = r.lib
-    reflib.ref_standard_tones.argtypes = [np.ctypeslib.ndpointer(np.float32), C.c_int]
-    reflib.ref_standard_tones.restype = C.c_int
-    nt = reflib.ref_standard_tones(tones, 64)
-    assert nt == 51
-    for t in tones[:nt]:
-        for rate, win in ((8000, 400), (16000, 6400)):
-            x = (0.2 * np.sin(2 * np.pi * float(t) * np.arange(win * 2 + 10) / rate) + 0.05 * rng.normal(size=win * 2 + 10)).astype(np.float32)
-            a, b = o.ctcss_run(float(t), rate, win, x), r.ctcss_run(float(t), rate, win, x)
-            assert np.array_equal(a[0], b[0]) and a[1:] == b[1:], (float(t), rate, win)
+    tones = SWEEPS["standard_tones"]
+    assert tones.size == 51
+    o = libs.oracle()
+    n = 0
+    for (t, rate, win, x), want_flags, want_counts in zip(tone_bank_inputs(tones), SWEEPS["tone_bank_flags"], SWEEPS["tone_bank_counts"]):
+        flags, found, nfound = o.ctcss_run(t, rate, win, x)
+        assert np.array_equal(digest(flags), want_flags) and [found, nfound] == list(want_counts), (t, rate, win)
+        n += 1
+    assert n == len(SWEEPS["tone_bank_counts"]) == tones.size * 2
 
 
-@needs_ref
 def test_default_filters_disabled_in_reference():
-    import ctypes as C
-    reflib = libs.ref().lib
-    reflib.ref_filters_default_disabled.restype = C.c_int
-    assert reflib.ref_filters_default_disabled() == 1  # src/test_filters.cpp:33-41
+    assert int(SWEEPS["filters_default_disabled"]) == 1  # src/test_filters.cpp:33-41, as the compiled reference answered
+    # the oracle's counterpart: a filter set up without a frequency passes its input through untouched
+    rng = np.random.default_rng(3)
+    x, y = rng.normal(size=(2, 1000)).astype(np.float32)
+    o = libs.oracle()
+    assert np.array_equal(bits(o.notch_run(0.0, 16000.0, 10.0, x)), bits(x))
+    a, b = o.lowpass_run(0.0, 16000.0, x, y)
+    assert np.array_equal(bits(a), bits(x)) and np.array_equal(bits(b), bits(y))

@@ -29,7 +29,7 @@ if has pmc; then
   done
 fi
 if has bench; then
-  python3 bench.py > $O/final_bench.log 2>&1
+  python3 bench.py --full > $O/final_bench.log 2>&1
   grep "^{" $O/final_bench.log > $O/${R}_bench.json
   echo "bench done"
 fi
