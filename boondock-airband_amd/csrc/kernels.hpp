@@ -199,6 +199,7 @@ struct TpArgs {
     int agc_hint;                              // segment lanes guess agcavgfast as the channel's last committed value (else 0.5)
     int core_decay;                            // ... the decays after bursts walked ahead by two more waves (decay_wave)
     int core_guess;                            // ... taken by guess-and-verify rounds instead of systolic passes (nf_chain_guess64)
+    int core_lean;                             // k_tp_core2: the round-4 run paths and restarts (0 = the round-3 ones)
 };
 inline uint32_t tp_chunk_unit(uint32_t L) {  // lcm(L, WAVE_BATCH = 2000) for L = 2^k >= 16: 2000 = 16 * 125
     return L * 125u;

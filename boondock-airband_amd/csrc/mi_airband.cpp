@@ -121,6 +121,7 @@ struct mi_demod {
     int opt_agc_hint = 1;        // (diagnostic, MI_AIRBAND_AGC_HINT=0) segment lanes start from agcavgfast = 0.5 instead of the channel's last value
     int opt_core_decay = 1;      // (diagnostic, MI_AIRBAND_CORE_DECAY=0) no decay waves: the walking wave steps every decay itself
     int opt_core_guess = 1;      // (diagnostic, MI_AIRBAND_CORE_GUESS) 0: the noise-floor wave walks systolic passes only; 2: the first guess-and-verify rounds (groups of 64)
+    int opt_core_lean = 1;       // (diagnostic, MI_AIRBAND_CORE_LEAN=0) k_tp_core2 without the round-4 run paths and restarts
     bool opt_core_split = true;  // MI_OPT_CORE_SPLIT: noise-floor passes of the core chain on their own wave (k_tp_core2)
     bool core_split_ok = false;  // ... the plan allows it: automatic squelch levels with a cap factor >= 1 on every channel
     bool opt_l64 = true;      // MI_OPT_LANE_FFT: the lane-resident stage 1 at N = 512 where the plan allows it
@@ -316,6 +317,8 @@ void tuning_from_env(mi_demod* h) {
         h->opt_core_decay = std::atoi(e) != 0;
     if (const char* e = get("MI_AIRBAND_CORE_GUESS"))
         h->opt_core_guess = std::max(0, std::min(2, std::atoi(e)));
+    if (const char* e = get("MI_AIRBAND_CORE_LEAN"))
+        h->opt_core_lean = std::atoi(e) != 0;
     if (const char* e = get("MI_AIRBAND_PRE_WAVE"))
         h->opt_pre_wave = std::atoi(e) < 0 ? -1 : std::min(2, std::atoi(e));
     if (const char* e = get("MI_AIRBAND_MIXED"))
@@ -615,6 +618,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         ta.core_lead = h->opt_core_lead;
         ta.core_guess = h->opt_core_guess;
         ta.core_decay = h->opt_core_decay;
+        ta.core_lean = h->opt_core_lean;
         ta.agc_hint = h->opt_agc_hint;
         ta.eager_samples = h->opt_tp_eager;
         // Speculative head: when this call's segment pass may run under the previous call's tail at all (seg_early) and that call

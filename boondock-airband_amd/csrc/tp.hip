@@ -702,7 +702,7 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
     const uint32_t bps_log = 31u - static_cast<uint32_t>(__builtin_clz(bps));
 
     int n_run = 0, n_single = 0, n_step = 0, n_fail = 0;  // diagnostics: blocks per path, failed hypotheses
-    CORE_PROF(unsigned long long t_begin = prof_now(); unsigned long long t_wait = 0, t_stepping = 0, t_mark = 0; int n_waits = 0, n_from_rec = 0, n_reclook = 0, n_fast4 = 0, n_capb = 0, n_sysr = 0, n_sysb = 0, n_f1 = 0, n_gen = 0, n_lazy = 0; unsigned long long t_lazy = 0, t_recwait = 0, t_capb = 0, t_sysr = 0, t_f4 = 0, t_f1 = 0, t_gen = 0;)
+    CORE_PROF(unsigned long long t_begin = prof_now(); unsigned long long t_wait = 0, t_stepping = 0, t_mark = 0; int n_waits = 0, n_from_rec = 0, n_reclook = 0, n_fast4 = 0, n_capb = 0, n_sysr = 0, n_sysb = 0, n_f1 = 0, n_gen = 0, n_lazy = 0, n_f4fail = 0, n_f4part = 0; unsigned long long t_lazy = 0, t_recwait = 0, t_capb = 0, t_sysr = 0, t_f4 = 0, t_f1 = 0, t_gen = 0;)
     // kSplit: the noise-floor passes come from the chain wave (CoreShare).  `own`: this wave advanced the noise floor itself since it
     // last took a value from there (single blocks, decays): the next value taken is only good if the chain wave agrees on the one
     // before it.  `solo`: the chain wave was given up on (a wait ran out): from then on this wave walks the chain itself.
@@ -717,9 +717,12 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
         nxt2 = core_load(a, x, bbase, a.blk0 + 64, lane);
     }
     uint32_t fetch_seen = a.blk0;  // kSplit: blocks whose aggregates the fetch waves are known to have delivered
+    // core_lean: the group a pass of four groups failed in (after the leading groups that passed were taken) -- the whole-group path
+    // judges it next; another pass of four from there would fail on the same block
+    uint32_t f4_fail = 0xffffffffu;
     for (uint32_t g0 = a.blk0; g0 < nblk; g0 += 64) {
         CORE_PROF(const unsigned long long t_it0 = prof_now();)
-        if (kSplit && !solo && !own && g0 + 256u <= nblk) {
+        if (kSplit && !solo && !own && g0 + 256u <= nblk && g0 != f4_fail) {
             // ---- four groups in one regime at once.  Under the hypothesis that the regime persists every block's check depends on ring
             // values alone (the state entering a block is the noise floor the chain wave left for the block before, full_ at its
             // start, and capped_ == full_ or == the cap), so 256 blocks are judged by one pass of straight-line code and one branch:
@@ -737,6 +740,7 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
                     if (lane == 0)
                         share_post(&sh->w1_pos, g0);
                     bool ok = true;
+                    unsigned long long okg[4];  // per group: the lanes that pass
                     float q_nfp[4], q_capp[4], q_ce[4], q_fe[4], vnf3 = 0.0f, fe3 = 0.0f;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -755,11 +759,13 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
                         const float full_entry = head ? full : fep_r;
                         const float c_entry = merged ? full_entry : cap_prev;
                         const float opw = head ? fe_group : fep_r;
-                        ok = ok && fm >= 0.0f && __builtin_fminf(c_entry, nf_prev) == __builtin_fminf(opw, nf_prev);
+                        bool okj = fm >= 0.0f && __builtin_fminf(c_entry, nf_prev) == __builtin_fminf(opw, nf_prev);
                         if (merged)
-                            ok = ok && c_entry < capj && fm < capj;
+                            okj = okj && c_entry < capj && fm < capj;
                         else
-                            ok = ok && capped_step(c_entry, x0, capj) == capj && xm >= capj;
+                            okj = okj && capped_step(c_entry, x0, capj) == capj && xm >= capj;
+                        ok = ok && okj;
+                        okg[j] = __ballot(okj);
                         q_nfp[j] = nf_prev, q_capp[j] = cap_prev, q_ce[j] = c_entry, q_fe[j] = full_entry;
                         if (j == 3)
                             vnf3 = vnf, fe3 = fe;
@@ -784,6 +790,37 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
                         fe_group = full;
                         g0 += 192u;
                         continue;
+                    }
+                    if (a.core_lean) {
+                        // The groups in front of the one that failed passed whole: group j's checks took the state entering it from the
+                        // rings, which is the true state once groups 0 .. j-1 have passed (induction from the head lane, which took this
+                        // wave's own state) -- the argument of the full pass, cut at a group boundary.  Take them; the failing group goes
+                        // to the whole-group path, which takes its leading run and sends the failing block to the stepping code.
+                        const int m = okg[0] != ~0ull ? 0 : (okg[1] != ~0ull ? 1 : (okg[2] != ~0ull ? 2 : 3));
+                        f4_fail = g0 + 64u * static_cast<uint32_t>(m);
+                        CORE_PROF(++n_f4fail;)
+                        if (m > 0) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) {
+                                const uint32_t bj = g0 + 64u * static_cast<uint32_t>(j) + static_cast<uint32_t>(lane);
+                                if (j < m && (bj & (bps - 1u)) == 0) {
+                                    TpCore t;
+                                    t.nf = q_nfp[j], t.cap = q_capp[j], t.c = q_ce[j], t.full = q_fe[j];
+                                    core[bj >> bps_log] = t;
+                                }
+                            }
+                            // the state after group m - 1: what its lane 63 judged against (entry e - 1 of nfring, entry e of opring)
+                            nf = uni(*(lds_vf32*)&sh->nfring[(f4_fail - 1u) & (kNfRing - 1u)]);
+                            full = uni(*(lds_vf32*)&sh->opring[f4_fail & (kOpRing - 1u)]);
+                            cap = cap_of(p, nf);
+                            c = merged ? full : cap;
+                            n_run += 64 * m;
+                            ++n_single;
+                            CORE_PROF(n_f4part += m; t_f4 += prof_now() - t_it0;)
+                            fe_group = full;
+                            g0 = f4_fail - 64u;
+                            continue;
+                        }
                     }
                 }
             }
@@ -1196,7 +1233,7 @@ __device__ __forceinline__ void core_walk(const TpArgs& a, LdsShare* sh, const i
         fe_group = rl(cur.fe, 63);
         CORE_PROF(++n_gen; t_gen += prof_now() - t_it0;)
     }
-    CORE_PROF(if (lane == 0 && r < 8) printf("core w1 row %d: groups by path: four at once %d in %llu us, whole group %d in %llu us, general %d in %llu us (stepping included); raw samples asked for when a block had to be stepped: %d times, %llu us until they were there\n", r, n_fast4, t_f4 / 100, n_f1, t_f1 / 100, n_gen, t_gen / 100, n_lazy, t_lazy / 100);)
+    CORE_PROF(if (lane == 0 && r < 8) printf("core w1 row %d: groups by path: four at once %d (+%d groups of %d failed passes) in %llu us, whole group %d in %llu us, general %d in %llu us (stepping included); raw samples asked for when a block had to be stepped: %d times, %llu us until they were there\n", r, n_fast4, n_f4part, n_f4fail, t_f4 / 100, n_f1, t_f1 / 100, n_gen, t_gen / 100, n_lazy, t_lazy / 100);)
     CORE_PROF(if (lane == 0 && r < 8) printf("core w1 row %d: total %llu us  wait-w0 %llu us (%d waits)  stepping %llu us (record waits %llu us, %d looks)  run %d accepted-runs %d step %d (from records %d) fail %d rollback %d solo %d fast4 %d; cap-binding blocks %d in %llu us, systolic rounds %d (%d blocks) in %llu us\n", r,
                                            (prof_now() - t_begin) / 100, t_wait / 100, n_waits, t_stepping / 100, t_recwait / 100, n_reclook, n_run, n_single, n_step, n_from_rec, n_fail, n_rollback, (int)solo, n_fast4, n_capb, t_capb / 100, n_sysr, n_sysb, t_sysr / 100);)
     if (kSplit && lane == 0)
