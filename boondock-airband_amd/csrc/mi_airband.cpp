@@ -89,6 +89,7 @@ struct mi_demod {
     // aggregates of a call need 0.85 ms before its own, so with the host reading at age 3 (four sets, rounds 2-3) the period could
     // not fall below (2.8 + 0.85) / 3 = 1.2 ms -- which is what the step took once the chain itself was down to 1.03
     static constexpr int kSets = 6;
+    static_assert(kSets % 2 == 0, "a call's scratch set picks its complex plane set by parity: the two must stay in step when the sets wrap");
     hipEvent_t ev[kSets][5] = {};  // per call: 0 begin, 1 stage 1 done, 2 call done, 3 serial k_demod begins (pipelined serial calls, mixed plans), 4 ... ends (mixed plans)
     static constexpr int kMaxChunks = 64, kEvPerChunk = 13, kSegStreams = 1;
     std::vector<hipEvent_t> chunk_ev[kSets];  // per chunk: stage1 begin/end, full end, core begin/end, seg begin/end, scan0/fix0/finish ends, rest begin
@@ -1010,14 +1011,14 @@ void mi_demod_destroy(mi_demod* h) {
         return;
     (void)hipSetDevice(h->gpu);
     (void)hipDeviceSynchronize();  // calls may still be in flight on the handle's own streams
-    void* ptrs[] = {h->d_window, h->d_tw, h->d_prune_t1, h->d_prune_t2, h->d_prune_rank, h->d_l64_chan, h->d_l64_chan_full, h->d_l64_tickets, h->d_levels,      h->d_sin,     h->d_cos,   h->d_cp, h->d_state, h->d_cplx_set[0], h->d_cplx_set[1], h->d_carry_set[0], h->d_carry_set[1], h->d_carry_set[2], h->d_carry_set[3],
+    void* ptrs[] = {h->d_window, h->d_tw, h->d_prune_t1, h->d_prune_t2, h->d_prune_rank, h->d_l64_chan, h->d_l64_chan_full, h->d_l64_tickets, h->d_levels,      h->d_sin,     h->d_cos,   h->d_cp, h->d_state, h->d_cplx_set[0], h->d_cplx_set[1],
                     h->d_ring,   h->d_ctcss_coeff, h->d_ctcss_q, h->d_stats, h->d_pre_timeouts,
                     h->d_rows,   h->d_srows, h->d_tstart, h->d_need, h->d_redo, h->d_fin, h->d_diag, h->d_core_carry, h->d_full0, h->d_fullbound, h->d_afc_spec};
     for (void* p : ptrs)
         if (p)
             (void)hipFree(p);
     for (int q = 0; q < mi_demod::kSets; ++q) {
-        void* sets[] = {h->d_mag_set[q], h->d_xmax[q], h->d_blk_fe[q], h->d_blk_fm[q], h->d_blk_x0[q], h->d_blk_xm[q], h->d_core[q], h->d_rec[q]};
+        void* sets[] = {h->d_mag_set[q], h->d_carry_set[q], h->d_xmax[q], h->d_blk_fe[q], h->d_blk_fm[q], h->d_blk_x0[q], h->d_blk_xm[q], h->d_core[q], h->d_rec[q]};
         for (void* p : sets)
             if (p)
                 (void)hipFree(p);

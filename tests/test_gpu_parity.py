@@ -986,14 +986,15 @@ def test_mixed_plan_rows_take_both_paths(pkg, monkeypatch, mixed):
     SNR threshold, low-pass, notch, raw I/Q, NFM, CTCSS) a call of 8 batches and more sends the plain AM rows down the time-parallel
     path and the rest through the serial kernel on a stream of its own -- the raw bins in alternating complex plane sets, the serial
     rows' carried samples left in the next call's planes, both halves sharing one audio lookahead buffer per call.  Two streams,
-    calls of 8 / 12 / 8 batches overlapping on alternating audio buffers, then a 2-batch call (serial for every row) and a last
-    mixed one after it, then a checkpoint taken in the middle is restored into a fresh handle: audio, flags and raw I/Q equal the
-    oracle's throughout, with the option on and off."""
+    calls of 8 / 12 / 8 batches overlapping on alternating audio buffers, then a 2-batch and a 3-batch call (serial for every row:
+    two consecutive pipelined serial calls right after a mixed one, so the complex plane set and the magnitude set each of them
+    picks have to agree by more than the parity of one call) and a last mixed one after them, then a checkpoint taken in the
+    middle is restored into a fresh handle: audio, flags and raw I/Q equal the oracle's throughout, with the option on and off."""
     import torch
     monkeypatch.delenv("MI_AIRBAND_TP", raising=False)
     centre, chans = _channel_zoo(pkg)
     dev = pkg.device_cfg(centerfreq=centre, fft_size_log=9)
-    calls = [8, 12, 8, 2, 10]
+    calls = [8, 12, 8, 2, 3, 10]
     nbat = sum(calls)
     nstreams = 2
     iqs = [_zoo_capture(pkg, dev, centre, chans, nbat, 1234 + st) for st in range(nstreams)]
@@ -1027,7 +1028,7 @@ def test_mixed_plan_rows_take_both_paths(pkg, monkeypatch, mixed):
     o1, f1, z1, done = run(d, 0, 3, 0)
     assert d.last_path()[0] == mixed
     state = d.get_state().copy()
-    o2, f2, z2, done2 = run(d, 3, 2, done)
+    o2, f2, z2, done2 = run(d, 3, 3, done)
     assert d.last_path() == (mixed, 0)
     assert d.pre_wave_timeouts() == 0
     d.close()
@@ -1036,7 +1037,7 @@ def test_mixed_plan_rows_take_both_paths(pkg, monkeypatch, mixed):
     d.set_option(pkg.OPT_EARLY_INPUT, 1)
     d.set_option(pkg.OPT_MIXED_PLAN, mixed)
     d.set_state(state)
-    o3, f3, z3, _ = run(d, 3, 2, done)
+    o3, f3, z3, _ = run(d, 3, 3, done)
     d.close()
     for name, outs, flags, zs in (("straight", o1 + o2, f1 + f2, z1 + z2), ("restored", o1 + o3, f1 + f3, z1 + z3)):
         wo = torch.cat(outs, dim=2).cpu().numpy()

@@ -1,5 +1,6 @@
-"""One-off fuzz against the oracle: the random plans and captures of test_steady_blocks_random_plans (every channel type, odd
-thresholds, carriers from under the squelch level to clipping), product vs oracle: audio, flags, raw I/Q bit for bit."""
+"""Fuzz against the oracle over any seed range: the random plans and captures of tests/fuzz_plans.py mixed_plan (every channel type, odd
+thresholds, carriers from under the squelch level to clipping, fft 256 .. 2048), product vs oracle: audio, flags, raw I/Q bit for bit.
+Seeds 0-19 run in the suite (test_fuzz_mixed_plans_equal_the_oracle)."""
 import os
 import sys
 
@@ -8,45 +9,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conftest  # noqa: E402
-from common import AGC_EXTRA, WAVE_BATCH, bytes_for_batches, oracle_run  # noqa: E402
+from common import AGC_EXTRA, WAVE_BATCH, oracle_run  # noqa: E402
+from fuzz_plans import mixed_plan  # noqa: E402  (the generator the suite runs: tests/test_bench_geometry.py)
 
 pkg = conftest.load_package()
 bad = 0
 first, last = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (0, 40)
 for seed in range(first, last):
-    rng = np.random.default_rng(10000 + seed)
-    centre = 120000000
-    nchan = int(rng.integers(3, 20))
-    chans, carriers = [], []
-    for k in range(nchan):
-        f = centre - 1200000 + 40000 + k * 120000 + int(rng.integers(0, 20)) * 5000
-        kw = {}
-        nfm = rng.random() < 0.5
-        if nfm:
-            kw["modulation"] = pkg.MOD_NFM
-        if rng.random() < 0.5:
-            kw["bandwidth"] = int(rng.choice([5000, 8000, 12500]))
-        if rng.random() < 0.25:
-            kw["notch"] = float(rng.choice([100.0, 400.0, 1000.0]))
-        if nfm and rng.random() < 0.4:
-            kw["ctcss"] = float(rng.choice([100.0, 123.0, 151.4]))
-        r = rng.random()
-        if r < 0.2:
-            kw["squelch_threshold_dbfs"] = int(rng.integers(-55, -30))
-        elif r < 0.5:
-            kw["squelch_snr_db"] = float(rng.choice([0.0, 3.0, 6.0, 12.0]))
-        if rng.random() < 0.3:
-            kw["ampfactor"] = float(rng.choice([0.5, 2.0, 4.0]))
-        if rng.random() < 0.3:
-            kw["has_iq_outputs"] = 1
-        chans.append(pkg.channel_cfg(f, **kw))
-        if rng.random() < 0.8:
-            carriers.append((f - centre, int(rng.integers(0, 3)), int(rng.choice([150, 300, 600, 1200, 2500, 5000])), int(rng.integers(0, 1000))))
-    dev = pkg.device_cfg(centerfreq=centre, fft_size_log=int(rng.choice([8, 9, 10])), fm_quadri=int(seed % 2))
-    nbat, per_call = 8, int(rng.choice([1, 2, 4, 8]))
-    n = bytes_for_batches(dev, nbat) // 2
-    cfg = pkg.iqgen_cfg(sample_rate=dev.sample_rate, seed=20000 + seed, gate_samples=dev.sample_rate // int(rng.integers(3, 9)), carriers=carriers)
-    iq = pkg.iqgen_host(cfg, 0, 0, n)
+    dev, chans, iq, nbat, per_call = mixed_plan(pkg, seed)
     nb, owo, oaxc, oiq = oracle_run(dev, chans, iq, nbat, want_iq=True)
     d = pkg.Demod(dev, chans, max_batches=per_call)
     outs, flags, zs = [], [], []

@@ -1,4 +1,5 @@
-"""One-off fuzz of the time-parallel path: random plain-AM plans (SNR / manual thresholds, amplification) and captures
+"""Fuzz of the time-parallel path over any seed range (seeds 0-19 run in the suite, test_fuzz_time_parallel_plans): the random
+plain-AM plans (SNR / manual thresholds, amplification) and captures of tests/fuzz_plans.py tp_plan
 (carriers from under the squelch level to clipping, random gate periods and phases), one 16-batch call (time-parallel) against
 the same capture in 4-batch calls (serial kernel): audio, flags and statistics must be identical.  Then the same capture as
 two overlapping 8-batch device calls (MI_OPT_EARLY_INPUT, two audio buffers: speculative head, chain handed over on the
@@ -11,34 +12,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import conftest  # noqa: E402
-from common import AGC_EXTRA, WAVE_BATCH, bytes_for_batches  # noqa: E402
+from common import AGC_EXTRA, WAVE_BATCH  # noqa: E402
+from fuzz_plans import tp_call_sizes, tp_plan  # noqa: E402  (the generator the suite runs: tests/test_bench_geometry.py)
 
 pkg = conftest.load_package()
 bad = 0
 first, last = int(sys.argv[1]) if len(sys.argv) > 1 else 0, int(sys.argv[2]) if len(sys.argv) > 2 else 40
 for seed in range(first, last):
-    rng = np.random.default_rng(seed)
-    centre = 120000000
-    nchan = int(rng.integers(2, 12))
-    chans, carriers = [], []
-    for k in range(nchan):
-        f = centre - 1200000 + 60000 + k * 200000 + int(rng.integers(0, 20)) * 5000
-        kw = {}
-        r = rng.random()
-        if r < 0.25:
-            kw["squelch_threshold_dbfs"] = int(rng.integers(-55, -30))
-        elif r < 0.6:
-            kw["squelch_snr_db"] = float(rng.choice([0.0, 1.0, 3.0, 6.0, 12.0]))
-        if rng.random() < 0.3:
-            kw["ampfactor"] = float(rng.choice([0.5, 2.0, 4.0]))
-        chans.append(pkg.channel_cfg(f, **kw))
-        if rng.random() < 0.8:
-            carriers.append((f - centre, 0, int(rng.choice([120, 250, 500, 1000, 2500, 6000])), int(rng.integers(0, 1000))))
-    dev = pkg.device_cfg(centerfreq=centre, fft_size_log=int(rng.choice([8, 9, 10])))
-    nbat = 16
-    n = bytes_for_batches(dev, nbat) // 2
-    cfg = pkg.iqgen_cfg(sample_rate=dev.sample_rate, seed=5000 + seed, gate_samples=dev.sample_rate // int(rng.integers(2, 12)), carriers=carriers)
-    iq = pkg.iqgen_host(cfg, 0, 0, n)
+    dev, chans, iq, nbat = tp_plan(pkg, seed)
     d = pkg.Demod(dev, chans, max_batches=nbat)
     wo_a, ax_a, _, _ = d.process([iq], nbat)
     path = d.last_path()[0]
@@ -66,7 +47,7 @@ for seed in range(first, last):
     side_ = torch.cuda.Stream() if seed % 3 == 0 else None
     s_ = side_.cuda_stream if side_ is not None else torch.cuda.current_stream().cuda_stream
     # (call sizes vary with the seed; every call has at least 8 batches, so all of them are time-parallel)
-    sizes = [[8, 8], [16], [8, 8], [8, 8]][seed % 4] if nbat == 16 else [nbat]
+    sizes = tp_call_sizes(seed)
     f = pkg.Demod(dev, chans, max_batches=max(sizes))
     f.set_option(pkg.OPT_EARLY_INPUT, 1)
     if seed % 5 == 0:
@@ -79,10 +60,13 @@ for seed in range(first, last):
         wo = torch.empty((1, len(chans), k * WAVE_BATCH), dtype=torch.float32, device="cuda")
         ax = torch.empty((1, len(chans), k), dtype=torch.uint8, device="cuda")
         f.process_device(d_iq.data_ptr() + pos, pad - pos, k, wo.data_ptr(), ax.data_ptr(), hip_stream=s_)
-        paths.append(f.last_path()[0])
         outs.append(wo)
         flags.append(ax)
         done += k
+    # (last_path() waits for the whole device: asked after every call it would keep the calls from overlapping.  The earlier calls'
+    #  paths come from their timing events, as in the suite's test_fuzz_time_parallel_plans)
+    paths = [1 if any(t[0] == "k_tp_core" for t in f.kernel_times(age=age)) else 0 for age in range(len(sizes))]
+    paths.append(f.last_path()[0])
     torch.cuda.synchronize()
     st_c = bytes(f.stats())
     f.close()
