@@ -103,7 +103,7 @@ ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_get_stats", "mi_demod_state_size",
     "mi_demod_get_state", "mi_demod_set_state", "mi_demod_read_planes", "mi_demod_process_planes", "mi_demod_last_path", "mi_demod_last_stage1", "mi_demod_pre_wave_timeouts", "mi_demod_tp_debug", "mi_demod_kernel_time", "mi_demod_kernel_time_prev", "mi_demod_event_ms", "mi_demod_set_option", "mi_demod_last_kernel_ms", "mi_plan_create", "mi_plan_destroy", "mi_plan_fft_size",
-    "mi_plan_window", "mi_plan_twiddles", "mi_plan_levels", "mi_plan_sincos_lut", "mi_plan_channel", "mi_plan_ctcss_coeffs",
+    "mi_plan_window", "mi_plan_twiddles", "mi_plan_levels", "mi_plan_sincos_lut", "mi_plan_channel", "mi_plan_lane_fft", "mi_plan_ctcss_coeffs",
     "mi_iqgen_host", "mi_iqgen_device", "mi_mixer_create", "mi_mixer_destroy", "mi_mixer_is_stereo", "mi_mixer_process_device",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
@@ -173,6 +173,7 @@ def lib():
             f.argtypes = [vp, vp]
         L.mi_plan_sincos_lut.argtypes = [vp, vp, vp]
         L.mi_plan_channel.argtypes = [vp, C.c_int, C.POINTER(ChannelDerived)]
+        L.mi_plan_lane_fft.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_int), vp, vp]
         L.mi_plan_ctcss_coeffs.argtypes = [vp, C.c_int, C.c_int, vp]
         L.mi_iqgen_host.argtypes = [C.POINTER(IqGenCfg), C.c_uint32, C.c_uint64, C.c_uint64, vp]
         L.mi_iqgen_device.argtypes = [C.POINTER(IqGenCfg), C.c_uint32, C.c_uint32, sz, C.c_uint64, C.c_uint64, vp, vp]
@@ -236,6 +237,18 @@ class Plan:
         d = ChannelDerived()
         _check(lib().mi_plan_channel(self._h, i, C.byref(d)))
         return d
+
+    def lane_fft(self):
+        """The lane-resident stage 1 as the plan derives it: (enabled, need[6] residue masks of the in-lane stages, lanes per
+        window, slots[nch] among the live classes mod 64, stage_tw[nch][log2n - 6][2] twiddles of the combining stages)."""
+        nst = max(self.fft_size.bit_length() - 1 - 6, 0)
+        enabled, lanes = C.c_int(0), C.c_int(0)
+        need = (C.c_uint64 * 6)()
+        slots = np.zeros(self.nch, np.int32)
+        tw = np.zeros((self.nch, nst, 2), np.float32)
+        _check(lib().mi_plan_lane_fft(self._h, C.byref(enabled), need, C.byref(lanes), slots.ctypes.data_as(C.c_void_p),
+                                      tw.ctypes.data_as(C.c_void_p)))
+        return bool(enabled.value), [int(x) for x in need], lanes.value, slots, tw
 
     def ctcss_coeffs(self, i, slow):
         d = self.channel(i)

@@ -573,8 +573,8 @@ hipError_t launch_channelize(const ChannelizeArgs& a, int log2n, int sfmt, int n
     if (a.nfft == 0 || nstreams == 0)
         return hipSuccess;
     // the pruned graphs have no complete spectrum: AFC launches (they want one) take the full kernel
-    if (log2n == 9 && a.l64.enabled && a.l64_chan && !a.afc_spec && !a.st)
-        return launch_channelize_l64(a, sfmt, nstreams, s);
+    if (a.l64.enabled && a.l64_chan && !a.afc_spec && !a.st && l64_supported(log2n, a.hop_bytes, sfmt == MI_SFMT_S16 ? 2 : (sfmt == MI_SFMT_F32 ? 4 : 1)))
+        return launch_channelize_l64(a, log2n, sfmt, nstreams, s);
     if (log2n == 9 && a.prune.enabled && a.prune_t1 && a.prune_t2 && a.prune_rank && !a.afc_spec && !a.st) {
         switch (sfmt) {
             case MI_SFMT_U8: return a.conv_arith ? launch_9p<kSfmtU8Arith>(a, nstreams, s) : launch_9p<MI_SFMT_U8>(a, nstreams, s);

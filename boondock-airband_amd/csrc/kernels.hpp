@@ -216,14 +216,15 @@ constexpr int TP_REST_MARKS = 3;  // marks (optional): after scan#0, after fix#0
 
 
 hipError_t launch_channelize(const ChannelizeArgs& a, int log2n, int sfmt, int nstreams, hipStream_t s);
-// channelize_l64.hip: the lane-resident N = 512 kernel (launch_channelize takes it when a.l64.enabled)
+// channelize_l64.hip: the lane-resident kernel for N = 512, 1024, 2048 (launch_channelize takes it when a.l64.enabled)
 bool l64_supported(int log2n, size_t hop_bytes, int bytes_per_sample);
-hipError_t launch_channelize_l64(const ChannelizeArgs& a, int sfmt, int nstreams, hipStream_t s);
-int l64_round_windows(int m6);
-int l64_zstride(int m6);
-// l64_jit.cpp: the kernel compiled for one plan's masks by hipRTC (cached per (device, hop, masks) for the life of the process;
-// null when hipRTC is missing or the compilation fails -- `why` then says so)
-const L64Jit* l64_jit_get(int device, int hop, const uint64_t need[6], const char** why);
+hipError_t launch_channelize_l64(const ChannelizeArgs& a, int log2n, int sfmt, int nstreams, hipStream_t s);
+int l64_round_windows(int log2n, int m6);
+int l64_zstride(int log2n, int m6);
+size_t l64_lds_bytes(int log2n, unsigned hop, int m6, int nch, int n_iq_rows, unsigned* region_bytes);  // dynamic LDS of a workgroup
+// l64_jit.cpp: the kernel compiled for one plan's masks by hipRTC (cached per (device, log2 N, hop, masks) for the life of the
+// process; null when hipRTC is missing or the compilation fails -- `why` then says so)
+const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why);
 int l64_jit_minwaves(const L64Jit* j);
 void l64_jit_set_cache_dir(const char* dir);            // null / "": no code objects on disk
 void l64_jit_counts(int* compiled, int* from_disk);     // kernels compiled / loaded from the cache directory by this process

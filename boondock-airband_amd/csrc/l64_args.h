@@ -3,11 +3,12 @@
 #ifndef MI_L64_ARGS_H
 #define MI_L64_ARGS_H
 
-// per channel: the row of its class { bin mod 64 } in the exchange buffer and the twiddles of stages 7, 8, 9 that lead to
-// its bin (the sign of an upper output folded in: a - w b == a + (-w) b bit for bit)
+// per channel: the row of its class { bin mod 64 } in the exchange buffer and the twiddles of stages 7 .. log2 N (at most
+// 11) that lead to its bin: stage 7 + j at w[2 j], w[2 j + 1] (the sign of an upper output folded in: a - w b == a + (-w) b
+// bit for bit); entries past log2 N are 0
 struct L64Chan {
     int slot, iq_row;
-    float w7x, w7y, w8x, w8y, w9x, w9y;
+    float w[10];
 };
 
 struct L64Args {
@@ -19,7 +20,7 @@ struct L64Args {
     float* mag;                         // [nstreams * nch][plane_stride]
     float* cplx;                        // [nstreams * n_iq_rows][plane_stride] of (re, im)
     unsigned long long plane_stride;
-    const float* window;                // 512 coefficients
+    const float* window;                // N coefficients
     const float* levels;                // 256-entry level table (u8 / s8)
     float conv_scale;                   // 1 / fullscale (s16 / f32)
     int nch, n_iq_rows;
@@ -27,8 +28,8 @@ struct L64Args {
     const L64Chan* chan;                // [nch]
     int nb_pad;                         // channels per window padded to a power of two, 8 .. 64
     unsigned zstride;                   // bytes per window in the exchange buffer
-    unsigned span_bytes;                // bytes of the float span of a tile (rows of HOP samples, padded)
-    unsigned ntiles;                    // tiles of 32 windows per stream
+    unsigned span_bytes;                // bytes of the float span of a tile (rows of HOP samples, padded) or of the exchange buffer over it, whichever is larger
+    unsigned ntiles;                    // tiles (4 waves x 64 / T windows: 32 / 16 / 8) per stream
     unsigned nstreams;
     int sfmt;                           // MI_SFMT_*
     int linear_tiles;                   // (unused)

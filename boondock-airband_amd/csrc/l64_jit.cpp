@@ -4,14 +4,14 @@
 // the first six stages.  With those masks as compile-time constants the kernel is straight-line code holding exactly the
 // plan's butterflies (for the 8-channel plan of BASELINE configs[1]: 152 of the 384 output halves, most of them plain adds).
 // hipRTC compiles the same source text hipcc compiles ahead of time for the full graph (embedded below by the Makefile),
-// the code object is loaded with the module API and kept for the life of the process, keyed by (device, hop, masks).
+// the code object is loaded with the module API and kept for the life of the process, keyed by (device, log2 N, hop, masks).
 // hipRTC is looked up with dlopen: the library has no link-time dependency on it, and where it is missing, or the
 // compilation fails, the caller runs the ahead-of-time full-graph instance instead.
 //
 // A compilation takes 0.3-0.6 s, and the reference's input ring holds 0.5 s of u8 IQ (config.cpp:799-805, overflow rule
 // input-helpers.cpp:56-61): it must not happen inside a processing call.  So mi_demod_create() asks for the kernel (init_demod()
 // runs before the input threads start, rtl_airband.cpp:1058-1082), and the code object is kept on disk under mi_set_cache_dir() /
-// $MI_AIRBAND_CACHE_DIR / $XDG_CACHE_HOME/mi_airband / ~/.cache/mi_airband, keyed by (arch, hop, masks, waves per SIMD, source
+// $MI_AIRBAND_CACHE_DIR / $XDG_CACHE_HOME/mi_airband / ~/.cache/mi_airband, keyed by (arch, log2 N, hop, masks, waves per SIMD, source
 // text, compiler options): the next process start loads it in a few milliseconds.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -82,11 +82,13 @@ Rtc& rtc() {
 }
 
 struct Key {
-    int device, hop;
+    int device, log2n, hop;
     uint64_t need[6];
     bool operator<(const Key& o) const {
         if (device != o.device)
             return device < o.device;
+        if (log2n != o.log2n)
+            return log2n < o.log2n;
         if (hop != o.hop)
             return hop < o.hop;
         return std::memcmp(need, o.need, sizeof(need)) < 0;
@@ -174,12 +176,13 @@ void disk_store(const std::string& path, uint64_t key, const std::vector<char>& 
 
 }  // namespace
 
-const L64Jit* l64_jit_get(int device, int hop, const uint64_t need[6], const char** why) {
+const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why) {
     static const char* none = "";
     if (why)
         *why = none;
     Key k{};
     k.device = device;
+    k.log2n = log2n;
     k.hop = hop;
     std::memcpy(k.need, need, sizeof(k.need));
     std::lock_guard<std::mutex> lock(g_mu);
@@ -209,7 +212,7 @@ const L64Jit* l64_jit_get(int device, int hop, const uint64_t need[6], const cha
     const char* mw = std::getenv("MI_AIRBAND_L64_MINWAVES");
     const int minwaves = (mw && *mw) ? std::max(1, std::min(4, std::atoi(mw))) : live;
     std::vector<std::string> opts = {"--offload-arch=" + arch, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-DMI_L64_JIT=1",
-                                     "-DL64_HOP=" + std::to_string(hop), "-DL64_MINWAVES=" + std::to_string(minwaves)};
+                                     "-DL64_LOG2N=" + std::to_string(log2n), "-DL64_HOP=" + std::to_string(hop), "-DL64_MINWAVES=" + std::to_string(minwaves)};
     for (int s = 0; s < 6; ++s) {
         char buf[64];
         std::snprintf(buf, sizeof(buf), "-DL64_N%d=0x%llxull", s + 1, static_cast<unsigned long long>(need[s]));

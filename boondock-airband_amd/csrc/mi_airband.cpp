@@ -125,7 +125,7 @@ struct mi_demod {
     int opt_core_lean = 1;       // (diagnostic, MI_AIRBAND_CORE_LEAN=0) k_tp_core2 without the round-4 run paths and restarts
     bool opt_core_split = true;  // MI_OPT_CORE_SPLIT: noise-floor passes of the core chain on their own wave (k_tp_core2)
     bool core_split_ok = false;  // ... the plan allows it: automatic squelch levels with a cap factor >= 1 on every channel
-    bool opt_l64 = true;      // MI_OPT_LANE_FFT: the lane-resident stage 1 at N = 512 where the plan allows it
+    bool opt_l64 = true;      // MI_OPT_LANE_FFT: the lane-resident stage 1 (N = 512, 1024, 2048) where the plan allows it
     int opt_l64_linear = 0;   // (diagnostic) tiles in blockIdx order instead of grouped per XCD
     bool opt_l64_jit = true;  // MI_OPT_LANE_FFT_JIT: compile the plan's own instance with hipRTC (else the full-graph instance)
     bool early_input = false;  // MI_OPT_EARLY_INPUT: the IQ of a call is valid when the call is made
@@ -162,6 +162,7 @@ struct mi_demod {
     unsigned l64_ticket_seq = 0;
     const mi::L64Jit* l64_jit = nullptr; // the kernel compiled for this plan's masks (owned by the process-wide cache), or null
     bool l64_jit_tried = false;
+    bool l64_why_said = false;           // MI_AIRBAND_DEBUG: why this plan does not get the lane-resident kernel, said once
     int last_stage1 = 0;  // MI_STAGE1_* of the last call
     float* d_levels = nullptr;
     float* d_sin = nullptr;
@@ -269,7 +270,7 @@ constexpr int kMixedMinBatches = 64;
 //   MI_AIRBAND_STEADY=0      serial stage 2 takes every step in the sample loop
 //   MI_AIRBAND_TP_SEGMENT=512|1024|2048|4096  steps per segment of the time-parallel path (default: by row count; sizes the scratch,
 //                            so it is read when the handle is created and has no mi_demod_set_option twin)
-//   MI_AIRBAND_L64=0         no lane-resident stage 1 at N = 512 (the pruned / full exchange kernels instead)
+//   MI_AIRBAND_L64=0         no lane-resident stage 1 at N = 512, 1024, 2048 (the pruned / full exchange kernels instead)
 //   MI_AIRBAND_UNI_ROWS=n, MI_AIRBAND_TP_CHUNKS=n, MI_AIRBAND_TP_RATIO=x, MI_AIRBAND_TP_LPW=n
 void tuning_from_env(mi_demod* h) {
     // (MI_AIRBAND_DEBUG=1: every tuning variable found in the environment is named on stderr when a handle is created -- a variable
@@ -349,7 +350,25 @@ void stage1_compile(mi_demod* h) {
         return;
     h->l64_jit_tried = true;
     const int hop = static_cast<int>(h->plan.hop_bytes / (2 * static_cast<size_t>(h->plan.bytes_per_sample)));
-    h->l64_jit = mi::l64_jit_get(h->gpu, hop, h->plan.l64.need, nullptr);
+    h->l64_jit = mi::l64_jit_get(h->gpu, h->plan.log2n, hop, h->plan.l64.need, nullptr);
+}
+
+// MI_AIRBAND_DEBUG=1: once per handle, why its plan does not get the lane-resident stage 1
+void stage1_explain(mi_demod* h) {
+    if (h->l64_why_said)
+        return;
+    h->l64_why_said = true;  // (decided on the handle's first call, whatever the outcome)
+    const char* dbg = std::getenv("MI_AIRBAND_DEBUG");
+    if (!dbg || std::atoi(dbg) == 0)
+        return;
+    const char* why = nullptr;
+    if (!h->plan.l64.enabled)
+        why = h->plan.l64.why ? h->plan.l64.why : "the plan does not allow it";
+    else if (h->opt_l64 && h->opt_l64_jit && h->l64_jit_tried && !h->l64_jit)
+        why = "hipRTC could not provide the plan's own instance";
+    if (!why)
+        return;
+    std::fprintf(stderr, "mi_airband: no lane-resident stage 1 for this plan (%s); the exchange kernel runs\n", why);
 }
 
 int lanes_per_wave_for(const mi_demod* h) {
@@ -424,6 +443,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     // only when asked for (MI_OPT_LANE_FFT_JIT = 0, tests); without hipRTC the pruned / full exchange kernels take over.
     if (ca.l64.enabled && h->opt_l64_jit && !ca.l64_jit)
         ca.l64.enabled = 0;
+    stage1_explain(h);
     ca.levels = h->d_levels;
     {
         const bool pruned = ca.prune.enabled && h->plan.log2n == 9 && !h->plan.any_afc;
@@ -434,7 +454,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     ca.cp = h->d_cp;
     ca.nch = h->nch;
     ca.n_iq_rows = h->plan.n_iq_rows;
-    h->last_stage1 = (ca.l64.enabled && h->plan.log2n == 9 && !h->plan.any_afc) ? (ca.l64_jit ? MI_STAGE1_LANE_PLAN : MI_STAGE1_LANE_FULL)
+    h->last_stage1 = (ca.l64.enabled && !h->plan.any_afc) ? (ca.l64_jit ? MI_STAGE1_LANE_PLAN : MI_STAGE1_LANE_FULL)
                      : ((ca.prune.enabled && h->plan.log2n == 9 && !h->plan.any_afc) ? MI_STAGE1_EXCHANGE_PRUNED : MI_STAGE1_EXCHANGE_FULL);
     const int env = h->opt_tp;
     const bool use_tp = h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
@@ -2151,6 +2171,27 @@ int mi_plan_channel(const mi_plan* p, int ch, mi_channel_derived* out) {
     out->ctcss_slow_window = c.ctcss_slow_window;
     out->ctcss_fast_ndet = c.ctcss_fast_ndet;
     out->ctcss_slow_ndet = c.ctcss_slow_ndet;
+    return MI_OK;
+}
+
+int mi_plan_lane_fft(const mi_plan* p, int* enabled, uint64_t need[6], int* lanes_per_window, int* slots, float* stage_tw) {
+    if (!p)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    const mi::Plan& pl = p->plan;
+    const bool on = pl.l64.enabled != 0;
+    const int nst = pl.log2n > 6 ? pl.log2n - 6 : 0;
+    if (enabled)
+        *enabled = on ? 1 : 0;
+    if (lanes_per_window)
+        *lanes_per_window = on ? pl.fft_size / 64 : 0;
+    for (int s = 0; need && s < 6; ++s)
+        need[s] = on ? pl.l64.need[s] : 0;
+    for (int i = 0; i < pl.nch; ++i) {
+        if (slots)
+            slots[i] = on ? pl.l64_chan[static_cast<size_t>(i)].slot : 0;
+        for (int k = 0; stage_tw && k < 2 * nst; ++k)
+            stage_tw[static_cast<size_t>(i) * 2 * nst + k] = (on && k < 10) ? pl.l64_chan[static_cast<size_t>(i)].w[k] : 0.0f;
+    }
     return MI_OK;
 }
 

@@ -357,14 +357,25 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
         lp = L64Plan{};
         p.l64_chan.clear();
         p.l64_chan_full.clear();
-        static const float kTwLit[256][2] = {
-#include "tw512.inc"
+        static const float kTwLit[32][2] = {
+#include "tw64.inc"
         };
-        bool lits_ok = p.fft_size == 512;
-        for (size_t k = 0; lits_ok && k < 256; ++k)  // the kernel's literal twiddles must be the spec's table, bit for bit
-            lits_ok = std::memcmp(&kTwLit[k][0], &p.tw[2 * k], 4) == 0 && std::memcmp(&kTwLit[k][1], &p.tw[2 * k + 1], 4) == 0;
+        const int L = p.log2n;
+        const size_t N = static_cast<size_t>(p.fft_size);
         const size_t hop = p.hop_bytes / (2 * static_cast<size_t>(p.bytes_per_sample));
-        if (lits_ok && !p.any_afc && nch <= 64 && (hop == 160 || hop == 128)) {
+        // the kernel's literal twiddles W_64^k of stages 1..6 must be the entries k N / 64 of the spec's table, bit for bit
+        bool lits_ok = L >= 6;
+        for (size_t k = 0; lits_ok && k < 32; ++k) {
+            const size_t e = k * (N / 64);
+            lits_ok = std::memcmp(&kTwLit[k][0], &p.tw[2 * e], 4) == 0 && std::memcmp(&kTwLit[k][1], &p.tw[2 * e + 1], 4) == 0;
+        }
+        lp.why = (L < 9 || L > 11)                 ? "fft_size is not 512, 1024 or 2048"
+                 : (hop != 160 && hop != 128)       ? "the hop (sample_rate / 8000) is not 160 or 128 samples"
+                 : p.any_afc                        ? "a channel has AFC"
+                 : nch > 64                         ? "more than 64 channels"
+                 : !lits_ok                         ? "the kernel's twiddle literals differ from the plan's table"
+                                                    : nullptr;
+        if (!lp.why) {
             for (int s = 1; s <= 6; ++s)
                 for (const ChanParams& c : p.cp)
                     lp.need[s - 1] |= 1ull << (c.bin & ((1u << s) - 1u));
@@ -372,9 +383,9 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
             lp.nb_pad = 8;
             while (lp.nb_pad < nch)
                 lp.nb_pad *= 2;
-            auto tw_signed = [&](unsigned bin, int s, float& x, float& y) {  // stage s = 7, 8, 9: W_{2^s}^{bin mod 2^(s-1)}, negated for an upper output
+            auto tw_signed = [&](unsigned bin, int s, float& x, float& y) {  // stage s = 7 .. log2 N: W_{2^s}^{bin mod 2^(s-1)}, negated for an upper output
                 const unsigned half = 1u << (s - 1);
-                const unsigned e = (bin & (half - 1u)) * (512u >> s);
+                const unsigned e = (bin & (half - 1u)) * (static_cast<unsigned>(N) >> s);
                 x = p.tw[2 * e], y = p.tw[2 * e + 1];
                 if (bin & half)
                     x = -x, y = -y;
@@ -384,11 +395,11 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
                 const ChanParams& c = p.cp[static_cast<size_t>(i)];
                 L64Chan& o = p.l64_chan[static_cast<size_t>(i)];
                 const unsigned cls = c.bin & 63u;
+                o = L64Chan{};
                 o.slot = __builtin_popcountll(lp.need[5] & ((1ull << cls) - 1ull));
                 o.iq_row = c.iq_row;
-                tw_signed(c.bin, 7, o.w7x, o.w7y);
-                tw_signed(c.bin, 8, o.w8x, o.w8y);
-                tw_signed(c.bin, 9, o.w9x, o.w9y);
+                for (int s = 7; s <= L; ++s)
+                    tw_signed(c.bin, s, o.w[2 * (s - 7)], o.w[2 * (s - 7) + 1]);
             }
             p.l64_chan_full = p.l64_chan;
             for (int i = 0; i < nch; ++i)

@@ -183,8 +183,8 @@ int mi_demod_set_state(mi_demod* h, const void* buf, size_t len);
 int mi_demod_last_path(mi_demod* h, int* time_parallel, int* unverified_rows);
 
 /* Which stage-1 kernel the last call ran (diagnostic; every one of them yields the same bits): the radix-8 exchange kernels
- * (full graph, or pruned to the picked bins at N = 512), or the lane-resident N = 512 kernel (prebuilt full graph, or compiled
- * for this plan's own FFT nodes by hipRTC -- MI_OPT_LANE_FFT / MI_OPT_LANE_FFT_JIT). */
+ * (full graph, or pruned to the picked bins at N = 512), or the lane-resident kernel at N = 512, 1024 and 2048 (prebuilt full
+ * graph, or compiled for this plan's own FFT nodes by hipRTC -- MI_OPT_LANE_FFT / MI_OPT_LANE_FFT_JIT). */
 enum { MI_STAGE1_EXCHANGE_FULL = 0, MI_STAGE1_EXCHANGE_PRUNED = 1, MI_STAGE1_LANE_FULL = 2, MI_STAGE1_LANE_PLAN = 3 };
 int mi_demod_last_stage1(mi_demod* h, int* kind);
 /* (diagnostic) how often, since the handle was created, a channel's wave of the serial kernel gave up waiting for the wave that walks
@@ -262,7 +262,7 @@ enum {
     MI_OPT_TP_CHUNKS = 7,     /* chunks a time-parallel call is cut into, 0 = default */
     MI_OPT_TP_RATIO_PCT = 8,  /* growth of consecutive chunks in percent (150 = 1.5x), 0 = default */
     MI_OPT_TP_SEG_LANES = 9,  /* lanes per wave of the segment pass, 0 = auto */
-    MI_OPT_LANE_FFT = 10,     /* 1 (default): at N = 512 the first six FFT stages stay in the lanes (l64_kernel.h) where the plan allows */
+    MI_OPT_LANE_FFT = 10,     /* 1 (default): at N = 512, 1024 and 2048 the first six FFT stages stay in the lanes (l64_kernel.h) where the plan allows */
     MI_OPT_CORE_SPLIT = 12,   /* 1 (default): the exact squelch core chain of the time-parallel path runs on three waves per channel -- one walks
                                * the noise-floor recurrence, one verifies, snapshots and steps, one fetches (tp.hip, k_tp_core2); 0: one wave */
     MI_OPT_SPEC_HEAD = 13,    /* 1 (default): when consecutive calls overlap (MI_OPT_EARLY_INPUT, alternating audio buffers) the first segments
@@ -293,7 +293,7 @@ enum {
                                * AM channels 344 -> 378 GS/s; with fewer rows the call is the serial kernel's latency either way.
                                * Set before the handle's first such call. */
     MI_OPT_LANE_FFT_JIT = 11  /* 1 (default): that kernel is compiled for the plan's own FFT nodes by hipRTC on first use (the code object is
-                               * cached per (device, hop, masks) for the life of the process); 0, or hipRTC missing: the prebuilt full graph */
+                               * cached per (device, fft size, hop, masks) for the life of the process); 0, or hipRTC missing: the prebuilt full graph */
 };
 int mi_demod_set_option(mi_demod* h, int option, int value);
 
@@ -321,6 +321,14 @@ int mi_plan_twiddles(const mi_plan* p, float* out /* fft_size/2 x {re,im} */);
 int mi_plan_levels(const mi_plan* p, float* out /* 256, the LUT of the device's sample format */);
 int mi_plan_sincos_lut(const mi_plan* p, float* sin_out /* 257 */, float* cos_out /* 257 */);
 int mi_plan_channel(const mi_plan* p, int ch, mi_channel_derived* out);
+/* The lane-resident stage 1 as the plan derives it (l64_kernel.h).  *enabled: the plan allows that kernel (fft_size 512, 1024 or
+ * 2048, hop 160 or 128, no AFC, at most 64 channels, the kernel's twiddle literals equal to the plan's table); when it is 0 the
+ * other outputs are zeroed.  need[s-1]: bit r is set when residue r = bin mod 2^s is live after in-lane stage s = 1..6.
+ * *lanes_per_window = fft_size / 64.  slots[ch]: rank of the channel's class (bin mod 64) among the live classes.  stage_tw: for
+ * each channel the twiddles of the combining stages s = 7 .. log2(fft_size) in that order, W_{2^s}^(bin mod 2^(s-1)) from the
+ * plan's table, negated when the bin is an upper output of the stage (bit s-1 set).  Any output pointer may be NULL. */
+int mi_plan_lane_fft(const mi_plan* p, int* enabled, uint64_t need[6], int* lanes_per_window, int* slots /* nch */,
+                     float* stage_tw /* nch x (log2n-6) x {re,im} */);
 int mi_plan_ctcss_coeffs(const mi_plan* p, int ch, int slow, float* out /* ndet */);
 
 /* ---- synthetic IQ: integer-only, counter-based, identical on host and device ---- */
