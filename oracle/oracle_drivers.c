@@ -212,6 +212,16 @@ void ao_squelch_core_trace(const ao_squelch_cfg* cfg, const float* raw, size_t n
     }
 }
 
+/* Per channel, after the last batch run: the level the squelch compares against (manual, or the larger of the two ratios
+ * times the noise floor -- read from the fields, the lazily cached value is left alone). */
+void ao_demod_squelch_levels(const ao_demod* d, float* squelch_level) {
+    for (int i = 0; i < d->nch; i++) {
+        const ao_squelch* s = &d->ch[i].squelch;
+        const float ratio = s->normal_signal_ratio > s->flappy_signal_ratio ? s->normal_signal_ratio : s->flappy_signal_ratio;
+        squelch_level[i] = s->using_manual_level ? s->manual_signal_level : ratio * s->noise_floor;
+    }
+}
+
 /* dev->bins[] as AFC left them (rtl_airband.cpp:224-249) */
 void ao_demod_bins(const ao_demod* d, int32_t* bins, int32_t* base_bins) {
     for (int i = 0; i < d->nch; i++) {

@@ -163,6 +163,8 @@ def oracle_lib():
         lib.ao_afc_check.restype = C.c_size_t
         lib.ao_demod_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ao_demod_bins.restype = None
+        lib.ao_demod_squelch_levels.argtypes = [C.c_void_p, f32p]
+        lib.ao_demod_squelch_levels.restype = None
         lib.ao_window.argtypes = [f32p, C.c_size_t]
         lib.ao_window.restype = None
         lib.ao_bin_for_freq.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t]
@@ -237,6 +239,12 @@ class OracleDemod:
         cur, base = np.zeros(self.nch, np.int32), np.zeros(self.nch, np.int32)
         self.lib.ao_demod_bins(self.h, cur.ctypes.data_as(C.c_void_p), base.ctypes.data_as(C.c_void_p))
         return cur, base
+
+    def squelch_levels(self):
+        """The level every channel's squelch compares against, as of the last batch run."""
+        out = np.zeros(self.nch, np.float32)
+        self.lib.ao_demod_squelch_levels(self.h, out)
+        return out
 
     def close(self):
         if self.h:
