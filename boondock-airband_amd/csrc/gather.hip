@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
+#include "hip_own.hpp"
 #include "plan.hpp"
 
 namespace mi {
@@ -136,8 +137,8 @@ constexpr char kLoopMagic[8] = {'M', 'I', 'L', 'O', 'O', 'P', '0', '1'};
 struct LoopMsg {
     const void* src = nullptr;
     size_t bytes = 0;
-    hipEvent_t ready = nullptr;  // recorded on the sender's stream: the data is there
-    hipEvent_t done = nullptr;   // recorded on the receiver's stream: the copy has been made
+    mi::Event ready;  // recorded on the sender's stream: the data is there
+    mi::Event done;   // recorded on the receiver's stream: the copy has been made
     bool taken = false, failed = false;
 };
 struct LoopHub {  // one per loopback id: the mailboxes (src rank, dst rank) of a job whose ranks are threads
@@ -155,7 +156,7 @@ struct LoopTransport : Transport {
     int send(const void* buf, size_t count, int type, int peer, hipStream_t s) override {
         LoopMsg m;
         m.src = buf, m.bytes = bytes_of(count, type);
-        if (hipEventCreateWithFlags(&m.ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&m.done, hipEventDisableTiming) != hipSuccess ||
+        if (hipEventCreateWithFlags(m.ready.put(), hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(m.done.put(), hipEventDisableTiming) != hipSuccess ||
             hipEventRecord(m.ready, s) != hipSuccess)
             return gfail(MI_ERR_HIP, "loopback send: event");
         std::unique_lock<std::mutex> lk(hub->mu);
@@ -173,10 +174,8 @@ struct LoopTransport : Transport {
         lk.unlock();
         // the buffer may be reused by whatever the sender enqueues next: behind the receiver's copy
         hipError_t e = (ok && !m.failed) ? hipStreamWaitEvent(s, m.done, 0) : hipSuccess;
-        (void)hipEventDestroy(m.ready);
         if (ok)
-            (void)hipEventSynchronize(m.done);  // (the event object dies with this frame)
-        (void)hipEventDestroy(m.done);
+            (void)hipEventSynchronize(m.done);  // (the event objects die with this frame)
         if (!ok)
             return gfail(MI_ERR_HIP, "loopback send: no matching recv within 60 s");
         if (m.failed || e != hipSuccess)
@@ -257,12 +256,12 @@ struct mi_gather {
     std::vector<size_t> row_lo;    // first row (stream * nch + channel) of each rank in the job-wide arrays
     size_t rows_local = 0, rows_total = 0;
     std::unique_ptr<Transport> tr;  // null at world 1
-    hipStream_t side = nullptr;
-    hipEvent_t ev_in = nullptr, ev_done = nullptr;
+    mi::Stream side;
+    mi::Event ev_in, ev_done;
     // open-batches-only mode
-    float* d_pack = nullptr;       // sender: compacted blocks; rank 0: landing area of the peers' blocks
-    int* d_idx = nullptr;
-    char* h_flags = nullptr;       // pinned: this rank's flags (sender) / everyone's flags (rank 0)
+    mi::DevBuf<float> d_pack;      // sender: compacted blocks; rank 0: landing area of the peers' blocks
+    mi::DevBuf<int> d_idx;
+    mi::PinnedBuf<char> h_flags;   // this rank's flags (sender) / everyone's flags (rank 0)
     std::vector<int> idx_host;
 };
 
@@ -293,19 +292,7 @@ void mi_gather_destroy(mi_gather* g) {
     (void)hipSetDevice(g->gpu);
     if (g->side)
         (void)hipStreamSynchronize(g->side);
-    g->tr.reset();
-    if (g->d_pack)
-        (void)hipFree(g->d_pack);
-    if (g->d_idx)
-        (void)hipFree(g->d_idx);
-    if (g->h_flags)
-        (void)hipHostFree(g->h_flags);
-    if (g->ev_in)
-        (void)hipEventDestroy(g->ev_in);
-    if (g->ev_done)
-        (void)hipEventDestroy(g->ev_done);
-    if (g->side)
-        (void)hipStreamDestroy(g->side);
+    g->tr.reset();  // (the communicator goes before the stream its transfers ran on)
     delete g;
 }
 
@@ -339,11 +326,11 @@ int mi_gather_create(const mi_gather_id* id, int rank, int world, int gpu, const
     };
     hipError_t e = hipSetDevice(gpu);
     if (e == hipSuccess)
-        e = hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking);
+        e = hipStreamCreateWithFlags(g->side.put(), hipStreamNonBlocking);
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&g->ev_in, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(g->ev_in.put(), hipEventDisableTiming);
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(g->ev_done.put(), hipEventDisableTiming);
     if (e != hipSuccess)
         return bail(gfail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MI_ERR_NO_DEVICE : MI_ERR_HIP, std::string("mi_gather_create: ") + hipGetErrorString(e)));
     if (world > 1 && std::memcmp(id->internal, kLoopMagic, sizeof(kLoopMagic)) == 0) {
@@ -417,22 +404,17 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
     // ---- open batches only ----
     const size_t max_blocks = (g->rank == 0 ? g->rows_total : g->rows_local) * static_cast<size_t>(g->max_batches);
     if (!g->d_pack && max_blocks) {  // all three or none: a half-allocated scratch must not reach the kernels below
-        float* pack = nullptr;
-        int* idx = nullptr;
-        char* flags = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&pack), max_blocks * mi::kWaveBatch * sizeof(float));
+        mi::DevBuf<float> pack;
+        mi::DevBuf<int> idx;
+        mi::PinnedBuf<char> flags;
+        hipError_t e = dalloc(pack, max_blocks * mi::kWaveBatch);
         if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&idx), max_blocks * sizeof(int));
+            e = dalloc(idx, max_blocks);
         if (e == hipSuccess)
-            e = hipHostMalloc(reinterpret_cast<void**>(&flags), max_blocks, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            if (pack)
-                (void)hipFree(pack);
-            if (idx)
-                (void)hipFree(idx);
+            e = hipHostMalloc(reinterpret_cast<void**>(flags.put()), max_blocks, hipHostMallocDefault);
+        if (e != hipSuccess)
             return gfail(MI_ERR_NOMEM, std::string("mi_gather_audio: scratch of the open-batches mode: ") + hipGetErrorString(e));
-        }
-        g->d_pack = pack, g->d_idx = idx, g->h_flags = flags;
+        g->d_pack = std::move(pack), g->d_idx = std::move(idx), g->h_flags = std::move(flags);
     }
     auto open_blocks = [&](const char* flags, size_t count, size_t base) {  // indices (relative to `base`) of the blocks that carry a signal
         for (size_t i = 0; i < count; ++i)
@@ -456,7 +438,7 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
         const size_t k = g->idx_host.size();
         if (k) {
             G_HIP_TRY(hipMemcpyAsync(g->d_idx, g->idx_host.data(), k * sizeof(int), hipMemcpyHostToDevice, q));
-            hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(k)), dim3(256), 0, q, d_waveout, g->d_pack, g->d_idx, static_cast<int>(k), 0);
+            hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(k)), dim3(256), 0, q, d_waveout, g->d_pack.get(), g->d_idx.get(), static_cast<int>(k), 0);
             G_HIP_TRY(hipGetLastError());
             Group grp(t);
             T_TRY(grp.start());
@@ -494,7 +476,7 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
         G_HIP_TRY(hipMemcpyAsync(g->d_idx, g->idx_host.data(), k * sizeof(int), hipMemcpyHostToDevice, q));
         if (first[1]) {  // rank 0's own open blocks: compact them like a sender would, so that one scatter serves all
             // (their indices are relative to the job-wide array, whose rank-0 part starts at row_lo[0] = 0)
-            hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(first[1])), dim3(256), 0, q, d_waveout, g->d_pack, g->d_idx, static_cast<int>(first[1]), 0);
+            hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(first[1])), dim3(256), 0, q, d_waveout, g->d_pack.get(), g->d_idx.get(), static_cast<int>(first[1]), 0);
             G_HIP_TRY(hipGetLastError());
         }
         if (g->world > 1) {
@@ -507,7 +489,7 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
             }
             T_TRY(grp.end());
         }
-        hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(k)), dim3(256), 0, q, g->d_pack, d_all_waveout, g->d_idx, static_cast<int>(k), 1);
+        hipLaunchKernelGGL(k_move_blocks, dim3(static_cast<unsigned>(k)), dim3(256), 0, q, g->d_pack.get(), d_all_waveout, g->d_idx.get(), static_cast<int>(k), 1);
         G_HIP_TRY(hipGetLastError());
     }
     G_HIP_TRY(hipEventRecord(g->ev_done, q));

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_own.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -58,14 +59,6 @@ const char kFailedMsg[] = "an earlier call on this handle failed after its state
         }                                                                            \
     } while (0)
 
-template <class T>
-hipError_t dalloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0)
-        return hipSuccess;
-    return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-}
-
 }  // namespace
 
 struct mi_plan {
@@ -78,7 +71,7 @@ struct mi_demod {
     int nstreams = 0, nch = 0, rows = 0, max_batches = 0;
     bool first_call = true;  // waveend starts at 0: the first batch needs AGC_EXTRA more windows (config.cpp:808)
     size_t plane_stride = 0;
-    hipStream_t own_stream = nullptr;
+    mi::Stream own_stream;
     // The time-parallel path keeps kSets sets of its per-call scratch (magnitude planes, block aggregates, core snapshots,
     // segment records, timing events) and cycles through them: stage 1, the aggregates, the core chain and the segment
     // passes of a call never touch what the tails of the two calls before it still read, so calls overlap (see enqueue()).
@@ -90,18 +83,36 @@ struct mi_demod {
     // not fall below (2.8 + 0.85) / 3 = 1.2 ms -- which is what the step took once the chain itself was down to 1.03
     static constexpr int kSets = 6;
     static_assert(kSets % 2 == 0, "a call's scratch set picks its complex plane set by parity: the two must stay in step when the sets wrap");
-    hipEvent_t ev[kSets][5] = {};  // per call: 0 begin, 1 stage 1 done, 2 call done, 3 serial k_demod begins (pipelined serial calls, mixed plans), 4 ... ends (mixed plans)
     static constexpr int kMaxChunks = 64, kEvPerChunk = 13, kSegStreams = 1;
-    std::vector<hipEvent_t> chunk_ev[kSets];  // per chunk: stage1 begin/end, full end, core begin/end, seg begin/end, scan0/fix0/finish ends, rest begin
-    hipStream_t aux_stream = nullptr;    // carries the serial core chain of the time-parallel path
-    hipStream_t front_stream = nullptr;  // stage 1 + aggregates of the time-parallel path
-    hipEvent_t ev_entry = nullptr;       // recorded on the caller's stream when a call starts
-    hipEvent_t ev_head = nullptr;        // ... and after the audio head of the call has been written
-    float* d_mag_set[kSets] = {};  // d_mag aliases d_mag_set[cur]
-    float2* d_cplx_set[2] = {};    // pipelined serial calls alternate two plane sets (d_mag_set[0 / 1], d_cplx_set[0 / 1])
+    struct CallSet {  // scratch set q: what one call in flight owns of the device, and what later calls have to know of it
+        mi::DevBuf<float> mag;    // magnitude planes (d_mag is a view of the last call's)
+        mi::DevBuf<float> carry;  // audio lookahead: a time-parallel call writes its own set's (the next call's segment pass may run
+                                  // before this call's tail has applied its fades and the next call has emitted the lookahead)
+        mi::DevBuf<unsigned> xmax;  // per row: the largest magnitude stage 1 wrote
+        mi::DevBuf<float> blk_fe, blk_fm, blk_x0, blk_xm;  // block aggregates
+        mi::DevBuf<mi::TpCore> core;                       // core snapshots
+        mi::DevBuf<int> rec;  // segment records: the segment passes of the next call write theirs while this call's tail reads its own
+        // per call: 0 begin, 1 stage 1 done, 2 call done, 3 serial k_demod begins (pipelined serial calls, mixed plans), 4 ... ends (mixed plans)
+        mi::Event ev[5];
+        // kEvPerChunk per chunk: 0 stage1 begin, 1 stage1 end, 2 k_tp_full end (front stream), 3 core begin, 4 core end (aux stream),
+        // 5 seg begin, 12 seg end, 6 all segment launches of the chunk done (segment stream), 10 scan#0 begin, 7 scan#0 end,
+        // 8 fix#0 + redo#0 end, 9 finish end (caller's stream), 11 k_tp_full begin
+        std::vector<mi::Event> chunk_ev;
+        uint64_t seq = 0;    // call number that last used this set (0 = never)
+        int path = 0;        // ... and its path: 0 serial kernel, 1 time-parallel, 2 pipelined serial
+        bool mixed = false;  // ... with the serial kernel beside the chain (a mixed plan)
+        int chunks = 0;      // ... the number of its chunks
+        uint32_t nseg = 0;   // ... and of its segments
+        const float *out_lo = nullptr, *out_hi = nullptr;  // audio buffer of the time-parallel call that used this set last
+    } set[kSets];
+    mi::Stream aux_stream;    // carries the serial core chain of the time-parallel path
+    mi::Stream front_stream;  // stage 1 + aggregates of the time-parallel path
+    mi::Event ev_entry;       // recorded on the caller's stream when a call starts
+    mi::Event ev_head;        // ... and after the audio head of the call has been written
+    mi::DevBuf<float2> d_cplx_set[2];  // pipelined serial calls alternate two plane sets (set[0 / 1].mag, d_cplx_set[0 / 1])
     int pset = 0;                  // ... the one holding the carried head
     bool serial_pipe = false;      // the last call was a pipelined serial call
-    float* d_mag_last = nullptr;   // ... and these are the planes it worked on (mi_demod_read_planes)
+    float* d_mag_last = nullptr;   // ... and these are the planes it worked on (mi_demod_read_planes): views
     float2* d_cplx_last = nullptr;
     uint32_t head_off = 0;     // plane index where the AGC_EXTRA carried samples of every row live (0 after a serial call)
     bool steady_blocks = true;  // MI_OPT_STEADY_BLOCKS
@@ -130,69 +141,64 @@ struct mi_demod {
     bool opt_l64_jit = true;  // MI_OPT_LANE_FFT_JIT: compile the plan's own instance with hipRTC (else the full-graph instance)
     bool early_input = false;  // MI_OPT_EARLY_INPUT: the IQ of a call is valid when the call is made
     bool chain_live = false;   // d_core_carry holds the chain state at the end of the previous call (it was time-parallel)
-    hipStream_t seg_stream[kSegStreams] = {nullptr};  // the speculative segment passes (need core(i) only)
+    mi::Stream seg_stream[kSegStreams];  // the speculative segment passes (need core(i) only)
     // MI_OPT_RESERVE_CUS: twins of the front and segment streams whose kernels keep off the last `reserve_cus` CUs (see enqueue)
-    hipStream_t front_stream_m = nullptr;
-    hipStream_t seg_stream_m[kSegStreams] = {nullptr};
+    mi::Stream front_stream_m;
+    mi::Stream seg_stream_m[kSegStreams];
     int opt_reserve_cus = -1;  // -1 auto: 32 for handles of up to 64 rows, none beyond; 0 none
     // MI_OPT_SPLIT_CUS: pipelined serial calls: stage 1 keeps off the last n CUs, k_demod runs on them alone; -1 auto (see enqueue)
     int opt_split_cus = -1;
     int split_state = 0;  // 0 undecided, 1 the two CU-masked streams exist, 2 none
-    hipStream_t ps_front_m = nullptr, ps_demod_m = nullptr;
-    hipEvent_t ev_ps_entry = nullptr, ev_ps_done = nullptr;
+    mi::Stream ps_front_m, ps_demod_m;
+    mi::Event ev_ps_entry, ev_ps_done;
     int last_masked = -1;      // which side the previous time-parallel call used
     int masked_state = 0;      // 0 undecided, 1 the masked twins carry the time-parallel passes of this handle, 2 the plain streams do
-    int tp_chunks[kSets] = {};
-    mi::TpCore* d_core_carry = nullptr;
-    float* d_full0 = nullptr;
-    float* d_fullbound = nullptr;
-    float* d_afc_spec = nullptr;  // [nstreams][fft_size] squared spectrum of the last window of a batch (AFC handles only)
-    uint64_t set_seq[kSets] = {};  // call number that last used each event set (0 = never)
+    mi::DevBuf<mi::TpCore> d_core_carry;
+    mi::DevBuf<float> d_full0;
+    mi::DevBuf<float> d_fullbound;
+    mi::DevBuf<float> d_afc_spec;  // [nstreams][fft_size] squared spectrum of the last window of a batch (AFC handles only)
     uint64_t call_seq = 0;
-    int set_path[kSets] = {};
     // device memory
-    float* d_window = nullptr;
-    float* d_tw = nullptr;
-    float* d_prune_t1 = nullptr;  // stage-1 pruning tables (plan.prune)
-    float* d_prune_t2 = nullptr;
-    int* d_prune_rank = nullptr;
-    L64Chan* d_l64_chan = nullptr;       // per-channel tables of the lane-resident stage 1 (plan.l64): the plan's own instance,
-    L64Chan* d_l64_chan_full = nullptr;  // the full-graph instance
-    unsigned* d_l64_tickets = nullptr;   // run counters of its launches (kernels.hpp, kL64Tickets)
+    mi::DevBuf<float> d_window;
+    mi::DevBuf<float> d_tw;
+    mi::DevBuf<float> d_prune_t1;  // stage-1 pruning tables (plan.prune)
+    mi::DevBuf<float> d_prune_t2;
+    mi::DevBuf<int> d_prune_rank;
+    mi::DevBuf<L64Chan> d_l64_chan;       // per-channel tables of the lane-resident stage 1 (plan.l64): the plan's own instance,
+    mi::DevBuf<L64Chan> d_l64_chan_full;  // the full-graph instance
+    mi::DevBuf<unsigned> d_l64_tickets;   // run counters of its launches (kernels.hpp, kL64Tickets)
     unsigned l64_ticket_seq = 0;
     const mi::L64Jit* l64_jit = nullptr; // the kernel compiled for this plan's masks (owned by the process-wide cache), or null
     bool l64_jit_tried = false;
     bool l64_why_said = false;           // MI_AIRBAND_DEBUG: why this plan does not get the lane-resident kernel, said once
     int last_stage1 = 0;  // MI_STAGE1_* of the last call
-    float* d_levels = nullptr;
-    float* d_sin = nullptr;
-    float* d_cos = nullptr;
-    mi::ChanParams* d_cp = nullptr;
-    mi::ChanState* d_state = nullptr;
-    float* d_mag = nullptr;
-    float2* d_cplx = nullptr;
-    float* d_carry = nullptr;        // the audio lookahead the last call left: aliases d_carry_set[.]
-    float* d_carry_set[kSets] = {};  // time-parallel calls write the one of their scratch set (the next call's segment pass may run
-                                     // before this call's tail has applied its fades and the next call has emitted the lookahead)
-    float* d_ring = nullptr;
-    float* d_ctcss_coeff = nullptr;
-    float* d_ctcss_q = nullptr;
-    mi_channel_stats* d_stats = nullptr;
-    unsigned* d_pre_timeouts = nullptr;  // waits of a channel wave for its pre-filter wave that ran out (k_demod_pw): expected 0
+    mi::DevBuf<float> d_levels;
+    mi::DevBuf<float> d_sin;
+    mi::DevBuf<float> d_cos;
+    mi::DevBuf<mi::ChanParams> d_cp;
+    mi::DevBuf<mi::ChanState> d_state;
+    float* d_mag = nullptr;    // view: the planes of the last call, one of set[.].mag
+    float2* d_cplx = nullptr;  // view: one of d_cplx_set[.]
+    float* d_carry = nullptr;  // view: the audio lookahead the last call left, one of set[.].carry
+    mi::DevBuf<float> d_ring;
+    mi::DevBuf<float> d_ctcss_coeff;
+    mi::DevBuf<float> d_ctcss_q;
+    mi::DevBuf<mi_channel_stats> d_stats;
+    mi::DevBuf<unsigned> d_pre_timeouts;  // waits of a channel wave for its pre-filter wave that ran out (k_demod_pw): expected 0
     // staging for the host-buffer entries: three slots, so that one call can be uploaded and one downloaded while a third
     // computes (mi_demod_submit / mi_demod_wait; mi_demod_process uses slot 0 alone).  A time-parallel call has ~2.5 ms of
     // latency whatever its length (segment pass -> scan -> fix -> ...), so with two slots a 16-s call could not be fed faster
     // than one per (upload + latency) / 2.
     static constexpr int kSlots = 3;
     struct Slot {
-        unsigned char* d_iq = nullptr;   // [nstreams][iq_stride]
-        float* d_wout = nullptr;         // [rows][max steps + AGC_EXTRA]: emitted audio + lookahead, the host layout
-        float2* d_iqout = nullptr;       // [rows][max steps]
-        char* d_axc = nullptr;           // [rows][max batches]
-        mi_channel_stats* d_stats = nullptr;  // [rows] snapshot of the statistics after this call
-        unsigned char* h_in = nullptr;   // pinned: upload staging for sources that are not pinned themselves
-        unsigned char* h_out = nullptr;  // pinned: audio / raw I/Q / flags / statistics on their way back
-        hipEvent_t up_done = nullptr, done = nullptr;
+        mi::DevBuf<unsigned char> d_iq;   // [nstreams][iq_stride]
+        mi::DevBuf<float> d_wout;         // [rows][max steps + AGC_EXTRA]: emitted audio + lookahead, the host layout
+        mi::DevBuf<float2> d_iqout;       // [rows][max steps]
+        mi::DevBuf<char> d_axc;           // [rows][max batches]
+        mi::DevBuf<mi_channel_stats> d_stats;  // [rows] snapshot of the statistics after this call
+        mi::PinnedBuf<unsigned char> h_in;   // upload staging for sources that are not pinned themselves
+        mi::PinnedBuf<unsigned char> h_out;  // audio / raw I/Q / flags / statistics on their way back
+        mi::Event up_done, done;
         bool busy = false;
         // where the results of the call in flight go
         int nbatches = 0;
@@ -206,40 +212,32 @@ struct mi_demod {
     bool slots_ready[kSlots] = {};
     int slot_next = 0, slot_oldest = 0, in_flight = 0;
     bool failed = false;  // a call advanced the DSP state and then could not deliver its results: every further call is refused
-    hipStream_t copy_stream = nullptr;  // uploads of submitted calls
-    hipStream_t down_stream = nullptr;  // their downloads
+    mi::Stream copy_stream;  // uploads of submitted calls
+    mi::Stream down_stream;  // their downloads
     // time-parallel stage 2 (tp.hip): the plain AM channels of the plan.  A mixed plan (tp_mixed) sends those rows down the time-parallel
     // path and the others through the serial kernel in the same call (MI_OPT_MIXED_PLAN), on a stream of its own beside the chain.
     bool tp_eligible = false;
     bool tp_mixed = false;
     bool opt_mixed = true;
     int tp_rows = 0, ser_rows = 0;       // rows of either kind (tp_rows + ser_rows == rows)
-    int* d_srows = nullptr;              // the serial kernel's rows of a mixed plan (d_rows: the time-parallel path's)
-    hipStream_t ser_stream = nullptr;    // ... and its stream
-    hipEvent_t ev_cplx_free[2] = {};     // the serial kernel of a mixed call has read complex plane set p
+    mi::DevBuf<int> d_srows;             // the serial kernel's rows of a mixed plan (d_rows: the time-parallel path's)
+    mi::Stream ser_stream;               // ... and its stream
+    mi::Event ev_cplx_free[2];           // the serial kernel of a mixed call has read complex plane set p
     bool cplx_busy[2] = {};
     bool ser_head_next = false;          // the serial kernel of the last (mixed) call left its rows' carried samples in the next plane set
-    bool set_mixed[kSets] = {};
     int last_path = 0;  // 0 = serial kernel, 1 = time-parallel
-    int* d_rows = nullptr;
-    unsigned* d_xmax[kSets] = {};
-    float *d_blk_fe[kSets] = {}, *d_blk_fm[kSets] = {}, *d_blk_x0[kSets] = {}, *d_blk_xm[kSets] = {};
-    mi::TpCore* d_core[kSets] = {};
-    int* d_rec[kSets] = {};  // per scratch set: the segment passes of the next call write theirs while this call's tail reads its own
-    const float* prev_out_lo = nullptr;  // audio buffer of the previous call (its tail may still be writing it)
+    mi::DevBuf<int> d_rows;
+    const float* prev_out_lo = nullptr;  // view: the caller's audio buffer of the previous call (its tail may still be writing it)
     const float* prev_out_hi = nullptr;
-    // mi_demod_process_planes (test entry): stage 1 is replaced by a copy of caller-supplied planes, [row][inject_count]
+    // mi_demod_process_planes (test entry): stage 1 is replaced by a copy of caller-supplied planes, [row][inject_count]: views
     const float* inject_mag = nullptr;
     const float2* inject_cplx = nullptr;
     size_t inject_count = 0;
-    const float* set_out_lo[kSets] = {};  // ... and of the time-parallel calls that used each scratch set last
-    const float* set_out_hi[kSets] = {};
-    int* d_tstart = nullptr;
-    int* d_need = nullptr;
-    int* d_redo = nullptr;  // [1 + rows*max_seg]: count, then the (row, segment) indices k_tp_fix leaves for k_tp_redo
-    mi::TpFinal* d_fin = nullptr;
-    int* d_diag = nullptr;
-    uint32_t last_nseg[kSets] = {};
+    mi::DevBuf<int> d_tstart;
+    mi::DevBuf<int> d_need;
+    mi::DevBuf<int> d_redo;  // [1 + rows*max_seg]: count, then the (row, segment) indices k_tp_fix leaves for k_tp_redo
+    mi::DevBuf<mi::TpFinal> d_fin;
+    mi::DevBuf<int> d_diag;
     size_t tp_max_blk = 0, tp_max_seg = 0;
     uint32_t tp_L = 512;  // steps per segment (kernels.hpp, TP_L_MIN .. TP_L_MAX), fixed when the handle is created
     int opt_tp_L = 0;     // MI_AIRBAND_TP_SEGMENT at create: 0 = by row count
@@ -380,27 +378,27 @@ int lanes_per_wave_for(const mi_demod* h) {
 // shared by both entry points; everything is enqueued on `s`
 // the second plane set of the pipelined serial path, allocated the first time it is wanted
 bool serial_sets_ready(mi_demod* h) {
-    if (h->d_mag_set[1] && (h->d_cplx_set[1] || !h->d_cplx_set[0]))
+    if (h->set[1].mag && (h->d_cplx_set[1] || !h->d_cplx_set[0]))
         return true;
     const size_t rows = static_cast<size_t>(h->rows);
-    if (!h->d_mag_set[1]) {
-        float* m = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&m), rows * h->plane_stride * 4) != hipSuccess) {
+    if (!h->set[1].mag) {
+        mi::DevBuf<float> m;
+        if (dalloc(m, rows * h->plane_stride) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
         (void)hipMemset(m, 0, rows * h->plane_stride * 4);
-        h->d_mag_set[1] = m;
+        h->set[1].mag = std::move(m);
     }
     if (h->d_cplx_set[0] && !h->d_cplx_set[1]) {
         const size_t zn = static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows * h->plane_stride;
-        float2* z = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&z), zn * 8) != hipSuccess) {
+        mi::DevBuf<float2> z;
+        if (dalloc(z, zn) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
         (void)hipMemset(z, 0, zn * 8);
-        h->d_cplx_set[1] = z;
+        h->d_cplx_set[1] = std::move(z);
     }
     return true;
 }
@@ -525,7 +523,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             e = mi::launch_row_max(cc.mag + cc.plane_off, cc.plane_stride, cc.nfft, h->rows, cc.xmax, st);
         return e;
     };
-    hipEvent_t* evc = h->ev[h->cur];  // (the time-parallel and the pipelined serial branch switch to the next set)
+    const mi::Event* evc = h->set[h->cur].ev;  // (the time-parallel and the pipelined serial branch switch to the next set)
     bool pipelined_serial = false;
     if (use_tp) {
         // ---- time-parallel stage 2, pipelined over chunks of the call and across calls ----
@@ -538,7 +536,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         // With MI_OPT_EARLY_INPUT the front and aux streams do not wait for the caller's stream, i.e. for the segment
         // and fix passes of the previous call: consecutive calls overlap and the core chain runs back to back.
         const int q = (h->cur + 1) % mi_demod::kSets;  // the scratch set of this call
-        float* const planes = h->d_mag_set[q];
+        float* const planes = h->set[q].mag;
         const bool overlap = early_input && h->chain_live && !h->first_call;
         const float* out_lo = d_wmain;
         const float* out_hi = d_wmain + static_cast<size_t>(h->rows - 1) * wmain_stride + da.nsteps;
@@ -589,13 +587,13 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         const int C = static_cast<int>(bound.size()) - 1;
         if (C > mi_demod::kMaxChunks)
             return fail(MI_ERR_INVALID, "too many chunks");
-        std::vector<hipEvent_t>& cev = h->chunk_ev[q];
+        std::vector<mi::Event>& cev = h->set[q].chunk_ev;
         while (static_cast<int>(cev.size()) < C * mi_demod::kEvPerChunk) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            cev.push_back(e);
+            mi::Event e;
+            HIP_TRY(hipEventCreate(e.put()));
+            cev.push_back(std::move(e));
         }
-        evc = h->ev[q];
+        evc = h->set[q].ev;
         mi::TpArgs ta{};
         ta.rows = h->d_rows;
         ta.nrows = h->tp_rows;
@@ -609,25 +607,25 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         ta.plane_stride = h->plane_stride;
         ta.wmain = d_wmain;
         ta.wmain_stride = wmain_stride;
-        ta.carry = h->d_carry_set[q];
+        ta.carry = h->set[q].carry;
         ta.carry_prev = h->d_carry;
         ta.axc = d_axc;
         ta.cp = h->d_cp;
         ta.st = h->d_state;
         ta.stats = h->d_stats;
-        ta.xmax = h->d_xmax[q];
-        ta.blk_fe = h->d_blk_fe[q];
-        ta.blk_fm = h->d_blk_fm[q];
-        ta.blk_x0 = h->d_blk_x0[q];
-        ta.blk_xm = h->d_blk_xm[q];
-        ta.core = h->d_core[q];
+        ta.xmax = h->set[q].xmax;
+        ta.blk_fe = h->set[q].blk_fe;
+        ta.blk_fm = h->set[q].blk_fm;
+        ta.blk_x0 = h->set[q].blk_x0;
+        ta.blk_xm = h->set[q].blk_xm;
+        ta.core = h->set[q].core;
         ta.core_carry = h->d_core_carry;
         ta.full0 = h->d_full0;
         ta.fullbound = h->d_fullbound;
         ta.prev_mag = overlap ? h->d_mag : nullptr;  // (still the previous call's planes here)
         ta.prev_n = h->head_off;
-        ta.xmax_prev = h->d_xmax[h->cur];
-        ta.rec = h->d_rec[q];
+        ta.xmax_prev = h->set[h->cur].xmax;
+        ta.rec = h->set[q].rec;
         ta.rec_stride = static_cast<size_t>(h->rows) * h->tp_max_seg;
         ta.tstart = h->d_tstart;
         ta.need = h->d_need;
@@ -645,15 +643,15 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         // Speculative head: when this call's segment pass may run under the previous call's tail at all (seg_early) and that call
         // left what the warm-up needs (aggregates, core states at boundaries of the same segment length, TP_W steps of them),
         // no lane starts from the carried ChanState and no launch of the pass waits for the previous call.
-        const bool spec_head = seg_early && h->opt_spec_head && h->head_off >= mi::TP_W && h->set_seq[h->cur] &&
-                               h->set_path[h->cur] == 1;
+        const bool spec_head = seg_early && h->opt_spec_head && h->head_off >= mi::TP_W && h->set[h->cur].seq &&
+                               h->set[h->cur].path == 1;
         ta.spec_head = spec_head ? 1 : 0;
-        ta.prev_blk_fe = h->d_blk_fe[h->cur], ta.prev_blk_fm = h->d_blk_fm[h->cur];
-        ta.prev_blk_x0 = h->d_blk_x0[h->cur], ta.prev_blk_xm = h->d_blk_xm[h->cur];
-        ta.prev_core = h->d_core[h->cur];
+        ta.prev_blk_fe = h->set[h->cur].blk_fe, ta.prev_blk_fm = h->set[h->cur].blk_fm;
+        ta.prev_blk_x0 = h->set[h->cur].blk_x0, ta.prev_blk_xm = h->set[h->cur].blk_xm;
+        ta.prev_core = h->set[h->cur].core;
         ta.prev_nblk = h->head_off / 16;
-        ta.prev_nseg = h->last_nseg[h->cur];
-        h->last_nseg[q] = ta.nseg;
+        ta.prev_nseg = h->set[h->cur].nseg;
+        h->set[q].nseg = ta.nseg;
         auto chunk = [&](int i) {
             mi::TpArgs c = ta;
             c.step0 = bound[static_cast<size_t>(i)] * chunk_unit;
@@ -691,10 +689,10 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
                 std::vector<uint32_t> mask(static_cast<size_t>((ncu + 31) / 32), 0u);
                 for (int i = 0; i < keep; ++i)
                     mask[static_cast<size_t>(i) / 32] |= 1u << (i % 32);
-                hipError_t me = hipExtStreamCreateWithCUMask(&h->front_stream_m, static_cast<uint32_t>(mask.size()), mask.data());
-                for (hipStream_t& ssm : h->seg_stream_m)
+                hipError_t me = hipExtStreamCreateWithCUMask(h->front_stream_m.put(), static_cast<uint32_t>(mask.size()), mask.data());
+                for (mi::Stream& ssm : h->seg_stream_m)
                     if (me == hipSuccess)
-                        me = hipExtStreamCreateWithCUMask(&ssm, static_cast<uint32_t>(mask.size()), mask.data());
+                        me = hipExtStreamCreateWithCUMask(ssm.put(), static_cast<uint32_t>(mask.size()), mask.data());
                 if (me == hipSuccess)
                     h->masked_state = 1;
                 else
@@ -720,10 +718,10 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             cc.nfft = f1 - f0;
             cc.plane_off = ca.plane_off + f0;
             cc.mag = planes;
-            cc.xmax = h->d_xmax[q];
+            cc.xmax = h->set[q].xmax;
             return stage1_launch(cc, f0, fs);
         };
-        auto ev = [&](int i, int k) { return cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + k]; };
+        auto ev = [&](int i, int k) -> hipEvent_t { return cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + k]; };
         HIP_TRY(hipEventRecord(h->ev_entry, s));
         HIP_TRY(hipEventRecord(evc[0], s));
         HIP_TRY(hipEventRecord(evc[1], s));
@@ -733,24 +731,24 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             HIP_TRY(hipStreamWaitEvent(fs, iq_ready, 0));
         if (!overlap)
             HIP_TRY(hipStreamWaitEvent(fs, h->ev_entry, 0));  // stage 1 honours the caller's stream order
-        else if (h->set_seq[q])
-            HIP_TRY(hipStreamWaitEvent(fs, h->ev[q][2], 0));  // the call that used this scratch set last (kSets back) has left it
+        else if (h->set[q].seq)
+            HIP_TRY(hipStreamWaitEvent(fs, h->set[q].ev[2], 0));  // the call that used this scratch set last (kSets back) has left it
         {
             // ... and the call after that one has read what its speculative head needed from that set (planes, aggregates, core
             // states): its segment pass is done (always long before; the wait costs nothing)
             const int qn = (q + 1) % mi_demod::kSets;
-            if (h->set_seq[qn] && h->set_path[qn] == 1 && h->tp_chunks[qn] > 0)
-                HIP_TRY(hipStreamWaitEvent(fs, h->chunk_ev[qn][static_cast<size_t>(h->tp_chunks[qn] - 1) * mi_demod::kEvPerChunk + 6], 0));
+            if (h->set[qn].seq && h->set[qn].path == 1 && h->set[qn].chunks > 0)
+                HIP_TRY(hipStreamWaitEvent(fs, h->set[qn].chunk_ev[static_cast<size_t>(h->set[qn].chunks - 1) * mi_demod::kEvPerChunk + 6], 0));
         }
         if (h->tp_mixed && h->cplx_busy[zp])  // (the serial kernel of the call before the previous one read this complex plane set)
             HIP_TRY(hipStreamWaitEvent(fs, h->ev_cplx_free[zp], 0));
         // the carried samples of the previous call (wherever they are) become the head of this call's planes -- of a mixed plan the
         // time-parallel rows' only where the serial kernel of the previous call has put its own rows' there itself
-        if (h->tp_mixed && h->ser_head_next && planes == h->d_mag_set[(h->cur + 1) % mi_demod::kSets])
+        if (h->tp_mixed && h->ser_head_next && planes == h->set[(h->cur + 1) % mi_demod::kSets].mag)
             HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->tp_rows, fs, h->d_rows));
         else
             HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->rows, fs));
-        HIP_TRY(hipMemsetAsync(h->d_xmax[q], 0, static_cast<size_t>(h->rows) * sizeof(unsigned), fs));
+        HIP_TRY(hipMemsetAsync(h->set[q].xmax, 0, static_cast<size_t>(h->rows) * sizeof(unsigned), fs));
         // Stage 1 + aggregates of every chunk first: nothing else feeds them (when calls overlap, k_tp_full warms its first
         // lanes up on the previous call's planes, so not even the chain state of that call).
         for (int i = 0; i < C; ++i) {
@@ -780,10 +778,10 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
                 // one before that -- then the pass has two tail periods of slack instead of one and the tails run back to back.
                 for (int back = 1; back < mi_demod::kSets - 1; ++back) {
                     const int pq = (h->cur + mi_demod::kSets - back) % mi_demod::kSets;
-                    if (!h->set_seq[pq])
+                    if (!h->set[pq].seq)
                         break;
-                    if (h->set_path[pq] != 1 || !(out_hi <= h->set_out_lo[pq] || out_lo >= h->set_out_hi[pq])) {
-                        HIP_TRY(hipStreamWaitEvent(ss, h->ev[pq][2], 0));
+                    if (h->set[pq].path != 1 || !(out_hi <= h->set[pq].out_lo || out_lo >= h->set[pq].out_hi)) {
+                        HIP_TRY(hipStreamWaitEvent(ss, h->set[pq].ev[2], 0));
                         break;
                     }
                 }
@@ -821,7 +819,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             hipEvent_t marks[mi::TP_REST_MARKS] = {ev(i, 7), ev(i, 8), ev(i, 9)};
             HIP_TRY(mi::launch_tp_rest(c, s, marks));
         }
-        h->set_mixed[q] = false;
+        h->set[q].mixed = false;
         h->ser_head_next = false;
         if (h->tp_mixed && h->ser_rows > 0) {
             // ---- the rows the time-parallel path does not take: k_demod on its own stream, beside the chain ----
@@ -838,9 +836,9 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             dm.nrows = h->ser_rows;
             dm.mag = planes;
             dm.cplx = h->d_cplx_set[zp];
-            dm.mag_head = h->d_mag_set[(q + 1) % mi_demod::kSets];  // (free: the call that used it last is four calls back)
+            dm.mag_head = h->set[(q + 1) % mi_demod::kSets].mag;  // (free: the call that used it last is four calls back)
             dm.cplx_head = h->d_cplx_set[znp];
-            dm.carry = h->d_carry_set[q];
+            dm.carry = h->set[q].carry;
             dm.carry_in = h->d_carry;
             dm.lanes_per_wave = std::min(64, std::max(1, (h->ser_rows + h->opt_uni_rows - 1) / h->opt_uni_rows));
             dm.pre_wave = (h->opt_pre_wave < 0 ? h->ser_rows <= 256 : h->opt_pre_wave != 0) ? 1 : 0;
@@ -853,19 +851,19 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             h->d_cplx = h->d_cplx_set[znp];
             h->d_cplx_last = h->d_cplx_set[zp];
             h->pset = znp;
-            h->set_mixed[q] = true;
+            h->set[q].mixed = true;
             h->ser_head_next = true;
         }
-        h->tp_chunks[q] = C;
+        h->set[q].chunks = C;
         h->cur = q;
-        h->d_carry = h->d_carry_set[q];
+        h->d_carry = h->set[q].carry;
         h->d_mag = planes;
         h->head_off = n;  // (first call: the planes hold AGC_EXTRA + n samples, the last AGC_EXTRA start at n as well)
         h->chain_live = true;
         h->prev_out_lo = out_lo;
         h->prev_out_hi = out_hi;
-        h->set_out_lo[q] = out_lo;
-        h->set_out_hi[q] = out_hi;
+        h->set[q].out_lo = out_lo;
+        h->set[q].out_hi = out_hi;
     } else if (h->plan.any_afc) {
         if (iq_ready)
             HIP_TRY(hipStreamWaitEvent(s, iq_ready, 0));
@@ -906,12 +904,12 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             HIP_TRY(mi::launch_afc(aa, s));
             f0 += nf;
         }
-    } else if (early_input && !h->first_call && (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->d_mag_set[0] || h->d_mag == h->d_mag_set[1]))) &&
+    } else if (early_input && !h->first_call && (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) &&
                serial_sets_ready(h)) {
         // (a handle whose plan the time-parallel path could take as well -- many rows, or MI_OPT_TIME_PARALLEL = 0 -- pipelines its serial
         //  calls like any other as long as its planes are where this branch keeps them: never after a time-parallel call)
         if (h->tp_eligible)
-            h->pset = h->d_mag == h->d_mag_set[1] ? 1 : 0;
+            h->pset = h->d_mag == h->set[1].mag ? 1 : 0;
         // ---- serial stage 2 with consecutive calls overlapping (MI_OPT_EARLY_INPUT) ----
         // Two plane sets alternate.  Stage 1 of this call fills the body of set p on the front stream while the previous
         // call's k_demod, which reads the other set, still runs on the caller's stream (all that k_demod writes into set p
@@ -920,7 +918,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         const int q = (h->cur + 1) % mi_demod::kSets;  // event / timing set of this call
         const int before_prev = (h->cur + mi_demod::kSets - 1) % mi_demod::kSets;
         const int p = h->pset, np = p ^ 1;
-        evc = h->ev[q];
+        evc = h->set[q].ev;
         if (h->split_state == 0) {
             h->split_state = 2;
             hipDeviceProp_t prop{};
@@ -935,13 +933,13 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
                 std::vector<uint32_t> m_front(static_cast<size_t>((ncu + 31) / 32), 0u), m_demod(m_front.size(), 0u);
                 for (int i = 0; i < ncu; ++i)
                     (i < keep ? m_front : m_demod)[static_cast<size_t>(i) / 32] |= 1u << (i % 32);
-                hipError_t me = hipExtStreamCreateWithCUMask(&h->ps_front_m, static_cast<uint32_t>(m_front.size()), m_front.data());
+                hipError_t me = hipExtStreamCreateWithCUMask(h->ps_front_m.put(), static_cast<uint32_t>(m_front.size()), m_front.data());
                 if (me == hipSuccess)
-                    me = hipExtStreamCreateWithCUMask(&h->ps_demod_m, static_cast<uint32_t>(m_demod.size()), m_demod.data());
+                    me = hipExtStreamCreateWithCUMask(h->ps_demod_m.put(), static_cast<uint32_t>(m_demod.size()), m_demod.data());
                 if (me == hipSuccess)
-                    me = hipEventCreateWithFlags(&h->ev_ps_entry, hipEventDisableTiming);
+                    me = hipEventCreateWithFlags(h->ev_ps_entry.put(), hipEventDisableTiming);
                 if (me == hipSuccess)
-                    me = hipEventCreateWithFlags(&h->ev_ps_done, hipEventDisableTiming);
+                    me = hipEventCreateWithFlags(h->ev_ps_done.put(), hipEventDisableTiming);
                 if (me == hipSuccess)
                     h->split_state = 1;
                 else
@@ -952,18 +950,18 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         hipStream_t fs = split ? h->ps_front_m : h->front_stream;
         if (iq_ready)
             HIP_TRY(hipStreamWaitEvent(fs, iq_ready, 0));
-        if (h->serial_pipe && h->set_seq[before_prev])  // the call before the previous one read the body of set p
-            HIP_TRY(hipStreamWaitEvent(fs, h->ev[before_prev][2], 0));
+        if (h->serial_pipe && h->set[before_prev].seq)  // the call before the previous one read the body of set p
+            HIP_TRY(hipStreamWaitEvent(fs, h->set[before_prev].ev[2], 0));
         else
-            HIP_TRY(hipStreamWaitEvent(fs, h->ev[h->cur][2], 0));  // (first pipelined call: everything before it)
-        ca.mag = h->d_mag_set[p];
+            HIP_TRY(hipStreamWaitEvent(fs, h->set[h->cur].ev[2], 0));  // (first pipelined call: everything before it)
+        ca.mag = h->set[p].mag;
         ca.cplx = h->d_cplx_set[p];
         HIP_TRY(hipEventRecord(evc[0], fs));
         HIP_TRY(stage1_launch(ca, 0, fs));
         HIP_TRY(hipEventRecord(evc[1], fs));
-        da.mag = h->d_mag_set[p];
+        da.mag = h->set[p].mag;
         da.cplx = h->d_cplx_set[p];
-        da.mag_head = h->d_mag_set[np];
+        da.mag_head = h->set[np].mag;
         da.cplx_head = h->d_cplx_set[np];
         if (split) {  // k_demod on the CUs stage 1 keeps off, in the caller's stream order all the same
             hipStream_t ds = h->ps_demod_m;
@@ -982,9 +980,9 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
         h->chain_live = false;
         h->cur = q;
         h->pset = np;
-        h->d_mag = h->d_mag_set[np];
+        h->d_mag = h->set[np].mag;
         h->d_cplx = h->d_cplx_set[np];
-        h->d_mag_last = h->d_mag_set[p];
+        h->d_mag_last = h->set[p].mag;
         h->d_cplx_last = h->d_cplx_set[p];
         h->serial_pipe = true;
         pipelined_serial = true;
@@ -1005,8 +1003,8 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     if (!use_tp)
         h->ser_head_next = false;
     HIP_TRY(hipEventRecord(evc[2], s));
-    h->set_seq[h->cur] = ++h->call_seq;
-    h->set_path[h->cur] = pipelined_serial ? 2 : h->last_path;
+    h->set[h->cur].seq = ++h->call_seq;
+    h->set[h->cur].path = pipelined_serial ? 2 : h->last_path;
     h->first_call = false;
     return MI_OK;
 }
@@ -1031,75 +1029,6 @@ void mi_demod_destroy(mi_demod* h) {
         return;
     (void)hipSetDevice(h->gpu);
     (void)hipDeviceSynchronize();  // calls may still be in flight on the handle's own streams
-    void* ptrs[] = {h->d_window, h->d_tw, h->d_prune_t1, h->d_prune_t2, h->d_prune_rank, h->d_l64_chan, h->d_l64_chan_full, h->d_l64_tickets, h->d_levels,      h->d_sin,     h->d_cos,   h->d_cp, h->d_state, h->d_cplx_set[0], h->d_cplx_set[1],
-                    h->d_ring,   h->d_ctcss_coeff, h->d_ctcss_q, h->d_stats, h->d_pre_timeouts,
-                    h->d_rows,   h->d_srows, h->d_tstart, h->d_need, h->d_redo, h->d_fin, h->d_diag, h->d_core_carry, h->d_full0, h->d_fullbound, h->d_afc_spec};
-    for (void* p : ptrs)
-        if (p)
-            (void)hipFree(p);
-    for (int q = 0; q < mi_demod::kSets; ++q) {
-        void* sets[] = {h->d_mag_set[q], h->d_carry_set[q], h->d_xmax[q], h->d_blk_fe[q], h->d_blk_fm[q], h->d_blk_x0[q], h->d_blk_xm[q], h->d_core[q], h->d_rec[q]};
-        for (void* p : sets)
-            if (p)
-                (void)hipFree(p);
-    }
-    for (mi_demod::Slot& sl : h->slot) {
-        void* dev[] = {sl.d_iq, sl.d_wout, sl.d_iqout, sl.d_axc, sl.d_stats};
-        for (void* p : dev)
-            if (p)
-                (void)hipFree(p);
-        if (sl.h_in)
-            (void)hipHostFree(sl.h_in);
-        if (sl.h_out)
-            (void)hipHostFree(sl.h_out);
-        if (sl.up_done)
-            (void)hipEventDestroy(sl.up_done);
-        if (sl.done)
-            (void)hipEventDestroy(sl.done);
-    }
-    if (h->copy_stream)
-        (void)hipStreamDestroy(h->copy_stream);
-    if (h->down_stream)
-        (void)hipStreamDestroy(h->down_stream);
-    for (int q = 0; q < mi_demod::kSets; ++q) {
-        for (hipEvent_t e : h->ev[q])
-            if (e)
-                (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->chunk_ev[q])
-            if (e)
-                (void)hipEventDestroy(e);
-    }
-    if (h->ev_entry)
-        (void)hipEventDestroy(h->ev_entry);
-    if (h->ev_head)
-        (void)hipEventDestroy(h->ev_head);
-    if (h->aux_stream)
-        (void)hipStreamDestroy(h->aux_stream);
-    if (h->ser_stream)
-        (void)hipStreamDestroy(h->ser_stream);
-    for (hipEvent_t e : h->ev_cplx_free)
-        if (e)
-            (void)hipEventDestroy(e);
-    if (h->front_stream_m)
-        (void)hipStreamDestroy(h->front_stream_m);
-    if (h->ps_front_m)
-        (void)hipStreamDestroy(h->ps_front_m);
-    if (h->ps_demod_m)
-        (void)hipStreamDestroy(h->ps_demod_m);
-    if (h->ev_ps_entry)
-        (void)hipEventDestroy(h->ev_ps_entry);
-    if (h->ev_ps_done)
-        (void)hipEventDestroy(h->ev_ps_done);
-    for (hipStream_t ss : h->seg_stream_m)
-        if (ss)
-            (void)hipStreamDestroy(ss);
-    if (h->front_stream)
-        (void)hipStreamDestroy(h->front_stream);
-    for (hipStream_t ss : h->seg_stream)
-        if (ss)
-            (void)hipStreamDestroy(ss);
-    if (h->own_stream)
-        (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
 
@@ -1154,59 +1083,59 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
     } while (0)
 
     TRY_OR_BAIL(hipSetDevice(gpu));
-    TRY_OR_BAIL(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    for (auto& evs : h->ev)
-        for (hipEvent_t& ev : evs)
-            TRY_OR_BAIL(hipEventCreate(&ev));
-    TRY_OR_BAIL(hipEventCreate(&h->ev_entry));
-    TRY_OR_BAIL(hipEventCreate(&h->ev_head));
+    TRY_OR_BAIL(hipStreamCreateWithFlags(h->own_stream.put(), hipStreamNonBlocking));
+    for (mi_demod::CallSet& cs : h->set)
+        for (mi::Event& ev : cs.ev)
+            TRY_OR_BAIL(hipEventCreate(ev.put()));
+    TRY_OR_BAIL(hipEventCreate(h->ev_entry.put()));
+    TRY_OR_BAIL(hipEventCreate(h->ev_head.put()));
     {
         // HIP multiplexes its streams onto a few hardware queues; two streams that share one run their kernels one after
         // the other.  The core chain must never queue behind a wide pass, so it gets the highest stream priority (its
         // own queue class), and the wide passes share as few other streams as the pipeline needs.
         int lo_prio = 0, hi_prio = 0;
         TRY_OR_BAIL(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-        TRY_OR_BAIL(hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, hi_prio));
+        TRY_OR_BAIL(hipStreamCreateWithPriority(h->aux_stream.put(), hipStreamNonBlocking, hi_prio));
     }
-    TRY_OR_BAIL(hipStreamCreateWithFlags(&h->front_stream, hipStreamNonBlocking));
-    for (hipStream_t& ss : h->seg_stream)
-        TRY_OR_BAIL(hipStreamCreateWithFlags(&ss, hipStreamNonBlocking));
+    TRY_OR_BAIL(hipStreamCreateWithFlags(h->front_stream.put(), hipStreamNonBlocking));
+    for (mi::Stream& ss : h->seg_stream)
+        TRY_OR_BAIL(hipStreamCreateWithFlags(ss.put(), hipStreamNonBlocking));
     const size_t rows = static_cast<size_t>(h->rows);
-    TRY_OR_BAIL(dalloc(&h->d_window, p.window.size()));
-    TRY_OR_BAIL(dalloc(&h->d_tw, p.tw.size()));
-    TRY_OR_BAIL(dalloc(&h->d_levels, 256));
-    TRY_OR_BAIL(dalloc(&h->d_sin, 257));
-    TRY_OR_BAIL(dalloc(&h->d_cos, 257));
-    TRY_OR_BAIL(dalloc(&h->d_cp, static_cast<size_t>(nch)));
-    TRY_OR_BAIL(dalloc(&h->d_state, rows));
-    TRY_OR_BAIL(dalloc(&h->d_mag_set[0], rows * h->plane_stride));
-    h->d_mag = h->d_mag_set[0];
-    TRY_OR_BAIL(dalloc(&h->d_cplx, static_cast<size_t>(nstreams) * p.n_iq_rows * h->plane_stride));
-    h->d_cplx_set[0] = h->d_cplx;
-    TRY_OR_BAIL(dalloc(&h->d_carry_set[0], rows * mi::kAgcExtra));
-    h->d_carry = h->d_carry_set[0];
-    TRY_OR_BAIL(dalloc(&h->d_ring, rows * mi::kSquelchRing));
-    TRY_OR_BAIL(dalloc(&h->d_ctcss_coeff, p.ctcss_coeff.size()));
-    TRY_OR_BAIL(dalloc(&h->d_ctcss_q, static_cast<size_t>(nstreams) * p.n_ctcss_rows * 4 * mi::kMaxTones));
-    TRY_OR_BAIL(dalloc(&h->d_stats, rows));
-    TRY_OR_BAIL(dalloc(&h->d_pre_timeouts, 1));
+    TRY_OR_BAIL(dalloc(h->d_window, p.window.size()));
+    TRY_OR_BAIL(dalloc(h->d_tw, p.tw.size()));
+    TRY_OR_BAIL(dalloc(h->d_levels, 256));
+    TRY_OR_BAIL(dalloc(h->d_sin, 257));
+    TRY_OR_BAIL(dalloc(h->d_cos, 257));
+    TRY_OR_BAIL(dalloc(h->d_cp, static_cast<size_t>(nch)));
+    TRY_OR_BAIL(dalloc(h->d_state, rows));
+    TRY_OR_BAIL(dalloc(h->set[0].mag, rows * h->plane_stride));
+    h->d_mag = h->set[0].mag;
+    TRY_OR_BAIL(dalloc(h->d_cplx_set[0], static_cast<size_t>(nstreams) * p.n_iq_rows * h->plane_stride));
+    h->d_cplx = h->d_cplx_set[0];
+    TRY_OR_BAIL(dalloc(h->set[0].carry, rows * mi::kAgcExtra));
+    h->d_carry = h->set[0].carry;
+    TRY_OR_BAIL(dalloc(h->d_ring, rows * mi::kSquelchRing));
+    TRY_OR_BAIL(dalloc(h->d_ctcss_coeff, p.ctcss_coeff.size()));
+    TRY_OR_BAIL(dalloc(h->d_ctcss_q, static_cast<size_t>(nstreams) * p.n_ctcss_rows * 4 * mi::kMaxTones));
+    TRY_OR_BAIL(dalloc(h->d_stats, rows));
+    TRY_OR_BAIL(dalloc(h->d_pre_timeouts, 1));
     TRY_OR_BAIL(hipMemset(h->d_pre_timeouts, 0, sizeof(unsigned)));
     TRY_OR_BAIL(hipMemcpy(h->d_window, p.window.data(), p.window.size() * 4, hipMemcpyHostToDevice));
     TRY_OR_BAIL(hipMemcpy(h->d_tw, p.tw.data(), p.tw.size() * 4, hipMemcpyHostToDevice));
     if (p.prune.enabled) {
-        TRY_OR_BAIL(dalloc(&h->d_prune_t1, p.prune_t1.size()));
+        TRY_OR_BAIL(dalloc(h->d_prune_t1, p.prune_t1.size()));
         TRY_OR_BAIL(hipMemcpy(h->d_prune_t1, p.prune_t1.data(), p.prune_t1.size() * 4, hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(&h->d_prune_t2, p.prune_t2.size()));
+        TRY_OR_BAIL(dalloc(h->d_prune_t2, p.prune_t2.size()));
         TRY_OR_BAIL(hipMemcpy(h->d_prune_t2, p.prune_t2.data(), p.prune_t2.size() * 4, hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(&h->d_prune_rank, p.prune_chan_rank.size()));
+        TRY_OR_BAIL(dalloc(h->d_prune_rank, p.prune_chan_rank.size()));
         TRY_OR_BAIL(hipMemcpy(h->d_prune_rank, p.prune_chan_rank.data(), p.prune_chan_rank.size() * 4, hipMemcpyHostToDevice));
     }
     if (p.l64.enabled) {
-        TRY_OR_BAIL(dalloc(&h->d_l64_chan, p.l64_chan.size()));
+        TRY_OR_BAIL(dalloc(h->d_l64_chan, p.l64_chan.size()));
         TRY_OR_BAIL(hipMemcpy(h->d_l64_chan, p.l64_chan.data(), p.l64_chan.size() * sizeof(L64Chan), hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(&h->d_l64_chan_full, p.l64_chan_full.size()));
+        TRY_OR_BAIL(dalloc(h->d_l64_chan_full, p.l64_chan_full.size()));
         TRY_OR_BAIL(hipMemcpy(h->d_l64_chan_full, p.l64_chan_full.data(), p.l64_chan_full.size() * sizeof(L64Chan), hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(&h->d_l64_tickets, mi::kL64Tickets));
+        TRY_OR_BAIL(dalloc(h->d_l64_tickets, mi::kL64Tickets));
         TRY_OR_BAIL(hipMemset(h->d_l64_tickets, 0, mi::kL64Tickets * sizeof(unsigned)));
     }
     TRY_OR_BAIL(hipMemcpy(h->d_levels, p.levels.data(), 256 * 4, hipMemcpyHostToDevice));
@@ -1236,7 +1165,7 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
         if (tp_ch[static_cast<size_t>(c)] && (p.cp[static_cast<size_t>(c)].using_manual_level || !(p.cp[static_cast<size_t>(c)].cap_factor >= 1.0f)))
             h->core_split_ok = false;  // (the chain wave's operand assumes cap >= noise floor in a burst)
     if (p.any_afc)
-        TRY_OR_BAIL(dalloc(&h->d_afc_spec, static_cast<size_t>(nstreams) * p.fft_size));
+        TRY_OR_BAIL(dalloc(h->d_afc_spec, static_cast<size_t>(nstreams) * p.fft_size));
     if (h->tp_eligible) {
         h->tp_max_blk = max_steps / 16;
         // segment length of the time-parallel path: short segments where rows are few (the parallelism has to come from time),
@@ -1249,10 +1178,10 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
         std::vector<int> tp_list, ser_list;  // handle rows (stream * nch + channel) of either kind, in row order
         for (size_t i = 0; i < rows; ++i)
             (tp_ch[i % static_cast<size_t>(nch)] ? tp_list : ser_list).push_back(static_cast<int>(i));
-        TRY_OR_BAIL(dalloc(&h->d_rows, rows));
+        TRY_OR_BAIL(dalloc(h->d_rows, rows));
         TRY_OR_BAIL(hipMemcpy(h->d_rows, tp_list.data(), tp_list.size() * sizeof(int), hipMemcpyHostToDevice));
         if (!ser_list.empty()) {
-            TRY_OR_BAIL(dalloc(&h->d_srows, ser_list.size()));
+            TRY_OR_BAIL(dalloc(h->d_srows, ser_list.size()));
             TRY_OR_BAIL(hipMemcpy(h->d_srows, ser_list.data(), ser_list.size() * sizeof(int), hipMemcpyHostToDevice));
             {
                 // HIP multiplexes its streams onto a few hardware queues and two streams that share one run their kernels one after the
@@ -1260,36 +1189,36 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
                 // call.  The lowest stream priority is a queue class of its own.
                 int lo_prio = 0, hi_prio = 0;
                 TRY_OR_BAIL(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-                TRY_OR_BAIL(hipStreamCreateWithPriority(&h->ser_stream, hipStreamNonBlocking, lo_prio));
+                TRY_OR_BAIL(hipStreamCreateWithPriority(h->ser_stream.put(), hipStreamNonBlocking, lo_prio));
             }
-            for (hipEvent_t& e : h->ev_cplx_free)
-                TRY_OR_BAIL(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (mi::Event& e : h->ev_cplx_free)
+                TRY_OR_BAIL(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
         }
         for (int q = 1; q < mi_demod::kSets; ++q) {
-            TRY_OR_BAIL(dalloc(&h->d_mag_set[q], rows * h->plane_stride));
-            TRY_OR_BAIL(hipMemset(h->d_mag_set[q], 0, rows * h->plane_stride * 4));
-            TRY_OR_BAIL(dalloc(&h->d_carry_set[q], rows * mi::kAgcExtra));
+            TRY_OR_BAIL(dalloc(h->set[q].mag, rows * h->plane_stride));
+            TRY_OR_BAIL(hipMemset(h->set[q].mag, 0, rows * h->plane_stride * 4));
+            TRY_OR_BAIL(dalloc(h->set[q].carry, rows * mi::kAgcExtra));
         }
         for (int q = 0; q < mi_demod::kSets; ++q) {
-            TRY_OR_BAIL(dalloc(&h->d_xmax[q], rows));
-            TRY_OR_BAIL(dalloc(&h->d_blk_fe[q], rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(&h->d_blk_fm[q], rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(&h->d_blk_x0[q], rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(&h->d_blk_xm[q], rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(&h->d_core[q], rows * (h->tp_max_seg + 1)));
+            TRY_OR_BAIL(dalloc(h->set[q].xmax, rows));
+            TRY_OR_BAIL(dalloc(h->set[q].blk_fe, rows * h->tp_max_blk));
+            TRY_OR_BAIL(dalloc(h->set[q].blk_fm, rows * h->tp_max_blk));
+            TRY_OR_BAIL(dalloc(h->set[q].blk_x0, rows * h->tp_max_blk));
+            TRY_OR_BAIL(dalloc(h->set[q].blk_xm, rows * h->tp_max_blk));
+            TRY_OR_BAIL(dalloc(h->set[q].core, rows * (h->tp_max_seg + 1)));
         }
         for (int q = 0; q < mi_demod::kSets; ++q)
-            TRY_OR_BAIL(dalloc(&h->d_rec[q], static_cast<size_t>(mi::TP_NREC) * rows * h->tp_max_seg));
-        TRY_OR_BAIL(dalloc(&h->d_tstart, rows * h->tp_max_seg * 8));
-        TRY_OR_BAIL(dalloc(&h->d_need, rows * h->tp_max_seg));
-        TRY_OR_BAIL(dalloc(&h->d_redo, rows * h->tp_max_seg + 1));
-        TRY_OR_BAIL(dalloc(&h->d_fin, rows));
+            TRY_OR_BAIL(dalloc(h->set[q].rec, static_cast<size_t>(mi::TP_NREC) * rows * h->tp_max_seg));
+        TRY_OR_BAIL(dalloc(h->d_tstart, rows * h->tp_max_seg * 8));
+        TRY_OR_BAIL(dalloc(h->d_need, rows * h->tp_max_seg));
+        TRY_OR_BAIL(dalloc(h->d_redo, rows * h->tp_max_seg + 1));
+        TRY_OR_BAIL(dalloc(h->d_fin, rows));
         TRY_OR_BAIL(hipMemset(h->d_fin, 0, rows * sizeof(mi::TpFinal)));
-        TRY_OR_BAIL(dalloc(&h->d_core_carry, rows));
-        TRY_OR_BAIL(dalloc(&h->d_full0, rows));
-        TRY_OR_BAIL(dalloc(&h->d_fullbound, rows));
+        TRY_OR_BAIL(dalloc(h->d_core_carry, rows));
+        TRY_OR_BAIL(dalloc(h->d_full0, rows));
+        TRY_OR_BAIL(dalloc(h->d_fullbound, rows));
         TRY_OR_BAIL(hipMemset(h->d_fullbound, 0, rows * sizeof(float)));
-        TRY_OR_BAIL(dalloc(&h->d_diag, rows * 8));
+        TRY_OR_BAIL(dalloc(h->d_diag, rows * 8));
         TRY_OR_BAIL(hipMemset(h->d_diag, 0, rows * 8 * sizeof(int)));
     }
     TRY_OR_BAIL(mi::launch_init_state(h->d_state, h->d_carry, h->d_ring, h->d_ctcss_q, h->d_cp, nstreams, nch, p.n_ctcss_rows, h->own_stream));
@@ -1315,8 +1244,8 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
     }
     // The runtime gives a stream its hardware queue (and a copy engine its first transfer) when the stream is first used: a few
     // milliseconds each.  One small operation on every stream of the handle now, so that the first batch does not pay for them.
-    unsigned* d_warm = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_warm), 256));
+    mi::DevBuf<unsigned char> d_warm;
+    HIP_TRY(dalloc(d_warm, 256));
     std::vector<hipStream_t> streams = {h->own_stream, h->aux_stream, h->front_stream, h->copy_stream, h->down_stream};
     for (hipStream_t ss : h->seg_stream)
         streams.push_back(ss);
@@ -1334,7 +1263,6 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
     for (hipStream_t st : streams)
         if (st && e == hipSuccess)
             e = hipStreamSynchronize(st);
-    (void)hipFree(d_warm);
     HIP_TRY(e);
     // ... and one rehearsal of the call itself (the first dispatch of a kernel on a queue sets up its scratch and kernel-argument
     // memory: 7 ms on the first batch otherwise).  The handle's state is saved before and restored after: a prepared handle is
@@ -1350,27 +1278,23 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
         const size_t need = mi_demod_bytes_needed(h, nb);
         const size_t stride = (need + 255) & ~static_cast<size_t>(255);
         const size_t nsteps = static_cast<size_t>(nb) * mi::kWaveBatch, rows = static_cast<size_t>(h->rows);
-        unsigned char* d_iq = nullptr;
-        float *d_wo = nullptr, *d_iqo = nullptr;
-        char* d_axc = nullptr;
-        e = hipMalloc(reinterpret_cast<void**>(&d_iq), stride * h->nstreams);
+        mi::DevBuf<unsigned char> d_iq;
+        mi::DevBuf<float> d_wo, d_iqo;
+        mi::DevBuf<char> d_axc;
+        e = dalloc(d_iq, stride * h->nstreams);
         if (e == hipSuccess)
             e = hipMemset(d_iq, 0x80, stride * h->nstreams);
         if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&d_wo), rows * nsteps * 4);
+            e = dalloc(d_wo, rows * nsteps);
         if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&d_iqo), rows * nsteps * 8);
+            e = dalloc(d_iqo, rows * nsteps * 2);
         if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&d_axc), rows * static_cast<size_t>(nb));
+            e = dalloc(d_axc, rows * static_cast<size_t>(nb));
         if (e == hipSuccess) {
             rc = mi_demod_process_device(h, d_iq, stride, nb, d_wo, d_iqo, d_axc, h->own_stream);
             if (rc == MI_OK)
                 e = hipDeviceSynchronize();
         }
-        void* tmp[] = {d_iq, d_wo, d_iqo, d_axc};
-        for (void* q : tmp)
-            if (q)
-                (void)hipFree(q);
         if (rc == MI_OK && e == hipSuccess)
             rc = mi_demod_set_state(h, saved.data(), saved.size());
         else if (rc == MI_OK)
@@ -1443,45 +1367,32 @@ int slot_prepare(mi_demod* h, int k) {
     const size_t max_fft = max_steps + mi::kAgcExtra;
     const size_t stride = ((max_fft - 1) * h->plan.hop_bytes + 2 * static_cast<size_t>(h->plan.bytes_per_sample) * h->plan.fft_size + 255) & ~static_cast<size_t>(255);
     const size_t out_bytes = rows * (max_steps + mi::kAgcExtra) * 4 + rows * max_steps * 8 + rows * static_cast<size_t>(h->max_batches) + rows * sizeof(mi_channel_stats) + 64;
-    hipError_t e = dalloc(&tmp.d_iq, stride * h->nstreams);
+    hipError_t e = dalloc(tmp.d_iq, stride * h->nstreams);
     if (e == hipSuccess)
-        e = dalloc(&tmp.d_wout, rows * (max_steps + mi::kAgcExtra));
+        e = dalloc(tmp.d_wout, rows * (max_steps + mi::kAgcExtra));
     if (e == hipSuccess)
-        e = dalloc(&tmp.d_iqout, rows * max_steps);
+        e = dalloc(tmp.d_iqout, rows * max_steps);
     if (e == hipSuccess)
-        e = dalloc(&tmp.d_axc, rows * static_cast<size_t>(h->max_batches));
+        e = dalloc(tmp.d_axc, rows * static_cast<size_t>(h->max_batches));
     if (e == hipSuccess)
-        e = dalloc(&tmp.d_stats, rows);
+        e = dalloc(tmp.d_stats, rows);
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void**>(&tmp.h_in), stride * h->nstreams, hipHostMallocDefault);
+        e = hipHostMalloc(reinterpret_cast<void**>(tmp.h_in.put()), stride * h->nstreams, hipHostMallocDefault);
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void**>(&tmp.h_out), out_bytes, hipHostMallocDefault);
+        e = hipHostMalloc(reinterpret_cast<void**>(tmp.h_out.put()), out_bytes, hipHostMallocDefault);
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&tmp.up_done, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(tmp.up_done.put(), hipEventDisableTiming);
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&tmp.done, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(tmp.done.put(), hipEventDisableTiming);
     if (e == hipSuccess && !h->copy_stream)
-        e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking);
+        e = hipStreamCreateWithFlags(h->copy_stream.put(), hipStreamNonBlocking);
     if (e == hipSuccess && !h->down_stream)
-        e = hipStreamCreateWithFlags(&h->down_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        void* dev[] = {tmp.d_iq, tmp.d_wout, tmp.d_iqout, tmp.d_axc, tmp.d_stats};
-        for (void* p : dev)
-            if (p)
-                (void)hipFree(p);
-        if (tmp.h_in)
-            (void)hipHostFree(tmp.h_in);
-        if (tmp.h_out)
-            (void)hipHostFree(tmp.h_out);
-        if (tmp.up_done)
-            (void)hipEventDestroy(tmp.up_done);
-        if (tmp.done)
-            (void)hipEventDestroy(tmp.done);
-        return hip_fail(e, "staging for the host-buffer entry");
-    }
+        e = hipStreamCreateWithFlags(h->down_stream.put(), hipStreamNonBlocking);
+    if (e != hipSuccess)
+        return hip_fail(e, "staging for the host-buffer entry");  // (tmp releases what it got)
     h->iq_stride = stride;
     h->h_out_bytes = out_bytes;
-    h->slot[k] = tmp;
+    h->slot[k] = std::move(tmp);
     h->slots_ready[k] = true;
     return MI_OK;
 }
@@ -1702,18 +1613,18 @@ int mi_demod_process_planes(mi_demod* h, const float* mag, const float* cplx, in
     HIP_TRY(hipSetDevice(h->gpu));
     const size_t rows = static_cast<size_t>(h->rows), count = static_cast<size_t>(n_fft_for(h, nbatches));
     const size_t nsteps = static_cast<size_t>(nbatches) * mi::kWaveBatch, wlen = nsteps + mi::kAgcExtra;
-    float *d_m = nullptr, *d_wo = nullptr;
-    float2 *d_z = nullptr, *d_io = nullptr;
-    char* d_ax = nullptr;
-    hipError_t e = dalloc(&d_m, rows * count);
+    mi::DevBuf<float> d_m, d_wo;
+    mi::DevBuf<float2> d_z, d_io;
+    mi::DevBuf<char> d_ax;
+    hipError_t e = dalloc(d_m, rows * count);
     if (e == hipSuccess && zrows)
-        e = dalloc(&d_z, zrows * count);
+        e = dalloc(d_z, zrows * count);
     if (e == hipSuccess)
-        e = dalloc(&d_wo, rows * wlen);
+        e = dalloc(d_wo, rows * wlen);
     if (e == hipSuccess && iq_out)
-        e = dalloc(&d_io, rows * nsteps);
+        e = dalloc(d_io, rows * nsteps);
     if (e == hipSuccess)
-        e = dalloc(&d_ax, rows * static_cast<size_t>(nbatches));
+        e = dalloc(d_ax, rows * static_cast<size_t>(nbatches));
     if (e == hipSuccess)
         e = hipMemcpy(d_m, mag, rows * count * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && zrows)
@@ -1722,7 +1633,7 @@ int mi_demod_process_planes(mi_demod* h, const float* mag, const float* cplx, in
     if (e == hipSuccess) {
         h->inject_mag = d_m, h->inject_cplx = d_z, h->inject_count = count;
         // (the IQ pointer is never read: stage 1 is the copy above; the audio goes to [row][wlen] like the host entry's)
-        rc = enqueue(h, reinterpret_cast<const unsigned char*>(d_m), 0, 0, nbatches, d_wo, wlen, d_io, nsteps, d_ax, h->own_stream);
+        rc = enqueue(h, reinterpret_cast<const unsigned char*>(d_m.get()), 0, 0, nbatches, d_wo, wlen, d_io, nsteps, d_ax, h->own_stream);
         h->inject_mag = nullptr, h->inject_cplx = nullptr, h->inject_count = 0;
         if (rc == MI_OK)
             e = hipDeviceSynchronize();
@@ -1737,10 +1648,6 @@ int mi_demod_process_planes(mi_demod* h, const float* mag, const float* cplx, in
         e = hipMemcpy(axc, d_ax, rows * static_cast<size_t>(nbatches), hipMemcpyDeviceToHost);
     if (rc == MI_OK && e == hipSuccess && stats)
         e = hipMemcpy(stats, h->d_stats, rows * sizeof(mi_channel_stats), hipMemcpyDeviceToHost);
-    void* tmp[] = {d_m, d_z, d_wo, d_io, d_ax};
-    for (void* q : tmp)
-        if (q)
-            (void)hipFree(q);
     if (rc != MI_OK)
         return rc;
     HIP_TRY(e);
@@ -1882,10 +1789,10 @@ int mi_demod_tp_debug(mi_demod* h, int row, float* core4, int max_entries, int* 
     HIP_TRY(hipSetDevice(h->gpu));
     HIP_TRY(hipDeviceSynchronize());
     if (nseg)
-        *nseg = static_cast<int>(h->last_nseg[h->cur]);
+        *nseg = static_cast<int>(h->set[h->cur].nseg);
     if (core4) {
-        const size_t n = std::min<size_t>(static_cast<size_t>(max_entries), h->last_nseg[h->cur] + 1);
-        HIP_TRY(hipMemcpy(core4, h->d_core[h->cur] + static_cast<size_t>(row) * (h->last_nseg[h->cur] + 1), n * sizeof(mi::TpCore), hipMemcpyDeviceToHost));
+        const size_t n = std::min<size_t>(static_cast<size_t>(max_entries), h->set[h->cur].nseg + 1);
+        HIP_TRY(hipMemcpy(core4, h->set[h->cur].core + static_cast<size_t>(row) * (h->set[h->cur].nseg + 1), n * sizeof(mi::TpCore), hipMemcpyDeviceToHost));
     }
     if (diag4) {  // [0..3] scan rounds, [4..7] core-chain blocks: in accepted runs, single O(1), stepped, failed hypotheses
         HIP_TRY(hipMemcpy(diag4, h->d_diag + static_cast<size_t>(row) * 4, 4 * sizeof(int), hipMemcpyDeviceToHost));
@@ -1917,28 +1824,27 @@ static int kernel_time_of(mi_demod* h, int age, int index, const char** name, fl
     if (!h || index < 0 || age < 0 || age >= mi_demod::kSets)
         return fail(MI_ERR_INVALID, "bad argument");
     const int q = (h->cur + mi_demod::kSets - age) % mi_demod::kSets;
-    if (!h->set_seq[q] || h->set_seq[q] + static_cast<uint64_t>(age) != h->set_seq[h->cur])
+    if (!h->set[q].seq || h->set[q].seq + static_cast<uint64_t>(age) != h->set[h->cur].seq)
         return fail(MI_ERR_INVALID, "that call has not been timed (or its events were reused)");
     HIP_TRY(hipSetDevice(h->gpu));
-    hipEvent_t* evq = h->ev[q];
+    const mi::Event* evq = h->set[q].ev;
     HIP_TRY(hipEventSynchronize(evq[2]));
     float t = 0.f;
     int n = 1;
     const char* nm = nullptr;
-    if (h->set_path[q] == 0 || h->set_path[q] == 2) {
+    if (h->set[q].path == 0 || h->set[q].path == 2) {
         if (index > 1)
             return fail(MI_ERR_INVALID, "kernel index out of range");
         nm = index == 0 ? "k_channelize" : "k_demod";
-        if (h->set_path[q] == 2 && index == 1)  // pipelined serial call: k_demod starts at its own event on the caller's stream
+        if (h->set[q].path == 2 && index == 1)  // pipelined serial call: k_demod starts at its own event on the caller's stream
             HIP_TRY(hipEventElapsedTime(&t, evq[3], evq[2]));
         else
             HIP_TRY(hipEventElapsedTime(&t, evq[index], evq[index + 1]));
     } else {
-        // per chunk events: 0 stage1 begin, 1 stage1 end, 2 k_tp_full end (front stream), 3 core begin, 4 core end (aux stream),
-        // 5 seg begin, 12 seg end, 6 all segment launches of the chunk done (segment stream), 10 scan#0 begin, 7 scan#0 end, 8 fix#0 + redo#0 end, 9 finish end (caller's stream), 11 k_tp_full begin
+        // (the chunk events: see mi_demod::CallSet::chunk_ev)
         static const char* const names[] = {"k_channelize", "k_tp_full", "k_tp_core", "k_tp_seg", "k_tp_scan#0", "k_tp_fix#0", "k_tp_rest"};
         static const int from[] = {0, 11, 3, 5, 10, 7, 8}, to[] = {1, 2, 4, 12, 7, 8, 9};
-        if (index == 7 && h->set_mixed[q]) {  // a mixed plan: the serial kernel of the other rows, on its own stream
+        if (index == 7 && h->set[q].mixed) {  // a mixed plan: the serial kernel of the other rows, on its own stream
             HIP_TRY(hipEventElapsedTime(&t, evq[3], evq[4]));
             if (name)
                 *name = "k_demod";
@@ -1951,8 +1857,8 @@ static int kernel_time_of(mi_demod* h, int age, int index, const char** name, fl
         if (index > 6)
             return fail(MI_ERR_INVALID, "kernel index out of range");
         nm = names[index];
-        n = h->tp_chunks[q];
-        const std::vector<hipEvent_t>& cev = h->chunk_ev[q];
+        n = h->set[q].chunks;
+        const std::vector<mi::Event>& cev = h->set[q].chunk_ev;
         for (int i = 0; i < n; ++i) {
             float d = 0.f;
             HIP_TRY(hipEventElapsedTime(&d, cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + from[index]],
@@ -1982,22 +1888,22 @@ int mi_demod_event_ms(mi_demod* h, int ref_age, int age, int chunk, int event, f
         return fail(MI_ERR_INVALID, "bad argument");
     const int q = (h->cur + mi_demod::kSets - age) % mi_demod::kSets, qr = (h->cur + mi_demod::kSets - ref_age) % mi_demod::kSets;
     for (const int s : {q, qr})
-        if (!h->set_seq[s] || h->set_path[s] != 1)
+        if (!h->set[s].seq || h->set[s].path != 1)
             return fail(MI_ERR_INVALID, "that call was not a time-parallel one (or its events were reused)");
-    if (h->set_seq[q] + static_cast<uint64_t>(age) != h->set_seq[h->cur] || h->set_seq[qr] + static_cast<uint64_t>(ref_age) != h->set_seq[h->cur] ||
-        chunk >= h->tp_chunks[q])
+    if (h->set[q].seq + static_cast<uint64_t>(age) != h->set[h->cur].seq || h->set[qr].seq + static_cast<uint64_t>(ref_age) != h->set[h->cur].seq ||
+        chunk >= h->set[q].chunks)
         return fail(MI_ERR_INVALID, "no such call or chunk");
     HIP_TRY(hipSetDevice(h->gpu));
-    HIP_TRY(hipEventSynchronize(h->ev[q][2]));
-    HIP_TRY(hipEventElapsedTime(ms, h->chunk_ev[qr][3], h->chunk_ev[q][static_cast<size_t>(chunk) * mi_demod::kEvPerChunk + event]));
+    HIP_TRY(hipEventSynchronize(h->set[q].ev[2]));
+    HIP_TRY(hipEventElapsedTime(ms, h->set[qr].chunk_ev[3], h->set[q].chunk_ev[static_cast<size_t>(chunk) * mi_demod::kEvPerChunk + event]));
     return MI_OK;
 }
 
 int mi_demod_last_kernel_ms(mi_demod* h, float* channelize_ms, float* demod_ms) {
-    if (!h || !h->set_seq[h->cur])
+    if (!h || !h->set[h->cur].seq)
         return fail(MI_ERR_INVALID, "no call has been timed yet");
     HIP_TRY(hipSetDevice(h->gpu));
-    hipEvent_t* evq = h->ev[h->cur];
+    const mi::Event* evq = h->set[h->cur].ev;
     HIP_TRY(hipEventSynchronize(evq[2]));
     float a = 0.f, b = 0.f;
     if (h->last_path == 0) {
@@ -2227,24 +2133,19 @@ int mi_iqgen_device(const mi_iqgen_cfg* cfg, uint32_t first_stream_id, uint32_t 
         return fail(MI_ERR_INVALID, "iqgen output must be 16-byte aligned");
     mi::IqGenDerived g;
     mi::iqgen_derive(*cfg, g);
-    mi::IqGenDerived* d_cfg = nullptr;
-    int16_t* d_tab = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_cfg), sizeof(g)));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_tab), 1024 * sizeof(int16_t));
-    if (e != hipSuccess) {
-        (void)hipFree(d_cfg);
-        return hip_fail(e, "hipMalloc");
-    }
+    mi::DevBuf<mi::IqGenDerived> d_cfg;
+    mi::DevBuf<int16_t> d_tab;
+    HIP_TRY(dalloc(d_cfg, 1));
+    HIP_TRY(dalloc(d_tab, 1024));
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     int rc = MI_OK;
+    hipError_t e;
     if ((e = hipMemcpy(d_cfg, &g, sizeof(g), hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipMemcpy(d_tab, mi::iqgen_sine_table(), 1024 * sizeof(int16_t), hipMemcpyHostToDevice)) != hipSuccess ||
         (e = mi::launch_iqgen(d_cfg, d_tab, first_stream_id, nstreams, stream_stride_bytes, first, count, static_cast<unsigned char*>(d_out), s)) !=
             hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess)
         rc = hip_fail(e, "mi_iqgen_device");
-    (void)hipFree(d_cfg);
-    (void)hipFree(d_tab);
     return rc;
 }
 

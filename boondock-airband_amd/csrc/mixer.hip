@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
+#include "hip_own.hpp"
 #include "plan.hpp"
 
 namespace mi {
@@ -25,7 +26,7 @@ struct mi_mixer {
     int gpu = 0;
     int n = 0;
     int stereo = 0;
-    MixIn* d_in = nullptr;
+    mi::DevBuf<MixIn> d_in;
 };
 
 namespace {
@@ -96,10 +97,8 @@ int mi_mixer_create(const mi_mix_input* inputs, int ninputs, int gpu, mi_mixer**
     m->gpu = gpu;
     m->n = ninputs;
     m->stereo = stereo;
-    if (hipSetDevice(gpu) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&m->d_in), v.size() * sizeof(MixIn)) != hipSuccess ||
+    if (hipSetDevice(gpu) != hipSuccess || dalloc(m->d_in, v.size()) != hipSuccess ||
         hipMemcpy(m->d_in, v.data(), v.size() * sizeof(MixIn), hipMemcpyHostToDevice) != hipSuccess) {
-        if (m->d_in)
-            (void)hipFree(m->d_in);
         delete m;
         return mfail(MI_ERR_HIP, "mixer: device allocation failed");
     }
@@ -111,8 +110,6 @@ void mi_mixer_destroy(mi_mixer* m) {
     if (!m)
         return;
     (void)hipSetDevice(m->gpu);
-    if (m->d_in)
-        (void)hipFree(m->d_in);
     delete m;
 }
 
@@ -132,7 +129,7 @@ int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stri
     if (hipSetDevice(m->gpu) != hipSuccess)
         return mfail(MI_ERR_HIP, "hipSetDevice failed");
     const size_t total = static_cast<size_t>(nbatches) * (mi::kWaveBatch / 4);
-    hipLaunchKernelGGL(k_mix, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), m->d_in, m->n,
+    hipLaunchKernelGGL(k_mix, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), m->d_in.get(), m->n,
                        m->stereo, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_left, d_right, d_axc_out);
     if (hipGetLastError() != hipSuccess)
         return mfail(MI_ERR_HIP, "mixer kernel launch failed");

@@ -475,3 +475,76 @@ def test_create_destroy_returns_the_handle_s_device_memory(pkg):
     assert max(f for f, _ in seen) >= 6 * nstreams * len(chans) * 64 * WAVE_BATCH * 4, "six sets of magnitude planes at least"
     assert lost <= footprint
     assert lost <= CHUNK, f"{lost} bytes of device memory lost over {rounds - 1} create / destroy pairs (every loop: {seen})"
+
+
+def test_create_destroy_returns_what_a_mixed_handle_took_while_it_ran(pkg, monkeypatch):
+    """The same measurement and the same bound as above -- at most one 2 MiB piece lost over the pairs after the first -- on handles
+    that have run, so that what a handle creates on its way is in play as well.  Each is a mixed plan (config3 channels x 16 streams,
+    max_batches = 64: 512 rows, 256 of them plain AM) and does, before it is destroyed:
+      - three 1-batch device calls with MI_OPT_EARLY_INPUT on a stream of the caller's: the first of a handle takes the plain serial
+        branch, the two after it overlap (the second complex plane set; with 512 rows the CU-masked pair of streams and their events
+        where the device grants them);
+      - one 64-batch call, which takes the mixed split (the chunk events of its scratch set, the serial kernel's stream, with
+        MI_OPT_RESERVE_CUS the CU-masked twins of the front and segment streams where the device grants them);
+      - one submit / wait pair (a staging slot with its pinned buffers and events, the upload and download streams).
+    The smallest per-row buffer, the audio lookahead of one scratch set (rows x AGC_EXTRA floats), forgotten once per destroy, costs
+    nearly five pieces over the 49 further pairs, as the docstring above argues; a slot's or a plane set's buffers are thousands of
+    times that.  The input is the constant byte 0x80 (mi_demod_prepare's rehearsal input): the paths do not depend on the signal."""
+    import torch
+    monkeypatch.delenv("MI_AIRBAND_TP", raising=False)
+    monkeypatch.delenv("MI_AIRBAND_MIXED", raising=False)
+    centre, chans = pkg.config3_channels()
+    dev = pkg.device_cfg(centerfreq=centre, fft_size_log=11)
+    rounds, nstreams, attempts, long_call = 50, 16, 3, 64
+    nch = len(chans)
+    nplain = sum(fuzz_plans.is_plain_am(pkg, c) for c in chans)
+    assert 0 < nplain < nch, "a mixed plan"
+    smallest = nstreams * nch * AGC_EXTRA * 4
+    assert (rounds - 1) * smallest >= 4 * CHUNK, "a forgotten buffer has to show"
+    nbytes = (bytes_for_batches(dev, long_call) + 255) // 256 * 256
+    d_iq = torch.full((nstreams, nbytes), 0x80, dtype=torch.uint8, device="cuda")
+    wo = torch.empty((nstreams, nch, long_call * WAVE_BATCH), dtype=torch.float32, device="cuda")
+    ax = torch.empty((nstreams, nch, long_call), dtype=torch.uint8, device="cuda")
+    h_iq = np.full(bytes_for_batches(dev, 1), 0x80, np.uint8)
+    side = torch.cuda.Stream()
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    def run(d):
+        d.set_option(pkg.OPT_EARLY_INPUT, 1)
+        d.set_option(pkg.OPT_RESERVE_CUS, 32)
+        for _ in range(3):
+            d.process_device(d_iq.data_ptr(), nbytes, 1, wo.data_ptr(), ax.data_ptr(), hip_stream=side.cuda_stream)
+        serial = [_kernel_names(d, age) for age in range(3)]
+        d.process_device(d_iq.data_ptr(), nbytes, long_call, wo.data_ptr(), ax.data_ptr(), hip_stream=side.cuda_stream)
+        split, path = _kernel_names(d, 0), d.last_path()
+        d.submit([h_iq] * nstreams, 1)
+        d.wait()
+        assert serial == [SERIAL_KERNELS] * 3, serial
+        assert path[0] == 1 and "k_tp_core" in split and "k_demod" in split, f"the {long_call}-batch call splits: {path}, {split}"
+
+    def loop():
+        footprint = base = None
+        for i in range(rounds):
+            before = free_bytes()
+            d = pkg.Demod(dev, chans, nstreams=nstreams, max_batches=long_call)
+            run(d)
+            if i == 0:
+                footprint = before - free_bytes()
+            d.close()
+            if i == 0:
+                base = free_bytes()  # (after the first pair: whatever the runtime keeps for itself once is taken by now)
+        return footprint, base - free_bytes()
+
+    seen = []
+    for _ in range(attempts):
+        seen.append(loop())
+        print(f"mixed handle, create / run / destroy x {rounds}: one handle takes {seen[-1][0]} bytes, the {rounds - 1} pairs after the first lost {seen[-1][1]} bytes")
+        if seen[-1][1] <= CHUNK:
+            break
+    footprint, lost = min(seen, key=lambda fl: fl[1])
+    assert max(f for f, _ in seen) >= 6 * nstreams * nch * long_call * WAVE_BATCH * 4, "six sets of magnitude planes at least"
+    assert lost <= footprint
+    assert lost <= CHUNK, f"{lost} bytes of device memory lost over {rounds - 1} create / run / destroy pairs (every loop: {seen})"
