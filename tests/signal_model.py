@@ -71,14 +71,30 @@ def samples_from_bytes(raw, sfmt, fullscale=127.5):
     return v[0::2] + 1j * v[1::2]
 
 
+def dft_basis(n, bins):
+    """w[m] e^{-2 pi j b m / N} for every bin b: [N][len(bins)]."""
+    m = np.arange(n, dtype=np.float64)
+    return np.stack([window(n) * np.exp(-2j * np.pi * ((int(b) * m) % n) / n) for b in bins], axis=1)
+
+
+def channelize_windows(x, sample_rate, n, bins, windows):
+    """channelize() for a list of windows that need not be consecutive: X[c][k] of window windows[k]."""
+    hop = hop_of(sample_rate)
+    x = np.asarray(x, dtype=np.complex128)
+    windows = np.asarray(windows, dtype=np.int64)
+    if windows.min() < 0 or windows.max() * hop + n > x.size:
+        raise ValueError("windows outside the capture")
+    frames = x[windows[:, None] * hop + np.arange(n)[None, :]]
+    return (frames @ dft_basis(n, bins)).T
+
+
 def channelize(x, sample_rate, n, bins, first, count, chunk=1024):
     """X[c][i] = sum_m x[(first + i) hop + m] w[m] e^{-2 pi j bins[c] m / N}: one DFT bin per channel as a dot product."""
     hop = hop_of(sample_rate)
     x = np.asarray(x, dtype=np.complex128)
     if first < 0 or (first + count - 1) * hop + n > x.size:
         raise ValueError("windows outside the capture")
-    m = np.arange(n, dtype=np.float64)
-    basis = np.stack([window(n) * np.exp(-2j * np.pi * ((int(b) * m) % n) / n) for b in bins], axis=1)  # [N][nch]
+    basis = dft_basis(n, bins)
     out = np.zeros((len(bins), count), np.complex128)
     for c0 in range(0, count, chunk):
         c1 = min(count, c0 + chunk)
