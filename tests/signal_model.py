@@ -9,8 +9,13 @@ backend's own output.
 Time axes (all at WAVE_RATE = 16 kHz):
   window w     the channelizer's w-th FFT: input samples [w*hop, w*hop + N), hop = round(rate / 16000)
   audio g      AM:  (|X_{g-100}| - agc_g) / (1.5 agc_g), agc running over |X_g|   (the AGC looks 100 windows ahead)
-               NFM: the discriminator of windows g-100 and g-101
-  raw I/Q s    the derotated window s; the audio sample that belongs to it is g = s + 100
+               AM on the raw-I/Q path (has_iq_outputs, or the bandwidth key present): step g derotates (and low-passes)
+                    window g-100 into z_{g-100} and stores its magnitude where |X_g| stood, so the sequence the AGC and
+                    the numerator read is m[g] = |z_{g-100}|: (m[g-100] - agc_g) / (1.5 agc_g) with agc running over m[g],
+                    i.e. the numerator is window g-200 and the average looks at window g-100 -- the plain channel's audio
+                    100 samples later, from filtered magnitudes when a low-pass is configured
+               NFM: the discriminator of windows g-100 and g-101 (of the low-passed samples when bandwidth > 0)
+  raw I/Q s    the derotated (bandwidth > 0: and low-passed) window s; the audio sample that belongs to it is g = s + 100
 
 Two modes for everything that touches an angle:
   exact         true sin / cos / atan2, derotation by the true phase advance 2 pi f hop / rate per window
@@ -206,6 +211,45 @@ def discriminator(z, mode, quadri=False):
     return fast_atan2(c.imag, c.real) / np.pi
 
 
+# ------------------------------------------------------------------ low-pass (bandwidth > 0)
+
+BESSEL2_POLE = complex(-1.10160133059, 0.636009824757)  # second-order Bessel, -3 dB at unit frequency
+
+
+def lowpass_coeffs(freq, rate=WAVE_RATE):
+    """(gain, c0, c1) of the second-order Bessel low-pass at cut-off `freq`: pre-warped alpha = tan(pi f / rate) / pi, poles
+    blt(2 pi alpha (-1.1016 +- 0.6360j)) with blt(p) = (2 + p) / (2 - p), a double zero at -1; gain = |top(1) / bot(1)| makes
+    the DC gain one, c_i = -bot[i] / bot[2]:  y[n] = (x[n-2] + x[n]) + 2 x[n-1] + c0 y[n-2] + c1 y[n-1], x = input / gain."""
+    alpha = math.tan(math.pi * freq / rate) / math.pi
+    p = 2.0 * math.pi * alpha * BESSEL2_POLE
+    p0, p1 = (2.0 + p) / (2.0 - p), (2.0 + p.conjugate()) / (2.0 - p.conjugate())
+    bot = [(p0 * p1).real, -(p0 + p1).real, 1.0]  # (z - p0)(z - p1), coefficients of z^0, z^1, z^2
+    gain = abs(4.0 / (bot[0] + bot[1] + bot[2]))  # top(1) = (1 + 1)^2
+    return gain, -bot[0] / bot[2], -bot[1] / bot[2]
+
+
+def lowpass(z, freq, rate=WAVE_RATE):
+    """The filter over a complex128 sequence, from rest."""
+    gain, c0, c1 = lowpass_coeffs(freq, rate)
+    x = np.asarray(z, dtype=np.complex128) / gain
+    out = np.zeros(x.size, np.complex128)
+    x0 = x1 = y0 = y1 = 0j
+    for i in range(x.size):
+        x2 = complex(x[i])
+        y2 = (x0 + x2) + 2.0 * x1 + c0 * y0 + c1 * y1
+        x0, x1 = x1, x2
+        y0, y1 = y1, y2
+        out[i] = y2
+    return out
+
+
+def lowpass_gain(freq, at_hz, rate=WAVE_RATE):
+    """H(e^{jw}) = (1 + 2 z + z^2) / gain / (1 - c1 z - c0 z^2), z = e^{-jw}."""
+    gain, c0, c1 = lowpass_coeffs(freq, rate)
+    z = np.exp(-2j * np.pi * at_hz / rate)
+    return complex((1.0 + 2.0 * z + z * z) / gain / (1.0 - c1 * z - c0 * z * z))
+
+
 def alpha_for_tau(tau_us):
     return 0.0 if tau_us == 0 else math.exp(-1.0 / (WAVE_RATE * 1e-6 * tau_us))
 
@@ -256,15 +300,25 @@ def notch_gain(freq, at_hz, q=10.0):
 
 # ------------------------------------------------------------------ a channel over a span
 
+def bandwidth_of(chan):
+    return int(getattr(chan, "bandwidth", 0))
+
+
+def needs_raw_iq(chan):
+    """NFM, a raw-I/Q output, or the bandwidth key present (any value but the 0 that stands for "absent")."""
+    return chan.modulation == MOD_NFM or bool(chan.has_iq_outputs) or bandwidth_of(chan) != 0
+
+
 def model_channel(x, dev, chan, g0, g1, mode="as_specified", warmup=10000, phase0=None, X=None):
     """The model's output for audio samples g0 .. g1 of one channel.
 
     x: complex samples of the capture.  dev / chan: objects with the fields of the device and channel configuration.
-    warmup: windows before the span over which the recursions (averages, de-emphasis, notch) run in.
+    warmup: windows before the span over which the recursions (averages, de-emphasis, notch, low-pass) run in.
     phase0: as_specified only -- the 24-bit accumulator at raw-I/Q sample g0 - 100 (the model has no squelch, so it cannot
     know how often the accumulator stepped before the span).
-    Returns a dict: audio (after ampfactor / clamp), audio_lin (before), mag (|X| of windows g0-100 .. g1), iq (derotated
-    windows g0-100 .. g1-100, None for a plain AM channel), bin.
+    Returns a dict: audio (after ampfactor / clamp), audio_lin (before), mag (|X| of windows g0-100 .. g1), agc_mag (AM: every
+    magnitude the slow average took, warm-up included), iq (derotated and, with bandwidth > 0, low-passed windows g0-100 ..
+    g1-100; None for a channel that needs no raw I/Q), bin.
     """
     n = 1 << dev.fft_size_log
     b = bin_index(chan.freq, dev.centerfreq, dev.sample_rate, n)
@@ -272,11 +326,10 @@ def model_channel(x, dev, chan, g0, g1, mode="as_specified", warmup=10000, phase
     if X is None:
         X = channelize(x, dev.sample_rate, n, [b], w0, g1 - w0)[0]
     res = {"bin": b, "iq": None, "mag": np.abs(X[warmup:])}
-    if chan.modulation == MOD_AM:
+    if not needs_raw_iq(chan):
         lin, out = am_audio(np.abs(X), chan.ampfactor)
-        res["audio_lin"], res["audio"] = lin[warmup:], out[warmup:]
-        if not chan.has_iq_outputs:
-            return res
+        res["audio_lin"], res["audio"], res["agc_mag"] = lin[warmup:], out[warmup:], np.abs(X)
+        return res
     # raw I/Q: windows w0 .. g1 - 100
     Z = X[:g1 - AGC_EXTRA - w0]
     if mode == "as_specified":
@@ -286,8 +339,15 @@ def model_channel(x, dev, chan, g0, g1, mode="as_specified", warmup=10000, phase
         z = derotate(Z, chan.freq, dev.centerfreq, dev.sample_rate, mode, phase0=start)
     else:
         z = derotate(Z, chan.freq, dev.centerfreq, dev.sample_rate, mode, first_window=w0)
+    if bandwidth_of(chan) > 0:
+        z = lowpass(z, bandwidth_of(chan) / 2.0)
     res["iq"] = z[warmup:]
-    if chan.modulation == MOD_NFM:
+    if chan.modulation == MOD_AM:
+        # m[w + 100] = |z_w|: am_audio's k-th output is audio g = w0 + 200 + k (numerator z_{g-200}, average up to z_{g-100})
+        lin, out = am_audio(np.abs(z), chan.ampfactor)
+        # (agc_mag: the first 100 magnitudes only seed the average, and a low-pass starting from rest leaves zeros among them)
+        res["audio_lin"], res["audio"], res["agc_mag"] = lin[warmup - AGC_EXTRA:], out[warmup - AGC_EXTRA:], np.abs(z)[AGC_EXTRA:]
+    else:
         d = discriminator(z, mode, quadri=bool(dev.fm_quadri))  # d[i] belongs to window w0 + 1 + i, audio g = that + 100
         y = dc_block_deemphasis(d, alpha_of(dev, chan))
         if chan.notch_freq > 0:
@@ -310,6 +370,28 @@ def accumulator_at(X0, z0, freq, centerfreq, sample_rate, steps):
     cand = accumulator_candidates(freq, centerfreq, sample_rate, steps)
     dist = np.abs((cand - want + PHASE_ONE / 2) % PHASE_ONE - PHASE_ONE / 2)
     return int(cand[int(np.argmin(dist))])
+
+
+def accumulator_fit(X, z, freq, centerfreq, sample_rate, steps, lowpass_hz, settle=200, nearest=8):
+    """The same integer for a low-passed row, where the backend's raw-I/Q sample is no longer one window times (cos - j sin).
+    X: windows s - settle .. s + len(z); z: the backend's raw I/Q from sample s on (a few hundred).  Taken from the backend:
+    those samples, used only to choose among the multiples of the increment.  The filter is linear, so a constant offset of
+    the accumulator turns its whole output: the turn between z and the model's output at accumulator 0 names the wanted value;
+    the `nearest` candidates to it are run through the model (table derotation, low-pass from rest `settle` windows before s --
+    the filter's poles have a radius below 0.8) and the one with the smallest residual is returned, as the accumulator at s."""
+    X = np.asarray(X, dtype=np.complex128)
+    z = np.asarray(z, dtype=np.complex128)
+    inc = dm_dphi(freq, centerfreq, sample_rate) & (PHASE_ONE - 1)
+
+    def run(at_s):
+        start = (int(at_s) - settle * inc) % PHASE_ONE
+        return lowpass(derotate(X, freq, centerfreq, sample_rate, "as_specified", phase0=start), lowpass_hz)[settle:]
+
+    want = (-np.angle(np.vdot(run(0), z)) / (2.0 * np.pi)) % 1.0 * PHASE_ONE
+    cand = np.unique(accumulator_candidates(freq, centerfreq, sample_rate, steps))
+    dist = np.abs((cand - want + PHASE_ONE / 2) % PHASE_ONE - PHASE_ONE / 2)
+    best = [int(c) for c in cand[np.argsort(dist)[:nearest]]]
+    return min(best, key=lambda c: rms(run(c) - z))
 
 
 # ------------------------------------------------------------------ measuring
