@@ -101,7 +101,7 @@ class MixInput(C.Structure):  # mi_mix_input
 
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
-    "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_get_stats", "mi_demod_state_size",
+    "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
     "mi_demod_get_state", "mi_demod_set_state", "mi_demod_read_planes", "mi_demod_process_planes", "mi_demod_last_path", "mi_demod_last_stage1", "mi_demod_pre_wave_timeouts", "mi_demod_tp_debug", "mi_demod_kernel_time", "mi_demod_kernel_time_prev", "mi_demod_event_ms", "mi_demod_set_option", "mi_demod_last_kernel_ms", "mi_plan_create", "mi_plan_destroy", "mi_plan_fft_size",
     "mi_plan_window", "mi_plan_twiddles", "mi_plan_levels", "mi_plan_sincos_lut", "mi_plan_channel", "mi_plan_lane_fft", "mi_plan_ctcss_coeffs",
     "mi_iqgen_host", "mi_iqgen_device", "mi_mixer_create", "mi_mixer_destroy", "mi_mixer_is_stereo", "mi_mixer_process_device",
@@ -148,6 +148,8 @@ def lib():
         L.mi_demod_process.argtypes = [vp, C.POINTER(vp), C.c_int, vp, vp, vp, vp]
         L.mi_demod_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp]
         L.mi_demod_get_stats.argtypes = [vp, vp]
+        L.mi_demod_set_active_streams.argtypes = [vp, vp]
+        L.mi_demod_get_active_streams.argtypes = [vp, vp]
         L.mi_demod_state_size.argtypes = [vp]
         L.mi_demod_state_size.restype = sz
         L.mi_demod_get_state.argtypes = [vp, vp, sz]
@@ -293,11 +295,11 @@ class Demod:
         current position.  Returns (waveout[ns][nch][nb*2000+100], axc[ns][nch][nb], iq_out or None, stats or None)."""
         assert len(iq_streams) == self.nstreams
         need = self.bytes_needed(nbatches)
-        keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in iq_streams]
+        keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in iq_streams]  # (None: a stream that sits the call out)
         for a in keep:
-            if a.size < need:
+            if a is not None and a.size < need:
                 raise ValueError(f"stream shorter than bytes_needed ({a.size} < {need})")
-        ptrs = (C.c_void_p * self.nstreams)(*[a.ctypes.data for a in keep])
+        ptrs = (C.c_void_p * self.nstreams)(*[None if a is None else a.ctypes.data for a in keep])
         # the library completes whatever was submitted before it runs this call: those results are ready for wait()
         self._done = getattr(self, "_done", []) + getattr(self, "_tickets", [])
         self._tickets = []
@@ -316,8 +318,8 @@ class Demod:
         like process().  The numpy arrays of a ticket stay referenced until it has been waited for."""
         assert len(iq_streams) == self.nstreams
         need = self.bytes_needed(nbatches)
-        keep = [a if isinstance(a, PinnedBuffer) else np.ascontiguousarray(a, dtype=np.uint8) for a in iq_streams]
-        addr = [a.ptr if isinstance(a, PinnedBuffer) else a.ctypes.data for a in keep]
+        keep = [a if a is None or isinstance(a, PinnedBuffer) else np.ascontiguousarray(a, dtype=np.uint8) for a in iq_streams]
+        addr = [None if a is None else (a.ptr if isinstance(a, PinnedBuffer) else a.ctypes.data) for a in keep]
         ptrs = (C.c_void_p * self.nstreams)(*addr)
         n = nbatches * WAVE_BATCH
         # waveout: an optional caller-owned float32 array [nstreams][nch][n + AGC_EXTRA] (e.g. a view of a PinnedBuffer)
@@ -348,6 +350,24 @@ class Demod:
     def process_device(self, d_iq_ptr, stream_stride, nbatches, d_waveout_ptr, d_axc_ptr, d_iq_out_ptr=None, hip_stream=None):
         """Device-resident entry: raw device pointers (ints), asynchronous on hip_stream."""
         _check(lib().mi_demod_process_device(self._h, d_iq_ptr, stream_stride, nbatches, d_waveout_ptr, d_iq_out_ptr, d_axc_ptr, hip_stream))
+
+    def set_active_streams(self, active=None):
+        """mi_demod_set_active_streams: `active` = one truth value per stream, or None for all.  Streams that are not active sit the
+        following calls out: their IQ is not read (pass None for them), their output regions and their state are left untouched."""
+        # the library completes whatever was submitted before it changes the mask: those results are ready for wait()
+        self._done = getattr(self, "_done", []) + getattr(self, "_tickets", [])
+        self._tickets = []
+        if active is None:
+            _check(lib().mi_demod_set_active_streams(self._h, None))
+            return
+        assert len(active) == self.nstreams
+        m = np.array([1 if a else 0 for a in active], np.uint8)
+        _check(lib().mi_demod_set_active_streams(self._h, m.ctypes.data_as(C.c_void_p)))
+
+    def get_active_streams(self):
+        m = np.zeros(self.nstreams, np.uint8)
+        _check(lib().mi_demod_get_active_streams(self._h, m.ctypes.data_as(C.c_void_p)))
+        return [bool(x) for x in m]
 
     def stats(self):
         st = (ChannelStats * (self.nstreams * self.nch))()

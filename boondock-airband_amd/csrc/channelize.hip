@@ -207,7 +207,7 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_channelize(const Channeli
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
-    const int stream = blockIdx.y;
+    const int stream = a.streams ? a.streams[blockIdx.y] : static_cast<int>(blockIdx.y);  // the handle's index: IQ, planes, xmax, st, afc_spec
     const unsigned w0 = blockIdx.x * TW;
     const int nw = min(static_cast<unsigned>(TW), a.nfft - w0);
 
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256, 4) void k_channelize9p(const ChannelizeArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
-    const int stream = blockIdx.y;
+    const int stream = a.streams ? a.streams[blockIdx.y] : static_cast<int>(blockIdx.y);  // the handle's index: IQ, planes, xmax, st, afc_spec
     const unsigned w0 = blockIdx.x * TW;
     const int nw = min(static_cast<unsigned>(TW), a.nfft - w0);
     const PrunePlan& pp = a.prune;
@@ -570,7 +570,9 @@ hipError_t launch_fmt(const ChannelizeArgs& a, int sfmt, int nstreams, hipStream
 }  // namespace
 
 hipError_t launch_channelize(const ChannelizeArgs& a, int log2n, int sfmt, int nstreams, hipStream_t s) {
-    if (a.nfft == 0 || nstreams == 0)
+    if (a.streams)  // a launch over some of the handle's streams: the grid covers those alone
+        nstreams = a.nactive;
+    if (a.nfft == 0 || nstreams <= 0)
         return hipSuccess;
     // the pruned graphs have no complete spectrum: AFC launches (they want one) take the full kernel
     if (a.l64.enabled && a.l64_chan && !a.afc_spec && !a.st && l64_supported(log2n, a.hop_bytes, sfmt == MI_SFMT_S16 ? 2 : (sfmt == MI_SFMT_F32 ? 4 : 1)))

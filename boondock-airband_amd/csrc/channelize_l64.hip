@@ -18,18 +18,19 @@ struct FullMasks {
     static constexpr unsigned long long n[6] = {0x3ull, 0xfull, 0xffull, 0xffffull, 0xffffffffull, ~0ull};
 };
 
-template <int HOP, int LOG2N>
+template <int HOP, int LOG2N, bool MASKED>
 __global__ __launch_bounds__(256, 2) void k_channelize_l64(const L64Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char l64_lds[];
-    mi_l64::l64_body<HOP, FullMasks, LOG2N>(a, l64_lds);
+    mi_l64::l64_body<HOP, FullMasks, LOG2N, MASKED>(a, l64_lds);
 }
 
 using Kern = void (*)(const L64Args);
+template <bool MASKED>
 Kern full_instance(int log2n, unsigned hop) {
     switch (log2n) {
-        case 9: return hop == 160 ? k_channelize_l64<160, 9> : k_channelize_l64<128, 9>;
-        case 10: return hop == 160 ? k_channelize_l64<160, 10> : k_channelize_l64<128, 10>;
-        case 11: return hop == 160 ? k_channelize_l64<160, 11> : k_channelize_l64<128, 11>;
+        case 9: return hop == 160 ? k_channelize_l64<160, 9, MASKED> : k_channelize_l64<128, 9, MASKED>;
+        case 10: return hop == 160 ? k_channelize_l64<160, 10, MASKED> : k_channelize_l64<128, 10, MASKED>;
+        case 11: return hop == 160 ? k_channelize_l64<160, 11, MASKED> : k_channelize_l64<128, 11, MASKED>;
     }
     return nullptr;
 }
@@ -85,7 +86,7 @@ hipError_t launch_channelize_l64(const ChannelizeArgs& c, int log2n, int sfmt, i
     const unsigned hop = c.hop_bytes / bps2;
     if (!l64_supported(log2n, c.hop_bytes, static_cast<int>(bps2 / 2u)))
         return hipErrorInvalidValue;
-    const L64Jit* jit = c.l64_jit;  // the plan's own instance, if it could be compiled
+    const L64Jit* jit = c.l64_jit;  // the plan's own instance, if it could be compiled (of a launch with a stream list: the one that takes it)
     const int m6 = jit ? c.l64.m6 : 64;
     const unsigned tile = geo_of(log2n, m6).tile;
     L64Args a{};
@@ -112,9 +113,12 @@ hipError_t launch_channelize_l64(const ChannelizeArgs& c, int log2n, int sfmt, i
     a.ntiles = (c.nfft + tile - 1) / tile;
     a.sfmt = sfmt;
     a.linear_tiles = c.l64.linear_tiles;
+    if (c.streams)  // a launch over some of the handle's streams
+        nstreams = c.nactive;
     if (lds > 160 * 1024 || static_cast<unsigned long long>(a.ntiles) * static_cast<unsigned>(nstreams) >= (1ull << 32))
         return hipErrorInvalidValue;
     a.nstreams = static_cast<unsigned>(nstreams);
+    a.streams = c.streams;
     // persistent workgroups that draw runs of contiguous tiles from a ticket counter (l64_kernel.h): as many as the machine
     // holds at once when this launch has it to itself -- fewer are resident when other kernels of the pipeline run alongside,
     // the rest then find the tickets gone
@@ -146,7 +150,7 @@ hipError_t launch_channelize_l64(const ChannelizeArgs& c, int log2n, int sfmt, i
     }
     if (jit)
         return l64_jit_launch(jit, a, gx, 1u, lds, s);
-    const Kern kern = full_instance(log2n, hop);
+    const Kern kern = c.streams ? full_instance<true>(log2n, hop) : full_instance<false>(log2n, hop);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess)

@@ -2667,10 +2667,12 @@ __device__ uint32_t afc_check(const float* __restrict__ sq, const uint32_t fft_s
 }
 
 __global__ void k_afc(const AfcArgs a) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= a.nstreams * a.nch)
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.nstreams * a.nch)
         return;
-    const int stream = row / a.nch, ch = row - stream * a.nch;
+    const int si = idx / a.nch, ch = idx - si * a.nch;
+    const int stream = a.streams ? a.streams[si] : si;
+    const int row = stream * a.nch + ch;
     const ChanParams& P = a.cp[ch];
     if (P.afc == 0)
         return;

@@ -74,6 +74,10 @@ struct ChannelizeArgs {
     unsigned* l64_ticket_seq;      // host: launches so far
     const ChanState* st;  // AFC handles: the bin of (stream, channel) is st[..].afc_bin; null: ChanParams::bin
     float* afc_spec;      // AFC handles: [nstreams][fft_size] re^2+im^2 of the LAST window of the launch (AFC::square), or null
+    // A launch over some of the handle's streams (mi_demod_set_active_streams): the y-th stream of the launch is handle stream
+    // streams[y].  IQ, planes, xmax, st and afc_spec are addressed by the handle's index; tiles and tickets count nactive streams.
+    const int* streams;   // [nactive] ascending, device memory; null: the identity over all nstreams of the launch
+    int nactive;
 };
 
 struct DemodArgs {
@@ -114,6 +118,7 @@ struct DemodArgs {
 // AFC::finalize for one batch (rtl_airband.cpp:224-249), one thread per (stream, channel)
 struct AfcArgs {
     int nstreams, nch, fft_size;
+    const int* streams;  // the handle streams this launch takes (nstreams of them), or null: the identity
     const ChanParams* cp;
     ChanState* st;
     const float* spec;  // [nstreams][fft_size]
@@ -224,7 +229,8 @@ int l64_zstride(int log2n, int m6);
 size_t l64_lds_bytes(int log2n, unsigned hop, int m6, int nch, int n_iq_rows, unsigned* region_bytes);  // dynamic LDS of a workgroup
 // l64_jit.cpp: the kernel compiled for one plan's masks by hipRTC (cached per (device, log2 N, hop, masks) for the life of the
 // process; null when hipRTC is missing or the compilation fails -- `why` then says so)
-const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why);
+// (masked: the instance that takes L64Args::streams, a kernel of its own)
+const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why, bool masked = false);
 int l64_jit_minwaves(const L64Jit* j);
 void l64_jit_set_cache_dir(const char* dir);            // null / "": no code objects on disk
 void l64_jit_counts(int* compiled, int* from_disk);     // kernels compiled / loaded from the cache directory by this process

@@ -30,11 +30,12 @@ struct L64Args {
     unsigned zstride;                   // bytes per window in the exchange buffer
     unsigned span_bytes;                // bytes of the float span of a tile (rows of HOP samples, padded) or of the exchange buffer over it, whichever is larger
     unsigned ntiles;                    // tiles (4 waves x 64 / T windows: 32 / 16 / 8) per stream
-    unsigned nstreams;
+    unsigned nstreams;                  // streams of this launch
     int sfmt;                           // MI_SFMT_*
     int linear_tiles;                   // (unused)
     unsigned* ticket;                   // zero before the launch: runs of tiles are handed out through it
     unsigned run_tiles;                 // tiles per run
+    const int* streams;                 // [nstreams] the handle's stream of each stream of the launch (IQ, planes and xmax are addressed by it), or null: the identity
 };
 
 #endif

@@ -82,11 +82,13 @@ Rtc& rtc() {
 }
 
 struct Key {
-    int device, log2n, hop;
+    int device, log2n, hop, masked;
     uint64_t need[6];
     bool operator<(const Key& o) const {
         if (device != o.device)
             return device < o.device;
+        if (masked != o.masked)
+            return masked < o.masked;
         if (log2n != o.log2n)
             return log2n < o.log2n;
         if (hop != o.hop)
@@ -176,7 +178,7 @@ void disk_store(const std::string& path, uint64_t key, const std::vector<char>& 
 
 }  // namespace
 
-const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why) {
+const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6], const char** why, bool masked) {
     static const char* none = "";
     if (why)
         *why = none;
@@ -184,6 +186,7 @@ const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6]
     k.device = device;
     k.log2n = log2n;
     k.hop = hop;
+    k.masked = masked ? 1 : 0;
     std::memcpy(k.need, need, sizeof(k.need));
     std::lock_guard<std::mutex> lock(g_mu);
     auto it = g_cache.find(k);
@@ -213,6 +216,8 @@ const L64Jit* l64_jit_get(int device, int log2n, int hop, const uint64_t need[6]
     const int minwaves = (mw && *mw) ? std::max(1, std::min(4, std::atoi(mw))) : live;
     std::vector<std::string> opts = {"--offload-arch=" + arch, "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-DMI_L64_JIT=1",
                                      "-DL64_LOG2N=" + std::to_string(log2n), "-DL64_HOP=" + std::to_string(hop), "-DL64_MINWAVES=" + std::to_string(minwaves)};
+    if (masked)
+        opts.push_back("-DL64_MASKED=1");
     for (int s = 0; s < 6; ++s) {
         char buf[64];
         std::snprintf(buf, sizeof(buf), "-DL64_N%d=0x%llxull", s + 1, static_cast<unsigned long long>(need[s]));

@@ -146,14 +146,17 @@ struct TileGeom {
     unsigned nsamp;              // samples its windows span
     unsigned mis;                // misalignment of the first pair load (0 or one sample)
     unsigned npairs;
-    int stream;
+    int stream;                  // the handle's index of the stream: what IQ, planes and xmax are addressed by
 };
 
-template <int HOP, int LOG2N>
+template <int HOP, int LOG2N, bool MASKED>
 __device__ __forceinline__ TileGeom tile_geom(const L64Args& a, const int stream, const unsigned tile, const unsigned bps2) {
     constexpr int kN = Geo<LOG2N>::kN, kTile = Geo<LOG2N>::kTile;
     TileGeom g;
-    g.stream = stream;
+    if constexpr (MASKED)
+        g.stream = a.streams[stream];  // (`stream` counts the streams of the launch)
+    else
+        g.stream = stream;
     g.w0 = tile * kTile;
     g.nw = static_cast<int>(min(static_cast<unsigned>(kTile), a.nfft - g.w0));
     g.nsamp = static_cast<unsigned>(g.nw - 1) * HOP + kN;
@@ -228,7 +231,9 @@ __device__ __forceinline__ void load_pair(const L64Args& a, const TileGeom& g, c
 // part of the grid is resident at a time, and with fixed shares the launch lasted as long as the workgroups that started last.
 // The raw bytes of tile k+1 are requested before the FFTs of tile k start and converted after them: HBM latency hides under the
 // arithmetic (byte formats: kRawTrips dwords per lane stay in registers meanwhile).
-template <int HOP, class M, int LOG2N>
+// MASKED: a launch over some of the handle's streams (L64Args::streams).  An instantiation of its own: the launches over all
+// streams run exactly the code they ran before there was such a list.
+template <int HOP, class M, int LOG2N, bool MASKED = false>
 __device__ __forceinline__ void l64_body(const L64Args& a, unsigned char* lds) {
     using GE = Geo<LOG2N>;
     constexpr int kN = GE::kN, kT = GE::kT, kLT = GE::kLT, kW = GE::kW, kTile = GE::kTile, kZRow = GE::kZRow, kRawTrips = GE::kRawTrips;
@@ -295,7 +300,7 @@ __device__ __forceinline__ void l64_body(const L64Args& a, unsigned char* lds) {
         for (int k = 0; k < kRawTrips; ++k)
             pre[k] = (tid0 + 256u * k < q.npairs) ? src[256 * k] : 0u;
     };
-    TileGeom geo = tile_geom<HOP, LOG2N>(a, nx_stream, nx_tile, bps2);
+    TileGeom geo = tile_geom<HOP, LOG2N, MASKED>(a, nx_stream, nx_tile, bps2);
     bool fast = is_fast(geo);
     if (fast)
         prefetch(geo);
@@ -352,7 +357,7 @@ __device__ __forceinline__ void l64_body(const L64Args& a, unsigned char* lds) {
             }
         }
         if (more) {
-            geo = tile_geom<HOP, LOG2N>(a, nx_stream, nx_tile, bps2);
+            geo = tile_geom<HOP, LOG2N, MASKED>(a, nx_stream, nx_tile, bps2);
             fast = is_fast(geo);
             if (fast)
                 prefetch(geo);
@@ -479,13 +484,16 @@ __device__ __forceinline__ void l64_body(const L64Args& a, unsigned char* lds) {
 }  // namespace mi_l64
 
 #ifdef MI_L64_JIT
-// run-time compilation for one plan: the masks, the hop and log2 N arrive as macros
+// run-time compilation for one plan: the masks, the hop and log2 N arrive as macros (L64_MASKED=1: the instance that takes a stream list)
+#ifndef L64_MASKED
+#define L64_MASKED 0
+#endif
 struct L64JitMasks {
     static constexpr unsigned long long n[6] = {L64_N1, L64_N2, L64_N3, L64_N4, L64_N5, L64_N6};
 };
 extern "C" __global__ __launch_bounds__(256, L64_MINWAVES) void l64_entry(const L64Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char l64_lds[];
-    mi_l64::l64_body<L64_HOP, L64JitMasks, L64_LOG2N>(a, l64_lds);
+    mi_l64::l64_body<L64_HOP, L64JitMasks, L64_LOG2N, L64_MASKED != 0>(a, l64_lds);
 }
 #endif
 

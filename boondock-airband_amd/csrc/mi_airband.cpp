@@ -170,6 +170,8 @@ struct mi_demod {
     unsigned l64_ticket_seq = 0;
     const mi::L64Jit* l64_jit = nullptr; // the kernel compiled for this plan's masks (owned by the process-wide cache), or null
     bool l64_jit_tried = false;
+    const mi::L64Jit* l64_jit_masked = nullptr;  // ... its twin that takes a stream list, asked for when a mask first sets a stream aside
+    bool l64_jit_masked_tried = false;
     bool l64_why_said = false;           // MI_AIRBAND_DEBUG: why this plan does not get the lane-resident kernel, said once
     int last_stage1 = 0;  // MI_STAGE1_* of the last call
     mi::DevBuf<float> d_levels;
@@ -207,6 +209,7 @@ struct mi_demod {
         char* axc = nullptr;
         mi_channel_stats* stats = nullptr;
         bool wave_direct = false;  // waveout is page-locked: the audio is downloaded straight into it
+        bool masked = false;       // a call of some streams only: the regions of the others in the caller's arrays stay as they are
     } slot[kSlots];
     size_t iq_stride = 0, h_out_bytes = 0;
     bool slots_ready[kSlots] = {};
@@ -241,6 +244,15 @@ struct mi_demod {
     size_t tp_max_blk = 0, tp_max_seg = 0;
     uint32_t tp_L = 512;  // steps per segment (kernels.hpp, TP_L_MIN .. TP_L_MAX), fixed when the handle is created
     int opt_tp_L = 0;     // MI_AIRBAND_TP_SEGMENT at create: 0 = by row count
+    // mi_demod_set_active_streams: the streams that take part in the calls made from now on.  A masked call (not every stream
+    // active) runs stage 1 and the serial stage 2 over the lists below and nothing else: what the other streams carry between
+    // calls (ChanState rows, lookahead, plane heads, squelch ring, CTCSS table, AFC bin) is in arrays indexed by handle row or
+    // stream, which the kernels of such a call address through the lists alone.
+    std::vector<uint8_t> active;   // [nstreams] 0 / 1
+    int nactive = 0;
+    bool masked = false;           // nactive < nstreams
+    mi::DevBuf<int> d_act_streams; // [nactive] the active streams, ascending (uploaded when the mask is set, not per call)
+    mi::DevBuf<int> d_act_rows;    // [nactive * nch] their handle rows
 };
 
 namespace {
@@ -351,6 +363,17 @@ void stage1_compile(mi_demod* h) {
     h->l64_jit = mi::l64_jit_get(h->gpu, h->plan.log2n, hop, h->plan.l64.need, nullptr);
 }
 
+// ... and the instance that takes a stream list (calls of some streams only): compiled, or loaded from the cache, when
+// mi_demod_set_active_streams first sets a stream aside -- a host that cannot afford the compilation between two batches sets
+// such a mask once before its input threads start
+void stage1_compile_masked(mi_demod* h) {
+    if (h->l64_jit_masked_tried || !h->opt_l64_jit || !h->opt_l64 || !h->plan.l64.enabled || !h->d_l64_chan || h->plan.any_afc)
+        return;
+    h->l64_jit_masked_tried = true;
+    const int hop = static_cast<int>(h->plan.hop_bytes / (2 * static_cast<size_t>(h->plan.bytes_per_sample)));
+    h->l64_jit_masked = mi::l64_jit_get(h->gpu, h->plan.log2n, hop, h->plan.l64.need, nullptr, /*masked=*/true);
+}
+
 // MI_AIRBAND_DEBUG=1: once per handle, why its plan does not get the lane-resident stage 1
 void stage1_explain(mi_demod* h) {
     if (h->l64_why_said)
@@ -369,9 +392,9 @@ void stage1_explain(mi_demod* h) {
     std::fprintf(stderr, "mi_airband: no lane-resident stage 1 for this plan (%s); the exchange kernel runs\n", why);
 }
 
-int lanes_per_wave_for(const mi_demod* h) {
+int lanes_per_wave_for(const mi_demod* h, int rows) {
     // up to opt_uni_rows waves keep one channel each (the uniform instantiation of k_demod); beyond that pack lanes
-    int lpw = (h->rows + h->opt_uni_rows - 1) / h->opt_uni_rows;
+    int lpw = (rows + h->opt_uni_rows - 1) / h->opt_uni_rows;
     return std::min(64, std::max(1, lpw));
 }
 
@@ -408,6 +431,15 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     // iq_ready (host-buffer entry, calls in flight): the IQ becomes valid when this event fires -- the streams that read it wait
     // for it and for nothing else, exactly as if the caller had vouched for the bytes (MI_OPT_EARLY_INPUT)
     const bool early_input = h->early_input || iq_ready != nullptr;
+    // A masked call (mi_demod_set_active_streams): one stage-1 launch and the serial stage 2 over the active streams, enqueued as a
+    // call without a predecessor (heads in place first, no overlap).  It leaves chain_live and serial_pipe clear, so the full
+    // call after it takes nothing from the previous call's arrays (prev_mag, prev_blk_*, prev_core, spec_head, xmax_prev: they
+    // would not hold every row) and seeds its chain from the ChanState rows.
+    const bool partial = h->masked;
+    if (partial && h->first_call)
+        return fail(MI_ERR_INVALID, "the handle's first call needs every stream active");
+    const int act_streams = partial ? h->nactive : h->nstreams;
+    const int act_rows = act_streams * h->nch;
     const int nfft = n_fft_for(h, nbatches);
     mi::ChannelizeArgs ca{};
     ca.iq = d_iq;
@@ -434,9 +466,12 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     ca.l64_tickets = h->d_l64_tickets;
     ca.l64_ticket_seq = &h->l64_ticket_seq;
     ca.l64_chan_full = h->d_l64_chan_full;
-    if (ca.l64.enabled)  // (normally done by mi_demod_create; here only if the option was switched on afterwards)
+    if (ca.l64.enabled) {  // (normally done by mi_demod_create / _set_active_streams; here only if the option was switched on afterwards)
         stage1_compile(h);
-    ca.l64_jit = h->opt_l64_jit ? h->l64_jit : nullptr;
+        if (partial)
+            stage1_compile_masked(h);
+    }
+    ca.l64_jit = h->opt_l64_jit ? (partial ? h->l64_jit_masked : h->l64_jit) : nullptr;
     // The prebuilt full-graph instance keeps all 64 points of a lane live and is slower than the exchange kernels: it runs
     // only when asked for (MI_OPT_LANE_FFT_JIT = 0, tests); without hipRTC the pruned / full exchange kernels take over.
     if (ca.l64.enabled && h->opt_l64_jit && !ca.l64_jit)
@@ -452,18 +487,20 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     ca.cp = h->d_cp;
     ca.nch = h->nch;
     ca.n_iq_rows = h->plan.n_iq_rows;
+    ca.streams = partial ? h->d_act_streams.get() : nullptr;
+    ca.nactive = act_streams;
     h->last_stage1 = (ca.l64.enabled && !h->plan.any_afc) ? (ca.l64_jit ? MI_STAGE1_LANE_PLAN : MI_STAGE1_LANE_FULL)
                      : ((ca.prune.enabled && h->plan.log2n == 9 && !h->plan.any_afc) ? MI_STAGE1_EXCHANGE_PRUNED : MI_STAGE1_EXCHANGE_FULL);
     const int env = h->opt_tp;
-    const bool use_tp = h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
+    const bool use_tp = !partial && h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
                         (env == 1 || (nbatches >= (h->tp_mixed ? kMixedMinBatches : kTpMinBatches) && h->tp_rows <= kTpAutoMaxRows));
     ca.xmax = nullptr;  // (the time-parallel branch points it at its scratch set)
 
     mi::DemodArgs da{};
     da.nstreams = h->nstreams;
     da.nch = h->nch;
-    da.rows = nullptr;
-    da.nrows = h->rows;
+    da.rows = partial ? h->d_act_rows.get() : nullptr;
+    da.nrows = act_rows;
     da.carry_in = nullptr;
     da.n_iq_rows = h->plan.n_iq_rows;
     da.n_ctcss_rows = h->plan.n_ctcss_rows;
@@ -490,14 +527,14 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     da.ctcss_q = h->d_ctcss_q;
     da.stats = h->d_stats;
     da.fm_quadri = h->plan.dev.fm_quadri;
-    da.lanes_per_wave = lanes_per_wave_for(h);
+    da.lanes_per_wave = lanes_per_wave_for(h, act_rows);
     da.steady_blocks = h->steady_blocks ? 1 : 0;
     // the pre-filter wave pays where a call is bound by the latency of its rows (4 / 8 / 16 streams x 32 mixed channels: +44 / +37 /
     // +12 %); with a thousand rows and more the machine is full and a second wave per row only takes LDS and issue slots from
     // stage 1 (32 streams: +-0, 64 streams: -27 %)
     // (round 3: four waves per channel, each with a SIMD's register file to itself: one channel per CU, so up to 256 rows)
     // ... and two waves per channel (the channel with its audio, the pre-filter wave) up to 1 024 rows: 2 = k_demod_pw2
-    da.pre_wave = h->opt_pre_wave < 0 ? (h->rows <= 256 ? 1 : (h->rows <= 1024 ? 2 : 0)) : std::min(2, h->opt_pre_wave);
+    da.pre_wave = h->opt_pre_wave < 0 ? (act_rows <= 256 ? 1 : (act_rows <= 1024 ? 2 : 0)) : std::min(2, h->opt_pre_wave);
     da.audio_wave = h->opt_audio_wave ? 1 : 0;
     da.pre_timeouts = h->d_pre_timeouts;
 
@@ -893,7 +930,8 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             db.axc = d_axc + b;
             HIP_TRY(mi::launch_demod(db, s));
             mi::AfcArgs aa{};
-            aa.nstreams = h->nstreams;
+            aa.nstreams = act_streams;
+            aa.streams = ca.streams;
             aa.nch = h->nch;
             aa.fft_size = h->plan.fft_size;
             aa.cp = h->d_cp;
@@ -904,7 +942,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             HIP_TRY(mi::launch_afc(aa, s));
             f0 += nf;
         }
-    } else if (early_input && !h->first_call && (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) &&
+    } else if (!partial && early_input && !h->first_call && (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) &&
                serial_sets_ready(h)) {
         // (a handle whose plan the time-parallel path could take as well -- many rows, or MI_OPT_TIME_PARALLEL = 0 -- pipelines its serial
         //  calls like any other as long as its planes are where this branch keeps them: never after a time-parallel call)
@@ -1065,6 +1103,8 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
     h->nch = nch;
     h->rows = nstreams * nch;
     h->max_batches = max_batches;
+    h->active.assign(static_cast<size_t>(nstreams), 1);
+    h->nactive = nstreams;
     const mi::Plan& p = h->plan;
     const size_t max_steps = static_cast<size_t>(max_batches) * mi::kWaveBatch;
     h->plane_stride = (max_steps + 2 * mi::kAgcExtra + 3) & ~static_cast<size_t>(3);
@@ -1271,6 +1311,12 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
     int rc = mi_demod_get_state(h, saved.data(), saved.size());
     if (rc != MI_OK)
         return rc;
+    struct AllActive {  // the rehearsals take every stream (a handle's first call must), whatever mask the caller has set
+        mi_demod* h;
+        bool masked;
+        explicit AllActive(mi_demod* hh) : h(hh), masked(hh->masked) { h->masked = false; }
+        ~AllActive() { h->masked = masked; }
+    } all_active(h);
     std::vector<int> rehearsals = {1};
     if (h->tp_eligible && h->opt_tp != 0 && h->max_batches >= kTpMinBatches)
         rehearsals.push_back(kTpMinBatches);
@@ -1431,7 +1477,12 @@ int slot_launch(mi_demod* h, int k, const uint8_t* const* iq, int nbatches, bool
     const size_t need = mi_demod_bytes_needed(h, nbatches);
     hipStream_t s = h->own_stream;
     hipStream_t up = pipelined ? h->copy_stream : s;
+    if (h->masked && h->first_call)  // (before anything is staged)
+        return fail(MI_ERR_INVALID, "the handle's first call needs every stream active");
+    sl.masked = h->masked;
     for (int i = 0; i < h->nstreams; ++i) {
+        if (sl.masked && !h->active[static_cast<size_t>(i)])
+            continue;  // a stream that sits this call out: its pointer is not looked at, nothing is staged or uploaded
         if (!iq[i])
             return fail(MI_ERR_INVALID, "NULL stream pointer");
         const unsigned char* src = iq[i];
@@ -1469,12 +1520,12 @@ int slot_launch(mi_demod* h, int k, const uint8_t* const* iq, int nbatches, bool
         down = h->down_stream;
     }
     const OutLayout o = out_layout(h, nbatches);
-    sl.wave_direct = is_pinned(sl.waveout);
+    sl.wave_direct = !sl.masked && is_pinned(sl.waveout);  // (a masked call hands over the active streams' regions only: slot_collect)
     HIP_TRY_F(hipMemcpyAsync(sl.wave_direct ? reinterpret_cast<unsigned char*>(sl.waveout) : sl.h_out + o.wave, sl.d_wout, rows * wstride * sizeof(float),
                            hipMemcpyDeviceToHost, down));
     if (want_iq) {
         for (size_t r = 0; r < rows; ++r) {
-            if (!h->plan.cp[r % h->nch].has_iq_outputs)
+            if (!h->plan.cp[r % h->nch].has_iq_outputs || (sl.masked && !h->active[r / static_cast<size_t>(h->nch)]))
                 continue;
             HIP_TRY_F(hipMemcpyAsync(sl.h_out + o.iq + r * nsteps * 8, sl.d_iqout + r * nsteps, nsteps * sizeof(float2), hipMemcpyDeviceToHost, down));
         }
@@ -1490,19 +1541,28 @@ int slot_launch(mi_demod* h, int k, const uint8_t* const* iq, int nbatches, bool
 int slot_collect(mi_demod* h, int k) {
     mi_demod::Slot& sl = h->slot[k];
     HIP_TRY(hipEventSynchronize(sl.done));
-    const size_t rows = static_cast<size_t>(h->rows);
     const size_t nsteps = static_cast<size_t>(sl.nbatches) * mi::kWaveBatch;
     const OutLayout o = out_layout(h, sl.nbatches);
-    if (!sl.wave_direct)
-        std::memcpy(sl.waveout, sl.h_out + o.wave, rows * (nsteps + mi::kAgcExtra) * sizeof(float));
-    if (sl.iq_out) {
-        for (size_t r = 0; r < rows; ++r)
-            if (h->plan.cp[r % h->nch].has_iq_outputs)  // rows of channels without iq outputs are untouched
+    const size_t nch = static_cast<size_t>(h->nch), wlen = nsteps + mi::kAgcExtra, nb = static_cast<size_t>(sl.nbatches);
+    // the regions of streams [s0, s0 + n) of the caller's arrays
+    auto hand_over = [&](size_t s0, size_t n) {
+        const size_t r0 = s0 * nch, nr = n * nch;
+        if (!sl.wave_direct)
+            std::memcpy(sl.waveout + r0 * wlen, sl.h_out + o.wave + r0 * wlen * sizeof(float), nr * wlen * sizeof(float));
+        for (size_t r = r0; sl.iq_out && r < r0 + nr; ++r)
+            if (h->plan.cp[r % nch].has_iq_outputs)  // rows of channels without iq outputs are untouched
                 std::memcpy(sl.iq_out + r * nsteps * 2, sl.h_out + o.iq + r * nsteps * 8, nsteps * 8);
+        std::memcpy(sl.axc + r0 * nb, sl.h_out + o.axc + r0 * nb, nr * nb);
+        if (sl.stats)
+            std::memcpy(sl.stats + r0, sl.h_out + o.stats + r0 * sizeof(mi_channel_stats), nr * sizeof(mi_channel_stats));
+    };
+    if (!sl.masked) {
+        hand_over(0, static_cast<size_t>(h->nstreams));
+    } else {  // (the mask cannot have changed since the call was made: setting one completes what is in flight)
+        for (size_t st = 0; st < static_cast<size_t>(h->nstreams); ++st)
+            if (h->active[st])
+                hand_over(st, 1);
     }
-    std::memcpy(sl.axc, sl.h_out + o.axc, rows * static_cast<size_t>(sl.nbatches));
-    if (sl.stats)
-        std::memcpy(sl.stats, sl.h_out + o.stats, rows * sizeof(mi_channel_stats));
     sl.busy = false;
     return MI_OK;
 }
@@ -1607,6 +1667,8 @@ int mi_demod_process_planes(mi_demod* h, const float* mag, const float* cplx, in
         return fail(MI_ERR_UNSUPPORTED, "AFC channels read the spectrum of stage 1: no plane entry for them");
     if (h->in_flight)
         return fail(MI_ERR_INVALID, "submitted calls are in flight");
+    if (h->masked)
+        return fail(MI_ERR_UNSUPPORTED, "the plane entry takes every stream: not while mi_demod_set_active_streams has set some aside");
     const size_t zrows = static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows;
     if (zrows && !cplx)
         return fail(MI_ERR_INVALID, "this plan has raw-I/Q rows: cplx planes are needed");
@@ -1745,6 +1807,57 @@ int mi_demod_set_state(mi_demod* h, const void* buf, size_t len) {
         HIP_TRY(hipMemcpy2D(h->d_cplx, h->plane_stride * 8, o, mi::kAgcExtra * 8, mi::kAgcExtra * 8, zrows, hipMemcpyHostToDevice));
     h->first_call = hd.first_call != 0;
     h->failed = false;
+    return MI_OK;
+}
+
+int mi_demod_set_active_streams(mi_demod* h, const uint8_t* active) {
+    if (!h)
+        return fail(MI_ERR_INVALID, "NULL handle");
+    const size_t ns = static_cast<size_t>(h->nstreams), nch = static_cast<size_t>(h->nch);
+    std::vector<uint8_t> want(ns, 1);
+    std::vector<int> streams, rows;
+    for (size_t s = 0; s < ns; ++s) {
+        want[s] = (!active || active[s]) ? 1 : 0;
+        if (!want[s])
+            continue;
+        streams.push_back(static_cast<int>(s));
+        for (size_t c = 0; c < nch; ++c)
+            rows.push_back(static_cast<int>(s * nch + c));
+    }
+    if (streams.empty())
+        return fail(MI_ERR_INVALID, "no active stream");
+    HIP_TRY(hipSetDevice(h->gpu));
+    while (h->in_flight > 0) {  // submitted calls were made under the mask they saw
+        const int rc = mi_demod_wait(h);
+        if (rc != MI_OK)
+            return rc;
+    }
+    if (want == h->active)
+        return MI_OK;
+    if (streams.size() < ns) {
+        // (the lists of the previous mask may still be read by a device-entry call on the caller's stream)
+        HIP_TRY(hipDeviceSynchronize());
+        if (!h->d_act_streams) {
+            mi::DevBuf<int> ds, dr;
+            HIP_TRY(dalloc(ds, ns));
+            HIP_TRY(dalloc(dr, ns * nch));
+            h->d_act_streams = std::move(ds);
+            h->d_act_rows = std::move(dr);
+        }
+        HIP_TRY(hipMemcpy(h->d_act_streams, streams.data(), streams.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->d_act_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+        stage1_compile_masked(h);  // (a failure leaves the exchange kernels: never an error)
+    }
+    h->active = want;
+    h->nactive = static_cast<int>(streams.size());
+    h->masked = streams.size() < ns;
+    return MI_OK;
+}
+
+int mi_demod_get_active_streams(const mi_demod* h, uint8_t* active) {
+    if (!h || !active)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    std::memcpy(active, h->active.data(), h->active.size());
     return MI_OK;
 }
 

@@ -232,6 +232,14 @@ int init_demod(demod_params_t* params, Signal* signal, int device_start, int dev
         int rc = mi_demod_create(&dc, cc.data(), dev->channel_count, (int)members.size(), 1, gpu, &engine);
         if (rc == MI_OK)
             rc = mi_demod_prepare(engine, 1);  // staging + a rehearsal now: the first batch must not pay for them
+        if (rc == MI_OK && members.size() > 1) {
+            // ... nor the first turn a member sits out for the stage-1 kernel that takes a stream list: a partial mask, set and lifted
+            std::vector<uint8_t> all_but_one(members.size(), 1);
+            all_but_one.back() = 0;
+            rc = mi_demod_set_active_streams(engine, all_but_one.data());
+            if (rc == MI_OK)
+                rc = mi_demod_set_active_streams(engine, NULL);
+        }
         if (rc != MI_OK) {
             fprintf(stderr, "init_demod: device %d: %s\n", d, mi_last_error());
             if (engine)
@@ -279,7 +287,8 @@ std::vector<EngineGroup> engine_groups(int first, int end) {
 // Scratch of one demod thread: what one engine call returns before it is published into channel_t.
 struct BatchScratch {
     std::vector<std::vector<unsigned char>> linear;  // per stream: a batch that wraps in its ring, assembled
-    std::vector<unsigned char> silence;              // what a retired device's stream is fed
+    std::vector<uint8_t> active;                     // per stream: takes part in this turn (mi_demod_set_active_streams)
+    std::vector<unsigned char> silence;              // the engine's first call only: the batch of a member that never ran
     std::vector<float> wave, iq;
     std::vector<char> axc;
     std::vector<mi_channel_stats> stats;
@@ -321,9 +330,12 @@ void publish_batch(device_t* dev, const BatchScratch& b, int stream) {
 // The demod thread.  Control flow of the reference's loop (rtl_airband.cpp:381-422, 671-691) with one engine call per
 // WAVE_BATCH in place of the per-window body: exit flag, "all receivers failed", skipping inputs that are not running
 // (a failed one is retired once), the availability rule, the 10 ms nap when the ring is short, publish, signal, advance.
-// The unit of a turn is an engine: its devices (equal plans, hence equal sample rates: their rings fill in step) are served by
-// ONE submit / wait pair, each device's batch uploaded from its own ring; a turn happens when every running device of the
-// engine has a batch.  A retired device's stream is fed silence (streams are independent: nobody else notices).
+// The unit of a turn is an engine: its devices (equal plans) are served by ONE submit / wait pair, each device's batch uploaded from
+// its own ring.  A turn happens when AT LEAST ONE running device of the engine has a batch: the reference visits each device on its
+// own and skips a short ring, so a dongle that stalls or runs a few ppm slow never holds its siblings back until their rings
+// overflow.  Members whose ring is short, and members that are not running (retired ones included), sit the turn out through the
+// engine's active-stream mask: their `bufs` stay where they are, nothing is published for them, and their streams' state is
+// untouched.
 void* demodulate(void* params) {
     demod_params_t* const dp = (demod_params_t*)params;
     std::vector<EngineGroup> groups = engine_groups(dp->device_start, dp->device_end);
@@ -340,9 +352,10 @@ void* demodulate(void* params) {
         const int nstreams = (int)g.members.size();
         const size_t consumed = mi_demod_bytes_consumed(g.engine, 1);
         const size_t needed = mi_demod_bytes_needed(g.engine, 1);
-        int running = 0;
-        bool short_ring = false;
-        for (int m : g.members) {
+        int running = 0, ready = 0;
+        scratch.active.assign((size_t)nstreams, 0);
+        for (int k = 0; k < nstreams; k++) {
+            const int m = g.members[(size_t)k];
             input_t* const in = devices[m].input;
             if (in->state != INPUT_RUNNING) {
                 if (in->state == INPUT_FAILED) {  // retire it: its outputs stay silent from now on
@@ -354,14 +367,19 @@ void* demodulate(void* params) {
             running++;
             // The reference starts a window when the ring holds one hop plus one window (rtl_airband.cpp:417).  Applied to the
             // LAST window of a batch: everything the batch consumes, plus one window.
-            if (ring_fill(in) < consumed + fft_size * (size_t)in->bytes_per_sample * 2)
-                short_ring = true;
+            if (ring_fill(in) >= consumed + fft_size * (size_t)in->bytes_per_sample * 2) {
+                scratch.active[(size_t)k] = 1;
+                ready++;
+            }
         }
         if (running == 0) {
             next();
             continue;
         }
-        if (short_ring) {
+        // The engine's first call (`consumed` is then AGC_EXTRA windows longer) takes every stream: it waits for every running
+        // member, and a member that is not running by then is given silence for that single call.
+        const bool first_turn = consumed != (size_t)WAVE_BATCH * mi_demod_hop_bytes(g.engine);
+        if (ready == 0 || (first_turn && ready < running)) {
             next();
             SLEEP(10);
             continue;
@@ -371,27 +389,28 @@ void* demodulate(void* params) {
         std::vector<const uint8_t*> streams((size_t)nstreams);
         for (int k = 0; k < nstreams; k++) {
             input_t* const in = devices[g.members[(size_t)k]].input;
-            if (in->state == INPUT_RUNNING) {
-                streams[(size_t)k] = ring_contiguous(in, needed, scratch.linear[(size_t)k]);
-            } else {
+            streams[(size_t)k] = scratch.active[(size_t)k] ? ring_contiguous(in, needed, scratch.linear[(size_t)k]) : NULL;
+            if (first_turn && !scratch.active[(size_t)k]) {
                 scratch.silence.assign(needed, in->sfmt == SFMT_U8 ? 0x80 : 0);
                 streams[(size_t)k] = scratch.silence.data();
             }
         }
-        int rc = mi_demod_submit(g.engine, streams.data(), 1, scratch.wave.data(), scratch.iq.data(), scratch.axc.data(), scratch.stats.data());
+        int rc = mi_demod_set_active_streams(g.engine, (first_turn || ready == nstreams) ? NULL : scratch.active.data());
+        if (rc == MI_OK)
+            rc = mi_demod_submit(g.engine, streams.data(), 1, scratch.wave.data(), scratch.iq.data(), scratch.axc.data(), scratch.stats.data());
         if (rc == MI_OK)
             rc = mi_demod_wait(g.engine);
         if (rc != MI_OK) {  // an engine failure at run time is an input failure of its devices
             fprintf(stderr, "demodulate: engine of device %d: %s\n", g.members[0], mi_last_error());
-            for (int m : g.members)
-                if (devices[m].input->state == INPUT_RUNNING)
-                    devices[m].input->state = INPUT_FAILED;
+            for (int k = 0; k < nstreams; k++)  // ... of the ones that took part in this call
+                if (scratch.active[(size_t)k] && devices[g.members[(size_t)k]].input->state == INPUT_RUNNING)
+                    devices[g.members[(size_t)k]].input->state = INPUT_FAILED;
             continue;
         }
         for (int k = 0; k < nstreams; k++) {
             device_t* const dev = devices + g.members[(size_t)k];
             input_t* const in = dev->input;
-            if (in->state != INPUT_RUNNING)
+            if (!scratch.active[(size_t)k] || in->state != INPUT_RUNNING)
                 continue;
             publish_batch(dev, scratch, k);
             in->bufs = (in->bufs + consumed) % in->buf_size;  // rtl_airband.cpp:691

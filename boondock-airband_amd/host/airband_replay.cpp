@@ -212,22 +212,15 @@ int main(int argc, char** argv) {
         pthread_mutex_unlock(&in->buffer_lock);
         return avail < mi_demod_bytes_consumed(devices[d].engine, 1) + fft_size * (size_t)in->bytes_per_sample * 2;
     };
-    // the demod thread cannot run (every engine has a device whose ring is short -- its devices advance in step) and the output
-    // side has consumed what it produced
+    // the demod thread cannot run (every member of every engine is short: a member with a batch gets its turn whatever its
+    // siblings hold, so captures may differ in length) and the output side has consumed what it produced
     auto idle = [&]() {
         for (size_t d = 0; d < ndev; d++)
             if (devices[d].waveavail)
                 return false;
-        for (size_t d = 0; d < ndev; d++) {
-            if (!devices[d].engine_owner)
-                continue;
-            bool any_short = false;
-            for (size_t e = 0; e < ndev; e++)
-                if (devices[e].engine == devices[d].engine && starved(e))
-                    any_short = true;
-            if (!any_short)
+        for (size_t d = 0; d < ndev; d++)
+            if (!starved(d))
                 return false;
-        }
         return true;
     };
     auto settle = [&]() {

@@ -168,6 +168,27 @@ void mi_host_free(void* p);
 int mi_demod_process_device(mi_demod* h, const void* d_iq, size_t stream_stride_bytes, int nbatches, float* d_waveout,
                             float* d_iq_out, char* d_axc, void* hip_stream);
 
+/* Which streams of the handle take part in the calls made from now on (mi_demod_process, _submit, _process_device), until it is
+ * changed: active[s] != 0 -- stream s takes part; NULL -- all streams (the default).  A live host lets a device whose ring is short,
+ * or which has been retired, sit a turn out (the reference visits each device on its own and skips a short ring,
+ * rtl_airband.cpp:381-422); a bulk replay puts captures of unequal length on one handle.
+ * For a stream that is inactive in a call:
+ *   - its IQ is not read: iq[s] may be NULL on the host entries, nothing is staged or uploaded for it, and the device entry
+ *     touches nothing at d_iq + s*stream_stride_bytes;
+ *   - its regions of waveout / d_waveout, iq_out, axc and stats are not written;
+ *   - everything it carries between calls keeps its bytes (channel state, audio lookahead, the AGC_EXTRA carried samples, squelch
+ *     ring, CTCSS detectors, AFC bin): when it is active again it continues as if the calls in between had never been made, bit for
+ *     bit what the stream would have produced on a handle of its own.
+ * mi_demod_bytes_needed / _consumed / _hop_bytes are per stream and do not change.  A call with a stream set aside takes the serial
+ * stage 2 (mi_demod_last_path reports 0) and does not overlap its neighbours; calls of all streams keep every path they have.
+ * Setting a mask first completes whatever mi_demod_submit has in flight.  MI_ERR_INVALID: no stream active; also returned by the
+ * handle's first call (the one with AGC_EXTRA more windows) while a stream is set aside -- it needs every stream.
+ * mi_demod_process_planes returns MI_ERR_UNSUPPORTED while a stream is set aside.
+ * The first mask of a handle that sets a stream aside obtains the stage-1 kernel instance that takes a stream list (hipRTC, 0.3-0.6 s,
+ * or the code-object cache): like mi_demod_prepare, do it once before the input threads start. */
+int mi_demod_set_active_streams(mi_demod* h, const uint8_t* active /* [nstreams] or NULL */);
+int mi_demod_get_active_streams(const mi_demod* h, uint8_t* active /* [nstreams] */);
+
 /* stats of the last completed call (synchronises the handle's stream) */
 int mi_demod_get_stats(mi_demod* h, mi_channel_stats* stats /* [nstreams][nch] */);
 
