@@ -99,12 +99,20 @@ class MixInput(C.Structure):  # mi_mix_input
     _fields_ = [("row", C.c_int), ("ampfactor", C.c_float), ("balance", C.c_float)]
 
 
+class GateBlock(C.Structure):  # mi_gate_block
+    _fields_ = [("row", C.c_uint32), ("batch", C.c_uint32)]
+
+
+GATE_NONE, GATE_OPEN, GATE_OPEN_TRAIL, GATE_ALL = 0, 1, 2, 3  # MI_GATE_*
+
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
     "mi_demod_get_state", "mi_demod_set_state", "mi_demod_read_planes", "mi_demod_process_planes", "mi_demod_last_path", "mi_demod_last_stage1", "mi_demod_pre_wave_timeouts", "mi_demod_tp_debug", "mi_demod_kernel_time", "mi_demod_kernel_time_prev", "mi_demod_event_ms", "mi_demod_set_option", "mi_demod_last_kernel_ms", "mi_plan_create", "mi_plan_destroy", "mi_plan_fft_size",
     "mi_plan_window", "mi_plan_twiddles", "mi_plan_levels", "mi_plan_sincos_lut", "mi_plan_channel", "mi_plan_lane_fft", "mi_plan_ctcss_coeffs",
     "mi_iqgen_host", "mi_iqgen_device", "mi_mixer_create", "mi_mixer_destroy", "mi_mixer_is_stereo", "mi_mixer_process_device",
+    "mi_outgate_create", "mi_outgate_destroy", "mi_outgate_set_rules", "mi_outgate_process_device", "mi_outgate_download", "mi_outgate_state_size",
+    "mi_outgate_get_state", "mi_outgate_set_state", "mi_outgate_set_timing", "mi_outgate_last_launch_ms", "mi_gate_plan_host",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
 
@@ -167,6 +175,19 @@ def lib():
         L.mi_mixer_destroy.restype = None
         L.mi_mixer_is_stereo.argtypes = [vp]
         L.mi_mixer_process_device.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp, vp, vp]
+        L.mi_outgate_create.argtypes = [vp, vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_outgate_destroy.argtypes = [vp]
+        L.mi_outgate_destroy.restype = None
+        L.mi_outgate_set_rules.argtypes = [vp, vp]
+        L.mi_outgate_process_device.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.mi_outgate_download.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.mi_outgate_state_size.argtypes = [vp]
+        L.mi_outgate_state_size.restype = sz
+        L.mi_outgate_get_state.argtypes = [vp, vp, sz]
+        L.mi_outgate_set_state.argtypes = [vp, vp, sz]
+        L.mi_outgate_set_timing.argtypes = [vp, C.c_int]
+        L.mi_outgate_last_launch_ms.argtypes = [vp, vp]
+        L.mi_gate_plan_host.argtypes = [vp, C.c_int, vp, sz, C.c_int, vp, vp, vp, vp]
         L.mi_plan_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(ChannelCfg), C.c_int, C.POINTER(vp)]
         L.mi_plan_destroy.argtypes = [vp]
         L.mi_plan_destroy.restype = None
@@ -602,6 +623,94 @@ class Mixer:
             self.close()
         except Exception:
             pass
+
+
+class OutputGate:
+    """mi_outgate: the (row, batch) blocks the reference's outputs consume, packed on the device.  row_rule: one GATE_* per row
+    (row = stream * nch + channel); row_has_iq: truth value per row or None; max_blocks: capacity of the destination buffers in
+    blocks, 0 = rows * max_batches."""
+
+    def __init__(self, row_rule, row_has_iq=None, max_batches=1, max_blocks=0, gpu=0):
+        rule = np.ascontiguousarray(row_rule, dtype=np.uint8)
+        self.rows, self.max_batches = rule.size, max_batches
+        self.max_blocks = min(max_blocks, self.rows * max_batches) if max_blocks else self.rows * max_batches
+        has_iq = None if row_has_iq is None else np.array([1 if x else 0 for x in row_has_iq], np.uint8)
+        assert has_iq is None or has_iq.size == self.rows
+        self._h = C.c_void_p()
+        _check(lib().mi_outgate_create(rule.ctypes.data_as(C.c_void_p), None if has_iq is None else has_iq.ctypes.data_as(C.c_void_p),
+                                       self.rows, max_batches, max_blocks, gpu, C.byref(self._h)))
+
+    def set_rules(self, row_rule):
+        rule = np.ascontiguousarray(row_rule, dtype=np.uint8)
+        assert rule.size == self.rows
+        _check(lib().mi_outgate_set_rules(self._h, rule.ctypes.data_as(C.c_void_p)))
+
+    def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_blocks, d_index, d_row_first, d_count, d_iq_out=None,
+                       iq_row_stride=0, d_iq_blocks=None, hip_stream=None):
+        """Raw device pointers (ints), strides in floats (audio, raw I/Q) and bytes (flags); asynchronous on hip_stream."""
+        _check(lib().mi_outgate_process_device(self._h, d_waveout, row_stride, d_iq_out, iq_row_stride, d_axc, axc_stride, nbatches, d_blocks,
+                                               d_iq_blocks, d_index, d_row_first, d_count, hip_stream))
+
+    def download(self, hip_stream=None, want_iq=False):
+        """Results of the last process_device (enqueued on hip_stream): (blocks [k][WAVE_BATCH], iq_blocks [k][WAVE_BATCH][2] or None,
+        index [k][2] = (row, batch), row_first [rows + 1], count [2]) with k = count[1], the number of blocks stored."""
+        blocks = np.empty((self.max_blocks, WAVE_BATCH), np.float32)
+        iq = np.empty((self.max_blocks, WAVE_BATCH, 2), np.float32) if want_iq else None
+        index = np.empty((self.max_blocks, 2), np.uint32)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_outgate_download(self._h, hip_stream, blocks.ctypes.data_as(C.c_void_p), None if iq is None else iq.ctypes.data_as(C.c_void_p),
+                                         index.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+        k = int(count[1])
+        return blocks[:k], None if iq is None else iq[:k], index[:k], row_first, count
+
+    def state(self):
+        """The carried flags, one byte per row (mi_outgate_get_state)."""
+        n = lib().mi_outgate_state_size(self._h)
+        buf = np.zeros(n, np.uint8)
+        _check(lib().mi_outgate_get_state(self._h, buf.ctypes.data_as(C.c_void_p), n))
+        return buf
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        _check(lib().mi_outgate_set_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
+
+    def set_timing(self, on=True):
+        _check(lib().mi_outgate_set_timing(self._h, 1 if on else 0))
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of the rank pass, the scan and the block copy of the last call made with set_timing(True)"""
+        ms = (C.c_float * 3)()
+        _check(lib().mi_outgate_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            lib().mi_outgate_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gate_plan_host(row_rule, axc, carried=None):
+    """mi_gate_plan_host: the gate's index from flags on the host, no GPU.  axc: uint8 [rows][nbatches]; carried: uint8 [rows] or
+    None (all false).  Returns (index [k][2] = (row, batch), row_first [rows + 1], count [2], carried after the call)."""
+    rule = np.ascontiguousarray(row_rule, dtype=np.uint8)
+    axc = np.ascontiguousarray(axc, dtype=np.uint8)
+    assert axc.ndim == 2 and axc.shape[0] == rule.size
+    rows, nb = axc.shape
+    carried = np.zeros(rows, np.uint8) if carried is None else np.array(carried, dtype=np.uint8)
+    assert carried.size == rows
+    index = np.empty((rows * nb, 2), np.uint32)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_gate_plan_host(rule.ctypes.data_as(C.c_void_p), rows, axc.ctypes.data_as(C.c_void_p), nb, nb, carried.ctypes.data_as(C.c_void_p),
+                                   index.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+    return index[:int(count[0])], row_first, count, carried
 
 
 # ---- the BASELINE.json channel plans (SURVEY 8d) ----

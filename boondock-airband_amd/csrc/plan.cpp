@@ -9,6 +9,7 @@
 #include <cmath>
 #include <complex>
 #include <cstring>
+#include <string>
 
 namespace mi {
 namespace {
@@ -411,3 +412,48 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
 }
 
 }  // namespace mi
+
+// ---- output gate, host side (include/mi_airband.h "output gate"): the index mi_outgate_process_device computes, from flags the
+// caller already has.  One pass per row in batch order with the row's carried flag as output_t::active (output.cpp:518-520, 560,
+// 568-570); outgate.hip holds the device twin.
+namespace mi {
+std::string& last_error_ref();  // mi_airband.cpp
+}
+
+extern "C" int mi_gate_plan_host(const uint8_t* row_rule, int rows, const char* axc, size_t axc_stride, int nbatches, uint8_t* carried_inout,
+                                 mi_gate_block* index, uint32_t* row_first, uint32_t* count) {
+    auto fail = [](const char* msg) {
+        mi::last_error_ref() = msg;
+        return static_cast<int>(MI_ERR_INVALID);
+    };
+    if (!row_rule || !axc || !carried_inout || !index || !row_first || !count)
+        return fail("NULL argument");
+    if (rows < 1 || nbatches < 1 || axc_stride < static_cast<size_t>(nbatches))
+        return fail("gate plan needs rows >= 1 and 1 <= nbatches <= axc_stride");
+    if (static_cast<uint64_t>(rows) * static_cast<uint64_t>(nbatches) > UINT32_MAX)
+        return fail("gate plan: rows * nbatches does not fit the 32-bit block index");
+    for (int r = 0; r < rows; ++r)
+        if (row_rule[r] > MI_GATE_ALL)
+            return fail("gate rule out of range 0..3");
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first[r] = k;
+        const uint8_t rule = row_rule[r];
+        if (rule == MI_GATE_NONE)
+            continue;
+        bool active = carried_inout[r] != 0;
+        for (int b = 0; b < nbatches; ++b) {
+            const bool signal = axc[static_cast<size_t>(r) * axc_stride + b] != MI_NO_SIGNAL;
+            if (rule == MI_GATE_ALL || signal || (rule == MI_GATE_OPEN_TRAIL && active)) {
+                index[k].row = static_cast<uint32_t>(r);
+                index[k].batch = static_cast<uint32_t>(b);
+                ++k;
+            }
+            active = signal;
+        }
+        carried_inout[r] = active ? 1 : 0;
+    }
+    row_first[rows] = k;
+    count[0] = count[1] = k;
+    return MI_OK;
+}

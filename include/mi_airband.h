@@ -399,6 +399,68 @@ int mi_mixer_is_stereo(const mi_mixer* m);
 int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
                             float* d_left, float* d_right, char* d_axc_out, void* hip_stream);
 
+/* ---------------- output gate: the batches the outputs consume, compacted on the device ----------------
+ * Every output of the reference except a `continuous` one drops a batch whose axcindicate is NO_SIGNAL; the gate applies that
+ * rule on the device to the buffers mi_demod_process_device wrote and packs the (row, batch) blocks that travel, so that only
+ * they cross the link.  One rule per row (row = stream * nch + channel):
+ *   MI_GATE_NONE        nothing travels, and the row's carried flag is not touched (a row whose stream sits a call out under
+ *                       mi_demod_set_active_streams keeps its state)
+ *   MI_GATE_OPEN        axc[row][b] != MI_NO_SIGNAL: udp_stream and pulse, src/output.cpp:568-570, :581-582 (MI_AFC_UP / MI_AFC_DOWN
+ *                       are signal)
+ *   MI_GATE_OPEN_TRAIL  as MI_GATE_OPEN, or the batch before it was not MI_NO_SIGNAL: file and rawfile, src/output.cpp:518-520 with
+ *                       output_t::active set at :560.  "Before" crosses call boundaries through a carried flag per row, which
+ *                       starts false as output_t::active does
+ *   MI_GATE_ALL         every batch: a `continuous` output (the same lines, continuous == true)
+ * After a call the carried flag of every row whose rule is not MI_GATE_NONE is "the last batch of this call had a signal".
+ * (The wall-clock file rotation of close_if_necessary stays with the host.) */
+enum { MI_GATE_NONE = 0, MI_GATE_OPEN = 1, MI_GATE_OPEN_TRAIL = 2, MI_GATE_ALL = 3 };
+typedef struct { uint32_t row, batch; } mi_gate_block;
+typedef struct mi_outgate mi_outgate;
+
+/* row_rule [rows] MI_GATE_*; row_has_iq [rows] or NULL (no row has raw I/Q); 1 <= rows < 2^20, rows * max_batches < 2^24.
+ * max_blocks: capacity of the caller's destination buffers in blocks, 0 = rows * max_batches. */
+int mi_outgate_create(const uint8_t* row_rule, const uint8_t* row_has_iq, int rows, int max_batches, size_t max_blocks, int gpu,
+                      mi_outgate** out);
+void mi_outgate_destroy(mi_outgate* g);
+/* Other rules from the next call on; the carried flags stay.  Completes the work queued on the device first. */
+int mi_outgate_set_rules(mi_outgate* g, const uint8_t* row_rule /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches.  Inputs as mi_demod_process_device wrote them, strides as in
+ * mi_mixer_process_device: d_waveout [rows][row_stride] floats, d_iq_out [rows][iq_row_stride] floats ({re, im} pairs,
+ * 2 * WAVE_BATCH floats a batch) or NULL, d_axc [rows][axc_stride]; audio and I/Q 16-byte aligned with strides that are multiples
+ * of 4 floats.  Outputs, all in device memory:
+ *   d_blocks     [max_blocks][WAVE_BATCH]  the travelling audio blocks densely packed, rows ascending and batches ascending within
+ *                a row: one row's blocks are one contiguous slice in time order (16-byte aligned)
+ *   d_iq_blocks  [max_blocks][WAVE_BATCH][2]  for the same k the block of d_iq_out where row_has_iq[row] is set, untouched where it
+ *                is not; may be NULL when d_iq_out is NULL or no row has raw I/Q (16-byte aligned)
+ *   d_index      [max_blocks]  {row, batch} of block k (8-byte aligned)
+ *   d_row_first  [rows + 1]  exclusive prefix of the rows' block counts
+ *   d_count      [2]  number of travelling blocks, and min(that, max_blocks) = the number stored
+ * A block whose position is at or beyond max_blocks is not stored and nothing is written there in any destination.
+ * Asynchronous on `hip_stream`, no host synchronisation; three kernels without atomics, so the order is deterministic. */
+int mi_outgate_process_device(mi_outgate* g, const float* d_waveout, size_t row_stride, const float* d_iq_out, size_t iq_row_stride,
+                              const char* d_axc, size_t axc_stride, int nbatches, float* d_blocks, float* d_iq_blocks,
+                              mi_gate_block* d_index, uint32_t* d_row_first, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_outgate_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the two
+ * counts, then copies exactly count[1] blocks (and their raw I/Q blocks if iq_blocks is not NULL), their index entries and
+ * row_first to the host.  The destinations hold max_blocks blocks / entries (row_first: rows + 1); pinned ones are written by the
+ * copy engine directly.  blocks, iq_blocks, index and row_first may each be NULL (not wanted).  The one place that synchronises. */
+int mi_outgate_download(mi_outgate* g, void* hip_stream, float* blocks, float* iq_blocks, mi_gate_block* index, uint32_t* row_first,
+                        uint32_t* count /* [2] */);
+/* Checkpoint / resume of the carried flags, `rows` bytes (0 / 1): the companion of mi_demod_get_state, so that a checkpointed
+ * replay resumes with the same trailing batches.  Both complete the work queued on the device first. */
+size_t mi_outgate_state_size(const mi_outgate* g);
+int mi_outgate_get_state(mi_outgate* g, void* buf, size_t len);
+int mi_outgate_set_state(mi_outgate* g, const void* buf, size_t len);
+/* (diagnostic) on != 0: HIP events are recorded around each of the three launches of the calls made from now on;
+ * mi_outgate_last_launch_ms waits for the last such call and gives ms[3] = {rank pass, scan, block copy}.  tools/gate_rate.py. */
+int mi_outgate_set_timing(mi_outgate* g, int on);
+int mi_outgate_last_launch_ms(mi_outgate* g, float* ms /* [3] */);
+/* The same index on the host, for a caller that already has the flags: no GPU and no HIP call.  axc [rows][axc_stride];
+ * carried_inout [rows] (0 / 1) is read and updated as the gate's own flags are; index holds up to rows * nbatches entries;
+ * row_first [rows + 1]; count[0] = count[1] = the number of travelling blocks (there is no capacity here). */
+int mi_gate_plan_host(const uint8_t* row_rule, int rows, const char* axc, size_t axc_stride, int nbatches, uint8_t* carried_inout,
+                      mi_gate_block* index, uint32_t* row_first, uint32_t* count /* [2] */);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
