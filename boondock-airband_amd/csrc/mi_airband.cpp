@@ -65,6 +65,40 @@ struct mi_plan {
     mi::Plan plan;
 };
 
+// The timing events of a call.  The numbers are public (mi_demod_event_ms takes those of ChunkEv) and stay as they are.
+enum CallEv {  // per call (CallSet::ev)
+    kEvBegin = 0,
+    kEvStage1Done = 1,
+    kEvDone = 2,
+    kEvSerialBegin = 3,  // serial k_demod begins (pipelined serial calls, mixed plans)
+    kEvSerialEnd = 4,    // ... ends (mixed plans)
+    kEvPerCall
+};
+enum ChunkEv {  // per chunk of a time-parallel call (CallSet::chunk_ev)
+    kEvStage1Begin = 0,  // front stream: stage 1
+    kEvStage1End = 1,
+    kEvFullBegin = 11,  // ... k_tp_full
+    kEvFullEnd = 2,
+    kEvCoreBegin = 3,  // aux stream: the core chain
+    kEvCoreEnd = 4,
+    kEvSegBegin = 5,  // segment stream: the segment pass
+    kEvSegEnd = 12,
+    kEvSegLaunched = 6,  // ... all segment launches of the chunk done
+    kEvScanBegin = 10,   // caller's stream: scan#0
+    kEvScanEnd = 7,
+    kEvFixEnd = 8,     // ... fix#0 + redo#0
+    kEvFinishEnd = 9,  // ... finish
+    kEvPerChunk = 13
+};
+static_assert(kEvPerCall == 5 && kEvStage1Begin == 0 && kEvStage1End == 1 && kEvFullEnd == 2 && kEvCoreBegin == 3 && kEvCoreEnd == 4 &&
+                  kEvSegBegin == 5 && kEvSegLaunched == 6 && kEvScanEnd == 7 && kEvFixEnd == 8 && kEvFinishEnd == 9 && kEvScanBegin == 10 &&
+                  kEvFullBegin == 11 && kEvSegEnd == 12 && kEvPerChunk == 13,
+              "callers of mi_demod_event_ms pass these numbers");
+// The stage-2 path of a call.  mi_demod_last_path returns kPathSerial / kPathTimeParallel; a CallSet also tells a pipelined serial
+// call apart; kPathAfc is a schedule of enqueue() only (an AFC call is recorded, and timed, as a serial one).
+enum Path { kPathSerial = 0, kPathTimeParallel = 1, kPathSerialPipelined = 2, kPathAfc = 3 };
+static_assert(kPathSerial == 0 && kPathTimeParallel == 1 && kPathSerialPipelined == 2, "mi_demod_last_path returns the first two");
+
 struct mi_demod {
     mi::Plan plan;
     int gpu = 0;
@@ -74,7 +108,7 @@ struct mi_demod {
     mi::Stream own_stream;
     // The time-parallel path keeps kSets sets of its per-call scratch (magnitude planes, block aggregates, core snapshots,
     // segment records, timing events) and cycles through them: stage 1, the aggregates, the core chain and the segment
-    // passes of a call never touch what the tails of the two calls before it still read, so calls overlap (see enqueue()).
+    // passes of a call never touch what the tails of the two calls before it still read, so calls overlap (see enqueue_time_parallel()).
     // `cur` is the set of the last call; the serial path stays on it.
     int cur = 0;
     // a call writes the set of the call six back: the host may then keep four or five calls queued behind the one whose timings it
@@ -83,7 +117,7 @@ struct mi_demod {
     // not fall below (2.8 + 0.85) / 3 = 1.2 ms -- which is what the step took once the chain itself was down to 1.03
     static constexpr int kSets = 6;
     static_assert(kSets % 2 == 0, "a call's scratch set picks its complex plane set by parity: the two must stay in step when the sets wrap");
-    static constexpr int kMaxChunks = 64, kEvPerChunk = 13, kSegStreams = 1;
+    static constexpr int kMaxChunks = 64, kSegStreams = 1;
     struct CallSet {  // scratch set q: what one call in flight owns of the device, and what later calls have to know of it
         mi::DevBuf<float> mag;    // magnitude planes (d_mag is a view of the last call's)
         mi::DevBuf<float> carry;  // audio lookahead: a time-parallel call writes its own set's (the next call's segment pass may run
@@ -92,14 +126,11 @@ struct mi_demod {
         mi::DevBuf<float> blk_fe, blk_fm, blk_x0, blk_xm;  // block aggregates
         mi::DevBuf<mi::TpCore> core;                       // core snapshots
         mi::DevBuf<int> rec;  // segment records: the segment passes of the next call write theirs while this call's tail reads its own
-        // per call: 0 begin, 1 stage 1 done, 2 call done, 3 serial k_demod begins (pipelined serial calls, mixed plans), 4 ... ends (mixed plans)
-        mi::Event ev[5];
-        // kEvPerChunk per chunk: 0 stage1 begin, 1 stage1 end, 2 k_tp_full end (front stream), 3 core begin, 4 core end (aux stream),
-        // 5 seg begin, 12 seg end, 6 all segment launches of the chunk done (segment stream), 10 scan#0 begin, 7 scan#0 end,
-        // 8 fix#0 + redo#0 end, 9 finish end (caller's stream), 11 k_tp_full begin
-        std::vector<mi::Event> chunk_ev;
-        uint64_t seq = 0;    // call number that last used this set (0 = never)
-        int path = 0;        // ... and its path: 0 serial kernel, 1 time-parallel, 2 pipelined serial
+        mi::Event ev[kEvPerCall];          // indexed by CallEv
+        std::vector<mi::Event> chunk_ev;   // kEvPerChunk per chunk, indexed by ChunkEv
+        hipEvent_t chunk(int i, ChunkEv k) const { return chunk_ev[static_cast<size_t>(i) * kEvPerChunk + k]; }
+        uint64_t seq = 0;          // call number that last used this set (0 = never)
+        Path path = kPathSerial;   // ... and its path (an AFC call: kPathSerial)
         bool mixed = false;  // ... with the serial kernel beside the chain (a mixed plan)
         int chunks = 0;      // ... the number of its chunks
         uint32_t nseg = 0;   // ... and of its segments
@@ -142,11 +173,11 @@ struct mi_demod {
     bool early_input = false;  // MI_OPT_EARLY_INPUT: the IQ of a call is valid when the call is made
     bool chain_live = false;   // d_core_carry holds the chain state at the end of the previous call (it was time-parallel)
     mi::Stream seg_stream[kSegStreams];  // the speculative segment passes (need core(i) only)
-    // MI_OPT_RESERVE_CUS: twins of the front and segment streams whose kernels keep off the last `reserve_cus` CUs (see enqueue)
+    // MI_OPT_RESERVE_CUS: twins of the front and segment streams whose kernels keep off the last `reserve_cus` CUs (see enqueue_time_parallel)
     mi::Stream front_stream_m;
     mi::Stream seg_stream_m[kSegStreams];
     int opt_reserve_cus = -1;  // -1 auto: 32 for handles of up to 64 rows, none beyond; 0 none
-    // MI_OPT_SPLIT_CUS: pipelined serial calls: stage 1 keeps off the last n CUs, k_demod runs on them alone; -1 auto (see enqueue)
+    // MI_OPT_SPLIT_CUS: pipelined serial calls: stage 1 keeps off the last n CUs, k_demod runs on them alone; -1 auto (see enqueue_serial_pipelined)
     int opt_split_cus = -1;
     int split_state = 0;  // 0 undecided, 1 the two CU-masked streams exist, 2 none
     mi::Stream ps_front_m, ps_demod_m;
@@ -228,7 +259,7 @@ struct mi_demod {
     mi::Event ev_cplx_free[2];           // the serial kernel of a mixed call has read complex plane set p
     bool cplx_busy[2] = {};
     bool ser_head_next = false;          // the serial kernel of the last (mixed) call left its rows' carried samples in the next plane set
-    int last_path = 0;  // 0 = serial kernel, 1 = time-parallel
+    Path last_path = kPathSerial;  // kPathSerial (any serial kernel) or kPathTimeParallel
     mi::DevBuf<int> d_rows;
     const float* prev_out_lo = nullptr;  // view: the caller's audio buffer of the previous call (its tail may still be writing it)
     const float* prev_out_hi = nullptr;
@@ -398,7 +429,6 @@ int lanes_per_wave_for(const mi_demod* h, int rows) {
     return std::min(64, std::max(1, lpw));
 }
 
-// shared by both entry points; everything is enqueued on `s`
 // the second plane set of the pipelined serial path, allocated the first time it is wanted
 bool serial_sets_ready(mi_demod* h) {
     if (h->set[1].mag && (h->d_cplx_set[1] || !h->d_cplx_set[0]))
@@ -426,27 +456,35 @@ bool serial_sets_ready(mi_demod* h) {
     return true;
 }
 
-int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t valid_bytes, int nbatches, float* d_wmain, size_t wmain_stride,
-            float2* d_iq_out, size_t iq_out_stride, char* d_axc, hipStream_t s, hipEvent_t iq_ready = nullptr) {
-    // iq_ready (host-buffer entry, calls in flight): the IQ becomes valid when this event fires -- the streams that read it wait
-    // for it and for nothing else, exactly as if the caller had vouched for the bytes (MI_OPT_EARLY_INPUT)
-    const bool early_input = h->early_input || iq_ready != nullptr;
-    // A masked call (mi_demod_set_active_streams): one stage-1 launch and the serial stage 2 over the active streams, enqueued as a
-    // call without a predecessor (heads in place first, no overlap).  It leaves chain_live and serial_pipe clear, so the full
-    // call after it takes nothing from the previous call's arrays (prev_mag, prev_blk_*, prev_core, spec_head, xmax_prev: they
-    // would not hold every row) and seeds its chain from the ChanState rows.
-    const bool partial = h->masked;
-    if (partial && h->first_call)
-        return fail(MI_ERR_INVALID, "the handle's first call needs every stream active");
-    const int act_streams = partial ? h->nactive : h->nstreams;
-    const int act_rows = act_streams * h->nch;
-    const int nfft = n_fft_for(h, nbatches);
-    mi::ChannelizeArgs ca{};
-    ca.iq = d_iq;
-    ca.stream_stride = stream_stride;
-    ca.valid_bytes = valid_bytes;
+// One call on its way to the GPU: what every path reads of it
+struct Call {
+    // the arguments of enqueue()
+    const unsigned char* d_iq;
+    size_t stream_stride, valid_bytes;
+    int nbatches;
+    float* d_wmain;
+    size_t wmain_stride;
+    float2* d_iq_out;
+    size_t iq_out_stride;
+    char* d_axc;
+    hipStream_t s;
+    hipEvent_t iq_ready;
+    bool early_input;  // the IQ is valid when the streams that read it have waited for iq_ready (if any) and for nothing else
+    bool partial;      // a masked call: some streams sit it out
+    int act_streams, act_rows;
+    mi::ChannelizeArgs ca;   // stage 1 of the whole call on the planes of the last call (the paths point it elsewhere)
+    mi::DemodArgs da;        // ... and the serial stage 2
+    const mi::Event* evc;    // the per-call events (CallEv) of the scratch set this call records on
+};
+
+void make_channelize_args(mi_demod* h, Call& call) {
+    const bool partial = call.partial;
+    mi::ChannelizeArgs& ca = call.ca;
+    ca.iq = call.d_iq;
+    ca.stream_stride = call.stream_stride;
+    ca.valid_bytes = call.valid_bytes;
     ca.hop_bytes = static_cast<uint32_t>(h->plan.hop_bytes);
-    ca.nfft = static_cast<uint32_t>(nfft);
+    ca.nfft = static_cast<uint32_t>(n_fft_for(h, call.nbatches));
     ca.mag = h->d_mag;
     ca.cplx = h->d_cplx;
     ca.plane_stride = h->plane_stride;
@@ -488,15 +526,16 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     ca.nch = h->nch;
     ca.n_iq_rows = h->plan.n_iq_rows;
     ca.streams = partial ? h->d_act_streams.get() : nullptr;
-    ca.nactive = act_streams;
+    ca.nactive = call.act_streams;
     h->last_stage1 = (ca.l64.enabled && !h->plan.any_afc) ? (ca.l64_jit ? MI_STAGE1_LANE_PLAN : MI_STAGE1_LANE_FULL)
                      : ((ca.prune.enabled && h->plan.log2n == 9 && !h->plan.any_afc) ? MI_STAGE1_EXCHANGE_PRUNED : MI_STAGE1_EXCHANGE_FULL);
-    const int env = h->opt_tp;
-    const bool use_tp = !partial && h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
-                        (env == 1 || (nbatches >= (h->tp_mixed ? kMixedMinBatches : kTpMinBatches) && h->tp_rows <= kTpAutoMaxRows));
-    ca.xmax = nullptr;  // (the time-parallel branch points it at its scratch set)
+    ca.xmax = nullptr;  // (the time-parallel path points it at its scratch set)
+}
 
-    mi::DemodArgs da{};
+void make_demod_args(const mi_demod* h, Call& call) {
+    const bool partial = call.partial;
+    const int nbatches = call.nbatches, act_rows = call.act_rows;
+    mi::DemodArgs& da = call.da;
     da.nstreams = h->nstreams;
     da.nch = h->nch;
     da.rows = partial ? h->d_act_rows.get() : nullptr;
@@ -511,12 +550,12 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     da.mag_head = h->d_mag;
     da.cplx_head = h->d_cplx;
     da.plane_stride = h->plane_stride;
-    da.wmain = d_wmain;
-    da.wmain_stride = wmain_stride;
+    da.wmain = call.d_wmain;
+    da.wmain_stride = call.wmain_stride;
     da.carry = h->d_carry;
-    da.iq_out = d_iq_out;
-    da.iq_out_stride = iq_out_stride;
-    da.axc = d_axc;
+    da.iq_out = call.d_iq_out;
+    da.iq_out_stride = call.iq_out_stride;
+    da.axc = call.d_axc;
     da.axc_stride = static_cast<uint32_t>(nbatches);
     da.cp = h->d_cp;
     da.st = h->d_state;
@@ -537,512 +576,597 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
     da.pre_wave = h->opt_pre_wave < 0 ? (act_rows <= 256 ? 1 : (act_rows <= 1024 ? 2 : 0)) : std::min(2, h->opt_pre_wave);
     da.audio_wave = h->opt_audio_wave ? 1 : 0;
     da.pre_timeouts = h->d_pre_timeouts;
+}
 
-    // the serial kernels expect the carried AGC_EXTRA samples of every row at the front of the planes they work on
-    auto head_in_place = [&]() -> int {
-        if (h->head_off != 0) {
-            HIP_TRY(mi::launch_move_head(h->d_mag, h->d_mag + h->head_off, h->plane_stride, h->rows, s));
-            h->head_off = 0;
+// The path of a call.  The conditions are evaluated left to right and no further than they decide: serial_sets_ready() allocates the
+// second plane set, which a handle gets only when a call of its own is about to use it.
+Path choose_path(mi_demod* h, const Call& call) {
+    const int env = h->opt_tp;
+    if (!call.partial && h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
+        (env == 1 || (call.nbatches >= (h->tp_mixed ? kMixedMinBatches : kTpMinBatches) && h->tp_rows <= kTpAutoMaxRows)))
+        return kPathTimeParallel;
+    if (h->plan.any_afc)
+        return kPathAfc;
+    // (a handle whose plan the time-parallel path could take as well -- many rows, or MI_OPT_TIME_PARALLEL = 0 -- pipelines its serial
+    //  calls like any other as long as its planes are where that path keeps them: never after a time-parallel call)
+    if (!call.partial && call.early_input && !h->first_call &&
+        (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) && serial_sets_ready(h))
+        return kPathSerialPipelined;
+    return kPathSerial;
+}
+
+// the serial kernels expect the carried AGC_EXTRA samples of every row at the front of the planes they work on
+int head_in_place(mi_demod* h, const Call& call) {
+    if (h->head_off != 0) {
+        HIP_TRY(mi::launch_move_head(h->d_mag, h->d_mag + h->head_off, h->plane_stride, h->rows, call.s));
+        h->head_off = 0;
+    }
+    return MI_OK;
+}
+
+// stage 1 of the windows [f0, f0 + cc.nfft) of this call -- or, for mi_demod_process_planes, the caller's planes in their place
+hipError_t stage1_launch(const mi_demod* h, const mi::ChannelizeArgs& cc, uint32_t f0, hipStream_t st) {
+    if (!h->inject_mag)
+        return mi::launch_channelize(cc, h->plan.log2n, h->plan.dev.sfmt, h->nstreams, st);
+    hipError_t e = hipMemcpy2DAsync(cc.mag + cc.plane_off, cc.plane_stride * 4, h->inject_mag + f0, h->inject_count * 4, static_cast<size_t>(cc.nfft) * 4,
+                                    static_cast<size_t>(h->rows), hipMemcpyDeviceToDevice, st);
+    const size_t zrows = static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows;
+    if (e == hipSuccess && zrows && h->inject_cplx)
+        e = hipMemcpy2DAsync(cc.cplx + cc.plane_off, cc.plane_stride * 8, h->inject_cplx + f0, h->inject_count * 8, static_cast<size_t>(cc.nfft) * 8, zrows,
+                             hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && cc.xmax)
+        e = mi::launch_row_max(cc.mag + cc.plane_off, cc.plane_stride, cc.nfft, h->rows, cc.xmax, st);
+    return e;
+}
+
+// CU mask of a stream (hipExtStreamCreateWithCUMask) over the CUs [lo, hi) of ncu
+std::vector<uint32_t> cu_mask(int ncu, int lo, int hi) {
+    std::vector<uint32_t> mask(static_cast<size_t>((ncu + 31) / 32), 0u);
+    for (int i = lo; i < hi; ++i)
+        mask[static_cast<size_t>(i) / 32] |= 1u << (i % 32);
+    return mask;
+}
+
+hipError_t cu_stream_create(mi::Stream& st, const std::vector<uint32_t>& mask) {
+    return hipExtStreamCreateWithCUMask(st.put(), static_cast<uint32_t>(mask.size()), mask.data());
+}
+
+// Chunk i of a time-parallel call covers units [bound[i], bound[i+1]): `want` chunks (at most one per unit), each `ratio` times the
+// one before it
+std::vector<uint32_t> tp_chunk_bounds(uint32_t units, int want, double ratio) {
+    std::vector<uint32_t> bound{0};
+    if (units > 0) {
+        want = std::min<int>(want, static_cast<int>(units));
+        double total = 0.0, w = 1.0;
+        for (int i = 0; i < want; ++i, w *= ratio)
+            total += w;
+        double acc = 0.0;
+        w = 1.0;
+        for (int i = 0; i < want; ++i, w *= ratio) {
+            acc += w;
+            uint32_t bd = (i == want - 1) ? units : static_cast<uint32_t>(acc / total * units + 0.5);
+            bd = std::max(bd, bound.back() + 1);
+            bd = std::min(bd, units - static_cast<uint32_t>(want - 1 - i));
+            bound.push_back(bd);
         }
-        return MI_OK;
+    } else {
+        bound.push_back(0);
+    }
+    return bound;
+}
+
+// what every chunk of a time-parallel call on scratch set q shares (the chunks add their own ranges)
+mi::TpArgs make_tp_args(const mi_demod* h, const Call& call, int q, bool overlap, bool spec_head) {
+    const uint32_t n = call.da.nsteps, L = h->tp_L;
+    mi::TpArgs ta{};
+    ta.rows = h->d_rows;
+    ta.nrows = h->tp_rows;
+    ta.nch = h->nch;
+    ta.nsteps = n;
+    ta.nbatches = call.da.nbatches;
+    ta.nblk = n / 16;
+    ta.L = L;
+    ta.nseg = (n + L - 1) / L;
+    ta.mag = h->set[q].mag;
+    ta.plane_stride = h->plane_stride;
+    ta.wmain = call.d_wmain;
+    ta.wmain_stride = call.wmain_stride;
+    ta.carry = h->set[q].carry;
+    ta.carry_prev = h->d_carry;
+    ta.axc = call.d_axc;
+    ta.cp = h->d_cp;
+    ta.st = h->d_state;
+    ta.stats = h->d_stats;
+    ta.xmax = h->set[q].xmax;
+    ta.blk_fe = h->set[q].blk_fe;
+    ta.blk_fm = h->set[q].blk_fm;
+    ta.blk_x0 = h->set[q].blk_x0;
+    ta.blk_xm = h->set[q].blk_xm;
+    ta.core = h->set[q].core;
+    ta.core_carry = h->d_core_carry;
+    ta.full0 = h->d_full0;
+    ta.fullbound = h->d_fullbound;
+    ta.prev_mag = overlap ? h->d_mag : nullptr;  // (still the previous call's planes here)
+    ta.prev_n = h->head_off;
+    ta.xmax_prev = h->set[h->cur].xmax;
+    ta.rec = h->set[q].rec;
+    ta.rec_stride = static_cast<size_t>(h->rows) * h->tp_max_seg;
+    ta.tstart = h->d_tstart;
+    ta.need = h->d_need;
+    ta.redo = h->d_redo;
+    ta.fin = h->d_fin;
+    ta.diag = h->d_diag;
+    ta.seg_lpw = h->opt_tp_lpw;
+    ta.core_split = (h->opt_core_split && h->core_split_ok) ? 1 : 0;
+    ta.core_lead = h->opt_core_lead;
+    ta.core_guess = h->opt_core_guess;
+    ta.core_decay = h->opt_core_decay;
+    ta.core_lean = h->opt_core_lean;
+    ta.agc_hint = h->opt_agc_hint;
+    ta.eager_samples = h->opt_tp_eager;
+    ta.spec_head = spec_head ? 1 : 0;
+    ta.prev_blk_fe = h->set[h->cur].blk_fe, ta.prev_blk_fm = h->set[h->cur].blk_fm;
+    ta.prev_blk_x0 = h->set[h->cur].blk_x0, ta.prev_blk_xm = h->set[h->cur].blk_xm;
+    ta.prev_core = h->set[h->cur].core;
+    ta.prev_nblk = h->head_off / 16;
+    ta.prev_nseg = h->set[h->cur].nseg;
+    return ta;
+}
+
+// ---- time-parallel stage 2, pipelined over chunks of the call and across calls ----
+// The exact core chain (k_tp_core) is serial per channel and latency bound on 8 waves; everything else is wide.
+//   front stream : head carry, then per chunk stage 1 + k_tp_full           (needs the IQ; chunk 0's k_tp_full needs
+//                                                                             the chain state at the call start)
+//   aux stream   : k_tp_core(i) as soon as chunk i's aggregates exist         (one chain across chunks AND calls)
+//   seg streams  : k_tp_seg(i) as soon as core(i) is done and the previous call has left its final state
+//   caller's     : audio head, then scan / fix / redo / finish of chunk i after seg(i) and the chain of chunk i-1
+// With MI_OPT_EARLY_INPUT the front and aux streams do not wait for the caller's stream, i.e. for the segment
+// and fix passes of the previous call: consecutive calls overlap and the core chain runs back to back.
+int enqueue_time_parallel(mi_demod* h, Call& call) {
+    const hipStream_t s = call.s;
+    mi::ChannelizeArgs& ca = call.ca;
+    const int q = (h->cur + 1) % mi_demod::kSets;  // the scratch set of this call
+    mi_demod::CallSet& cs = h->set[q];
+    float* const planes = cs.mag;
+    const bool overlap = call.early_input && h->chain_live && !h->first_call;
+    const float* out_lo = call.d_wmain;
+    const float* out_hi = call.d_wmain + static_cast<size_t>(h->rows - 1) * call.wmain_stride + call.da.nsteps;
+    // segment passes may run under the previous call's tail only if they write a different audio buffer
+    const bool seg_early = overlap && (out_hi <= h->prev_out_lo || out_lo >= h->prev_out_hi);
+    const uint32_t n = call.da.nsteps;
+    const uint32_t L = h->tp_L;
+    const uint32_t chunk_unit = mi::tp_chunk_unit(L);
+    const uint32_t units = n / chunk_unit;
+    // Chunk sizes grow geometrically: a short first chunk gets the serial core chain going early (its stage 1 +
+    // aggregates are all that precedes it), later chunks are long because every wide pass has a fixed latency per
+    // launch.  MI_AIRBAND_TP_CHUNKS / MI_AIRBAND_TP_RATIO override the measured defaults.
+    // An isolated call: 3 chunks growing by 1.5x (round 1; see below).  When calls overlap the chain is already running and stage 1 of this
+    // call hides under the previous call: one chunk then -- every chunk boundary costs the chain a launch gap and the
+    // tail passes on the caller's stream (scan / fix / redo / settle / finish) their fixed latencies once more, and with
+    // two chunks those passes took as long per call as the chain itself (1 / 2 / 3 / 4 chunks over 20 steps: 2.21 / 2.40 /
+    // 2.9 / 3.5 ms per step; over 5 steps, where the last call's drain weighs more, 1 and 2 are level).
+    // (that is the few-rows case, where the per-channel chain is the critical path; with hundreds of rows the wide passes
+    // are, and two chunks let stage 1 of the second run under the segment / fix passes of the first: 64 streams x 8
+    // channels 168 vs 147 GS/s)
+    // (isolated calls, round 2: with the chain on three waves an isolated call is a sum of fixed latencies -- stage 1, aggregates,
+    // chain, segment pass, scan, fix, finish -- and every chunk adds the last four once more: 2 chunks, the second twice the
+    // first, 3.7 instead of 4.1 ms per 64-s call and 2.6 instead of 3.3 per 16-s call; with many rows 2, 3 and 4 are level)
+    int want = overlap ? (h->tp_rows <= 64 ? 1 : 2) : (h->tp_rows <= 64 ? 2 : 3);
+    double ratio = overlap ? 1.0 : (h->tp_rows <= 64 ? 2.0 : 1.5);
+    if (h->opt_tp_chunks > 0)
+        want = h->opt_tp_chunks;
+    if (h->opt_tp_ratio > 0)
+        ratio = h->opt_tp_ratio;
+    const std::vector<uint32_t> bound = tp_chunk_bounds(units, want, ratio);
+    const int C = static_cast<int>(bound.size()) - 1;
+    if (C > mi_demod::kMaxChunks)
+        return fail(MI_ERR_INVALID, "too many chunks");
+    while (static_cast<int>(cs.chunk_ev.size()) < C * kEvPerChunk) {
+        mi::Event e;
+        HIP_TRY(hipEventCreate(e.put()));
+        cs.chunk_ev.push_back(std::move(e));
+    }
+    call.evc = cs.ev;
+    const mi::Event* const evc = call.evc;
+    // Speculative head: when this call's segment pass may run under the previous call's tail at all (seg_early) and that call
+    // left what the warm-up needs (aggregates, core states at boundaries of the same segment length, TP_W steps of them),
+    // no lane starts from the carried ChanState and no launch of the pass waits for the previous call.
+    const bool spec_head = seg_early && h->opt_spec_head && h->head_off >= mi::TP_W && h->set[h->cur].seq &&
+                           h->set[h->cur].path == kPathTimeParallel;
+    const mi::TpArgs ta = make_tp_args(h, call, q, overlap, spec_head);
+    cs.nseg = ta.nseg;
+    auto chunk = [&](int i) {
+        mi::TpArgs c = ta;
+        c.step0 = bound[static_cast<size_t>(i)] * chunk_unit;
+        c.step1 = (i == C - 1) ? n : bound[static_cast<size_t>(i) + 1] * chunk_unit;
+        c.seg0 = c.step0 / L;
+        c.seg1 = (c.step1 + L - 1) / L;
+        c.blk0 = c.step0 / 16;
+        c.blk1 = c.step1 / 16;
+        c.bat0 = c.step0 / mi::kWaveBatch;
+        c.bat1 = c.step1 / mi::kWaveBatch;
+        c.first_chunk = i == 0;
+        c.last_chunk = i == C - 1;
+        return c;
     };
-    // stage 1 of the windows [f0, f0 + cc.nfft) of this call -- or, for mi_demod_process_planes, the caller's planes in their place
-    auto stage1_launch = [&](const mi::ChannelizeArgs& cc, uint32_t f0, hipStream_t st) -> hipError_t {
-        if (!h->inject_mag)
-            return mi::launch_channelize(cc, h->plan.log2n, h->plan.dev.sfmt, h->nstreams, st);
-        hipError_t e = hipMemcpy2DAsync(cc.mag + cc.plane_off, cc.plane_stride * 4, h->inject_mag + f0, h->inject_count * 4, static_cast<size_t>(cc.nfft) * 4,
-                                        static_cast<size_t>(h->rows), hipMemcpyDeviceToDevice, st);
-        const size_t zrows = static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows;
-        if (e == hipSuccess && zrows && h->inject_cplx)
-            e = hipMemcpy2DAsync(cc.cplx + cc.plane_off, cc.plane_stride * 8, h->inject_cplx + f0, h->inject_count * 8, static_cast<size_t>(cc.nfft) * 8, zrows,
-                                 hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && cc.xmax)
-            e = mi::launch_row_max(cc.mag + cc.plane_off, cc.plane_stride, cc.nfft, h->rows, cc.xmax, st);
-        return e;
-    };
-    const mi::Event* evc = h->set[h->cur].ev;  // (the time-parallel and the pipelined serial branch switch to the next set)
-    bool pipelined_serial = false;
-    if (use_tp) {
-        // ---- time-parallel stage 2, pipelined over chunks of the call and across calls ----
-        // The exact core chain (k_tp_core) is serial per channel and latency bound on 8 waves; everything else is wide.
-        //   front stream : head carry, then per chunk stage 1 + k_tp_full           (needs the IQ; chunk 0's k_tp_full needs
-        //                                                                             the chain state at the call start)
-        //   aux stream   : k_tp_core(i) as soon as chunk i's aggregates exist         (one chain across chunks AND calls)
-        //   seg streams  : k_tp_seg(i) as soon as core(i) is done and the previous call has left its final state
-        //   caller's     : audio head, then scan / fix / redo / finish of chunk i after seg(i) and the chain of chunk i-1
-        // With MI_OPT_EARLY_INPUT the front and aux streams do not wait for the caller's stream, i.e. for the segment
-        // and fix passes of the previous call: consecutive calls overlap and the core chain runs back to back.
-        const int q = (h->cur + 1) % mi_demod::kSets;  // the scratch set of this call
-        float* const planes = h->set[q].mag;
-        const bool overlap = early_input && h->chain_live && !h->first_call;
-        const float* out_lo = d_wmain;
-        const float* out_hi = d_wmain + static_cast<size_t>(h->rows - 1) * wmain_stride + da.nsteps;
-        // segment passes may run under the previous call's tail only if they write a different audio buffer
-        const bool seg_early = overlap && (out_hi <= h->prev_out_lo || out_lo >= h->prev_out_hi);
-        const uint32_t n = da.nsteps;
-        const uint32_t L = h->tp_L;
-        const uint32_t chunk_unit = mi::tp_chunk_unit(L);
-        const uint32_t units = n / chunk_unit;
-        // Chunk sizes grow geometrically: a short first chunk gets the serial core chain going early (its stage 1 +
-        // aggregates are all that precedes it), later chunks are long because every wide pass has a fixed latency per
-        // launch.  MI_AIRBAND_TP_CHUNKS / MI_AIRBAND_TP_RATIO override the measured defaults.
-        // An isolated call: 3 chunks growing by 1.5x (round 1; see below).  When calls overlap the chain is already running and stage 1 of this
-        // call hides under the previous call: one chunk then -- every chunk boundary costs the chain a launch gap and the
-        // tail passes on the caller's stream (scan / fix / redo / settle / finish) their fixed latencies once more, and with
-        // two chunks those passes took as long per call as the chain itself (1 / 2 / 3 / 4 chunks over 20 steps: 2.21 / 2.40 /
-        // 2.9 / 3.5 ms per step; over 5 steps, where the last call's drain weighs more, 1 and 2 are level).
-        // (that is the few-rows case, where the per-channel chain is the critical path; with hundreds of rows the wide passes
-        // are, and two chunks let stage 1 of the second run under the segment / fix passes of the first: 64 streams x 8
-        // channels 168 vs 147 GS/s)
-        // (isolated calls, round 2: with the chain on three waves an isolated call is a sum of fixed latencies -- stage 1, aggregates,
-        // chain, segment pass, scan, fix, finish -- and every chunk adds the last four once more: 2 chunks, the second twice the
-        // first, 3.7 instead of 4.1 ms per 64-s call and 2.6 instead of 3.3 per 16-s call; with many rows 2, 3 and 4 are level)
-        int want = overlap ? (h->tp_rows <= 64 ? 1 : 2) : (h->tp_rows <= 64 ? 2 : 3);
-        double ratio = overlap ? 1.0 : (h->tp_rows <= 64 ? 2.0 : 1.5);
-        if (h->opt_tp_chunks > 0)
-            want = h->opt_tp_chunks;
-        if (h->opt_tp_ratio > 0)
-            ratio = h->opt_tp_ratio;
-        std::vector<uint32_t> bound{0};  // chunk i covers units [bound[i], bound[i+1])
-        if (units > 0) {
-            want = std::min<int>(want, static_cast<int>(units));
-            double total = 0.0, w = 1.0;
-            for (int i = 0; i < want; ++i, w *= ratio)
-                total += w;
-            double acc = 0.0;
-            w = 1.0;
-            for (int i = 0; i < want; ++i, w *= ratio) {
-                acc += w;
-                uint32_t bd = (i == want - 1) ? units : static_cast<uint32_t>(acc / total * units + 0.5);
-                bd = std::max(bd, bound.back() + 1);
-                bd = std::min(bd, units - static_cast<uint32_t>(want - 1 - i));
-                bound.push_back(bd);
-            }
-        } else {
-            bound.push_back(0);
-        }
-        const int C = static_cast<int>(bound.size()) - 1;
-        if (C > mi_demod::kMaxChunks)
-            return fail(MI_ERR_INVALID, "too many chunks");
-        std::vector<mi::Event>& cev = h->set[q].chunk_ev;
-        while (static_cast<int>(cev.size()) < C * mi_demod::kEvPerChunk) {
-            mi::Event e;
-            HIP_TRY(hipEventCreate(e.put()));
-            cev.push_back(std::move(e));
-        }
-        evc = h->set[q].ev;
-        mi::TpArgs ta{};
-        ta.rows = h->d_rows;
-        ta.nrows = h->tp_rows;
-        ta.nch = h->nch;
-        ta.nsteps = n;
-        ta.nbatches = da.nbatches;
-        ta.nblk = n / 16;
-        ta.L = L;
-        ta.nseg = (n + L - 1) / L;
-        ta.mag = planes;
-        ta.plane_stride = h->plane_stride;
-        ta.wmain = d_wmain;
-        ta.wmain_stride = wmain_stride;
-        ta.carry = h->set[q].carry;
-        ta.carry_prev = h->d_carry;
-        ta.axc = d_axc;
-        ta.cp = h->d_cp;
-        ta.st = h->d_state;
-        ta.stats = h->d_stats;
-        ta.xmax = h->set[q].xmax;
-        ta.blk_fe = h->set[q].blk_fe;
-        ta.blk_fm = h->set[q].blk_fm;
-        ta.blk_x0 = h->set[q].blk_x0;
-        ta.blk_xm = h->set[q].blk_xm;
-        ta.core = h->set[q].core;
-        ta.core_carry = h->d_core_carry;
-        ta.full0 = h->d_full0;
-        ta.fullbound = h->d_fullbound;
-        ta.prev_mag = overlap ? h->d_mag : nullptr;  // (still the previous call's planes here)
-        ta.prev_n = h->head_off;
-        ta.xmax_prev = h->set[h->cur].xmax;
-        ta.rec = h->set[q].rec;
-        ta.rec_stride = static_cast<size_t>(h->rows) * h->tp_max_seg;
-        ta.tstart = h->d_tstart;
-        ta.need = h->d_need;
-        ta.redo = h->d_redo;
-        ta.fin = h->d_fin;
-        ta.diag = h->d_diag;
-        ta.seg_lpw = h->opt_tp_lpw;
-        ta.core_split = (h->opt_core_split && h->core_split_ok) ? 1 : 0;
-        ta.core_lead = h->opt_core_lead;
-        ta.core_guess = h->opt_core_guess;
-        ta.core_decay = h->opt_core_decay;
-        ta.core_lean = h->opt_core_lean;
-        ta.agc_hint = h->opt_agc_hint;
-        ta.eager_samples = h->opt_tp_eager;
-        // Speculative head: when this call's segment pass may run under the previous call's tail at all (seg_early) and that call
-        // left what the warm-up needs (aggregates, core states at boundaries of the same segment length, TP_W steps of them),
-        // no lane starts from the carried ChanState and no launch of the pass waits for the previous call.
-        const bool spec_head = seg_early && h->opt_spec_head && h->head_off >= mi::TP_W && h->set[h->cur].seq &&
-                               h->set[h->cur].path == 1;
-        ta.spec_head = spec_head ? 1 : 0;
-        ta.prev_blk_fe = h->set[h->cur].blk_fe, ta.prev_blk_fm = h->set[h->cur].blk_fm;
-        ta.prev_blk_x0 = h->set[h->cur].blk_x0, ta.prev_blk_xm = h->set[h->cur].blk_xm;
-        ta.prev_core = h->set[h->cur].core;
-        ta.prev_nblk = h->head_off / 16;
-        ta.prev_nseg = h->set[h->cur].nseg;
-        h->set[q].nseg = ta.nseg;
-        auto chunk = [&](int i) {
-            mi::TpArgs c = ta;
-            c.step0 = bound[static_cast<size_t>(i)] * chunk_unit;
-            c.step1 = (i == C - 1) ? n : bound[static_cast<size_t>(i) + 1] * chunk_unit;
-            c.seg0 = c.step0 / L;
-            c.seg1 = (c.step1 + L - 1) / L;
-            c.blk0 = c.step0 / 16;
-            c.blk1 = c.step1 / 16;
-            c.bat0 = c.step0 / mi::kWaveBatch;
-            c.bat1 = c.step1 / mi::kWaveBatch;
-            c.first_chunk = i == 0;
-            c.last_chunk = i == C - 1;
-            return c;
-        };
-        const bool first_call = h->first_call;
-        // A mixed plan: stage 1 leaves the raw bins of this call in complex plane set p, the serial kernel reads them there and leaves
-        // its carried head in the other set for the next call (as the pipelined serial calls do).
-        const int zp = (h->d_cplx && h->d_cplx == h->d_cplx_set[1]) ? 1 : 0, znp = zp ^ 1;
-        if (h->tp_mixed) {
-            ca.cplx = h->d_cplx_set[zp];
-        }
-        // The wide passes of a call (stage 1, aggregates, segment pass: thousands of waves that hold most of a SIMD's registers for a
-        // millisecond) run beside the latency-bound kernels of its neighbours: the core chains, and the tail (scan / fix / redo /
-        // settle / finish: a handful of lanes, 280-430 VGPRs a wave), which then wait for a wide wave to retire before they can
-        // start at all -- 1.5 ms per call for 0.65 ms of work.  So on plans of few rows the wide passes keep off a few CUs
-        // (hipExtStreamCreateWithCUMask), where the others always find room.  Such a stream is a blocking one (it synchronises
-        // with the NULL stream): the twins are created at the handle's first time-parallel call and used by every call whose stream
-        // is not the NULL stream.
-        if (h->masked_state == 0) {
-            const int want = h->opt_reserve_cus >= 0 ? h->opt_reserve_cus : (h->tp_rows <= 64 ? 32 : 0);
-            h->masked_state = 2;
-            hipDeviceProp_t prop{};
-            if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
-                const int ncu = prop.multiProcessorCount, keep = ncu - want;
-                std::vector<uint32_t> mask(static_cast<size_t>((ncu + 31) / 32), 0u);
-                for (int i = 0; i < keep; ++i)
-                    mask[static_cast<size_t>(i) / 32] |= 1u << (i % 32);
-                hipError_t me = hipExtStreamCreateWithCUMask(h->front_stream_m.put(), static_cast<uint32_t>(mask.size()), mask.data());
-                for (mi::Stream& ssm : h->seg_stream_m)
-                    if (me == hipSuccess)
-                        me = hipExtStreamCreateWithCUMask(ssm.put(), static_cast<uint32_t>(mask.size()), mask.data());
+    const bool first_call = h->first_call;
+    // A mixed plan: stage 1 leaves the raw bins of this call in complex plane set p, the serial kernel reads them there and leaves
+    // its carried head in the other set for the next call (as the pipelined serial calls do).
+    const int zp = (h->d_cplx && h->d_cplx == h->d_cplx_set[1]) ? 1 : 0, znp = zp ^ 1;
+    if (h->tp_mixed) {
+        ca.cplx = h->d_cplx_set[zp];
+    }
+    // The wide passes of a call (stage 1, aggregates, segment pass: thousands of waves that hold most of a SIMD's registers for a
+    // millisecond) run beside the latency-bound kernels of its neighbours: the core chains, and the tail (scan / fix / redo /
+    // settle / finish: a handful of lanes, 280-430 VGPRs a wave), which then wait for a wide wave to retire before they can
+    // start at all -- 1.5 ms per call for 0.65 ms of work.  So on plans of few rows the wide passes keep off a few CUs
+    // (hipExtStreamCreateWithCUMask), where the others always find room.  Such a stream is a blocking one (it synchronises
+    // with the NULL stream): the twins are created at the handle's first time-parallel call and used by every call whose stream
+    // is not the NULL stream.
+    if (h->masked_state == 0) {
+        const int want = h->opt_reserve_cus >= 0 ? h->opt_reserve_cus : (h->tp_rows <= 64 ? 32 : 0);
+        h->masked_state = 2;
+        hipDeviceProp_t prop{};
+        if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
+            const int ncu = prop.multiProcessorCount, keep = ncu - want;
+            const std::vector<uint32_t> mask = cu_mask(ncu, 0, keep);
+            hipError_t me = cu_stream_create(h->front_stream_m, mask);
+            for (mi::Stream& ssm : h->seg_stream_m)
                 if (me == hipSuccess)
-                    h->masked_state = 1;
-                else
-                    (void)hipGetLastError();  // (no such streams here: the plain ones serve)
-            }
+                    me = cu_stream_create(ssm, mask);
+            if (me == hipSuccess)
+                h->masked_state = 1;
+            else
+                (void)hipGetLastError();  // (no such streams here: the plain ones serve)
         }
-        // (a call on the NULL stream takes the plain streams whatever the handle decided; changing sides between calls is rare and
-        //  costs a host wait: the passes of consecutive calls are ordered by their stream, not by events)
-        const bool masked = h->masked_state == 1 && s != nullptr;
-        if (h->last_masked >= 0 && h->last_masked != (masked ? 1 : 0)) {
-            HIP_TRY(hipStreamSynchronize(h->last_masked ? h->front_stream_m : h->front_stream));
-            for (int i = 0; i < mi_demod::kSegStreams; ++i)
-                HIP_TRY(hipStreamSynchronize(h->last_masked ? h->seg_stream_m[i] : h->seg_stream[i]));
-        }
-        h->last_masked = masked ? 1 : 0;
-        hipStream_t fs = masked ? h->front_stream_m : h->front_stream;
-        auto stage1 = [&](const mi::TpArgs& c) -> hipError_t {  // the windows whose magnitudes are the chunk's squelch samples
-            mi::ChannelizeArgs cc = ca;
-            const uint32_t f0 = first_call ? (c.first_chunk ? 0u : c.step0 + mi::kAgcExtra) : c.step0;
-            const uint32_t f1 = first_call ? c.step1 + mi::kAgcExtra : c.step1;
-            cc.iq = ca.iq + static_cast<size_t>(f0) * ca.hop_bytes;
-            cc.valid_bytes = ca.valid_bytes - static_cast<size_t>(f0) * ca.hop_bytes;
-            cc.nfft = f1 - f0;
-            cc.plane_off = ca.plane_off + f0;
-            cc.mag = planes;
-            cc.xmax = h->set[q].xmax;
-            return stage1_launch(cc, f0, fs);
-        };
-        auto ev = [&](int i, int k) -> hipEvent_t { return cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + k]; };
-        HIP_TRY(hipEventRecord(h->ev_entry, s));
-        HIP_TRY(hipEventRecord(evc[0], s));
-        HIP_TRY(hipEventRecord(evc[1], s));
-        HIP_TRY(mi::launch_tp_audio_head(ta, s));
-        HIP_TRY(hipEventRecord(h->ev_head, s));  // the previous call is complete and its lookahead has been taken over
-        if (iq_ready)
-            HIP_TRY(hipStreamWaitEvent(fs, iq_ready, 0));
-        if (!overlap)
-            HIP_TRY(hipStreamWaitEvent(fs, h->ev_entry, 0));  // stage 1 honours the caller's stream order
-        else if (h->set[q].seq)
-            HIP_TRY(hipStreamWaitEvent(fs, h->set[q].ev[2], 0));  // the call that used this scratch set last (kSets back) has left it
-        {
-            // ... and the call after that one has read what its speculative head needed from that set (planes, aggregates, core
-            // states): its segment pass is done (always long before; the wait costs nothing)
-            const int qn = (q + 1) % mi_demod::kSets;
-            if (h->set[qn].seq && h->set[qn].path == 1 && h->set[qn].chunks > 0)
-                HIP_TRY(hipStreamWaitEvent(fs, h->set[qn].chunk_ev[static_cast<size_t>(h->set[qn].chunks - 1) * mi_demod::kEvPerChunk + 6], 0));
-        }
-        if (h->tp_mixed && h->cplx_busy[zp])  // (the serial kernel of the call before the previous one read this complex plane set)
-            HIP_TRY(hipStreamWaitEvent(fs, h->ev_cplx_free[zp], 0));
-        // the carried samples of the previous call (wherever they are) become the head of this call's planes -- of a mixed plan the
-        // time-parallel rows' only where the serial kernel of the previous call has put its own rows' there itself
-        if (h->tp_mixed && h->ser_head_next && planes == h->set[(h->cur + 1) % mi_demod::kSets].mag)
-            HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->tp_rows, fs, h->d_rows));
-        else
-            HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->rows, fs));
-        HIP_TRY(hipMemsetAsync(h->set[q].xmax, 0, static_cast<size_t>(h->rows) * sizeof(unsigned), fs));
-        // Stage 1 + aggregates of every chunk first: nothing else feeds them (when calls overlap, k_tp_full warms its first
-        // lanes up on the previous call's planes, so not even the chain state of that call).
-        for (int i = 0; i < C; ++i) {
-            const mi::TpArgs c = chunk(i);
-            HIP_TRY(hipEventRecord(ev(i, 0), fs));
-            HIP_TRY(stage1(c));
-            HIP_TRY(hipEventRecord(ev(i, 1), fs));
-            HIP_TRY(hipEventRecord(ev(i, 11), fs));
-            HIP_TRY(mi::launch_tp_front(c, fs, /*seed_chain=*/!overlap));
-            HIP_TRY(hipEventRecord(ev(i, 2), fs));
-        }
-        for (int i = 0; i < C; ++i) {
-            const mi::TpArgs c = chunk(i);
-            HIP_TRY(hipStreamWaitEvent(h->aux_stream, ev(i, 2), 0));
-            HIP_TRY(hipEventRecord(ev(i, 3), h->aux_stream));
-            HIP_TRY(mi::launch_tp_core(c, h->aux_stream));
-            HIP_TRY(hipEventRecord(ev(i, 4), h->aux_stream));
-            hipStream_t ss = masked ? h->seg_stream_m[i % mi_demod::kSegStreams] : h->seg_stream[i % mi_demod::kSegStreams];
-            // A segment pass needs core(i).  It also has to wait for the previous call (ev_head) where it touches what
-            // that call's tail still owns: the carried ChanState (the lanes of the first TP_W / L + 1 segments start
-            // from it), the audio lookahead (written by the last segments) and the caller's audio buffer if it is the
-            // one the previous call wrote.
-            HIP_TRY(hipStreamWaitEvent(ss, ev(i, 4), 0));
-            if (seg_early) {
-                // The pass writes the caller's audio buffer: the last call that wrote the same memory has to be complete (its fades
-                // rewrite audio).  Not the previous call (seg_early); with two buffers alternating the one before it, with three the
-                // one before that -- then the pass has two tail periods of slack instead of one and the tails run back to back.
-                for (int back = 1; back < mi_demod::kSets - 1; ++back) {
-                    const int pq = (h->cur + mi_demod::kSets - back) % mi_demod::kSets;
-                    if (!h->set[pq].seq)
-                        break;
-                    if (h->set[pq].path != 1 || !(out_hi <= h->set[pq].out_lo || out_lo >= h->set[pq].out_hi)) {
-                        HIP_TRY(hipStreamWaitEvent(ss, h->set[pq].ev[2], 0));
-                        break;
-                    }
+    }
+    // (a call on the NULL stream takes the plain streams whatever the handle decided; changing sides between calls is rare and
+    //  costs a host wait: the passes of consecutive calls are ordered by their stream, not by events)
+    const bool masked = h->masked_state == 1 && s != nullptr;
+    if (h->last_masked >= 0 && h->last_masked != (masked ? 1 : 0)) {
+        HIP_TRY(hipStreamSynchronize(h->last_masked ? h->front_stream_m : h->front_stream));
+        for (int i = 0; i < mi_demod::kSegStreams; ++i)
+            HIP_TRY(hipStreamSynchronize(h->last_masked ? h->seg_stream_m[i] : h->seg_stream[i]));
+    }
+    h->last_masked = masked ? 1 : 0;
+    hipStream_t fs = masked ? h->front_stream_m : h->front_stream;
+    auto stage1 = [&](const mi::TpArgs& c) -> hipError_t {  // the windows whose magnitudes are the chunk's squelch samples
+        mi::ChannelizeArgs cc = ca;
+        const uint32_t f0 = first_call ? (c.first_chunk ? 0u : c.step0 + mi::kAgcExtra) : c.step0;
+        const uint32_t f1 = first_call ? c.step1 + mi::kAgcExtra : c.step1;
+        cc.iq = ca.iq + static_cast<size_t>(f0) * ca.hop_bytes;
+        cc.valid_bytes = ca.valid_bytes - static_cast<size_t>(f0) * ca.hop_bytes;
+        cc.nfft = f1 - f0;
+        cc.plane_off = ca.plane_off + f0;
+        cc.mag = planes;
+        cc.xmax = cs.xmax;
+        return stage1_launch(h, cc, f0, fs);
+    };
+    HIP_TRY(hipEventRecord(h->ev_entry, s));
+    HIP_TRY(hipEventRecord(evc[kEvBegin], s));
+    HIP_TRY(hipEventRecord(evc[kEvStage1Done], s));
+    HIP_TRY(mi::launch_tp_audio_head(ta, s));
+    HIP_TRY(hipEventRecord(h->ev_head, s));  // the previous call is complete and its lookahead has been taken over
+    if (call.iq_ready)
+        HIP_TRY(hipStreamWaitEvent(fs, call.iq_ready, 0));
+    if (!overlap)
+        HIP_TRY(hipStreamWaitEvent(fs, h->ev_entry, 0));  // stage 1 honours the caller's stream order
+    else if (cs.seq)
+        HIP_TRY(hipStreamWaitEvent(fs, cs.ev[kEvDone], 0));  // the call that used this scratch set last (kSets back) has left it
+    {
+        // ... and the call after that one has read what its speculative head needed from that set (planes, aggregates, core
+        // states): its segment pass is done (always long before; the wait costs nothing)
+        const mi_demod::CallSet& next = h->set[(q + 1) % mi_demod::kSets];
+        if (next.seq && next.path == kPathTimeParallel && next.chunks > 0)
+            HIP_TRY(hipStreamWaitEvent(fs, next.chunk(next.chunks - 1, kEvSegLaunched), 0));
+    }
+    if (h->tp_mixed && h->cplx_busy[zp])  // (the serial kernel of the call before the previous one read this complex plane set)
+        HIP_TRY(hipStreamWaitEvent(fs, h->ev_cplx_free[zp], 0));
+    // the carried samples of the previous call (wherever they are) become the head of this call's planes -- of a mixed plan the
+    // time-parallel rows' only where the serial kernel of the previous call has put its own rows' there itself
+    if (h->tp_mixed && h->ser_head_next && planes == h->set[(h->cur + 1) % mi_demod::kSets].mag)
+        HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->tp_rows, fs, h->d_rows));
+    else
+        HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->rows, fs));
+    HIP_TRY(hipMemsetAsync(cs.xmax, 0, static_cast<size_t>(h->rows) * sizeof(unsigned), fs));
+    // Stage 1 + aggregates of every chunk first: nothing else feeds them (when calls overlap, k_tp_full warms its first
+    // lanes up on the previous call's planes, so not even the chain state of that call).
+    for (int i = 0; i < C; ++i) {
+        const mi::TpArgs c = chunk(i);
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvStage1Begin), fs));
+        HIP_TRY(stage1(c));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvStage1End), fs));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvFullBegin), fs));
+        HIP_TRY(mi::launch_tp_front(c, fs, /*seed_chain=*/!overlap));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvFullEnd), fs));
+    }
+    for (int i = 0; i < C; ++i) {
+        const mi::TpArgs c = chunk(i);
+        HIP_TRY(hipStreamWaitEvent(h->aux_stream, cs.chunk(i, kEvFullEnd), 0));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvCoreBegin), h->aux_stream));
+        HIP_TRY(mi::launch_tp_core(c, h->aux_stream));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvCoreEnd), h->aux_stream));
+        hipStream_t ss = masked ? h->seg_stream_m[i % mi_demod::kSegStreams] : h->seg_stream[i % mi_demod::kSegStreams];
+        // A segment pass needs core(i).  It also has to wait for the previous call (ev_head) where it touches what
+        // that call's tail still owns: the carried ChanState (the lanes of the first TP_W / L + 1 segments start
+        // from it), the audio lookahead (written by the last segments) and the caller's audio buffer if it is the
+        // one the previous call wrote.
+        HIP_TRY(hipStreamWaitEvent(ss, cs.chunk(i, kEvCoreEnd), 0));
+        if (seg_early) {
+            // The pass writes the caller's audio buffer: the last call that wrote the same memory has to be complete (its fades
+            // rewrite audio).  Not the previous call (seg_early); with two buffers alternating the one before it, with three the
+            // one before that -- then the pass has two tail periods of slack instead of one and the tails run back to back.
+            for (int back = 1; back < mi_demod::kSets - 1; ++back) {
+                const mi_demod::CallSet& past = h->set[(h->cur + mi_demod::kSets - back) % mi_demod::kSets];
+                if (!past.seq)
+                    break;
+                if (past.path != kPathTimeParallel || !(out_hi <= past.out_lo || out_lo >= past.out_hi)) {
+                    HIP_TRY(hipStreamWaitEvent(ss, past.ev[kEvDone], 0));
+                    break;
                 }
             }
-            // (events 5 -> 12 time the pass itself: they sit inside every wait of the segment stream; of a split first chunk
-            // the body is timed, its few head segments are not)
-            const uint32_t head_end = std::min<uint32_t>(c.seg1, mi::TP_W / L + 1);
-            if (spec_head) {
-                HIP_TRY(hipEventRecord(ev(i, 5), ss));
-                HIP_TRY(mi::launch_tp_seg(c, ss));
-                HIP_TRY(hipEventRecord(ev(i, 12), ss));
-            } else if (!seg_early || c.last_chunk) {
-                HIP_TRY(hipStreamWaitEvent(ss, h->ev_head, 0));
-                HIP_TRY(hipEventRecord(ev(i, 5), ss));
-                HIP_TRY(mi::launch_tp_seg(c, ss));
-                HIP_TRY(hipEventRecord(ev(i, 12), ss));
-            } else if (c.first_chunk && c.seg0 < head_end) {
-                mi::TpArgs body = c, head = c;
-                body.seg0 = head_end;
-                head.seg1 = head_end;
-                HIP_TRY(hipEventRecord(ev(i, 5), ss));
-                if (body.seg0 < body.seg1)
-                    HIP_TRY(mi::launch_tp_seg(body, ss));
-                HIP_TRY(hipEventRecord(ev(i, 12), ss));
-                HIP_TRY(hipStreamWaitEvent(ss, h->ev_head, 0));
-                HIP_TRY(mi::launch_tp_seg(head, ss));
-            } else {
-                HIP_TRY(hipEventRecord(ev(i, 5), ss));
-                HIP_TRY(mi::launch_tp_seg(c, ss));
-                HIP_TRY(hipEventRecord(ev(i, 12), ss));
-            }
-            HIP_TRY(hipEventRecord(ev(i, 6), ss));
-            HIP_TRY(hipStreamWaitEvent(s, ev(i, 6), 0));
-            HIP_TRY(hipEventRecord(ev(i, 10), s));
-            hipEvent_t marks[mi::TP_REST_MARKS] = {ev(i, 7), ev(i, 8), ev(i, 9)};
-            HIP_TRY(mi::launch_tp_rest(c, s, marks));
         }
-        h->set[q].mixed = false;
-        h->ser_head_next = false;
-        if (h->tp_mixed && h->ser_rows > 0) {
-            // ---- the rows the time-parallel path does not take: k_demod on its own stream, beside the chain ----
-            // It needs stage 1 of the whole call (the last chunk's end on the front stream), the serial kernel of the previous call
-            // (same stream) and, where calls do not overlap, the caller's stream order.
-            hipStream_t zs = h->ser_stream;
-            HIP_TRY(hipStreamWaitEvent(zs, ev(C - 1, 1), 0));
-            if (!overlap)
-                HIP_TRY(hipStreamWaitEvent(zs, h->ev_entry, 0));
-            if (!seg_early)
-                HIP_TRY(hipStreamWaitEvent(zs, h->ev_head, 0));  // (it writes the audio buffer the previous call wrote)
-            mi::DemodArgs dm = da;
-            dm.rows = h->d_srows;
-            dm.nrows = h->ser_rows;
-            dm.mag = planes;
-            dm.cplx = h->d_cplx_set[zp];
-            dm.mag_head = h->set[(q + 1) % mi_demod::kSets].mag;  // (free: the call that used it last is four calls back)
-            dm.cplx_head = h->d_cplx_set[znp];
-            dm.carry = h->set[q].carry;
-            dm.carry_in = h->d_carry;
-            dm.lanes_per_wave = std::min(64, std::max(1, (h->ser_rows + h->opt_uni_rows - 1) / h->opt_uni_rows));
-            dm.pre_wave = (h->opt_pre_wave < 0 ? h->ser_rows <= 256 : h->opt_pre_wave != 0) ? 1 : 0;
-            HIP_TRY(hipEventRecord(evc[3], zs));
-            HIP_TRY(mi::launch_demod(dm, zs));
-            HIP_TRY(hipEventRecord(evc[4], zs));
-            HIP_TRY(hipEventRecord(h->ev_cplx_free[zp], zs));
-            h->cplx_busy[zp] = true;
-            HIP_TRY(hipStreamWaitEvent(s, evc[4], 0));
-            h->d_cplx = h->d_cplx_set[znp];
-            h->d_cplx_last = h->d_cplx_set[zp];
-            h->pset = znp;
-            h->set[q].mixed = true;
-            h->ser_head_next = true;
+        // (events kEvSegBegin -> kEvSegEnd time the pass itself: they sit inside every wait of the segment stream; of a split first
+        // chunk the body is timed, its few head segments are not)
+        // With a speculative head nothing of the pass waits for the previous call; otherwise the whole pass does where it may not
+        // run early at all or is the call's last chunk, and of a first chunk only the few head segments, launched after the body.
+        const uint32_t head_end = std::min<uint32_t>(c.seg1, mi::TP_W / L + 1);
+        const bool wait_first = !spec_head && (!seg_early || c.last_chunk);
+        const bool split_head = !spec_head && !wait_first && c.first_chunk && c.seg0 < head_end;
+        mi::TpArgs body = c, head = c;
+        if (split_head)
+            body.seg0 = head.seg1 = head_end;
+        if (wait_first)
+            HIP_TRY(hipStreamWaitEvent(ss, h->ev_head, 0));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvSegBegin), ss));
+        if (!split_head || body.seg0 < body.seg1)
+            HIP_TRY(mi::launch_tp_seg(body, ss));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvSegEnd), ss));
+        if (split_head) {
+            HIP_TRY(hipStreamWaitEvent(ss, h->ev_head, 0));
+            HIP_TRY(mi::launch_tp_seg(head, ss));
         }
-        h->set[q].chunks = C;
-        h->cur = q;
-        h->d_carry = h->set[q].carry;
-        h->d_mag = planes;
-        h->head_off = n;  // (first call: the planes hold AGC_EXTRA + n samples, the last AGC_EXTRA start at n as well)
-        h->chain_live = true;
-        h->prev_out_lo = out_lo;
-        h->prev_out_hi = out_hi;
-        h->set[q].out_lo = out_lo;
-        h->set[q].out_hi = out_hi;
-    } else if (h->plan.any_afc) {
-        if (iq_ready)
-            HIP_TRY(hipStreamWaitEvent(s, iq_ready, 0));
-        // AFC (rtl_airband.cpp:180-251): the bins stage 1 picks in batch b+1 depend on the squelch outcome of batch b, so
-        // the batches are enqueued one at a time -- stage 1, channel loop, AFC::finalize -- with the bin table and the
-        // previous indicator resident in ChanState: no host round trip inside the call.
-        HIP_TRY(hipEventRecord(evc[0], s));
-        size_t f0 = 0;  // first window of the batch, relative to the call
-        for (int b = 0; b < nbatches; ++b) {
-            const bool first = h->first_call && b == 0;
-            const uint32_t nf = mi::kWaveBatch + (first ? mi::kAgcExtra : 0);
-            mi::ChannelizeArgs cb = ca;
-            cb.iq = ca.iq + f0 * ca.hop_bytes;
-            cb.valid_bytes = ca.valid_bytes - f0 * ca.hop_bytes;
-            cb.nfft = nf;
-            cb.plane_off = first ? 0 : mi::kAgcExtra;
-            cb.st = h->d_state;
-            cb.afc_spec = h->d_afc_spec;
-            HIP_TRY(mi::launch_channelize(cb, h->plan.log2n, h->plan.dev.sfmt, h->nstreams, s));
-            if (b == 0)
-                HIP_TRY(hipEventRecord(evc[1], s));
-            mi::DemodArgs db = da;
-            db.nsteps = mi::kWaveBatch;
-            db.nbatches = 1;
-            db.wmain = d_wmain + static_cast<size_t>(b) * mi::kWaveBatch;
-            db.iq_out = d_iq_out ? d_iq_out + static_cast<size_t>(b) * mi::kWaveBatch : nullptr;
-            db.axc = d_axc + b;
-            HIP_TRY(mi::launch_demod(db, s));
-            mi::AfcArgs aa{};
-            aa.nstreams = act_streams;
-            aa.streams = ca.streams;
-            aa.nch = h->nch;
-            aa.fft_size = h->plan.fft_size;
-            aa.cp = h->d_cp;
-            aa.st = h->d_state;
-            aa.spec = h->d_afc_spec;
-            aa.axc = d_axc + b;
-            aa.axc_stride = static_cast<uint32_t>(nbatches);
-            HIP_TRY(mi::launch_afc(aa, s));
-            f0 += nf;
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvSegLaunched), ss));
+        HIP_TRY(hipStreamWaitEvent(s, cs.chunk(i, kEvSegLaunched), 0));
+        HIP_TRY(hipEventRecord(cs.chunk(i, kEvScanBegin), s));
+        hipEvent_t marks[mi::TP_REST_MARKS] = {cs.chunk(i, kEvScanEnd), cs.chunk(i, kEvFixEnd), cs.chunk(i, kEvFinishEnd)};
+        HIP_TRY(mi::launch_tp_rest(c, s, marks));
+    }
+    cs.mixed = false;
+    h->ser_head_next = false;
+    if (h->tp_mixed && h->ser_rows > 0) {
+        // ---- the rows the time-parallel path does not take: k_demod on its own stream, beside the chain ----
+        // It needs stage 1 of the whole call (the last chunk's end on the front stream), the serial kernel of the previous call
+        // (same stream) and, where calls do not overlap, the caller's stream order.
+        hipStream_t zs = h->ser_stream;
+        HIP_TRY(hipStreamWaitEvent(zs, cs.chunk(C - 1, kEvStage1End), 0));
+        if (!overlap)
+            HIP_TRY(hipStreamWaitEvent(zs, h->ev_entry, 0));
+        if (!seg_early)
+            HIP_TRY(hipStreamWaitEvent(zs, h->ev_head, 0));  // (it writes the audio buffer the previous call wrote)
+        mi::DemodArgs dm = call.da;
+        dm.rows = h->d_srows;
+        dm.nrows = h->ser_rows;
+        dm.mag = planes;
+        dm.cplx = h->d_cplx_set[zp];
+        dm.mag_head = h->set[(q + 1) % mi_demod::kSets].mag;  // (free: the call that used it last is four calls back)
+        dm.cplx_head = h->d_cplx_set[znp];
+        dm.carry = cs.carry;
+        dm.carry_in = h->d_carry;
+        dm.lanes_per_wave = std::min(64, std::max(1, (h->ser_rows + h->opt_uni_rows - 1) / h->opt_uni_rows));
+        dm.pre_wave = (h->opt_pre_wave < 0 ? h->ser_rows <= 256 : h->opt_pre_wave != 0) ? 1 : 0;
+        HIP_TRY(hipEventRecord(evc[kEvSerialBegin], zs));
+        HIP_TRY(mi::launch_demod(dm, zs));
+        HIP_TRY(hipEventRecord(evc[kEvSerialEnd], zs));
+        HIP_TRY(hipEventRecord(h->ev_cplx_free[zp], zs));
+        h->cplx_busy[zp] = true;
+        HIP_TRY(hipStreamWaitEvent(s, evc[kEvSerialEnd], 0));
+        h->d_cplx = h->d_cplx_set[znp];
+        h->d_cplx_last = h->d_cplx_set[zp];
+        h->pset = znp;
+        cs.mixed = true;
+        h->ser_head_next = true;
+    }
+    cs.chunks = C;
+    h->cur = q;
+    h->d_carry = cs.carry;
+    h->d_mag = planes;
+    h->head_off = n;  // (first call: the planes hold AGC_EXTRA + n samples, the last AGC_EXTRA start at n as well)
+    h->chain_live = true;
+    h->prev_out_lo = out_lo;
+    h->prev_out_hi = out_hi;
+    cs.out_lo = out_lo;
+    cs.out_hi = out_hi;
+    return MI_OK;
+}
+
+// AFC (rtl_airband.cpp:180-251): the bins stage 1 picks in batch b+1 depend on the squelch outcome of batch b, so
+// the batches are enqueued one at a time -- stage 1, channel loop, AFC::finalize -- with the bin table and the
+// previous indicator resident in ChanState: no host round trip inside the call.
+int enqueue_afc(mi_demod* h, const Call& call) {
+    const hipStream_t s = call.s;
+    const mi::ChannelizeArgs& ca = call.ca;
+    if (call.iq_ready)
+        HIP_TRY(hipStreamWaitEvent(s, call.iq_ready, 0));
+    HIP_TRY(hipEventRecord(call.evc[kEvBegin], s));
+    size_t f0 = 0;  // first window of the batch, relative to the call
+    for (int b = 0; b < call.nbatches; ++b) {
+        const bool first = h->first_call && b == 0;
+        const uint32_t nf = mi::kWaveBatch + (first ? mi::kAgcExtra : 0);
+        mi::ChannelizeArgs cb = ca;
+        cb.iq = ca.iq + f0 * ca.hop_bytes;
+        cb.valid_bytes = ca.valid_bytes - f0 * ca.hop_bytes;
+        cb.nfft = nf;
+        cb.plane_off = first ? 0 : mi::kAgcExtra;
+        cb.st = h->d_state;
+        cb.afc_spec = h->d_afc_spec;
+        HIP_TRY(mi::launch_channelize(cb, h->plan.log2n, h->plan.dev.sfmt, h->nstreams, s));
+        if (b == 0)
+            HIP_TRY(hipEventRecord(call.evc[kEvStage1Done], s));
+        mi::DemodArgs db = call.da;
+        db.nsteps = mi::kWaveBatch;
+        db.nbatches = 1;
+        db.wmain = call.d_wmain + static_cast<size_t>(b) * mi::kWaveBatch;
+        db.iq_out = call.d_iq_out ? call.d_iq_out + static_cast<size_t>(b) * mi::kWaveBatch : nullptr;
+        db.axc = call.d_axc + b;
+        HIP_TRY(mi::launch_demod(db, s));
+        mi::AfcArgs aa{};
+        aa.nstreams = call.act_streams;
+        aa.streams = ca.streams;
+        aa.nch = h->nch;
+        aa.fft_size = h->plan.fft_size;
+        aa.cp = h->d_cp;
+        aa.st = h->d_state;
+        aa.spec = h->d_afc_spec;
+        aa.axc = call.d_axc + b;
+        aa.axc_stride = static_cast<uint32_t>(call.nbatches);
+        HIP_TRY(mi::launch_afc(aa, s));
+        f0 += nf;
+    }
+    return MI_OK;
+}
+
+// ---- serial stage 2 with consecutive calls overlapping (MI_OPT_EARLY_INPUT) ----
+// Two plane sets alternate.  Stage 1 of this call fills the body of set p on the front stream while the previous
+// call's k_demod, which reads the other set, still runs on the caller's stream (all that k_demod writes into set p
+// is the carried head, entries [0, AGC_EXTRA), which stage 1 does not touch).  k_demod of this call waits for its
+// stage 1 and leaves the head in the other set for the next call.
+int enqueue_serial_pipelined(mi_demod* h, Call& call) {
+    const hipStream_t s = call.s;
+    mi::ChannelizeArgs& ca = call.ca;
+    mi::DemodArgs& da = call.da;
+    if (h->tp_eligible)
+        h->pset = h->d_mag == h->set[1].mag ? 1 : 0;
+    const int q = (h->cur + 1) % mi_demod::kSets;  // event / timing set of this call
+    const int before_prev = (h->cur + mi_demod::kSets - 1) % mi_demod::kSets;
+    const int p = h->pset, np = p ^ 1;
+    call.evc = h->set[q].ev;
+    const mi::Event* const evc = call.evc;
+    if (h->split_state == 0) {
+        h->split_state = 2;
+        hipDeviceProp_t prop{};
+        // Two waves per row (k_demod_pw2) of 449 .. 512 rows fill 128 CUs two to a SIMD -- the kernel's pace alone -- and stage 1 of
+        // that many streams takes as long on the other 128 as the kernel does: side by side on disjoint CUs 3.47 ms per 8-s call of
+        // 64 x 8 AM channels, sharing every SIMD 3.8 (stage 1 3.4-3.5 ms beside the kernel's waves against 1.9 alone).  With fewer
+        // rows the call is the kernel's latency either way and the split only takes CUs from stage 1 (tools/split_rows.sh); with
+        // more the kernel needs more than 128 CUs (112 for 512 rows: 3.7 ms).
+        const int want = h->opt_split_cus >= 0 ? h->opt_split_cus : ((da.pre_wave == 2 && h->rows > 448 && h->rows <= 512) ? 128 : 0);
+        if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
+            const int ncu = prop.multiProcessorCount, keep = ncu - want;
+            hipError_t me = cu_stream_create(h->ps_front_m, cu_mask(ncu, 0, keep));
+            if (me == hipSuccess)
+                me = cu_stream_create(h->ps_demod_m, cu_mask(ncu, keep, ncu));
+            if (me == hipSuccess)
+                me = hipEventCreateWithFlags(h->ev_ps_entry.put(), hipEventDisableTiming);
+            if (me == hipSuccess)
+                me = hipEventCreateWithFlags(h->ev_ps_done.put(), hipEventDisableTiming);
+            if (me == hipSuccess)
+                h->split_state = 1;
+            else
+                (void)hipGetLastError();
         }
-    } else if (!partial && early_input && !h->first_call && (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) &&
-               serial_sets_ready(h)) {
-        // (a handle whose plan the time-parallel path could take as well -- many rows, or MI_OPT_TIME_PARALLEL = 0 -- pipelines its serial
-        //  calls like any other as long as its planes are where this branch keeps them: never after a time-parallel call)
-        if (h->tp_eligible)
-            h->pset = h->d_mag == h->set[1].mag ? 1 : 0;
-        // ---- serial stage 2 with consecutive calls overlapping (MI_OPT_EARLY_INPUT) ----
-        // Two plane sets alternate.  Stage 1 of this call fills the body of set p on the front stream while the previous
-        // call's k_demod, which reads the other set, still runs on the caller's stream (all that k_demod writes into set p
-        // is the carried head, entries [0, AGC_EXTRA), which stage 1 does not touch).  k_demod of this call waits for its
-        // stage 1 and leaves the head in the other set for the next call.
-        const int q = (h->cur + 1) % mi_demod::kSets;  // event / timing set of this call
-        const int before_prev = (h->cur + mi_demod::kSets - 1) % mi_demod::kSets;
-        const int p = h->pset, np = p ^ 1;
-        evc = h->set[q].ev;
-        if (h->split_state == 0) {
-            h->split_state = 2;
-            hipDeviceProp_t prop{};
-            // Two waves per row (k_demod_pw2) of 449 .. 512 rows fill 128 CUs two to a SIMD -- the kernel's pace alone -- and stage 1 of
-            // that many streams takes as long on the other 128 as the kernel does: side by side on disjoint CUs 3.47 ms per 8-s call of
-            // 64 x 8 AM channels, sharing every SIMD 3.8 (stage 1 3.4-3.5 ms beside the kernel's waves against 1.9 alone).  With fewer
-            // rows the call is the kernel's latency either way and the split only takes CUs from stage 1 (tools/split_rows.sh); with
-            // more the kernel needs more than 128 CUs (112 for 512 rows: 3.7 ms).
-            const int want = h->opt_split_cus >= 0 ? h->opt_split_cus : ((da.pre_wave == 2 && h->rows > 448 && h->rows <= 512) ? 128 : 0);
-            if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
-                const int ncu = prop.multiProcessorCount, keep = ncu - want;
-                std::vector<uint32_t> m_front(static_cast<size_t>((ncu + 31) / 32), 0u), m_demod(m_front.size(), 0u);
-                for (int i = 0; i < ncu; ++i)
-                    (i < keep ? m_front : m_demod)[static_cast<size_t>(i) / 32] |= 1u << (i % 32);
-                hipError_t me = hipExtStreamCreateWithCUMask(h->ps_front_m.put(), static_cast<uint32_t>(m_front.size()), m_front.data());
-                if (me == hipSuccess)
-                    me = hipExtStreamCreateWithCUMask(h->ps_demod_m.put(), static_cast<uint32_t>(m_demod.size()), m_demod.data());
-                if (me == hipSuccess)
-                    me = hipEventCreateWithFlags(h->ev_ps_entry.put(), hipEventDisableTiming);
-                if (me == hipSuccess)
-                    me = hipEventCreateWithFlags(h->ev_ps_done.put(), hipEventDisableTiming);
-                if (me == hipSuccess)
-                    h->split_state = 1;
-                else
-                    (void)hipGetLastError();
-            }
-        }
-        const bool split = h->split_state == 1 && s != nullptr;
-        hipStream_t fs = split ? h->ps_front_m : h->front_stream;
-        if (iq_ready)
-            HIP_TRY(hipStreamWaitEvent(fs, iq_ready, 0));
-        if (h->serial_pipe && h->set[before_prev].seq)  // the call before the previous one read the body of set p
-            HIP_TRY(hipStreamWaitEvent(fs, h->set[before_prev].ev[2], 0));
-        else
-            HIP_TRY(hipStreamWaitEvent(fs, h->set[h->cur].ev[2], 0));  // (first pipelined call: everything before it)
-        ca.mag = h->set[p].mag;
-        ca.cplx = h->d_cplx_set[p];
-        HIP_TRY(hipEventRecord(evc[0], fs));
-        HIP_TRY(stage1_launch(ca, 0, fs));
-        HIP_TRY(hipEventRecord(evc[1], fs));
-        da.mag = h->set[p].mag;
-        da.cplx = h->d_cplx_set[p];
-        da.mag_head = h->set[np].mag;
-        da.cplx_head = h->d_cplx_set[np];
-        if (split) {  // k_demod on the CUs stage 1 keeps off, in the caller's stream order all the same
-            hipStream_t ds = h->ps_demod_m;
-            HIP_TRY(hipEventRecord(h->ev_ps_entry, s));
-            HIP_TRY(hipStreamWaitEvent(ds, h->ev_ps_entry, 0));
-            HIP_TRY(hipStreamWaitEvent(ds, evc[1], 0));
-            HIP_TRY(hipEventRecord(evc[3], ds));
-            HIP_TRY(mi::launch_demod(da, ds));
-            HIP_TRY(hipEventRecord(h->ev_ps_done, ds));
-            HIP_TRY(hipStreamWaitEvent(s, h->ev_ps_done, 0));
-        } else {
-            HIP_TRY(hipStreamWaitEvent(s, evc[1], 0));
-            HIP_TRY(hipEventRecord(evc[3], s));
-            HIP_TRY(mi::launch_demod(da, s));
-        }
-        h->chain_live = false;
-        h->cur = q;
-        h->pset = np;
-        h->d_mag = h->set[np].mag;
-        h->d_cplx = h->d_cplx_set[np];
-        h->d_mag_last = h->set[p].mag;
-        h->d_cplx_last = h->d_cplx_set[p];
-        h->serial_pipe = true;
-        pipelined_serial = true;
+    }
+    const bool split = h->split_state == 1 && s != nullptr;
+    hipStream_t fs = split ? h->ps_front_m : h->front_stream;
+    if (call.iq_ready)
+        HIP_TRY(hipStreamWaitEvent(fs, call.iq_ready, 0));
+    if (h->serial_pipe && h->set[before_prev].seq)  // the call before the previous one read the body of set p
+        HIP_TRY(hipStreamWaitEvent(fs, h->set[before_prev].ev[kEvDone], 0));
+    else
+        HIP_TRY(hipStreamWaitEvent(fs, h->set[h->cur].ev[kEvDone], 0));  // (first pipelined call: everything before it)
+    ca.mag = h->set[p].mag;
+    ca.cplx = h->d_cplx_set[p];
+    HIP_TRY(hipEventRecord(evc[kEvBegin], fs));
+    HIP_TRY(stage1_launch(h, ca, 0, fs));
+    HIP_TRY(hipEventRecord(evc[kEvStage1Done], fs));
+    da.mag = h->set[p].mag;
+    da.cplx = h->d_cplx_set[p];
+    da.mag_head = h->set[np].mag;
+    da.cplx_head = h->d_cplx_set[np];
+    if (split) {  // k_demod on the CUs stage 1 keeps off, in the caller's stream order all the same
+        hipStream_t ds = h->ps_demod_m;
+        HIP_TRY(hipEventRecord(h->ev_ps_entry, s));
+        HIP_TRY(hipStreamWaitEvent(ds, h->ev_ps_entry, 0));
+        HIP_TRY(hipStreamWaitEvent(ds, evc[kEvStage1Done], 0));
+        HIP_TRY(hipEventRecord(evc[kEvSerialBegin], ds));
+        HIP_TRY(mi::launch_demod(da, ds));
+        HIP_TRY(hipEventRecord(h->ev_ps_done, ds));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_ps_done, 0));
     } else {
-        if (iq_ready)
-            HIP_TRY(hipStreamWaitEvent(s, iq_ready, 0));
-        int rc = head_in_place();
-        if (rc != MI_OK)
-            return rc;
-        h->chain_live = false;  // k_demod does not maintain the time-parallel chain state
-        h->serial_pipe = false;
-        HIP_TRY(hipEventRecord(evc[0], s));
-        HIP_TRY(stage1_launch(ca, 0, s));
-        HIP_TRY(hipEventRecord(evc[1], s));
+        HIP_TRY(hipStreamWaitEvent(s, evc[kEvStage1Done], 0));
+        HIP_TRY(hipEventRecord(evc[kEvSerialBegin], s));
         HIP_TRY(mi::launch_demod(da, s));
     }
-    h->last_path = use_tp ? 1 : 0;
-    if (!use_tp)
+    h->chain_live = false;
+    h->cur = q;
+    h->pset = np;
+    h->d_mag = h->set[np].mag;
+    h->d_cplx = h->d_cplx_set[np];
+    h->d_mag_last = h->set[p].mag;
+    h->d_cplx_last = h->d_cplx_set[p];
+    h->serial_pipe = true;
+    return MI_OK;
+}
+
+int enqueue_serial(mi_demod* h, const Call& call) {
+    const hipStream_t s = call.s;
+    if (call.iq_ready)
+        HIP_TRY(hipStreamWaitEvent(s, call.iq_ready, 0));
+    int rc = head_in_place(h, call);
+    if (rc != MI_OK)
+        return rc;
+    h->chain_live = false;  // k_demod does not maintain the time-parallel chain state
+    h->serial_pipe = false;
+    HIP_TRY(hipEventRecord(call.evc[kEvBegin], s));
+    HIP_TRY(stage1_launch(h, call.ca, 0, s));
+    HIP_TRY(hipEventRecord(call.evc[kEvStage1Done], s));
+    HIP_TRY(mi::launch_demod(call.da, s));
+    return MI_OK;
+}
+
+// shared by both entry points; everything is enqueued on `s`
+int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t valid_bytes, int nbatches, float* d_wmain, size_t wmain_stride,
+            float2* d_iq_out, size_t iq_out_stride, char* d_axc, hipStream_t s, hipEvent_t iq_ready = nullptr) {
+    // iq_ready (host-buffer entry, calls in flight): the IQ becomes valid when this event fires -- the streams that read it wait
+    // for it and for nothing else, exactly as if the caller had vouched for the bytes (MI_OPT_EARLY_INPUT)
+    const bool early_input = h->early_input || iq_ready != nullptr;
+    // A masked call (mi_demod_set_active_streams): one stage-1 launch and the serial stage 2 over the active streams, enqueued as a
+    // call without a predecessor (heads in place first, no overlap).  It leaves chain_live and serial_pipe clear, so the full
+    // call after it takes nothing from the previous call's arrays (prev_mag, prev_blk_*, prev_core, spec_head, xmax_prev: they
+    // would not hold every row) and seeds its chain from the ChanState rows.
+    const bool partial = h->masked;
+    if (partial && h->first_call)
+        return fail(MI_ERR_INVALID, "the handle's first call needs every stream active");
+    const int act_streams = partial ? h->nactive : h->nstreams;
+    Call call{d_iq, stream_stride, valid_bytes, nbatches, d_wmain, wmain_stride, d_iq_out, iq_out_stride, d_axc, s, iq_ready,
+              early_input, partial, act_streams, act_streams * h->nch, /*ca=*/{}, /*da=*/{},
+              /*evc=*/h->set[h->cur].ev};  // (the time-parallel and the pipelined serial path switch to the next set)
+    make_channelize_args(h, call);
+    make_demod_args(h, call);
+    const Path path = choose_path(h, call);
+    int rc = MI_OK;
+    switch (path) {
+        case kPathTimeParallel:
+            rc = enqueue_time_parallel(h, call);
+            break;
+        case kPathAfc:
+            rc = enqueue_afc(h, call);
+            break;
+        case kPathSerialPipelined:
+            rc = enqueue_serial_pipelined(h, call);
+            break;
+        case kPathSerial:
+            rc = enqueue_serial(h, call);
+            break;
+    }
+    if (rc != MI_OK)
+        return rc;
+    h->last_path = path == kPathTimeParallel ? kPathTimeParallel : kPathSerial;
+    if (path != kPathTimeParallel)
         h->ser_head_next = false;
-    HIP_TRY(hipEventRecord(evc[2], s));
+    HIP_TRY(hipEventRecord(call.evc[kEvDone], s));
     h->set[h->cur].seq = ++h->call_seq;
-    h->set[h->cur].path = pipelined_serial ? 2 : h->last_path;
+    h->set[h->cur].path = path == kPathSerialPipelined ? kPathSerialPipelined : h->last_path;  // (an AFC call is timed as a serial one)
     h->first_call = false;
     return MI_OK;
 }
@@ -1870,7 +1994,7 @@ int mi_demod_last_path(mi_demod* h, int* time_parallel, int* unverified_rows) {
         *time_parallel = h->last_path;
     if (unverified_rows) {
         *unverified_rows = 0;
-        if (h->last_path == 1) {
+        if (h->last_path == kPathTimeParallel) {
             std::vector<mi::TpFinal> f(static_cast<size_t>(h->tp_rows));
             HIP_TRY(hipMemcpy(f.data(), h->d_fin, f.size() * sizeof(mi::TpFinal), hipMemcpyDeviceToHost));
             for (const mi::TpFinal& x : f)
@@ -1897,7 +2021,7 @@ int mi_demod_last_stage1(mi_demod* h, int* kind) {
 }
 
 int mi_demod_tp_debug(mi_demod* h, int row, float* core4, int max_entries, int* diag4, int* nseg) {
-    if (!h || row < 0 || row >= h->tp_rows || !h->tp_eligible || h->last_path != 1)
+    if (!h || row < 0 || row >= h->tp_rows || !h->tp_eligible || h->last_path != kPathTimeParallel)
         return fail(MI_ERR_INVALID, "the last call did not take the time-parallel path");
     HIP_TRY(hipSetDevice(h->gpu));
     HIP_TRY(hipDeviceSynchronize());
@@ -1941,24 +2065,27 @@ static int kernel_time_of(mi_demod* h, int age, int index, const char** name, fl
         return fail(MI_ERR_INVALID, "that call has not been timed (or its events were reused)");
     HIP_TRY(hipSetDevice(h->gpu));
     const mi::Event* evq = h->set[q].ev;
-    HIP_TRY(hipEventSynchronize(evq[2]));
+    HIP_TRY(hipEventSynchronize(evq[kEvDone]));
     float t = 0.f;
     int n = 1;
     const char* nm = nullptr;
-    if (h->set[q].path == 0 || h->set[q].path == 2) {
+    if (h->set[q].path != kPathTimeParallel) {
         if (index > 1)
             return fail(MI_ERR_INVALID, "kernel index out of range");
         nm = index == 0 ? "k_channelize" : "k_demod";
-        if (h->set[q].path == 2 && index == 1)  // pipelined serial call: k_demod starts at its own event on the caller's stream
-            HIP_TRY(hipEventElapsedTime(&t, evq[3], evq[2]));
-        else
-            HIP_TRY(hipEventElapsedTime(&t, evq[index], evq[index + 1]));
+        if (index == 0)
+            HIP_TRY(hipEventElapsedTime(&t, evq[kEvBegin], evq[kEvStage1Done]));
+        else  // (a pipelined serial call: k_demod starts at its own event on the caller's stream)
+            HIP_TRY(hipEventElapsedTime(&t, evq[h->set[q].path == kPathSerialPipelined ? kEvSerialBegin : kEvStage1Done], evq[kEvDone]));
     } else {
-        // (the chunk events: see mi_demod::CallSet::chunk_ev)
-        static const char* const names[] = {"k_channelize", "k_tp_full", "k_tp_core", "k_tp_seg", "k_tp_scan#0", "k_tp_fix#0", "k_tp_rest"};
-        static const int from[] = {0, 11, 3, 5, 10, 7, 8}, to[] = {1, 2, 4, 12, 7, 8, 9};
+        static const struct {
+            const char* name;
+            ChunkEv from, to;
+        } timed[] = {{"k_channelize", kEvStage1Begin, kEvStage1End}, {"k_tp_full", kEvFullBegin, kEvFullEnd},  {"k_tp_core", kEvCoreBegin, kEvCoreEnd},
+                     {"k_tp_seg", kEvSegBegin, kEvSegEnd},           {"k_tp_scan#0", kEvScanBegin, kEvScanEnd}, {"k_tp_fix#0", kEvScanEnd, kEvFixEnd},
+                     {"k_tp_rest", kEvFixEnd, kEvFinishEnd}};
         if (index == 7 && h->set[q].mixed) {  // a mixed plan: the serial kernel of the other rows, on its own stream
-            HIP_TRY(hipEventElapsedTime(&t, evq[3], evq[4]));
+            HIP_TRY(hipEventElapsedTime(&t, evq[kEvSerialBegin], evq[kEvSerialEnd]));
             if (name)
                 *name = "k_demod";
             if (ms_total)
@@ -1969,13 +2096,11 @@ static int kernel_time_of(mi_demod* h, int age, int index, const char** name, fl
         }
         if (index > 6)
             return fail(MI_ERR_INVALID, "kernel index out of range");
-        nm = names[index];
+        nm = timed[index].name;
         n = h->set[q].chunks;
-        const std::vector<mi::Event>& cev = h->set[q].chunk_ev;
         for (int i = 0; i < n; ++i) {
             float d = 0.f;
-            HIP_TRY(hipEventElapsedTime(&d, cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + from[index]],
-                                        cev[static_cast<size_t>(i) * mi_demod::kEvPerChunk + to[index]]));
+            HIP_TRY(hipEventElapsedTime(&d, h->set[q].chunk(i, timed[index].from), h->set[q].chunk(i, timed[index].to)));
             t += d;
         }
     }
@@ -1997,18 +2122,18 @@ int mi_demod_kernel_time_prev(mi_demod* h, int age, int index, const char** name
 }
 
 int mi_demod_event_ms(mi_demod* h, int ref_age, int age, int chunk, int event, float* ms) {
-    if (!h || !ms || age < 0 || ref_age < age || ref_age >= mi_demod::kSets || event < 0 || event >= mi_demod::kEvPerChunk || chunk < 0)
+    if (!h || !ms || age < 0 || ref_age < age || ref_age >= mi_demod::kSets || event < 0 || event >= kEvPerChunk || chunk < 0)
         return fail(MI_ERR_INVALID, "bad argument");
     const int q = (h->cur + mi_demod::kSets - age) % mi_demod::kSets, qr = (h->cur + mi_demod::kSets - ref_age) % mi_demod::kSets;
     for (const int s : {q, qr})
-        if (!h->set[s].seq || h->set[s].path != 1)
+        if (!h->set[s].seq || h->set[s].path != kPathTimeParallel)
             return fail(MI_ERR_INVALID, "that call was not a time-parallel one (or its events were reused)");
     if (h->set[q].seq + static_cast<uint64_t>(age) != h->set[h->cur].seq || h->set[qr].seq + static_cast<uint64_t>(ref_age) != h->set[h->cur].seq ||
         chunk >= h->set[q].chunks)
         return fail(MI_ERR_INVALID, "no such call or chunk");
     HIP_TRY(hipSetDevice(h->gpu));
-    HIP_TRY(hipEventSynchronize(h->set[q].ev[2]));
-    HIP_TRY(hipEventElapsedTime(ms, h->set[qr].chunk_ev[3], h->set[q].chunk_ev[static_cast<size_t>(chunk) * mi_demod::kEvPerChunk + event]));
+    HIP_TRY(hipEventSynchronize(h->set[q].ev[kEvDone]));
+    HIP_TRY(hipEventElapsedTime(ms, h->set[qr].chunk(0, kEvCoreBegin), h->set[q].chunk(chunk, static_cast<ChunkEv>(event))));
     return MI_OK;
 }
 
@@ -2017,14 +2142,14 @@ int mi_demod_last_kernel_ms(mi_demod* h, float* channelize_ms, float* demod_ms) 
         return fail(MI_ERR_INVALID, "no call has been timed yet");
     HIP_TRY(hipSetDevice(h->gpu));
     const mi::Event* evq = h->set[h->cur].ev;
-    HIP_TRY(hipEventSynchronize(evq[2]));
+    HIP_TRY(hipEventSynchronize(evq[kEvDone]));
     float a = 0.f, b = 0.f;
-    if (h->last_path == 0) {
-        HIP_TRY(hipEventElapsedTime(&a, evq[0], evq[1]));
-        HIP_TRY(hipEventElapsedTime(&b, evq[h->serial_pipe ? 3 : 1], evq[2]));
+    if (h->last_path == kPathSerial) {
+        HIP_TRY(hipEventElapsedTime(&a, evq[kEvBegin], evq[kEvStage1Done]));
+        HIP_TRY(hipEventElapsedTime(&b, evq[h->serial_pipe ? kEvSerialBegin : kEvStage1Done], evq[kEvDone]));
     } else {  // pipelined: stage 1 summed over the chunks, stage 2 = the rest of the call's wall time on the stream
         float total = 0.f;
-        HIP_TRY(hipEventElapsedTime(&total, evq[0], evq[2]));
+        HIP_TRY(hipEventElapsedTime(&total, evq[kEvBegin], evq[kEvDone]));
         int rc = mi_demod_kernel_time(h, 0, nullptr, &a, nullptr);
         if (rc != MI_OK)
             return rc;

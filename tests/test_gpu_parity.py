@@ -7,7 +7,8 @@ asserted as well."""
 import numpy as np
 import pytest
 
-from common import AGC_EXTRA, WAVE_BATCH, assert_same, bytes_for_batches, gen_iq, oracle_run, rms
+import libs
+from common import AGC_EXTRA, WAVE_BATCH, assert_same, bytes_for_batches, gen_iq, oracle_run, rms, to_oracle_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -270,6 +271,56 @@ def test_time_parallel_streaming_calls_and_path_switch(pkg, monkeypatch):
     for c in range(len(chans)):
         for f in ("noise_level", "signal_level", "squelch_level", "agcavgfast", "open_count", "flappy_count", "active_counter", "squelch_state"):
             assert getattr(st[c], f) == getattr(st2[c], f), (c, f)
+
+
+def test_one_handle_visits_every_path_in_turn(pkg, monkeypatch):
+    """What each stage-2 path leaves on the handle for the next one, on a single handle that takes them all in turn: 2 streams x
+    (a plain AM channel, an NFM channel with raw I/Q outputs) at fft 512 -- a mixed plan -- with MI_OPT_EARLY_INPUT.  A first call
+    of one batch (the serial kernel), a mixed time-parallel call of 8 batches, two one-batch calls with the time-parallel path
+    off (the heads moved back in place, then a pipelined serial call right after a mixed one), a call that stream 1 sits out, a
+    full call, and a time-parallel call again.  Per stream, what the calls it took part in produced equals the oracle over the
+    IQ it consumed: audio, raw I/Q, flags and the squelch levels of the final statistics."""
+    monkeypatch.delenv("MI_AIRBAND_TP", raising=False)
+    centre = 120000000
+    chans = [pkg.channel_cfg(centre + 250000), pkg.channel_cfg(centre - 500000, modulation=pkg.MOD_NFM, has_iq_outputs=1)]
+    dev = pkg.device_cfg(centerfreq=centre, fft_size_log=9)
+    # (batches, MI_OPT_TIME_PARALLEL, the streams that take part, mi_demod_last_path)
+    calls = [(1, -1, "11", 0), (8, 1, "11", 1), (1, 0, "11", 0), (1, 0, "11", 0), (1, 0, "10", 0), (1, 0, "11", 0), (8, 1, "11", 1)]
+    ns = 2
+    nbat = [sum(k for k, _, mask, _ in calls if mask[s] == "1") for s in range(ns)]
+    iqs = [gen_iq(pkg, dev, centre, chans, nbat[s], stream=s, gate_div=5 + s, active=lambda k: True)[0] for s in range(ns)]
+    oracle = []
+    for s in range(ns):
+        od = libs.OracleDemod(*to_oracle_cfg(dev, chans))
+        nb, owo, oaxc, oiq = od.run(iqs[s], nbat[s], want_iq=True)
+        assert nb == nbat[s]
+        oracle.append((owo, oaxc, oiq, od.squelch_levels()))
+        od.close()
+    d = pkg.Demod(dev, chans, nstreams=ns, max_batches=max(k for k, _, _, _ in calls))
+    d.set_option(pkg.OPT_EARLY_INPUT, 1)
+    got = [dict(wo=[], axc=[], iqo=[]) for _ in range(ns)]
+    done = [0] * ns
+    for ci, (k, tp, mask, path) in enumerate(calls):
+        d.set_option(pkg.OPT_TIME_PARALLEL, tp)
+        d.set_active_streams([m == "1" for m in mask])
+        pos = [0 if done[s] == 0 else (done[s] * WAVE_BATCH + AGC_EXTRA) * d.hop_bytes for s in range(ns)]
+        wo, axc, iqo, stats = d.process([iqs[s][pos[s]:] if mask[s] == "1" else None for s in range(ns)], k, want_iq=True)
+        assert d.last_path() == (path, 0), f"call {ci}: stage-2 path"
+        for s in range(ns):
+            if mask[s] == "1":
+                got[s]["wo"].append(wo[s, :, :k * WAVE_BATCH]), got[s]["axc"].append(axc[s]), got[s]["iqo"].append(iqo[s])
+                done[s] += k
+    assert d.pre_wave_timeouts() == 0
+    d.close()
+    for s in range(ns):
+        owo, oaxc, oiq, olevels = oracle[s]
+        assert_same(np.concatenate(got[s]["axc"], axis=1), oaxc, f"stream {s}: flags")
+        assert_same(np.concatenate(got[s]["wo"], axis=1), owo, f"stream {s}: audio")
+        assert_same(np.concatenate(got[s]["iqo"], axis=1)[1].reshape(-1), oiq[1], f"stream {s}: raw I/Q of the NFM channel")
+        levels = np.array([stats[s * len(chans) + c].squelch_level for c in range(len(chans))], np.float32)
+        assert_same(levels, oracle[s][3], f"stream {s}: squelch levels of the final statistics")
+        for c in range(len(chans)):
+            assert (oaxc[c] == ord("*")).any() and (oaxc[c] == ord(" ")).any(), f"stream {s}, channel {c}: the squelch should open and close"
 
 
 def test_time_parallel_hard_signals(pkg, monkeypatch):
