@@ -229,3 +229,22 @@ void ao_demod_bins(const ao_demod* d, int32_t* bins, int32_t* base_bins) {
         base_bins[i] = (int32_t)d->ch[i].base_bin;
     }
 }
+
+/* re^2 + im^2 of every bin of the last window pushed -- after a run that ended on a batch, the spectrum AFC::finalize was
+ * handed for that batch (rtl_airband.cpp:186-192, :648-652), in the walk's own float arithmetic */
+void ao_demod_afc_spectrum(const ao_demod* d, float* sq) {
+    for (size_t k = 0; k < d->fft_size; k++)
+        sq[k] = d->fftout[2 * k] * d->fftout[2 * k] + d->fftout[2 * k + 1] * d->fftout[2 * k + 1];
+}
+
+/* per channel: open_count, flappy_count, ctcss found / not found, active_counter -- the counters of mi_channel_stats */
+void ao_demod_counters(const ao_demod* d, uint64_t* out) {
+    for (int i = 0; i < d->nch; i++) {
+        const ao_squelch* s = &d->ch[i].squelch;
+        out[5 * i + 0] = s->open_count;
+        out[5 * i + 1] = s->flappy_count;
+        out[5 * i + 2] = s->ctcss_slow.found_count;
+        out[5 * i + 3] = s->ctcss_slow.not_found_count;
+        out[5 * i + 4] = d->ch[i].active_counter;
+    }
+}

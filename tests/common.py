@@ -53,3 +53,28 @@ def assert_same(a, b, what):
 
 def rms(x):
     return float(np.sqrt(np.mean(np.square(np.asarray(x, dtype=np.float64)))))
+
+
+# ---- the checkpoint blob (mi_demod_get_state): [header][ChanState rows][carry][ring][ctcss_q][mag head][cplx head]
+AFC_BIN_OFFSET = 164                  # ChanState::afc_bin (csrc/kernels.hpp)
+PREV_AXC_OFFSET = AFC_BIN_OFFSET + 4  # ChanState::prev_axc, the field after it
+
+
+def blob_rows(blob, nstreams):
+    """the checkpoint blob cut into one piece per stream (every section of it is stream-major), header aside"""
+    hd = blob[:32].view(np.uint32)
+    rows, nch, niq, nct = int(hd[1]), int(hd[2]), int(hd[3]), int(hd[4])
+    assert rows == nstreams * nch
+    fixed = rows * AGC_EXTRA * 4 * 2 + rows * 102 * 4 + nstreams * nct * 4 * 52 * 4 + nstreams * niq * AGC_EXTRA * 8
+    state = blob.size - 32 - fixed
+    assert state % rows == 0
+    sections = [state, rows * AGC_EXTRA * 4, rows * 102 * 4, nstreams * nct * 4 * 52 * 4, rows * AGC_EXTRA * 4, nstreams * niq * AGC_EXTRA * 8]
+    per = [[] for _ in range(nstreams)]
+    at = 32
+    for sz in sections:
+        assert sz % nstreams == 0
+        for s in range(nstreams):
+            per[s].append(blob[at + s * (sz // nstreams):at + (s + 1) * (sz // nstreams)])
+        at += sz
+    assert at == blob.size
+    return [np.concatenate(p) for p in per], state // rows

@@ -163,6 +163,10 @@ def oracle_lib():
         lib.ao_afc_check.restype = C.c_size_t
         lib.ao_demod_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ao_demod_bins.restype = None
+        lib.ao_demod_afc_spectrum.argtypes = [C.c_void_p, f32p]
+        lib.ao_demod_afc_spectrum.restype = None
+        lib.ao_demod_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ao_demod_counters.restype = None
         lib.ao_demod_squelch_levels.argtypes = [C.c_void_p, f32p]
         lib.ao_demod_squelch_levels.restype = None
         lib.ao_window.argtypes = [f32p, C.c_size_t]
@@ -239,6 +243,18 @@ class OracleDemod:
         cur, base = np.zeros(self.nch, np.int32), np.zeros(self.nch, np.int32)
         self.lib.ao_demod_bins(self.h, cur.ctypes.data_as(C.c_void_p), base.ctypes.data_as(C.c_void_p))
         return cur, base
+
+    def afc_spectrum(self):
+        """re^2 + im^2 of the last window pushed: after run() the spectrum AFC::finalize walked for the last batch."""
+        out = np.zeros(1 << self.dev.fft_size_log, np.float32)
+        self.lib.ao_demod_afc_spectrum(self.h, out)
+        return out
+
+    def counters(self):
+        """[nch][5]: open_count, flappy_count, ctcss_count, no_ctcss_count, active_counter."""
+        out = np.zeros((self.nch, 5), np.uint64)
+        self.lib.ao_demod_counters(self.h, out.ctypes.data_as(C.c_void_p))
+        return out
 
     def squelch_levels(self):
         """The level every channel's squelch compares against, as of the last batch run."""

@@ -11,13 +11,12 @@ import numpy as np
 import pytest
 
 import libs
-from common import AGC_EXTRA, WAVE_BATCH, assert_same, bytes_for_batches, to_oracle_cfg
+from common import AFC_BIN_OFFSET, AGC_EXTRA, WAVE_BATCH, assert_same, blob_rows, bytes_for_batches, to_oracle_cfg
 
 pytestmark = pytest.mark.gpu
 
 SENT32 = 0xDEADBEEF  # what every output buffer holds before a call
 SENT8 = 0xEE
-AFC_BIN_OFFSET = 164  # ChanState::afc_bin (csrc/kernels.hpp)
 SCHEDULE3 = ["111", "101", "001", "110", "010", "111"]
 SCHEDULE5 = ["11111", "10101", "00100", "11010", "01011", "11111"]
 CENTRE = 120_000_000
@@ -107,26 +106,6 @@ def case_data(name):
         solo.append(bytes(st))
         d.close()
     return dev, chans, iqs, oracle, solo, schedule
-
-
-def blob_rows(blob, nstreams):
-    """the checkpoint blob cut into one piece per stream (every section of it is stream-major), header aside"""
-    hd = blob[:32].view(np.uint32)
-    rows, nch, niq, nct = int(hd[1]), int(hd[2]), int(hd[3]), int(hd[4])
-    assert rows == nstreams * nch
-    fixed = rows * AGC_EXTRA * 4 * 2 + rows * 102 * 4 + nstreams * nct * 4 * 52 * 4 + nstreams * niq * AGC_EXTRA * 8
-    state = blob.size - 32 - fixed
-    assert state % rows == 0
-    sections = [state, rows * AGC_EXTRA * 4, rows * 102 * 4, nstreams * nct * 4 * 52 * 4, rows * AGC_EXTRA * 4, nstreams * niq * AGC_EXTRA * 8]
-    per = [[] for _ in range(nstreams)]
-    at = 32
-    for sz in sections:
-        assert sz % nstreams == 0
-        for s in range(nstreams):
-            per[s].append(blob[at + s * (sz // nstreams):at + (s + 1) * (sz // nstreams)])
-        at += sz
-    assert at == blob.size
-    return [np.concatenate(p) for p in per], state // rows
 
 
 class HostCall:
