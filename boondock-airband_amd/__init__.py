@@ -43,8 +43,8 @@ OPT_LANE_FFT = 10
 OPT_LANE_FFT_JIT = 11
 OPT_CORE_SPLIT = 12
 OPT_SPEC_HEAD = 13
-OPT_RESERVE_CUS = 15
 OPT_PRE_WAVE = 14
+OPT_RESERVE_CUS = 15
 OPT_AUDIO_WAVE = 16
 OPT_MIXED_PLAN = 17
 OPT_SPLIT_CUS = 18

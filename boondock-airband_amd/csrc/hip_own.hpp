@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <iterator>
 #include <type_traits>
 #include <utility>
 
@@ -72,6 +73,21 @@ hipError_t dalloc(DevBuf<T>& b, size_t count) {
     if (count == 0)
         return hipSuccess;
     return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+}
+
+// ... all zero
+template <class T>
+hipError_t dalloc_zero(DevBuf<T>& b, size_t count) {
+    const hipError_t e = dalloc(b, count);
+    return (e != hipSuccess || count == 0) ? e : hipMemset(b, 0, count * sizeof(T));
+}
+
+// ... holding the elements of a host array or vector (in `room` elements, where more are wanted than are uploaded)
+template <class T, class Src>
+hipError_t dalloc_copy(DevBuf<T>& b, const Src& src, size_t room = 0) {
+    const size_t count = std::size(src);
+    const hipError_t e = dalloc(b, room > count ? room : count);
+    return (e != hipSuccess || count == 0) ? e : hipMemcpy(b, std::data(src), count * sizeof(T), hipMemcpyHostToDevice);
 }
 
 }  // namespace mi

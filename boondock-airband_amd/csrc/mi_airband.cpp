@@ -7,7 +7,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -16,6 +15,7 @@
 #include "hip_own.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "tuning.hpp"
 
 namespace {
 
@@ -146,39 +146,13 @@ struct mi_demod {
     float* d_mag_last = nullptr;   // ... and these are the planes it worked on (mi_demod_read_planes): views
     float2* d_cplx_last = nullptr;
     uint32_t head_off = 0;     // plane index where the AGC_EXTRA carried samples of every row live (0 after a serial call)
-    bool steady_blocks = true;  // MI_OPT_STEADY_BLOCKS
-    // Tuning switches of this handle (mi_demod_set_option; defaults from the MI_AIRBAND_* environment at mi_demod_create --
-    // read per handle, the library keeps no process-wide state)
-    int opt_tp = -1;          // MI_OPT_TIME_PARALLEL: -1 auto, 0 serial kernel, 1 time-parallel whenever eligible
-    int opt_conv = -1;        // MI_OPT_U8_CONVERSION: -1 auto, 0 level table, 1 arithmetic
-    bool opt_prune = true;    // MI_OPT_PRUNE_FFT
-    int opt_uni_rows = 4096;  // MI_OPT_UNI_ROWS: up to this many rows keep one channel per wave in k_demod
-    int opt_tp_chunks = 0;    // MI_OPT_TP_CHUNKS: 0 = measured default
-    double opt_tp_ratio = 0;  // MI_OPT_TP_RATIO_PCT / 100: 0 = measured default
-    int opt_tp_lpw = 0;       // MI_OPT_TP_SEG_LANES: lanes per wave of the segment pass, 0 = auto
-    int opt_pre_wave = -1;       // MI_OPT_PRE_WAVE: serial kernel, one channel per wave: further waves per channel walk the squelch pre-filter ahead and the audio behind (k_demod_pw); -1 = up to 256 rows
-    bool opt_audio_wave = true;  // MI_OPT_AUDIO_WAVE: ... and NFM channels a third wave for everything behind the filtered I/Q (audio, CTCSS, gate, stores)
-    bool opt_spec_head = true;   // MI_OPT_SPEC_HEAD: overlapped calls start their first segments from a guessed state (see TpArgs)
-    int opt_tp_eager = 0;        // (diagnostic, MI_AIRBAND_TP_EAGER)
-    int opt_core_lead = 0;       // (diagnostic, MI_AIRBAND_CORE_LEAD) blocks the noise-floor wave may run ahead, 0 = default
-    int opt_agc_hint = 1;        // (diagnostic, MI_AIRBAND_AGC_HINT=0) segment lanes start from agcavgfast = 0.5 instead of the channel's last value
-    int opt_core_decay = 1;      // (diagnostic, MI_AIRBAND_CORE_DECAY=0) no decay waves: the walking wave steps every decay itself
-    int opt_core_guess = 1;      // (diagnostic, MI_AIRBAND_CORE_GUESS) 0: the noise-floor wave walks systolic passes only; 2: the first guess-and-verify rounds (groups of 64)
-    int opt_core_lean = 1;       // (diagnostic, MI_AIRBAND_CORE_LEAN=0) k_tp_core2 without the round-4 run paths and restarts
-    bool opt_core_split = true;  // MI_OPT_CORE_SPLIT: noise-floor passes of the core chain on their own wave (k_tp_core2)
-    bool core_split_ok = false;  // ... the plan allows it: automatic squelch levels with a cap factor >= 1 on every channel
-    bool opt_l64 = true;      // MI_OPT_LANE_FFT: the lane-resident stage 1 (N = 512, 1024, 2048) where the plan allows it
-    int opt_l64_linear = 0;   // (diagnostic) tiles in blockIdx order instead of grouped per XCD
-    bool opt_l64_jit = true;  // MI_OPT_LANE_FFT_JIT: compile the plan's own instance with hipRTC (else the full-graph instance)
-    bool early_input = false;  // MI_OPT_EARLY_INPUT: the IQ of a call is valid when the call is made
+    mi::Tuning opt;  // the tuning switches of this handle (tuning.hpp)
     bool chain_live = false;   // d_core_carry holds the chain state at the end of the previous call (it was time-parallel)
     mi::Stream seg_stream[kSegStreams];  // the speculative segment passes (need core(i) only)
     // MI_OPT_RESERVE_CUS: twins of the front and segment streams whose kernels keep off the last `reserve_cus` CUs (see enqueue_time_parallel)
     mi::Stream front_stream_m;
     mi::Stream seg_stream_m[kSegStreams];
-    int opt_reserve_cus = -1;  // -1 auto: 32 for handles of up to 64 rows, none beyond; 0 none
-    // MI_OPT_SPLIT_CUS: pipelined serial calls: stage 1 keeps off the last n CUs, k_demod runs on them alone; -1 auto (see enqueue_serial_pipelined)
-    int opt_split_cus = -1;
+    // MI_OPT_SPLIT_CUS: pipelined serial calls: stage 1 keeps off the last n CUs, k_demod runs on them alone (see enqueue_serial_pipelined)
     int split_state = 0;  // 0 undecided, 1 the two CU-masked streams exist, 2 none
     mi::Stream ps_front_m, ps_demod_m;
     mi::Event ev_ps_entry, ev_ps_done;
@@ -248,12 +222,9 @@ struct mi_demod {
     bool failed = false;  // a call advanced the DSP state and then could not deliver its results: every further call is refused
     mi::Stream copy_stream;  // uploads of submitted calls
     mi::Stream down_stream;  // their downloads
-    // time-parallel stage 2 (tp.hip): the plain AM channels of the plan.  A mixed plan (tp_mixed) sends those rows down the time-parallel
-    // path and the others through the serial kernel in the same call (MI_OPT_MIXED_PLAN), on a stream of its own beside the chain.
-    bool tp_eligible = false;
-    bool tp_mixed = false;
-    bool opt_mixed = true;
-    int tp_rows = 0, ser_rows = 0;       // rows of either kind (tp_rows + ser_rows == rows)
+    // time-parallel stage 2 (tp.hip): the plain AM channels of the plan.  A mixed plan (cls.tp_mixed) sends those rows down that path and
+    // the others through the serial kernel in the same call (MI_OPT_MIXED_PLAN), on a stream of its own beside the chain.
+    mi::RowClasses cls;                  // rows of either kind (cls.tp_rows + cls.ser_rows == rows)
     mi::DevBuf<int> d_srows;             // the serial kernel's rows of a mixed plan (d_rows: the time-parallel path's)
     mi::Stream ser_stream;               // ... and its stream
     mi::Event ev_cplx_free[2];           // the serial kernel of a mixed call has read complex plane set p
@@ -274,7 +245,6 @@ struct mi_demod {
     mi::DevBuf<int> d_diag;
     size_t tp_max_blk = 0, tp_max_seg = 0;
     uint32_t tp_L = 512;  // steps per segment (kernels.hpp, TP_L_MIN .. TP_L_MAX), fixed when the handle is created
-    int opt_tp_L = 0;     // MI_AIRBAND_TP_SEGMENT at create: 0 = by row count
     // mi_demod_set_active_streams: the streams that take part in the calls made from now on.  A masked call (not every stream
     // active) runs stage 1 and the serial stage 2 over the lists below and nothing else: what the other streams carry between
     // calls (ChanState rows, lookahead, plane heads, squelch ring, CTCSS table, AFC bin) is in arrays indexed by handle row or
@@ -304,105 +274,19 @@ constexpr int kTpAutoMaxRows = 256;
 // split against 0.70 / 1.41 / 2.58 whole; 1 stream x 32 at fft 2048, 8 s: 1.85 against 2.51).
 constexpr int kMixedMinBatches = 64;
 
-// Defaults of a new handle's tuning switches from the caller's environment (A/B measurements, tests):
-//   MI_AIRBAND_TP=0|1        serial kernel / time-parallel path whenever eligible
-//   MI_AIRBAND_PRUNE=0       full FFT graph at N = 512 (the pruned one is bit-exact and faster where it applies)
-//   MI_AIRBAND_CONV=lut|arith  u8 conversion through the level table / the arithmetic form the plan has checked against it
-//   MI_AIRBAND_STEADY=0      serial stage 2 takes every step in the sample loop
-//   MI_AIRBAND_TP_SEGMENT=512|1024|2048|4096  steps per segment of the time-parallel path (default: by row count; sizes the scratch,
-//                            so it is read when the handle is created and has no mi_demod_set_option twin)
-//   MI_AIRBAND_L64=0         no lane-resident stage 1 at N = 512, 1024, 2048 (the pruned / full exchange kernels instead)
-//   MI_AIRBAND_UNI_ROWS=n, MI_AIRBAND_TP_CHUNKS=n, MI_AIRBAND_TP_RATIO=x, MI_AIRBAND_TP_LPW=n
-void tuning_from_env(mi_demod* h) {
-    // (MI_AIRBAND_DEBUG=1: every tuning variable found in the environment is named on stderr when a handle is created -- a variable
-    //  exported for a test changes what a production handle does just as silently as it changes the test's)
-    static const bool debug = [] {
-        const char* e = std::getenv("MI_AIRBAND_DEBUG");
-        return e && *e && std::atoi(e) != 0;
-    }();
-    auto get = [](const char* k) -> const char* {
-        const char* e = std::getenv(k);
-        if (e && *e && debug)
-            std::fprintf(stderr, "mi_airband: %s=%s (from the environment)\n", k, e);
-        return (e && *e) ? e : nullptr;
-    };
-    if (const char* e = get("MI_AIRBAND_TP"))
-        h->opt_tp = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = get("MI_AIRBAND_CONV"))
-        h->opt_conv = (e[0] == 'a' || e[0] == 'A') ? 1 : 0;
-    if (const char* e = get("MI_AIRBAND_STEADY"))
-        h->steady_blocks = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_PRUNE"))
-        h->opt_prune = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_UNI_ROWS"))
-        h->opt_uni_rows = std::max(1, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_TP_CHUNKS"))
-        h->opt_tp_chunks = std::max(1, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_TP_RATIO"))
-        h->opt_tp_ratio = std::max(0.25, std::atof(e));
-    if (const char* e = get("MI_AIRBAND_TP_SEGMENT")) {
-        const int v = std::atoi(e);
-        h->opt_tp_L = (v == 512 || v == 1024 || v == 2048 || v == 4096) ? v : 0;
-    }
-    if (const char* e = get("MI_AIRBAND_CORE_SPLIT"))
-        h->opt_core_split = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_TP_EAGER"))
-        h->opt_tp_eager = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_CORE_LEAD"))
-        h->opt_core_lead = std::max(0, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_RESERVE_CUS"))
-        h->opt_reserve_cus = std::max(-1, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_SPLIT_CUS"))
-        h->opt_split_cus = std::max(-1, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_AGC_HINT"))
-        h->opt_agc_hint = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_CORE_DECAY"))
-        h->opt_core_decay = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_CORE_GUESS"))
-        h->opt_core_guess = std::max(0, std::min(2, std::atoi(e)));
-    if (const char* e = get("MI_AIRBAND_CORE_LEAN"))
-        h->opt_core_lean = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_PRE_WAVE"))
-        h->opt_pre_wave = std::atoi(e) < 0 ? -1 : std::min(2, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_MIXED"))
-        h->opt_mixed = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_AUDIO_WAVE"))
-        h->opt_audio_wave = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_SPEC_HEAD"))
-        h->opt_spec_head = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_L64"))
-        h->opt_l64 = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_L64_JIT"))
-        h->opt_l64_jit = std::atoi(e) != 0;
-    if (const char* e = get("MI_AIRBAND_L64_WGS"))
-        h->opt_l64_linear = std::max(0, std::atoi(e));
-    if (const char* e = get("MI_AIRBAND_TP_LPW")) {
-        const int v = std::atoi(e);
-        h->opt_tp_lpw = (v >= 1 && v <= 64) ? v : 0;
-    }
-}
-
 int slot_prepare(mi_demod* h, int k);  // (defined with the host-buffer entries below)
 
 // The plan's own instance of the lane-resident stage 1 (hipRTC, or the code object an earlier start left on disk): 0.3-0.6 s
 // when it has to be compiled, so it is asked for when the handle is created -- before any input thread fills a ring.
-void stage1_compile(mi_demod* h) {
-    if (h->l64_jit_tried || !h->opt_l64_jit || !h->opt_l64 || !h->plan.l64.enabled || !h->d_l64_chan)
+// `masked`: the instance that takes a stream list (calls of some streams only; never with AFC): compiled, or loaded from the
+// cache, when mi_demod_set_active_streams first sets a stream aside -- a host that cannot afford the compilation between two
+// batches sets such a mask once before its input threads start
+void stage1_compile(mi_demod* h, bool masked) {
+    bool& tried = masked ? h->l64_jit_masked_tried : h->l64_jit_tried;
+    if (tried || !h->opt.l64_jit || !h->opt.l64 || !h->plan.l64.enabled || !h->d_l64_chan || (masked && h->plan.any_afc))
         return;
-    h->l64_jit_tried = true;
-    const int hop = static_cast<int>(h->plan.hop_bytes / (2 * static_cast<size_t>(h->plan.bytes_per_sample)));
-    h->l64_jit = mi::l64_jit_get(h->gpu, h->plan.log2n, hop, h->plan.l64.need, nullptr);
-}
-
-// ... and the instance that takes a stream list (calls of some streams only): compiled, or loaded from the cache, when
-// mi_demod_set_active_streams first sets a stream aside -- a host that cannot afford the compilation between two batches sets
-// such a mask once before its input threads start
-void stage1_compile_masked(mi_demod* h) {
-    if (h->l64_jit_masked_tried || !h->opt_l64_jit || !h->opt_l64 || !h->plan.l64.enabled || !h->d_l64_chan || h->plan.any_afc)
-        return;
-    h->l64_jit_masked_tried = true;
-    const int hop = static_cast<int>(h->plan.hop_bytes / (2 * static_cast<size_t>(h->plan.bytes_per_sample)));
-    h->l64_jit_masked = mi::l64_jit_get(h->gpu, h->plan.log2n, hop, h->plan.l64.need, nullptr, /*masked=*/true);
+    tried = true;
+    (masked ? h->l64_jit_masked : h->l64_jit) = mi::l64_jit_get(h->gpu, h->plan.log2n, h->plan.hop_samples(), h->plan.l64.need, nullptr, masked);
 }
 
 // MI_AIRBAND_DEBUG=1: once per handle, why its plan does not get the lane-resident stage 1
@@ -410,13 +294,12 @@ void stage1_explain(mi_demod* h) {
     if (h->l64_why_said)
         return;
     h->l64_why_said = true;  // (decided on the handle's first call, whatever the outcome)
-    const char* dbg = std::getenv("MI_AIRBAND_DEBUG");
-    if (!dbg || std::atoi(dbg) == 0)
+    if (!mi::debug_enabled())
         return;
     const char* why = nullptr;
     if (!h->plan.l64.enabled)
         why = h->plan.l64.why ? h->plan.l64.why : "the plan does not allow it";
-    else if (h->opt_l64 && h->opt_l64_jit && h->l64_jit_tried && !h->l64_jit)
+    else if (h->opt.l64 && h->opt.l64_jit && h->l64_jit_tried && !h->l64_jit)
         why = "hipRTC could not provide the plan's own instance";
     if (!why)
         return;
@@ -424,8 +307,8 @@ void stage1_explain(mi_demod* h) {
 }
 
 int lanes_per_wave_for(const mi_demod* h, int rows) {
-    // up to opt_uni_rows waves keep one channel each (the uniform instantiation of k_demod); beyond that pack lanes
-    int lpw = (rows + h->opt_uni_rows - 1) / h->opt_uni_rows;
+    // up to opt.uni_rows waves keep one channel each (the uniform instantiation of k_demod); beyond that pack lanes
+    int lpw = (rows + h->opt.uni_rows - 1) / h->opt.uni_rows;
     return std::min(64, std::max(1, lpw));
 }
 
@@ -433,26 +316,17 @@ int lanes_per_wave_for(const mi_demod* h, int rows) {
 bool serial_sets_ready(mi_demod* h) {
     if (h->set[1].mag && (h->d_cplx_set[1] || !h->d_cplx_set[0]))
         return true;
-    const size_t rows = static_cast<size_t>(h->rows);
-    if (!h->set[1].mag) {
-        mi::DevBuf<float> m;
-        if (dalloc(m, rows * h->plane_stride) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        (void)hipMemset(m, 0, rows * h->plane_stride * 4);
+    mi::DevBuf<float> m;
+    mi::DevBuf<float2> z;
+    if ((!h->set[1].mag && dalloc_zero(m, static_cast<size_t>(h->rows) * h->plane_stride) != hipSuccess) ||
+        (h->d_cplx_set[0] && !h->d_cplx_set[1] && dalloc_zero(z, static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows * h->plane_stride) != hipSuccess)) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (m)
         h->set[1].mag = std::move(m);
-    }
-    if (h->d_cplx_set[0] && !h->d_cplx_set[1]) {
-        const size_t zn = static_cast<size_t>(h->nstreams) * h->plan.n_iq_rows * h->plane_stride;
-        mi::DevBuf<float2> z;
-        if (dalloc(z, zn) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        (void)hipMemset(z, 0, zn * 8);
+    if (z)
         h->d_cplx_set[1] = std::move(z);
-    }
     return true;
 }
 
@@ -492,33 +366,33 @@ void make_channelize_args(mi_demod* h, Call& call) {
     ca.window = h->d_window;
     ca.tw = h->d_tw;
     ca.prune = h->plan.prune;
-    ca.prune.enabled = (ca.prune.enabled && h->opt_prune) ? 1 : 0;
+    ca.prune.enabled = (ca.prune.enabled && h->opt.prune) ? 1 : 0;
     ca.prune_t1 = h->d_prune_t1;
     ca.prune_t2 = h->d_prune_t2;
     ca.prune_rank = h->d_prune_rank;
     ca.l64 = h->plan.l64;
-    ca.l64.enabled = (ca.l64.enabled && h->opt_l64 && h->d_l64_chan) ? 1 : 0;
+    ca.l64.enabled = (ca.l64.enabled && h->opt.l64 && h->d_l64_chan) ? 1 : 0;
     ca.l64.linear_tiles = 0;
-    ca.l64.wg_per_cu = h->opt_l64_linear;  // (MI_AIRBAND_L64_WGS: workgroups per CU of the persistent stage-1 launch, 0 = default)
+    ca.l64.wg_per_cu = h->opt.l64_wgs;  // (MI_AIRBAND_L64_WGS: workgroups per CU of the persistent stage-1 launch, 0 = default)
     ca.l64_chan = h->d_l64_chan;
     ca.l64_tickets = h->d_l64_tickets;
     ca.l64_ticket_seq = &h->l64_ticket_seq;
     ca.l64_chan_full = h->d_l64_chan_full;
     if (ca.l64.enabled) {  // (normally done by mi_demod_create / _set_active_streams; here only if the option was switched on afterwards)
-        stage1_compile(h);
+        stage1_compile(h, false);
         if (partial)
-            stage1_compile_masked(h);
+            stage1_compile(h, true);
     }
-    ca.l64_jit = h->opt_l64_jit ? (partial ? h->l64_jit_masked : h->l64_jit) : nullptr;
+    ca.l64_jit = h->opt.l64_jit ? (partial ? h->l64_jit_masked : h->l64_jit) : nullptr;
     // The prebuilt full-graph instance keeps all 64 points of a lane live and is slower than the exchange kernels: it runs
     // only when asked for (MI_OPT_LANE_FFT_JIT = 0, tests); without hipRTC the pruned / full exchange kernels take over.
-    if (ca.l64.enabled && h->opt_l64_jit && !ca.l64_jit)
+    if (ca.l64.enabled && h->opt.l64_jit && !ca.l64_jit)
         ca.l64.enabled = 0;
     stage1_explain(h);
     ca.levels = h->d_levels;
     {
         const bool pruned = ca.prune.enabled && h->plan.log2n == 9 && !h->plan.any_afc;
-        const int cc = h->opt_conv;
+        const int cc = h->opt.conv;
         ca.conv_arith = (h->plan.conv_arith && (cc < 0 ? !pruned : cc == 1)) ? 1 : 0;
     }
     ca.conv_scale = h->plan.conv_scale;
@@ -567,30 +441,30 @@ void make_demod_args(const mi_demod* h, Call& call) {
     da.stats = h->d_stats;
     da.fm_quadri = h->plan.dev.fm_quadri;
     da.lanes_per_wave = lanes_per_wave_for(h, act_rows);
-    da.steady_blocks = h->steady_blocks ? 1 : 0;
+    da.steady_blocks = h->opt.steady_blocks ? 1 : 0;
     // the pre-filter wave pays where a call is bound by the latency of its rows (4 / 8 / 16 streams x 32 mixed channels: +44 / +37 /
     // +12 %); with a thousand rows and more the machine is full and a second wave per row only takes LDS and issue slots from
     // stage 1 (32 streams: +-0, 64 streams: -27 %)
     // (round 3: four waves per channel, each with a SIMD's register file to itself: one channel per CU, so up to 256 rows)
     // ... and two waves per channel (the channel with its audio, the pre-filter wave) up to 1 024 rows: 2 = k_demod_pw2
-    da.pre_wave = h->opt_pre_wave < 0 ? (act_rows <= 256 ? 1 : (act_rows <= 1024 ? 2 : 0)) : std::min(2, h->opt_pre_wave);
-    da.audio_wave = h->opt_audio_wave ? 1 : 0;
+    da.pre_wave = h->opt.pre_wave < 0 ? (act_rows <= 256 ? 1 : (act_rows <= 1024 ? 2 : 0)) : std::min(2, h->opt.pre_wave);
+    da.audio_wave = h->opt.audio_wave ? 1 : 0;
     da.pre_timeouts = h->d_pre_timeouts;
 }
 
 // The path of a call.  The conditions are evaluated left to right and no further than they decide: serial_sets_ready() allocates the
 // second plane set, which a handle gets only when a call of its own is about to use it.
 Path choose_path(mi_demod* h, const Call& call) {
-    const int env = h->opt_tp;
-    if (!call.partial && h->tp_eligible && env != 0 && (!h->tp_mixed || (h->opt_mixed && serial_sets_ready(h))) &&
-        (env == 1 || (call.nbatches >= (h->tp_mixed ? kMixedMinBatches : kTpMinBatches) && h->tp_rows <= kTpAutoMaxRows)))
+    const int env = h->opt.tp;
+    if (!call.partial && h->cls.tp_eligible && env != 0 && (!h->cls.tp_mixed || (h->opt.mixed && serial_sets_ready(h))) &&
+        (env == 1 || (call.nbatches >= (h->cls.tp_mixed ? kMixedMinBatches : kTpMinBatches) && h->cls.tp_rows <= kTpAutoMaxRows)))
         return kPathTimeParallel;
     if (h->plan.any_afc)
         return kPathAfc;
     // (a handle whose plan the time-parallel path could take as well -- many rows, or MI_OPT_TIME_PARALLEL = 0 -- pipelines its serial
     //  calls like any other as long as its planes are where that path keeps them: never after a time-parallel call)
     if (!call.partial && call.early_input && !h->first_call &&
-        (!h->tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) && serial_sets_ready(h))
+        (!h->cls.tp_eligible || (h->head_off == 0 && (h->d_mag == h->set[0].mag || h->d_mag == h->set[1].mag))) && serial_sets_ready(h))
         return kPathSerialPipelined;
     return kPathSerial;
 }
@@ -631,6 +505,30 @@ hipError_t cu_stream_create(mi::Stream& st, const std::vector<uint32_t>& mask) {
     return hipExtStreamCreateWithCUMask(st.put(), static_cast<uint32_t>(mask.size()), mask.data());
 }
 
+// A non-blocking stream at the highest or the lowest priority: a queue class of its own either way.  HIP multiplexes its streams onto
+// a few hardware queues and two streams that share one run their kernels one after the other (so the wide passes share few streams).
+hipError_t priority_stream(mi::Stream& st, bool highest) {
+    int lo_prio = 0, hi_prio = 0;
+    const hipError_t e = hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio);
+    return e != hipSuccess ? e : hipStreamCreateWithPriority(st.put(), hipStreamNonBlocking, highest ? hi_prio : lo_prio);
+}
+
+// Scratch set q of a handle the time-parallel path can serve (set 0 has its planes and lookahead already: every handle needs them)
+int alloc_call_set(mi_demod* h, int q) {
+    mi_demod::CallSet& cs = h->set[q];
+    const size_t rows = static_cast<size_t>(h->rows);
+    if (q >= 1) {
+        HIP_TRY(dalloc_zero(cs.mag, rows * h->plane_stride));
+        HIP_TRY(dalloc(cs.carry, rows * mi::kAgcExtra));
+    }
+    HIP_TRY(dalloc(cs.xmax, rows));
+    for (mi::DevBuf<float>* agg : {&cs.blk_fe, &cs.blk_fm, &cs.blk_x0, &cs.blk_xm})
+        HIP_TRY(dalloc(*agg, rows * h->tp_max_blk));
+    HIP_TRY(dalloc(cs.core, rows * (h->tp_max_seg + 1)));
+    HIP_TRY(dalloc(cs.rec, static_cast<size_t>(mi::TP_NREC) * rows * h->tp_max_seg));
+    return MI_OK;
+}
+
 // Chunk i of a time-parallel call covers units [bound[i], bound[i+1]): `want` chunks (at most one per unit), each `ratio` times the
 // one before it
 std::vector<uint32_t> tp_chunk_bounds(uint32_t units, int want, double ratio) {
@@ -660,7 +558,7 @@ mi::TpArgs make_tp_args(const mi_demod* h, const Call& call, int q, bool overlap
     const uint32_t n = call.da.nsteps, L = h->tp_L;
     mi::TpArgs ta{};
     ta.rows = h->d_rows;
-    ta.nrows = h->tp_rows;
+    ta.nrows = h->cls.tp_rows;
     ta.nch = h->nch;
     ta.nsteps = n;
     ta.nbatches = call.da.nbatches;
@@ -696,14 +594,14 @@ mi::TpArgs make_tp_args(const mi_demod* h, const Call& call, int q, bool overlap
     ta.redo = h->d_redo;
     ta.fin = h->d_fin;
     ta.diag = h->d_diag;
-    ta.seg_lpw = h->opt_tp_lpw;
-    ta.core_split = (h->opt_core_split && h->core_split_ok) ? 1 : 0;
-    ta.core_lead = h->opt_core_lead;
-    ta.core_guess = h->opt_core_guess;
-    ta.core_decay = h->opt_core_decay;
-    ta.core_lean = h->opt_core_lean;
-    ta.agc_hint = h->opt_agc_hint;
-    ta.eager_samples = h->opt_tp_eager;
+    ta.seg_lpw = h->opt.tp_lpw;
+    ta.core_split = (h->opt.core_split && h->cls.core_split_ok) ? 1 : 0;
+    ta.core_lead = h->opt.core_lead;
+    ta.core_guess = h->opt.core_guess;
+    ta.core_decay = h->opt.core_decay;
+    ta.core_lean = h->opt.core_lean;
+    ta.agc_hint = h->opt.agc_hint;
+    ta.eager_samples = h->opt.tp_eager;
     ta.spec_head = spec_head ? 1 : 0;
     ta.prev_blk_fe = h->set[h->cur].blk_fe, ta.prev_blk_fm = h->set[h->cur].blk_fm;
     ta.prev_blk_x0 = h->set[h->cur].blk_x0, ta.prev_blk_xm = h->set[h->cur].blk_xm;
@@ -751,12 +649,12 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
     // (isolated calls, round 2: with the chain on three waves an isolated call is a sum of fixed latencies -- stage 1, aggregates,
     // chain, segment pass, scan, fix, finish -- and every chunk adds the last four once more: 2 chunks, the second twice the
     // first, 3.7 instead of 4.1 ms per 64-s call and 2.6 instead of 3.3 per 16-s call; with many rows 2, 3 and 4 are level)
-    int want = overlap ? (h->tp_rows <= 64 ? 1 : 2) : (h->tp_rows <= 64 ? 2 : 3);
-    double ratio = overlap ? 1.0 : (h->tp_rows <= 64 ? 2.0 : 1.5);
-    if (h->opt_tp_chunks > 0)
-        want = h->opt_tp_chunks;
-    if (h->opt_tp_ratio > 0)
-        ratio = h->opt_tp_ratio;
+    int want = overlap ? (h->cls.tp_rows <= 64 ? 1 : 2) : (h->cls.tp_rows <= 64 ? 2 : 3);
+    double ratio = overlap ? 1.0 : (h->cls.tp_rows <= 64 ? 2.0 : 1.5);
+    if (h->opt.tp_chunks > 0)
+        want = h->opt.tp_chunks;
+    if (h->opt.tp_ratio > 0)
+        ratio = h->opt.tp_ratio;
     const std::vector<uint32_t> bound = tp_chunk_bounds(units, want, ratio);
     const int C = static_cast<int>(bound.size()) - 1;
     if (C > mi_demod::kMaxChunks)
@@ -771,7 +669,7 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
     // Speculative head: when this call's segment pass may run under the previous call's tail at all (seg_early) and that call
     // left what the warm-up needs (aggregates, core states at boundaries of the same segment length, TP_W steps of them),
     // no lane starts from the carried ChanState and no launch of the pass waits for the previous call.
-    const bool spec_head = seg_early && h->opt_spec_head && h->head_off >= mi::TP_W && h->set[h->cur].seq &&
+    const bool spec_head = seg_early && h->opt.spec_head && h->head_off >= mi::TP_W && h->set[h->cur].seq &&
                            h->set[h->cur].path == kPathTimeParallel;
     const mi::TpArgs ta = make_tp_args(h, call, q, overlap, spec_head);
     cs.nseg = ta.nseg;
@@ -793,7 +691,7 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
     // A mixed plan: stage 1 leaves the raw bins of this call in complex plane set p, the serial kernel reads them there and leaves
     // its carried head in the other set for the next call (as the pipelined serial calls do).
     const int zp = (h->d_cplx && h->d_cplx == h->d_cplx_set[1]) ? 1 : 0, znp = zp ^ 1;
-    if (h->tp_mixed) {
+    if (h->cls.tp_mixed) {
         ca.cplx = h->d_cplx_set[zp];
     }
     // The wide passes of a call (stage 1, aggregates, segment pass: thousands of waves that hold most of a SIMD's registers for a
@@ -804,7 +702,7 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
     // with the NULL stream): the twins are created at the handle's first time-parallel call and used by every call whose stream
     // is not the NULL stream.
     if (h->masked_state == 0) {
-        const int want = h->opt_reserve_cus >= 0 ? h->opt_reserve_cus : (h->tp_rows <= 64 ? 32 : 0);
+        const int want = h->opt.reserve_cus >= 0 ? h->opt.reserve_cus : (h->cls.tp_rows <= 64 ? 32 : 0);
         h->masked_state = 2;
         hipDeviceProp_t prop{};
         if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
@@ -860,12 +758,12 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
         if (next.seq && next.path == kPathTimeParallel && next.chunks > 0)
             HIP_TRY(hipStreamWaitEvent(fs, next.chunk(next.chunks - 1, kEvSegLaunched), 0));
     }
-    if (h->tp_mixed && h->cplx_busy[zp])  // (the serial kernel of the call before the previous one read this complex plane set)
+    if (h->cls.tp_mixed && h->cplx_busy[zp])  // (the serial kernel of the call before the previous one read this complex plane set)
         HIP_TRY(hipStreamWaitEvent(fs, h->ev_cplx_free[zp], 0));
     // the carried samples of the previous call (wherever they are) become the head of this call's planes -- of a mixed plan the
     // time-parallel rows' only where the serial kernel of the previous call has put its own rows' there itself
-    if (h->tp_mixed && h->ser_head_next && planes == h->set[(h->cur + 1) % mi_demod::kSets].mag)
-        HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->tp_rows, fs, h->d_rows));
+    if (h->cls.tp_mixed && h->ser_head_next && planes == h->set[(h->cur + 1) % mi_demod::kSets].mag)
+        HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->cls.tp_rows, fs, h->d_rows));
     else
         HIP_TRY(mi::launch_move_head(planes, h->d_mag + h->head_off, h->plane_stride, h->rows, fs));
     HIP_TRY(hipMemsetAsync(cs.xmax, 0, static_cast<size_t>(h->rows) * sizeof(unsigned), fs));
@@ -934,7 +832,7 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
     }
     cs.mixed = false;
     h->ser_head_next = false;
-    if (h->tp_mixed && h->ser_rows > 0) {
+    if (h->cls.tp_mixed && h->cls.ser_rows > 0) {
         // ---- the rows the time-parallel path does not take: k_demod on its own stream, beside the chain ----
         // It needs stage 1 of the whole call (the last chunk's end on the front stream), the serial kernel of the previous call
         // (same stream) and, where calls do not overlap, the caller's stream order.
@@ -946,15 +844,15 @@ int enqueue_time_parallel(mi_demod* h, Call& call) {
             HIP_TRY(hipStreamWaitEvent(zs, h->ev_head, 0));  // (it writes the audio buffer the previous call wrote)
         mi::DemodArgs dm = call.da;
         dm.rows = h->d_srows;
-        dm.nrows = h->ser_rows;
+        dm.nrows = h->cls.ser_rows;
         dm.mag = planes;
         dm.cplx = h->d_cplx_set[zp];
         dm.mag_head = h->set[(q + 1) % mi_demod::kSets].mag;  // (free: the call that used it last is four calls back)
         dm.cplx_head = h->d_cplx_set[znp];
         dm.carry = cs.carry;
         dm.carry_in = h->d_carry;
-        dm.lanes_per_wave = std::min(64, std::max(1, (h->ser_rows + h->opt_uni_rows - 1) / h->opt_uni_rows));
-        dm.pre_wave = (h->opt_pre_wave < 0 ? h->ser_rows <= 256 : h->opt_pre_wave != 0) ? 1 : 0;
+        dm.lanes_per_wave = lanes_per_wave_for(h, h->cls.ser_rows);
+        dm.pre_wave = (h->opt.pre_wave < 0 ? h->cls.ser_rows <= 256 : h->opt.pre_wave != 0) ? 1 : 0;
         HIP_TRY(hipEventRecord(evc[kEvSerialBegin], zs));
         HIP_TRY(mi::launch_demod(dm, zs));
         HIP_TRY(hipEventRecord(evc[kEvSerialEnd], zs));
@@ -1035,7 +933,7 @@ int enqueue_serial_pipelined(mi_demod* h, Call& call) {
     const hipStream_t s = call.s;
     mi::ChannelizeArgs& ca = call.ca;
     mi::DemodArgs& da = call.da;
-    if (h->tp_eligible)
+    if (h->cls.tp_eligible)
         h->pset = h->d_mag == h->set[1].mag ? 1 : 0;
     const int q = (h->cur + 1) % mi_demod::kSets;  // event / timing set of this call
     const int before_prev = (h->cur + mi_demod::kSets - 1) % mi_demod::kSets;
@@ -1050,7 +948,7 @@ int enqueue_serial_pipelined(mi_demod* h, Call& call) {
         // 64 x 8 AM channels, sharing every SIMD 3.8 (stage 1 3.4-3.5 ms beside the kernel's waves against 1.9 alone).  With fewer
         // rows the call is the kernel's latency either way and the split only takes CUs from stage 1 (tools/split_rows.sh); with
         // more the kernel needs more than 128 CUs (112 for 512 rows: 3.7 ms).
-        const int want = h->opt_split_cus >= 0 ? h->opt_split_cus : ((da.pre_wave == 2 && h->rows > 448 && h->rows <= 512) ? 128 : 0);
+        const int want = h->opt.split_cus >= 0 ? h->opt.split_cus : ((da.pre_wave == 2 && h->rows > 448 && h->rows <= 512) ? 128 : 0);
         if (want > 0 && hipGetDeviceProperties(&prop, h->gpu) == hipSuccess && prop.multiProcessorCount >= want + 32) {
             const int ncu = prop.multiProcessorCount, keep = ncu - want;
             hipError_t me = cu_stream_create(h->ps_front_m, cu_mask(ncu, 0, keep));
@@ -1129,7 +1027,7 @@ int enqueue(mi_demod* h, const unsigned char* d_iq, size_t stream_stride, size_t
             float2* d_iq_out, size_t iq_out_stride, char* d_axc, hipStream_t s, hipEvent_t iq_ready = nullptr) {
     // iq_ready (host-buffer entry, calls in flight): the IQ becomes valid when this event fires -- the streams that read it wait
     // for it and for nothing else, exactly as if the caller had vouched for the bytes (MI_OPT_EARLY_INPUT)
-    const bool early_input = h->early_input || iq_ready != nullptr;
+    const bool early_input = h->opt.early_input || iq_ready != nullptr;
     // A masked call (mi_demod_set_active_streams): one stage-1 launch and the serial stage 2 over the active streams, enqueued as a
     // call without a predecessor (heads in place first, no overlap).  It leaves chain_live and serial_pipe clear, so the full
     // call after it takes nothing from the previous call's arrays (prev_mag, prev_blk_*, prev_core, spec_head, xmax_prev: they
@@ -1205,7 +1103,7 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
     mi_demod* h = new (std::nothrow) mi_demod();
     if (!h)
         return fail(MI_ERR_NOMEM, "host allocation failed");
-    tuning_from_env(h);
+    mi::tuning_from_env(h->opt);
     const char* msg = "";
     int rc = mi::build_plan(*dev, chans, nch, h->plan, &msg);
     if (rc != MI_OK) {
@@ -1253,143 +1151,75 @@ int mi_demod_create(const mi_device_cfg* dev, const mi_channel_cfg* chans, int n
             TRY_OR_BAIL(hipEventCreate(ev.put()));
     TRY_OR_BAIL(hipEventCreate(h->ev_entry.put()));
     TRY_OR_BAIL(hipEventCreate(h->ev_head.put()));
-    {
-        // HIP multiplexes its streams onto a few hardware queues; two streams that share one run their kernels one after
-        // the other.  The core chain must never queue behind a wide pass, so it gets the highest stream priority (its
-        // own queue class), and the wide passes share as few other streams as the pipeline needs.
-        int lo_prio = 0, hi_prio = 0;
-        TRY_OR_BAIL(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-        TRY_OR_BAIL(hipStreamCreateWithPriority(h->aux_stream.put(), hipStreamNonBlocking, hi_prio));
-    }
+    TRY_OR_BAIL(priority_stream(h->aux_stream, /*highest=*/true));  // the core chain must never queue behind a wide pass
     TRY_OR_BAIL(hipStreamCreateWithFlags(h->front_stream.put(), hipStreamNonBlocking));
     for (mi::Stream& ss : h->seg_stream)
         TRY_OR_BAIL(hipStreamCreateWithFlags(ss.put(), hipStreamNonBlocking));
+    // the plan's tables
+    TRY_OR_BAIL(dalloc_copy(h->d_window, p.window));
+    TRY_OR_BAIL(dalloc_copy(h->d_tw, p.tw));
+    TRY_OR_BAIL(dalloc_copy(h->d_levels, p.levels));
+    TRY_OR_BAIL(dalloc_copy(h->d_sin, p.sin_lut));
+    TRY_OR_BAIL(dalloc_copy(h->d_cos, p.cos_lut));
+    TRY_OR_BAIL(dalloc_copy(h->d_cp, p.cp));
+    TRY_OR_BAIL(dalloc_copy(h->d_ctcss_coeff, p.ctcss_coeff));
+    if (p.prune.enabled) {
+        TRY_OR_BAIL(dalloc_copy(h->d_prune_t1, p.prune_t1));
+        TRY_OR_BAIL(dalloc_copy(h->d_prune_t2, p.prune_t2));
+        TRY_OR_BAIL(dalloc_copy(h->d_prune_rank, p.prune_chan_rank));
+    }
+    if (p.l64.enabled) {
+        TRY_OR_BAIL(dalloc_copy(h->d_l64_chan, p.l64_chan));
+        TRY_OR_BAIL(dalloc_copy(h->d_l64_chan_full, p.l64_chan_full));
+        TRY_OR_BAIL(dalloc_zero(h->d_l64_tickets, mi::kL64Tickets));
+    }
+    // what the channels carry from call to call (zeroed here, or filled by launch_init_state below), and the first set's planes
     const size_t rows = static_cast<size_t>(h->rows);
-    TRY_OR_BAIL(dalloc(h->d_window, p.window.size()));
-    TRY_OR_BAIL(dalloc(h->d_tw, p.tw.size()));
-    TRY_OR_BAIL(dalloc(h->d_levels, 256));
-    TRY_OR_BAIL(dalloc(h->d_sin, 257));
-    TRY_OR_BAIL(dalloc(h->d_cos, 257));
-    TRY_OR_BAIL(dalloc(h->d_cp, static_cast<size_t>(nch)));
     TRY_OR_BAIL(dalloc(h->d_state, rows));
-    TRY_OR_BAIL(dalloc(h->set[0].mag, rows * h->plane_stride));
+    TRY_OR_BAIL(dalloc_zero(h->set[0].mag, rows * h->plane_stride));
     h->d_mag = h->set[0].mag;
-    TRY_OR_BAIL(dalloc(h->d_cplx_set[0], static_cast<size_t>(nstreams) * p.n_iq_rows * h->plane_stride));
+    TRY_OR_BAIL(dalloc_zero(h->d_cplx_set[0], static_cast<size_t>(nstreams) * p.n_iq_rows * h->plane_stride));
     h->d_cplx = h->d_cplx_set[0];
     TRY_OR_BAIL(dalloc(h->set[0].carry, rows * mi::kAgcExtra));
     h->d_carry = h->set[0].carry;
     TRY_OR_BAIL(dalloc(h->d_ring, rows * mi::kSquelchRing));
-    TRY_OR_BAIL(dalloc(h->d_ctcss_coeff, p.ctcss_coeff.size()));
     TRY_OR_BAIL(dalloc(h->d_ctcss_q, static_cast<size_t>(nstreams) * p.n_ctcss_rows * 4 * mi::kMaxTones));
-    TRY_OR_BAIL(dalloc(h->d_stats, rows));
-    TRY_OR_BAIL(dalloc(h->d_pre_timeouts, 1));
-    TRY_OR_BAIL(hipMemset(h->d_pre_timeouts, 0, sizeof(unsigned)));
-    TRY_OR_BAIL(hipMemcpy(h->d_window, p.window.data(), p.window.size() * 4, hipMemcpyHostToDevice));
-    TRY_OR_BAIL(hipMemcpy(h->d_tw, p.tw.data(), p.tw.size() * 4, hipMemcpyHostToDevice));
-    if (p.prune.enabled) {
-        TRY_OR_BAIL(dalloc(h->d_prune_t1, p.prune_t1.size()));
-        TRY_OR_BAIL(hipMemcpy(h->d_prune_t1, p.prune_t1.data(), p.prune_t1.size() * 4, hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(h->d_prune_t2, p.prune_t2.size()));
-        TRY_OR_BAIL(hipMemcpy(h->d_prune_t2, p.prune_t2.data(), p.prune_t2.size() * 4, hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(h->d_prune_rank, p.prune_chan_rank.size()));
-        TRY_OR_BAIL(hipMemcpy(h->d_prune_rank, p.prune_chan_rank.data(), p.prune_chan_rank.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (p.l64.enabled) {
-        TRY_OR_BAIL(dalloc(h->d_l64_chan, p.l64_chan.size()));
-        TRY_OR_BAIL(hipMemcpy(h->d_l64_chan, p.l64_chan.data(), p.l64_chan.size() * sizeof(L64Chan), hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(h->d_l64_chan_full, p.l64_chan_full.size()));
-        TRY_OR_BAIL(hipMemcpy(h->d_l64_chan_full, p.l64_chan_full.data(), p.l64_chan_full.size() * sizeof(L64Chan), hipMemcpyHostToDevice));
-        TRY_OR_BAIL(dalloc(h->d_l64_tickets, mi::kL64Tickets));
-        TRY_OR_BAIL(hipMemset(h->d_l64_tickets, 0, mi::kL64Tickets * sizeof(unsigned)));
-    }
-    TRY_OR_BAIL(hipMemcpy(h->d_levels, p.levels.data(), 256 * 4, hipMemcpyHostToDevice));
-    TRY_OR_BAIL(hipMemcpy(h->d_sin, p.sin_lut, 257 * 4, hipMemcpyHostToDevice));
-    TRY_OR_BAIL(hipMemcpy(h->d_cos, p.cos_lut, 257 * 4, hipMemcpyHostToDevice));
-    TRY_OR_BAIL(hipMemcpy(h->d_cp, p.cp.data(), p.cp.size() * sizeof(mi::ChanParams), hipMemcpyHostToDevice));
-    if (!p.ctcss_coeff.empty())
-        TRY_OR_BAIL(hipMemcpy(h->d_ctcss_coeff, p.ctcss_coeff.data(), p.ctcss_coeff.size() * 4, hipMemcpyHostToDevice));
-    TRY_OR_BAIL(hipMemset(h->d_mag, 0, rows * h->plane_stride * 4));
-    if (h->d_cplx)
-        TRY_OR_BAIL(hipMemset(h->d_cplx, 0, static_cast<size_t>(nstreams) * p.n_iq_rows * h->plane_stride * 8));
-    TRY_OR_BAIL(hipMemset(h->d_stats, 0, rows * sizeof(mi_channel_stats)));
-    // which channels the time-parallel path can take: plain AM (no raw I/Q, CTCSS, notch); none where AFC moves the bins batch by batch
-    std::vector<char> tp_ch(static_cast<size_t>(nch), 0);
-    int tp_nch = 0;
-    for (int c = 0; c < nch; ++c) {
-        const mi::ChanParams& cp = p.cp[static_cast<size_t>(c)];
-        tp_ch[static_cast<size_t>(c)] = !p.any_afc && cp.modulation == MI_MOD_AM && !cp.needs_raw_iq && !cp.ctcss_enabled && !cp.notch_enabled && cp.afc == 0;
-        tp_nch += tp_ch[static_cast<size_t>(c)] ? 1 : 0;
-    }
-    h->tp_eligible = tp_nch > 0;
-    h->tp_mixed = tp_nch > 0 && tp_nch < nch;
-    h->tp_rows = nstreams * tp_nch;
-    h->ser_rows = h->rows - h->tp_rows;
-    h->core_split_ok = h->tp_eligible;
-    for (int c = 0; c < nch; ++c)
-        if (tp_ch[static_cast<size_t>(c)] && (p.cp[static_cast<size_t>(c)].using_manual_level || !(p.cp[static_cast<size_t>(c)].cap_factor >= 1.0f)))
-            h->core_split_ok = false;  // (the chain wave's operand assumes cap >= noise floor in a burst)
-    if (p.any_afc)
-        TRY_OR_BAIL(dalloc(h->d_afc_spec, static_cast<size_t>(nstreams) * p.fft_size));
-    if (h->tp_eligible) {
+    TRY_OR_BAIL(dalloc_zero(h->d_stats, rows));
+    TRY_OR_BAIL(dalloc_zero(h->d_pre_timeouts, 1));
+    TRY_OR_BAIL(dalloc(h->d_afc_spec, p.any_afc ? static_cast<size_t>(nstreams) * p.fft_size : 0));
+    h->cls = mi::classify_rows(p, nstreams, nch);
+    if (h->cls.tp_eligible) {
         h->tp_max_blk = max_steps / 16;
         // segment length of the time-parallel path: short segments where rows are few (the parallelism has to come from time),
         // long ones where they are many (each lane pays TP_W steps of warm-up whatever its segment's length)
-        if (h->opt_tp_L == 0)
-            h->tp_L = h->tp_rows <= 32 ? 512u : 1024u;  // (2048 beyond 128 rows until the segment pass ran full waves: DESIGN 6)
-        else
-            h->tp_L = static_cast<uint32_t>(h->opt_tp_L);
+        // (by row count: 2048 beyond 128 rows until the segment pass ran full waves: DESIGN 6)
+        h->tp_L = h->opt.tp_L ? static_cast<uint32_t>(h->opt.tp_L) : (h->cls.tp_rows <= 32 ? 512u : 1024u);
         h->tp_max_seg = (max_steps + h->tp_L - 1) / h->tp_L;
-        std::vector<int> tp_list, ser_list;  // handle rows (stream * nch + channel) of either kind, in row order
-        for (size_t i = 0; i < rows; ++i)
-            (tp_ch[i % static_cast<size_t>(nch)] ? tp_list : ser_list).push_back(static_cast<int>(i));
-        TRY_OR_BAIL(dalloc(h->d_rows, rows));
-        TRY_OR_BAIL(hipMemcpy(h->d_rows, tp_list.data(), tp_list.size() * sizeof(int), hipMemcpyHostToDevice));
-        if (!ser_list.empty()) {
-            TRY_OR_BAIL(dalloc(h->d_srows, ser_list.size()));
-            TRY_OR_BAIL(hipMemcpy(h->d_srows, ser_list.data(), ser_list.size() * sizeof(int), hipMemcpyHostToDevice));
-            {
-                // HIP multiplexes its streams onto a few hardware queues and two streams that share one run their kernels one after the
-                // other: on a stream of the default class the serial kernel (a millisecond and more) took turns with stage 1 of the next
-                // call.  The lowest stream priority is a queue class of its own.
-                int lo_prio = 0, hi_prio = 0;
-                TRY_OR_BAIL(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
-                TRY_OR_BAIL(hipStreamCreateWithPriority(h->ser_stream.put(), hipStreamNonBlocking, lo_prio));
-            }
+        TRY_OR_BAIL(dalloc_copy(h->d_rows, h->cls.tp_list, rows));
+        if (!h->cls.ser_list.empty()) {
+            TRY_OR_BAIL(dalloc_copy(h->d_srows, h->cls.ser_list));
+            // (on a stream of the default class the serial kernel, a millisecond and more, took turns with stage 1 of the next call)
+            TRY_OR_BAIL(priority_stream(h->ser_stream, /*highest=*/false));
             for (mi::Event& e : h->ev_cplx_free)
                 TRY_OR_BAIL(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
         }
-        for (int q = 1; q < mi_demod::kSets; ++q) {
-            TRY_OR_BAIL(dalloc(h->set[q].mag, rows * h->plane_stride));
-            TRY_OR_BAIL(hipMemset(h->set[q].mag, 0, rows * h->plane_stride * 4));
-            TRY_OR_BAIL(dalloc(h->set[q].carry, rows * mi::kAgcExtra));
-        }
-        for (int q = 0; q < mi_demod::kSets; ++q) {
-            TRY_OR_BAIL(dalloc(h->set[q].xmax, rows));
-            TRY_OR_BAIL(dalloc(h->set[q].blk_fe, rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(h->set[q].blk_fm, rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(h->set[q].blk_x0, rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(h->set[q].blk_xm, rows * h->tp_max_blk));
-            TRY_OR_BAIL(dalloc(h->set[q].core, rows * (h->tp_max_seg + 1)));
-        }
         for (int q = 0; q < mi_demod::kSets; ++q)
-            TRY_OR_BAIL(dalloc(h->set[q].rec, static_cast<size_t>(mi::TP_NREC) * rows * h->tp_max_seg));
+            if (const int rc_set = alloc_call_set(h, q); rc_set != MI_OK)
+                return bail(rc_set);
         TRY_OR_BAIL(dalloc(h->d_tstart, rows * h->tp_max_seg * 8));
         TRY_OR_BAIL(dalloc(h->d_need, rows * h->tp_max_seg));
         TRY_OR_BAIL(dalloc(h->d_redo, rows * h->tp_max_seg + 1));
-        TRY_OR_BAIL(dalloc(h->d_fin, rows));
-        TRY_OR_BAIL(hipMemset(h->d_fin, 0, rows * sizeof(mi::TpFinal)));
+        TRY_OR_BAIL(dalloc_zero(h->d_fin, rows));
         TRY_OR_BAIL(dalloc(h->d_core_carry, rows));
         TRY_OR_BAIL(dalloc(h->d_full0, rows));
-        TRY_OR_BAIL(dalloc(h->d_fullbound, rows));
-        TRY_OR_BAIL(hipMemset(h->d_fullbound, 0, rows * sizeof(float)));
-        TRY_OR_BAIL(dalloc(h->d_diag, rows * 8));
-        TRY_OR_BAIL(hipMemset(h->d_diag, 0, rows * 8 * sizeof(int)));
+        TRY_OR_BAIL(dalloc_zero(h->d_fullbound, rows));
+        TRY_OR_BAIL(dalloc_zero(h->d_diag, rows * 8));
     }
     TRY_OR_BAIL(mi::launch_init_state(h->d_state, h->d_carry, h->d_ring, h->d_ctcss_q, h->d_cp, nstreams, nch, p.n_ctcss_rows, h->own_stream));
     TRY_OR_BAIL(hipStreamSynchronize(h->own_stream));
 #undef TRY_OR_BAIL
     if (!p.any_afc)
-        stage1_compile(h);  // (a failure leaves the exchange kernels: never an error)
+        stage1_compile(h, false);  // (a failure leaves the exchange kernels: never an error)
     *out = h;
     return MI_OK;
 }
@@ -1400,7 +1230,7 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
     if (host_slots < 0 || host_slots > mi_demod::kSlots)
         return fail(MI_ERR_INVALID, "host_slots out of range (0 .. 3)");
     HIP_TRY(hipSetDevice(h->gpu));
-    stage1_compile(h);
+    stage1_compile(h, false);
     for (int k = 0; k < host_slots; ++k) {
         const int rc = slot_prepare(h, k);
         if (rc != MI_OK)
@@ -1442,7 +1272,7 @@ int mi_demod_prepare(mi_demod* h, int host_slots) {
         ~AllActive() { h->masked = masked; }
     } all_active(h);
     std::vector<int> rehearsals = {1};
-    if (h->tp_eligible && h->opt_tp != 0 && h->max_batches >= kTpMinBatches)
+    if (h->cls.tp_eligible && h->opt.tp != 0 && h->max_batches >= kTpMinBatches)
         rehearsals.push_back(kTpMinBatches);
     for (const int nb : rehearsals) {
         const size_t need = mi_demod_bytes_needed(h, nb);
@@ -1625,11 +1455,11 @@ int slot_launch(mi_demod* h, int k, const uint8_t* const* iq, int nbatches, bool
     // mi_demod_submit: the upload has its own stream and event, which is all the front of the call waits for -- so consecutive
     // submitted calls overlap on the device like device-resident calls with the option set (their audio goes to the two
     // slots' buffers in turn, which is what lets the segment passes of one run under the tail of the other).
-    const bool early = h->early_input;
-    h->early_input = pipelined;
+    const bool early = h->opt.early_input;
+    h->opt.early_input = pipelined;
     const size_t wstride = nsteps + mi::kAgcExtra;  // the host layout: emitted audio followed by the lookahead (channel_t.waveout)
     int rc = enqueue(h, sl.d_iq, h->iq_stride, need, nbatches, sl.d_wout, wstride, want_iq ? sl.d_iqout : nullptr, nsteps, sl.d_axc, s, ready);
-    h->early_input = early;
+    h->opt.early_input = early;
     if (rc != MI_OK)
         return rc;
     // the lookahead and the statistics belong to the handle and move on with the next call: snapshot them behind this one
@@ -1970,7 +1800,7 @@ int mi_demod_set_active_streams(mi_demod* h, const uint8_t* active) {
         }
         HIP_TRY(hipMemcpy(h->d_act_streams, streams.data(), streams.size() * sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->d_act_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
-        stage1_compile_masked(h);  // (a failure leaves the exchange kernels: never an error)
+        stage1_compile(h, true);  // (a failure leaves the exchange kernels: never an error)
     }
     h->active = want;
     h->nactive = static_cast<int>(streams.size());
@@ -1995,7 +1825,7 @@ int mi_demod_last_path(mi_demod* h, int* time_parallel, int* unverified_rows) {
     if (unverified_rows) {
         *unverified_rows = 0;
         if (h->last_path == kPathTimeParallel) {
-            std::vector<mi::TpFinal> f(static_cast<size_t>(h->tp_rows));
+            std::vector<mi::TpFinal> f(static_cast<size_t>(h->cls.tp_rows));
             HIP_TRY(hipMemcpy(f.data(), h->d_fin, f.size() * sizeof(mi::TpFinal), hipMemcpyDeviceToHost));
             for (const mi::TpFinal& x : f)
                 *unverified_rows += x.all_ok ? 0 : 1;
@@ -2021,7 +1851,7 @@ int mi_demod_last_stage1(mi_demod* h, int* kind) {
 }
 
 int mi_demod_tp_debug(mi_demod* h, int row, float* core4, int max_entries, int* diag4, int* nseg) {
-    if (!h || row < 0 || row >= h->tp_rows || !h->tp_eligible || h->last_path != kPathTimeParallel)
+    if (!h || row < 0 || row >= h->cls.tp_rows || !h->cls.tp_eligible || h->last_path != kPathTimeParallel)
         return fail(MI_ERR_INVALID, "the last call did not take the time-parallel path");
     HIP_TRY(hipSetDevice(h->gpu));
     HIP_TRY(hipDeviceSynchronize());
@@ -2033,7 +1863,7 @@ int mi_demod_tp_debug(mi_demod* h, int row, float* core4, int max_entries, int* 
     }
     if (diag4) {  // [0..3] scan rounds, [4..7] core-chain blocks: in accepted runs, single O(1), stepped, failed hypotheses
         HIP_TRY(hipMemcpy(diag4, h->d_diag + static_cast<size_t>(row) * 4, 4 * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(diag4 + 4, h->d_diag + static_cast<size_t>(h->tp_rows) * 4 + static_cast<size_t>(row) * 4, 4 * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(diag4 + 4, h->d_diag + static_cast<size_t>(h->cls.tp_rows) * 4 + static_cast<size_t>(row) * 4, 4 * sizeof(int), hipMemcpyDeviceToHost));
     }
     return MI_OK;
 }
@@ -2165,70 +1995,13 @@ int mi_demod_last_kernel_ms(mi_demod* h, float* channelize_ms, float* demod_ms) 
 int mi_demod_set_option(mi_demod* h, int option, int value) {
     if (!h)
         return fail(MI_ERR_INVALID, "NULL handle");
-    switch (option) {
-        case MI_OPT_EARLY_INPUT:
-            h->early_input = value != 0;
-            return MI_OK;
-        case MI_OPT_STEADY_BLOCKS:
-            h->steady_blocks = value != 0;
-            return MI_OK;
-        case MI_OPT_TIME_PARALLEL:
-            h->opt_tp = value < 0 ? -1 : (value != 0 ? 1 : 0);
-            return MI_OK;
-        case MI_OPT_PRUNE_FFT:
-            h->opt_prune = value != 0;
-            return MI_OK;
-        case MI_OPT_U8_CONVERSION:
-            h->opt_conv = value < 0 ? -1 : (value != 0 ? 1 : 0);
-            return MI_OK;
-        case MI_OPT_UNI_ROWS:
-            if (value < 1)
-                return fail(MI_ERR_INVALID, "MI_OPT_UNI_ROWS must be >= 1");
-            h->opt_uni_rows = value;
-            return MI_OK;
-        case MI_OPT_TP_CHUNKS:
-            h->opt_tp_chunks = std::max(0, value);
-            return MI_OK;
-        case MI_OPT_TP_RATIO_PCT:
-            h->opt_tp_ratio = value <= 0 ? 0.0 : std::max(0.25, value / 100.0);
-            return MI_OK;
-        case MI_OPT_TP_SEG_LANES:
-            h->opt_tp_lpw = (value >= 1 && value <= 64) ? value : 0;
-            return MI_OK;
-        case MI_OPT_LANE_FFT:
-            h->opt_l64 = value != 0;
-            return MI_OK;
-        case MI_OPT_CORE_SPLIT:
-            h->opt_core_split = value != 0;
-            return MI_OK;
-        case MI_OPT_SPEC_HEAD:
-            h->opt_spec_head = value != 0;
-            return MI_OK;
-        case MI_OPT_RESERVE_CUS:
-            if (h->masked_state != 0)
-                return fail(MI_ERR_INVALID, "MI_OPT_RESERVE_CUS is decided at the handle's first time-parallel call: set it before");
-            h->opt_reserve_cus = value < 0 ? -1 : value;
-            return MI_OK;
-        case MI_OPT_PRE_WAVE:
-            h->opt_pre_wave = value < 0 ? -1 : std::min(2, value);
-            return MI_OK;
-        case MI_OPT_LANE_FFT_JIT:
-            h->opt_l64_jit = value != 0;
-            return MI_OK;
-        case MI_OPT_AUDIO_WAVE:
-            h->opt_audio_wave = value != 0;
-            return MI_OK;
-        case MI_OPT_MIXED_PLAN:
-            h->opt_mixed = value != 0;
-            return MI_OK;
-        case MI_OPT_SPLIT_CUS:
-            if (h->split_state != 0)
-                return fail(MI_ERR_INVALID, "MI_OPT_SPLIT_CUS is decided at the handle's first overlapped serial call: set it before");
-            h->opt_split_cus = value < 0 ? -1 : value;
-            return MI_OK;
-        default:
-            return fail(MI_ERR_INVALID, "unknown option");
-    }
+    if (option == MI_OPT_RESERVE_CUS && h->masked_state != 0)
+        return fail(MI_ERR_INVALID, "MI_OPT_RESERVE_CUS is decided at the handle's first time-parallel call: set it before");
+    if (option == MI_OPT_SPLIT_CUS && h->split_state != 0)
+        return fail(MI_ERR_INVALID, "MI_OPT_SPLIT_CUS is decided at the handle's first overlapped serial call: set it before");
+    const char* why = "";
+    const int rc = mi::tuning_set(h->opt, option, value, &why);
+    return rc == MI_OK ? MI_OK : fail(rc, why);
 }
 
 // ---------------- host-only plan views ----------------

@@ -363,7 +363,7 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
         };
         const int L = p.log2n;
         const size_t N = static_cast<size_t>(p.fft_size);
-        const size_t hop = p.hop_bytes / (2 * static_cast<size_t>(p.bytes_per_sample));
+        const int hop = p.hop_samples();
         // the kernel's literal twiddles W_64^k of stages 1..6 must be the entries k N / 64 of the spec's table, bit for bit
         bool lits_ok = L >= 6;
         for (size_t k = 0; lits_ok && k < 32; ++k) {
@@ -409,6 +409,25 @@ int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, P
         }
     }
     return MI_OK;
+}
+
+RowClasses classify_rows(const Plan& p, int nstreams, int nch) {
+    RowClasses rc;
+    auto plain_am = [&p](int c) {
+        const ChanParams& cp = p.cp[static_cast<size_t>(c)];
+        return !p.any_afc && cp.modulation == MI_MOD_AM && !cp.needs_raw_iq && !cp.ctcss_enabled && !cp.notch_enabled && cp.afc == 0;
+    };
+    for (int i = 0; i < nstreams * nch; ++i)
+        (plain_am(i % nch) ? rc.tp_list : rc.ser_list).push_back(i);
+    rc.tp_rows = static_cast<int>(rc.tp_list.size());
+    rc.ser_rows = static_cast<int>(rc.ser_list.size());
+    rc.tp_eligible = rc.tp_rows > 0;
+    rc.tp_mixed = rc.tp_rows > 0 && rc.ser_rows > 0;
+    rc.core_split_ok = rc.tp_eligible;
+    for (int c = 0; c < nch; ++c)
+        if (plain_am(c) && (p.cp[static_cast<size_t>(c)].using_manual_level || !(p.cp[static_cast<size_t>(c)].cap_factor >= 1.0f)))
+            rc.core_split_ok = false;  // (the chain wave's operand assumes cap >= noise floor in a burst)
+    return rc;
 }
 
 }  // namespace mi

@@ -83,6 +83,7 @@ struct Plan {
     int fft_size = 0;
     int bytes_per_sample = 1;
     size_t hop_bytes = 0;  // "bps", rtl_airband.cpp:416
+    int hop_samples() const { return static_cast<int>(hop_bytes / (2 * static_cast<size_t>(bytes_per_sample))); }
     int n_iq_rows = 0;     // channels with needs_raw_iq
     int n_ctcss_rows = 0;
     bool any_afc = false;  // some channel has afc > 0: bins follow the signal, batches are processed one at a time
@@ -103,6 +104,17 @@ struct Plan {
     std::vector<L64Chan> l64_chan_full;  // nch: slot = bin mod 64 (the full-graph instance)
     float initial_noise_floor = 5.0f;
 };
+
+// Which rows (stream * nch + channel) of a handle the time-parallel stage 2 can take: those of the plain AM channels (no raw I/Q,
+// CTCSS, notch); none where AFC moves the bins batch by batch
+struct RowClasses {
+    bool tp_eligible = false;    // some channel is plain AM
+    bool tp_mixed = false;       // ... and some channel is not
+    bool core_split_ok = false;  // k_tp_core2 may run: automatic squelch levels with a cap factor >= 1 on every plain AM channel
+    int tp_rows = 0, ser_rows = 0;
+    std::vector<int> tp_list, ser_list;  // the rows of either kind, in row order
+};
+RowClasses classify_rows(const Plan& p, int nstreams, int nch);
 
 // returns MI_OK or a negative mi_status; msg receives the reason
 int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, Plan& out, const char** msg);
