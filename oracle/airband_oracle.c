@@ -862,6 +862,29 @@ static void afc_finalize(ao_demod* d, ao_channel* channel, char prev_axcindicate
         channel->bin = channel->base_bin;
 }
 
+/* squelch_level() and signal_outside_filter() as the getters would answer, without filling the lazy cache (diagnostic views) */
+static float sq_level_peek(const ao_squelch* s) {
+    if (s->using_manual_level)
+        return s->manual_signal_level;
+    if (s->squelch_level_cache != 0.0f)
+        return s->squelch_level_cache;
+    if (sq_flapping(s) && s->flappy_signal_ratio < s->normal_signal_ratio)
+        return s->flappy_signal_ratio * s->noise_floor;
+    return s->normal_signal_ratio * s->noise_floor;
+}
+float ao_squelch_level_peek(const ao_squelch* s) {
+    return sq_level_peek(s);
+}
+int ao_squelch_signal_outside_filter_peek(const ao_squelch* s) {
+    const int pre = s->pre_capped >= sq_level_peek(s);
+    const int post = s->using_post_filter && s->post_capped >= s->buffer[s->buffer_tail];
+    return s->using_post_filter && pre && !post;
+}
+
+int ao_squelch_should_filter_peek(const ao_squelch* s) {
+    return (s->pre_capped >= sq_level_peek(s) || s->current_state != AO_SQ_CLOSED) && s->current_state != AO_SQ_LOW_SIGNAL_ABORT;
+}
+
 static void channel_batch(ao_demod* d, int ci) {
     ao_channel* channel = &d->ch[ci];
     ao_squelch* sq = &channel->squelch;
@@ -870,6 +893,7 @@ static void channel_batch(ao_demod* d, int ci) {
     for (int j = AO_AGC_EXTRA; j < AO_WAVE_BATCH + AO_AGC_EXTRA; j++) {
         float* real = &channel->iq_in[2 * (j - AO_AGC_EXTRA)];
         float* imag = &channel->iq_in[2 * (j - AO_AGC_EXTRA) + 1];
+        const uint64_t recent_before = sq->recent_open_count; /* (trace only) */
 
         ao_squelch_process_raw(sq, channel->wavein[j]);
 
@@ -951,8 +975,10 @@ static void channel_batch(ao_demod* d, int ci) {
         }
 
         if (d->trace && d->trace_len < d->trace_cap) {
-            uint8_t t = (uint8_t)((ao_squelch_is_open(sq) ? 1 : 0) | (ao_squelch_should_process_audio(sq) ? 2 : 0) |
-                                  (sq->current_state << 4));
+            const int filtering = ao_squelch_should_filter_peek(sq);
+            uint8_t t = (uint8_t)((ao_squelch_is_open(sq) ? 1 : 0) | (ao_squelch_should_process_audio(sq) ? 2 : 0) | (filtering ? 4 : 0) |
+                                  (ao_squelch_signal_outside_filter_peek(sq) ? 8 : 0) | (sq->current_state << 4) |
+                                  ((recent_before != 0 && sq->recent_open_count == 0) ? 128 : 0));
             d->trace[(size_t)ci * d->trace_cap + d->trace_len + (size_t)(j - AO_AGC_EXTRA)] = t;
         }
     }
@@ -962,6 +988,21 @@ static void channel_batch(ao_demod* d, int ci) {
     afc_finalize(d, channel, prev_axcindicate); /* rtl_airband.cpp:648-652 */
     if (channel->axcindicate != ' ')
         channel->active_counter++;
+}
+
+/* one more entry of every channel's wavein / iq_in is in place (rtl_airband.cpp:512-516, 670-689): run the sample loop once
+ * WAVE_BATCH + AGC_EXTRA of them are there.  Returns 1 when a batch completed. */
+static int entry_done(ao_demod* d) {
+    d->waveend += 1; /* FFT_BATCH == 1 */
+    if (d->waveend >= AO_WAVE_BATCH + AO_AGC_EXTRA) {
+        for (int i = 0; i < d->nch; i++)
+            channel_batch(d, i);
+        if (d->trace)
+            d->trace_len += AO_WAVE_BATCH;
+        d->waveend -= AO_WAVE_BATCH;
+        return 1;
+    }
+    return 0;
 }
 
 int ao_demod_push_window(ao_demod* d, const unsigned char* win) {
@@ -977,16 +1018,7 @@ int ao_demod_push_window(ao_demod* d, const unsigned char* win) {
             c->iq_in[2 * d->waveend + 1] = im;
         }
     }
-    d->waveend += 1; /* FFT_BATCH == 1 */
-    if (d->waveend >= AO_WAVE_BATCH + AO_AGC_EXTRA) {
-        for (int i = 0; i < d->nch; i++)
-            channel_batch(d, i);
-        if (d->trace)
-            d->trace_len += AO_WAVE_BATCH;
-        d->waveend -= AO_WAVE_BATCH;
-        return 1;
-    }
-    return 0;
+    return entry_done(d);
 }
 
 void ao_demod_output_carry(ao_demod* d) { /* output.cpp:948 */
@@ -994,23 +1026,48 @@ void ao_demod_output_carry(ao_demod* d) { /* output.cpp:948 */
         memcpy(d->ch[i].waveout, d->ch[i].waveout + AO_WAVE_BATCH, AO_AGC_EXTRA * 4);
 }
 
+/* the output thread's turn after a batch: channel-major copies into the caller's arrays, then the carry */
+static void emit_batch(ao_demod* d, int max_batches, int nb, float* waveout, float* iq_out, char* axc) {
+    for (int c = 0; c < d->nch; c++) {
+        memcpy(waveout + ((size_t)c * max_batches + nb) * AO_WAVE_BATCH, d->ch[c].waveout, AO_WAVE_BATCH * sizeof(float));
+        if (iq_out)
+            memcpy(iq_out + ((size_t)c * max_batches + nb) * 2 * AO_WAVE_BATCH, d->ch[c].iq_out, 2 * AO_WAVE_BATCH * sizeof(float));
+        axc[(size_t)c * max_batches + nb] = d->ch[c].axcindicate;
+    }
+    ao_demod_output_carry(d);
+}
+
 int ao_demod_run(ao_demod* d, const unsigned char* iq, size_t nbytes, int max_batches, float* waveout, float* iq_out, char* axc) {
     size_t bufs = 0;
     int nb = 0;
     const size_t need = d->hop_bytes + d->fft_size * (size_t)d->bytes_per_sample * 2; /* rtl_airband.cpp:417 */
     while (nb < max_batches && nbytes - bufs >= need) {
-        if (ao_demod_push_window(d, iq + bufs)) {
-            for (int c = 0; c < d->nch; c++) {
-                memcpy(waveout + ((size_t)c * max_batches + nb) * AO_WAVE_BATCH, d->ch[c].waveout, AO_WAVE_BATCH * sizeof(float));
-                if (iq_out)
-                    memcpy(iq_out + ((size_t)c * max_batches + nb) * 2 * AO_WAVE_BATCH, d->ch[c].iq_out,
-                           2 * AO_WAVE_BATCH * sizeof(float));
-                axc[(size_t)c * max_batches + nb] = d->ch[c].axcindicate;
-            }
-            ao_demod_output_carry(d);
-            nb++;
-        }
+        if (ao_demod_push_window(d, iq + bufs))
+            emit_batch(d, max_batches, nb++, waveout, iq_out, axc);
         bufs += d->hop_bytes; /* rtl_airband.cpp:691 */
+    }
+    return nb;
+}
+
+int ao_demod_run_planes(ao_demod* d, const float* mag, const float* cplx, size_t count, int max_batches, float* waveout, float* iq_out,
+                        char* axc) {
+    int nb = 0, n_iq = 0;
+    for (int c = 0; c < d->nch; c++)
+        if (d->ch[c].afc)
+            return -1; /* AFC walks the spectrum of stage 1: there is none here */
+    for (size_t k = 0; k < count && nb < max_batches; k++) {
+        n_iq = 0;
+        for (int j = 0; j < d->nch; j++) { /* in place of rtl_airband.cpp:424-511 */
+            ao_channel* c = &d->ch[j];
+            c->wavein[d->waveend] = mag[(size_t)j * count + k];
+            if (c->needs_raw_iq) {
+                const float* z = cplx + 2 * ((size_t)n_iq++ * count + k);
+                c->iq_in[2 * d->waveend] = z[0];
+                c->iq_in[2 * d->waveend + 1] = z[1];
+            }
+        }
+        if (entry_done(d))
+            emit_batch(d, max_batches, nb++, waveout, iq_out, axc);
     }
     return nb;
 }

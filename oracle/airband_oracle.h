@@ -214,7 +214,8 @@ typedef struct {
     float sin_lut[257], cos_lut[257];
     float *fftin, *fftout;
     /* optional per-sample trace of the stage-2 loop, channel-major, filled by ao_demod_push_window
-     * when non-NULL: bit0 is_open, bit1 should_process_audio, bit2 should_filter, bits 4..6 state */
+     * when non-NULL: bit0 is_open, bit1 should_process_audio, bit2 should_filter, bit3 signal_outside_filter, bits 4..6 state,
+     * bit7 this step reset recent_open_count_ (squelch.cpp:442-449) -- all as of the end of the step */
     uint8_t* trace;
     size_t trace_cap, trace_len; /* per channel */
 } ao_demod;
@@ -240,6 +241,21 @@ void ao_demod_output_carry(ao_demod* d);
  * Returns the number of complete batches (<= max_batches). */
 int ao_demod_run(ao_demod* d, const unsigned char* iq, size_t nbytes, int max_batches, float* waveout, float* iq_out,
                  char* axc);
+
+/* ao_demod_run with stage 1 (convert x window -> FFT -> bin pick) replaced by the caller's planes: entry k of every channel goes
+ * where the bin pick would have put it, wavein[waveend] = mag[ch][k] and, for the channels with needs_raw_iq,
+ * iq_in[waveend] = cplx[r][k] with r the channel's rank among those channels (the layout of mi_demod_process_planes); the
+ * sample loop, the carry and the outputs are ao_demod_run's own.  `count` entries are consumed (a handle's first batch needs
+ * WAVE_BATCH + AGC_EXTRA of them, as waveend starts at 0); consecutive calls continue the sequence.  cplx may be NULL when no
+ * channel needs raw I/Q.  Returns the number of complete batches, or -1 for a plan with AFC channels (they walk the spectrum). */
+int ao_demod_run_planes(ao_demod* d, const float* mag, const float* cplx, size_t count, int max_batches, float* waveout, float* iq_out,
+                        char* axc);
+
+/* Squelch::squelch_level() / should_filter_sample() / signal_outside_filter() as they would answer now, leaving the lazy cache
+ * alone (tests/test_oracle_planes.py holds them to the getters themselves, asked on a copy, along whole traces) */
+float ao_squelch_level_peek(const ao_squelch* s);
+int ao_squelch_should_filter_peek(const ao_squelch* s);
+int ao_squelch_signal_outside_filter_peek(const ao_squelch* s);
 
 /* AFC::check<STEP> (rtl_airband.cpp:193-219): walk from `base` in direction step (-1 / +1) over the squared magnitudes of
  * the interleaved spectrum while they keep rising fast enough; returns the bin reached. */

@@ -4,6 +4,7 @@
  * oracle/ref_driver.cpp so the two can be compared sample for sample.
  */
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "airband_oracle.h"
@@ -247,4 +248,85 @@ void ao_demod_counters(const ao_demod* d, uint64_t* out) {
         out[5 * i + 3] = s->ctcss_slow.not_found_count;
         out[5 * i + 4] = d->ch[i].active_counter;
     }
+}
+
+/* per channel, field for field what mi_channel_stats (include/mi_airband.h) mirrors back after a call */
+typedef struct {
+    float noise_level, signal_level, squelch_level, agcavgfast;
+    uint64_t open_count, flappy_count, ctcss_count, no_ctcss_count, active_counter;
+    int32_t squelch_state, signal_outside_filter;
+} ao_channel_stats;
+
+void ao_demod_channel_stats(const ao_demod* d, ao_channel_stats* out) {
+    for (int i = 0; i < d->nch; i++) {
+        const ao_squelch* s = &d->ch[i].squelch;
+        ao_channel_stats* o = &out[i];
+        memset(o, 0, sizeof(*o));
+        o->noise_level = s->noise_floor;
+        o->signal_level = s->pre_full;
+        o->squelch_level = ao_squelch_level_peek(s);
+        o->agcavgfast = d->ch[i].agcavgfast;
+        o->open_count = s->open_count;
+        o->flappy_count = s->flappy_count;
+        o->ctcss_count = s->ctcss_slow.found_count;
+        o->no_ctcss_count = s->ctcss_slow.not_found_count;
+        o->active_counter = d->ch[i].active_counter;
+        o->squelch_state = s->current_state;
+        o->signal_outside_filter = ao_squelch_signal_outside_filter_peek(s);
+    }
+}
+
+/* channel_t.waveout[WAVE_BATCH .. WAVE_BATCH + AGC_EXTRA) of every channel: the audio that is not final yet (a closing squelch
+ * still fades it, rtl_airband.cpp:567-571) -- after a run, what the next batch starts from */
+void ao_demod_lookahead(const ao_demod* d, float* out) {
+    for (int i = 0; i < d->nch; i++)
+        memcpy(out + (size_t)i * AO_AGC_EXTRA, d->ch[i].waveout + AO_WAVE_BATCH, AO_AGC_EXTRA * sizeof(float));
+}
+
+/* switch the per-step trace of ao_demod on, with room for `steps` steps per channel; what was recorded before is dropped */
+int ao_demod_trace_start(ao_demod* d, size_t steps) {
+    steps = (steps + AO_WAVE_BATCH - 1) / AO_WAVE_BATCH * AO_WAVE_BATCH; /* a batch is recorded whole */
+    free(d->trace);
+    d->trace = (uint8_t*)calloc((size_t)d->nch * steps + 1, 1);
+    d->trace_cap = d->trace ? steps : 0;
+    d->trace_len = 0;
+    return d->trace ? 0 : -1;
+}
+
+/* steps recorded so far; out (may be NULL): [nch][that many] */
+size_t ao_demod_trace_read(const ao_demod* d, uint8_t* out) {
+    const size_t n = d->trace_len < d->trace_cap ? d->trace_len : d->trace_cap;
+    if (out && d->trace)
+        for (int i = 0; i < d->nch; i++)
+            memcpy(out + (size_t)i * n, d->trace + (size_t)i * d->trace_cap, n);
+    return n;
+}
+
+/* The cache-neutral views against the getters they restate: a squelch fed raw (and, where it filters, filt) samples; after every
+ * step the getters are asked on a copy of the state.  Returns the number of steps at which a view disagreed with its getter. */
+size_t ao_squelch_peek_mismatches(const ao_squelch_cfg* cfg, const float* raw, const float* filt, size_t n) {
+    ao_squelch sq;
+    size_t bad = 0;
+    ao_squelch_init(&sq);
+    if (cfg->manual_level > 0)
+        ao_squelch_set_level_threshold(&sq, cfg->manual_level);
+    if (cfg->has_snr)
+        ao_squelch_set_snr_threshold(&sq, cfg->snr_db);
+    for (size_t i = 0; i < n; i++) {
+        ao_squelch_process_raw(&sq, raw[i]);
+        ao_squelch copy = sq;
+        const float level = ao_squelch_level(&copy);
+        int differs = memcmp(&level, &(float){ao_squelch_level_peek(&sq)}, sizeof(float)) != 0;
+        copy = sq;
+        differs |= ao_squelch_should_filter(&copy) != ao_squelch_should_filter_peek(&sq);
+        if (filt && ao_squelch_should_filter(&sq))
+            ao_squelch_process_filtered(&sq, filt[i]);
+        copy = sq;
+        differs |= ao_squelch_signal_outside_filter(&copy) != ao_squelch_signal_outside_filter_peek(&sq);
+        copy = sq;
+        const float level2 = ao_squelch_level(&copy);
+        differs |= memcmp(&level2, &(float){ao_squelch_level_peek(&sq)}, sizeof(float)) != 0;
+        bad += differs ? 1 : 0;
+    }
+    return bad;
 }

@@ -42,6 +42,22 @@ class SquelchFinal(C.Structure):
                 np.float32(self.squelch_level).tobytes())
 
 
+class OracleChannelStats(C.Structure):
+    """ao_channel_stats == mi_channel_stats field for field."""
+    _fields_ = [("noise_level", C.c_float), ("signal_level", C.c_float), ("squelch_level", C.c_float), ("agcavgfast", C.c_float),
+                ("open_count", C.c_uint64), ("flappy_count", C.c_uint64), ("ctcss_count", C.c_uint64), ("no_ctcss_count", C.c_uint64),
+                ("active_counter", C.c_uint64), ("squelch_state", C.c_int32), ("signal_outside_filter", C.c_int32)]
+
+
+STATS_LEVELS = ("noise_level", "signal_level", "squelch_level", "agcavgfast")  # compared by bits
+STATS_COUNTS = ("open_count", "flappy_count", "ctcss_count", "no_ctcss_count", "active_counter", "squelch_state", "signal_outside_filter")
+
+# the per-step trace of OracleDemod.trace(): one byte per step, as of the end of the step
+TRACE_OPEN, TRACE_AUDIO, TRACE_FILTER, TRACE_OUTSIDE_FILTER, TRACE_RESET = 1, 2, 4, 8, 128
+TRACE_STATE_SHIFT = 4  # (byte >> 4) & 7: CLOSED 0, OPENING 1, CLOSING 2, LOW_SIGNAL_ABORT 3, OPEN 4
+SQ_CLOSED, SQ_OPENING, SQ_CLOSING, SQ_LOW_SIGNAL_ABORT, SQ_OPEN = range(5)
+
+
 class DeviceCfg(C.Structure):
     """ao_device_cfg == mi_device_cfg field for field."""
     _fields_ = [("sample_rate", C.c_int), ("centerfreq", C.c_int), ("fft_size_log", C.c_int), ("sfmt", C.c_int),
@@ -155,6 +171,20 @@ def oracle_lib():
         lib.ao_demod_destroy.restype = None
         lib.ao_demod_run.argtypes = [C.c_void_p, u8p, C.c_size_t, C.c_int, f32p, C.c_void_p, C.c_void_p]
         lib.ao_demod_run.restype = C.c_int
+        lib.ao_demod_run_planes.argtypes = [C.c_void_p, f32p, C.c_void_p, C.c_size_t, C.c_int, f32p, C.c_void_p, C.c_void_p]
+        lib.ao_demod_run_planes.restype = C.c_int
+        lib.ao_demod_channel_stats.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ao_demod_channel_stats.restype = None
+        lib.ao_demod_lookahead.argtypes = [C.c_void_p, f32p]
+        lib.ao_demod_lookahead.restype = None
+        lib.ao_demod_trace_start.argtypes = [C.c_void_p, C.c_size_t]
+        lib.ao_demod_trace_start.restype = C.c_int
+        lib.ao_demod_trace_read.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ao_demod_trace_read.restype = C.c_size_t
+        lib.ao_squelch_peek_mismatches.argtypes = [C.POINTER(SquelchCfg), f32p, C.c_void_p, C.c_size_t]
+        lib.ao_squelch_peek_mismatches.restype = C.c_size_t
+        lib.ao_squelch_core_trace.argtypes = [C.POINTER(SquelchCfg), f32p, C.c_size_t, C.c_size_t, f32p]
+        lib.ao_squelch_core_trace.restype = None
         lib.ao_stage1.argtypes = [C.c_void_p, u8p, C.c_size_t, f32p, C.c_void_p]
         lib.ao_stage1.restype = None
         lib.ao_mixer_run.argtypes = [C.c_void_p, C.c_int, f32p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, f32p, C.c_void_p, C.c_void_p]
@@ -231,6 +261,46 @@ class OracleDemod:
                                    axc.ctypes.data_as(C.c_void_p))
         return nb, wo, axc, iqo
 
+    def run_planes(self, mag, max_batches, cplx=None, want_iq=False):
+        """ao_demod_run_planes: stage 2 over caller planes, continuing where the last call stopped.  mag: [nch][count] float32
+        (count = max_batches * WAVE_BATCH, + AGC_EXTRA on the first call); cplx: [channels with needs_raw_iq, in channel
+        order][count][2] or None -- the layout of mi_demod_process_planes.  Returns like run()."""
+        mag = np.ascontiguousarray(mag, dtype=np.float32)
+        assert mag.ndim == 2 and mag.shape[0] == self.nch
+        count = mag.shape[1]
+        zc = None if cplx is None else np.ascontiguousarray(cplx, dtype=np.float32)
+        assert zc is None or (zc.ndim == 3 and zc.shape[1:] == (count, 2))
+        wo = np.zeros((self.nch, max_batches * WAVE_BATCH), np.float32)
+        axc = np.zeros((self.nch, max_batches), np.uint8)
+        iqo = np.zeros((self.nch, max_batches * WAVE_BATCH * 2), np.float32) if want_iq else None
+        nb = self.lib.ao_demod_run_planes(self.h, mag.reshape(-1), None if zc is None else zc.ctypes.data_as(C.c_void_p), count, max_batches,
+                                          wo.reshape(-1), None if iqo is None else iqo.ctypes.data_as(C.c_void_p), axc.ctypes.data_as(C.c_void_p))
+        assert nb >= 0, "the plane entry refuses AFC plans"
+        return nb, wo, axc, iqo
+
+    def channel_stats(self):
+        """One OracleChannelStats per channel: every field of mi_channel_stats as of the last batch run."""
+        st = (OracleChannelStats * self.nch)()
+        self.lib.ao_demod_channel_stats(self.h, C.cast(st, C.c_void_p))
+        return list(st)
+
+    def lookahead(self):
+        """[nch][AGC_EXTRA]: waveout[WAVE_BATCH ..] after the last batch, the audio a closing squelch may still fade."""
+        out = np.zeros((self.nch, AGC_EXTRA), np.float32)
+        self.lib.ao_demod_lookahead(self.h, out.reshape(-1))
+        return out
+
+    def trace_start(self, steps):
+        """Record the per-step trace (TRACE_* bits) of the next `steps` steps of every channel."""
+        assert self.lib.ao_demod_trace_start(self.h, steps) == 0
+
+    def trace(self):
+        """[nch][steps recorded since trace_start]."""
+        n = self.lib.ao_demod_trace_read(self.h, None)
+        out = np.zeros((self.nch, n), np.uint8)
+        self.lib.ao_demod_trace_read(self.h, out.ctypes.data_as(C.c_void_p))
+        return out
+
     def stage1(self, iq, nfft, want_iq=True):
         iq = np.ascontiguousarray(iq, dtype=np.uint8)
         mag = np.zeros((self.nch, nfft), np.float32)
@@ -269,6 +339,17 @@ class OracleDemod:
 
     def __del__(self):
         self.close()
+
+
+def oracle_core_trace(raw, stride, manual_level=0.0, snr_db=None):
+    """ao_squelch_core_trace: [n // stride (rounded up) + 1][4] = (noise_floor_, moving_avg_cap_, pre_filter_.capped_, pre_filter_.full_)
+    before raw sample k * stride (the last row: after all n) of a plain squelch fed `raw`."""
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    n = raw.size
+    out = np.zeros(((n + stride - 1) // stride + 1, 4), np.float32)
+    cfg = SquelchCfg(manual_level, 0 if snr_db is None else 1, 0.0 if snr_db is None else snr_db, 0.0, float(WAVE_RATE))
+    oracle_lib().ao_squelch_core_trace(C.byref(cfg), raw, n, stride, out.reshape(-1))
+    return out
 
 
 class MixInput(C.Structure):  # ao_mix_input
