@@ -105,6 +105,21 @@ class GateBlock(C.Structure):  # mi_gate_block
 
 GATE_NONE, GATE_OPEN, GATE_OPEN_TRAIL, GATE_ALL = 0, 1, 2, 3  # MI_GATE_*
 
+
+class TxCfg(C.Structure):  # mi_tx_cfg: 0 = the reference's 8 / 4 / 28800 batches
+    _fields_ = [("min_batches", C.c_uint32), ("idle_batches", C.c_uint32), ("max_batches", C.c_uint32)]
+
+
+class TxRecord(C.Structure):  # mi_tx_record
+    _fields_ = [("row", C.c_uint32), ("seq", C.c_uint32), ("first_block", C.c_uint32), ("nblocks", C.c_uint32), ("first_batch", C.c_uint32),
+                ("close_batch", C.c_uint32), ("flags", C.c_uint32), ("peak", C.c_float), ("energy", C.c_double)]
+
+
+TX_RECORD_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in TxRecord._fields_])  # the same 40 bytes as a numpy record
+TX_STATE_DTYPE = np.dtype([("clock", "<u8"), ("opened", "<u8"), ("last_write", "<u8"), ("seq", "<u4"), ("open", "u1"), ("active", "u1"),
+                           ("zero", "<u2")])  # one row of the splitter's state blob, MI_TX_STATE_ROW_BYTES = 32
+TX_NONE = 0xFFFFFFFF  # first_batch of a record without blocks, close_batch of a file still open
+
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
@@ -113,6 +128,8 @@ ABI_SYMBOLS = [
     "mi_iqgen_host", "mi_iqgen_device", "mi_mixer_create", "mi_mixer_destroy", "mi_mixer_is_stereo", "mi_mixer_process_device",
     "mi_outgate_create", "mi_outgate_destroy", "mi_outgate_set_rules", "mi_outgate_process_device", "mi_outgate_download", "mi_outgate_state_size",
     "mi_outgate_get_state", "mi_outgate_set_state", "mi_outgate_set_timing", "mi_outgate_last_launch_ms", "mi_gate_plan_host",
+    "mi_txsplit_create", "mi_txsplit_destroy", "mi_txsplit_set_rows", "mi_txsplit_process_device", "mi_txsplit_download", "mi_txsplit_state_size",
+    "mi_txsplit_get_state", "mi_txsplit_set_state", "mi_txsplit_set_timing", "mi_txsplit_last_launch_ms", "mi_tx_plan_host",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
 
@@ -188,6 +205,19 @@ def lib():
         L.mi_outgate_set_timing.argtypes = [vp, C.c_int]
         L.mi_outgate_last_launch_ms.argtypes = [vp, vp]
         L.mi_gate_plan_host.argtypes = [vp, C.c_int, vp, sz, C.c_int, vp, vp, vp, vp]
+        L.mi_txsplit_create.argtypes = [C.POINTER(TxCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_txsplit_destroy.argtypes = [vp]
+        L.mi_txsplit_destroy.restype = None
+        L.mi_txsplit_set_rows.argtypes = [vp, vp]
+        L.mi_txsplit_process_device.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp, vp, vp]
+        L.mi_txsplit_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mi_txsplit_state_size.argtypes = [vp]
+        L.mi_txsplit_state_size.restype = sz
+        L.mi_txsplit_get_state.argtypes = [vp, vp, sz]
+        L.mi_txsplit_set_state.argtypes = [vp, vp, sz]
+        L.mi_txsplit_set_timing.argtypes = [vp, C.c_int]
+        L.mi_txsplit_last_launch_ms.argtypes = [vp, vp]
+        L.mi_tx_plan_host.argtypes = [C.POINTER(TxCfg), vp, C.c_int, vp, sz, C.c_int, vp, sz, vp, vp, sz, vp, vp]
         L.mi_plan_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(ChannelCfg), C.c_int, C.POINTER(vp)]
         L.mi_plan_destroy.argtypes = [vp]
         L.mi_plan_destroy.restype = None
@@ -711,6 +741,105 @@ def gate_plan_host(row_rule, axc, carried=None):
     _check(lib().mi_gate_plan_host(rule.ctypes.data_as(C.c_void_p), rows, axc.ctypes.data_as(C.c_void_p), nb, nb, carried.ctypes.data_as(C.c_void_p),
                                    index.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
     return index[:int(count[0])], row_first, count, carried
+
+
+def _tx_cfg(cfg):
+    """None, a TxCfg or (min_batches, idle_batches, max_batches) -> TxCfg"""
+    if cfg is None:
+        return TxCfg(0, 0, 0)
+    return cfg if isinstance(cfg, TxCfg) else TxCfg(*[int(x) for x in cfg])
+
+
+class TxSplit:
+    """mi_txsplit: one recording per transmission in signal time (split_on_transmission, src/output.cpp:353-376) on the device.
+    row_enabled: truth value per row (row = stream * nch + channel); cfg: (min, idle, max) in batches, 0 = the reference's 8 / 4 /
+    28800; max_records: capacity of the record buffer, 0 = rows * (max_batches + 1)."""
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_records=0, gpu=0):
+        en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+        self.rows, self.max_batches = en.size, max_batches
+        slots = self.rows * (max_batches + 1)
+        self.max_records = min(max_records, slots) if max_records else slots
+        self._h = C.c_void_p()
+        _check(lib().mi_txsplit_create(C.byref(_tx_cfg(cfg)), en.ctypes.data_as(C.c_void_p), self.rows, max_batches, max_records, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled):
+        en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+        assert en.size == self.rows
+        _check(lib().mi_txsplit_set_rows(self._h, en.ctypes.data_as(C.c_void_p)))
+
+    def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_records, d_row_first_record, d_count, hip_stream=None):
+        """Raw device pointers (ints; d_waveout may be None), strides in floats (audio) and bytes (flags); asynchronous on hip_stream."""
+        _check(lib().mi_txsplit_process_device(self._h, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_records, d_row_first_record, d_count,
+                                               hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (records [k] of TX_RECORD_DTYPE, row_first_record [rows + 1],
+        count [2]) with k = count[1], the number of records stored."""
+        records = np.zeros(self.max_records, TX_RECORD_DTYPE)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_txsplit_download(self._h, hip_stream, records.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p),
+                                         count.ctypes.data_as(C.c_void_p)))
+        return records[:int(count[1])], row_first, count
+
+    def state(self):
+        """The state blob, rows * 32 bytes (mi_txsplit_get_state); .view(TX_STATE_DTYPE) names its fields."""
+        n = lib().mi_txsplit_state_size(self._h)
+        buf = np.zeros(n, np.uint8)
+        _check(lib().mi_txsplit_get_state(self._h, buf.ctypes.data_as(C.c_void_p), n))
+        return buf
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        _check(lib().mi_txsplit_set_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
+
+    def set_timing(self, on=True):
+        _check(lib().mi_txsplit_set_timing(self._h, 1 if on else 0))
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of the walk, the scan, the block statistics and the combine pass of the last call made with set_timing(True)"""
+        ms = (C.c_float * 4)()
+        _check(lib().mi_txsplit_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            lib().mi_txsplit_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_records=0, nbatches=None):
+    """mi_tx_plan_host: the splitter's records from flags (and audio) on the host, no GPU.  axc: uint8 [rows][axc_stride]; waveout:
+    float32 [rows][row_stride] or None; state: the blob (rows * 32 bytes) or None (a fresh one); nbatches: batches of the call, default
+    axc's width; max_records: 0 = rows * (nbatches + 1).  Returns (records [count[1]], row_first_record [rows + 1], count [2], state
+    after the call)."""
+    en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+    axc = np.ascontiguousarray(axc, dtype=np.uint8)
+    assert axc.ndim == 2 and axc.shape[0] == en.size
+    rows, axc_stride = axc.shape
+    nb = axc_stride if nbatches is None else nbatches
+    state = np.zeros(rows * TX_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * TX_STATE_DTYPE.itemsize
+    row_stride = 0
+    if waveout is not None:
+        waveout = np.ascontiguousarray(waveout, dtype=np.float32)
+        assert waveout.ndim == 2 and waveout.shape[0] == rows
+        row_stride = waveout.shape[1]
+    cap = max_records or rows * (nb + 1)
+    records = np.zeros(cap, TX_RECORD_DTYPE)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_tx_plan_host(C.byref(_tx_cfg(cfg)), en.ctypes.data_as(C.c_void_p), rows, axc.ctypes.data_as(C.c_void_p), axc_stride, nb,
+                                 None if waveout is None else waveout.ctypes.data_as(C.c_void_p), row_stride, state.ctypes.data_as(C.c_void_p),
+                                 records.ctypes.data_as(C.c_void_p), cap, row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+    return records[:int(count[1])], row_first, count, state
 
 
 # ---- the BASELINE.json channel plans (SURVEY 8d) ----

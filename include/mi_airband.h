@@ -412,7 +412,8 @@ int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stri
  *                       starts false as output_t::active does
  *   MI_GATE_ALL         every batch: a `continuous` output (the same lines, continuous == true)
  * After a call the carried flag of every row whose rule is not MI_GATE_NONE is "the last batch of this call had a signal".
- * (The wall-clock file rotation of close_if_necessary stays with the host.) */
+ * (The wall-clock file rotation of close_if_necessary stays with the host; its split_on_transmission rule in signal time is the
+ * transmission splitter below.) */
 enum { MI_GATE_NONE = 0, MI_GATE_OPEN = 1, MI_GATE_OPEN_TRAIL = 2, MI_GATE_ALL = 3 };
 typedef struct { uint32_t row, batch; } mi_gate_block;
 typedef struct mi_outgate mi_outgate;
@@ -460,6 +461,80 @@ int mi_outgate_last_launch_ms(mi_outgate* g, float* ms /* [3] */);
  * row_first [rows + 1]; count[0] = count[1] = the number of travelling blocks (there is no capacity here). */
 int mi_gate_plan_host(const uint8_t* row_rule, int rows, const char* axc, size_t axc_stride, int nbatches, uint8_t* carried_inout,
                       mi_gate_block* index, uint32_t* row_first, uint32_t* count /* [2] */);
+
+/* ---------------- transmission splitter: one recording per transmission, decided in signal time on the device ----------------
+ * `split_on_transmission` (src/output.cpp:353-376) closes a transmission's file by gettimeofday(): duration > 1.0 s and idle > 0.5 s,
+ * or duration > 3600 s.  A replay has no meaningful wall clock, so the rule is restated on the jitter-free schedule: batch b of a
+ * row is handled at t0 + b * MI_WAVE_BATCH / MI_WAVE_RATE, and every time becomes a count of batches.  Per row the carried state is
+ *   open (fdata->f != NULL), active (output_t::active), seq (the running file number, 0 before the first file), the batch at which
+ *   the file was opened, the batch of the last write, and the row's own 64-bit batch clock.
+ * For each batch, with signal = (axc != MI_NO_SIGNAL):
+ *   check():  if open, d = clock - opened, i = clock - last write; the file closes when d > max or (d > min and i > idle)   :367-375
+ *   !signal && !active:  check(); the batch does not travel                                                               :518-520
+ *   otherwise:           check(); if not open: seq += 1, open, both stamps = clock (:404-414, :454); the batch travels into file
+ *                        seq; active = signal (:560); last write = clock (:561)
+ *   clock += 1
+ * Thresholds in batches, from the reference's constants through MI_WAVE_BATCH / MI_WAVE_RATE in integers: d * 2000 > 1.0 * 16000
+ * gives min = 8, i * 2000 > 0.5 * 16000 gives idle = 4, d * 2000 > 3600 * 16000 gives max = 28800.  The travelling set is exactly
+ * MI_GATE_OPEN_TRAIL's, so an MI_GATE_OPEN_TRAIL gate run over the same call packs the blocks the records slice: file seq's audio
+ * is blocks[row_first[row] + first_block ..][nblocks], its raw I/Q the same slice of d_iq_blocks.
+ *
+ * Order of `energy` (the device, mi_tx_plan_host and the tests' model all follow it).  Per block of 2000 floats = 500 float4, with
+ * q = (double)x * (double)x (exact): thread t < 256 adds in sequence the four elements of float4 number t and, if t < 244, then
+ * the four of float4 number 256 + t; the 256 partial sums are reduced by acc[t] += acc[t + d] for t < d, d = 128, 64, ..., 1; a
+ * record's energy is the sequential double sum of its blocks' sums in block order.  peak = max |x| is order-free.  Inputs are the
+ * demod's audio (finite, |x| <= 1, rtl_airband.cpp:625-632); NaN and Inf are unspecified.
+ *
+ * State blob: rows * 32 bytes, per row little-endian { uint64 clock; uint64 opened; uint64 last_write; uint32 seq; uint8 open;
+ * uint8 active; uint16 zero } -- the stamps are values of the row's clock and keep their last value while no file is open. */
+typedef struct { uint32_t min_batches, idle_batches, max_batches; } mi_tx_cfg; /* 0 = the reference's 8 / 4 / 28800 */
+typedef struct {
+    uint32_t row, seq;             /* seq: the row's file number since creation, 1-based */
+    uint32_t first_block, nblocks; /* slice of the row's travelling blocks OF THIS CALL (rank under MI_GATE_OPEN_TRAIL); nblocks may be 0 */
+    uint32_t first_batch;          /* call-relative batch of the first block; 0xFFFFFFFF when nblocks == 0 */
+    uint32_t close_batch;          /* call-relative batch whose check closed the file; 0xFFFFFFFF = still open after the call */
+    uint32_t flags;                /* bit 0: the file was open when the call began (these blocks are appended) */
+    float peak;                    /* max |x| over the record's blocks of this call */
+    double energy;                 /* sum of x * x over them, in the order above */
+} mi_tx_record;                    /* 40 bytes */
+typedef struct mi_txsplit mi_txsplit;
+enum { MI_TX_STATE_ROW_BYTES = 32 };
+
+/* row_enabled [rows] (0 = the row sits out: no record, and every byte of its state stays, clock included -- the companion of
+ * mi_demod_set_active_streams, as MI_GATE_NONE is); 1 <= rows < 2^20, rows * (max_batches + 1) < 2^24.  One record per row and
+ * file that a call touched (the file received a block or was closed), so a row has at most nbatches + 1 of them;
+ * max_records: capacity of the caller's record buffer, 0 = rows * (max_batches + 1). */
+int mi_txsplit_create(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_records, int gpu,
+                      mi_txsplit** out);
+void mi_txsplit_destroy(mi_txsplit* t);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_txsplit_set_rows(mi_txsplit* t, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the buffers mi_demod_process_device wrote; alignment and strides as for
+ * mi_outgate_process_device.  d_waveout may be NULL (a rawfile-only host): peak = 0 and energy = 0.  Outputs in device memory:
+ *   d_records           [max_records]  rows ascending, seq ascending within a row (8-byte aligned)
+ *   d_row_first_record  [rows + 1]     exclusive prefix of the rows' record counts
+ *   d_count             [2]            number of records, and min(that, max_records) = the number stored
+ * Nothing is written at or beyond max_records.  Asynchronous on `hip_stream`, no host synchronisation; four kernels (walk, scan,
+ * block statistics, combine) without atomics, so every byte is the same on every run. */
+int mi_txsplit_process_device(mi_txsplit* t, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
+                              mi_tx_record* d_records, uint32_t* d_row_first_record, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_txsplit_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] records.  records and row_first_record may each be NULL.  The one place that synchronises. */
+int mi_txsplit_download(mi_txsplit* t, void* hip_stream, mi_tx_record* records, uint32_t* row_first_record, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_TX_STATE_ROW_BYTES bytes in the layout above (mi_tx_plan_host reads and writes the same bytes).
+ * set_state refuses a blob whose open / active bytes are not 0 / 1 or whose padding is not zero.  Both complete queued work first. */
+size_t mi_txsplit_state_size(const mi_txsplit* t);
+int mi_txsplit_get_state(mi_txsplit* t, void* buf, size_t len);
+int mi_txsplit_set_state(mi_txsplit* t, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[4] = {walk, scan, block statistics, combine}.  tools/tx_rate.py. */
+int mi_txsplit_set_timing(mi_txsplit* t, int on);
+int mi_txsplit_last_launch_ms(mi_txsplit* t, float* ms /* [4] */);
+/* The host twin: no GPU and no HIP call; the same state blob byte for byte and the same records, peak and energy included.
+ * axc [rows][axc_stride]; waveout [rows][row_stride] or NULL; state_inout rows * MI_TX_STATE_ROW_BYTES bytes, read and updated;
+ * records holds max_records entries (max_records >= 1), of which min(count[0], max_records) = count[1] are written. */
+int mi_tx_plan_host(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, const char* axc, size_t axc_stride, int nbatches,
+                    const float* waveout, size_t row_stride, void* state_inout, mi_tx_record* records, size_t max_records,
+                    uint32_t* row_first_record, uint32_t* count /* [2] */);
 
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
