@@ -258,8 +258,62 @@ def _chan_array(chans):
     return (ChannelCfg * len(chans))(*chans)
 
 
-class Plan:
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _flags(x):
+    """truth values as 0 / 1 bytes"""
+    return np.array([1 if v else 0 for v in x], np.uint8)
+
+
+class _Handle:
+    """A library handle in `_h` (None once closed), released by the function `_destroy` names."""
+    _destroy = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _PostStage(_Handle):
+    """The handle of a post-stage with a state blob and per-launch timing: the calls `_prefix`_* over its `_launches` launches."""
+    _prefix = None
+    _launches = 0
+
+    def _call(self, name, *args):
+        _check(getattr(lib(), f"{self._prefix}_{name}")(self._h, *args))
+
+    def state(self):
+        """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
+        fields .view(TX_STATE_DTYPE) names."""
+        n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
+        buf = np.zeros(n, np.uint8)
+        self._call("get_state", _ptr(buf), n)
+        return buf
+
+    def set_timing(self, on=True):
+        self._call("set_timing", 1 if on else 0)
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
+        the splitter's walk, scan, block statistics and combine pass"""
+        ms = (C.c_float * self._launches)()
+        self._call("last_launch_ms", C.cast(ms, C.c_void_p))
+        return tuple(ms)
+
+
+class Plan(_Handle):
     """Host-only derived parameters (no GPU needed)."""
+    _destroy = "mi_plan_destroy"
 
     def __init__(self, dev, chans):
         self._h = C.c_void_p()
@@ -269,7 +323,7 @@ class Plan:
 
     def _vec(self, fn, n):
         out = np.zeros(n, np.float32)
-        _check(fn(self._h, out.ctypes.data_as(C.c_void_p)))
+        _check(fn(self._h, _ptr(out)))
         return out
 
     def window(self):
@@ -283,7 +337,7 @@ class Plan:
 
     def sincos_lut(self):
         s, c = np.zeros(257, np.float32), np.zeros(257, np.float32)
-        _check(lib().mi_plan_sincos_lut(self._h, s.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_plan_sincos_lut(self._h, _ptr(s), _ptr(c)))
         return s, c
 
     def channel(self, i):
@@ -299,31 +353,21 @@ class Plan:
         need = (C.c_uint64 * 6)()
         slots = np.zeros(self.nch, np.int32)
         tw = np.zeros((self.nch, nst, 2), np.float32)
-        _check(lib().mi_plan_lane_fft(self._h, C.byref(enabled), need, C.byref(lanes), slots.ctypes.data_as(C.c_void_p),
-                                      tw.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_plan_lane_fft(self._h, C.byref(enabled), need, C.byref(lanes), _ptr(slots),
+                                      _ptr(tw)))
         return bool(enabled.value), [int(x) for x in need], lanes.value, slots, tw
 
     def ctcss_coeffs(self, i, slow):
         d = self.channel(i)
         n = d.ctcss_slow_ndet if slow else d.ctcss_fast_ndet
         out = np.zeros(n, np.float32)
-        _check(lib().mi_plan_ctcss_coeffs(self._h, i, 1 if slow else 0, out.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_plan_ctcss_coeffs(self._h, i, 1 if slow else 0, _ptr(out)))
         return out
 
-    def close(self):
-        if self._h:
-            lib().mi_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Demod:
+class Demod(_Handle):
     """nstreams x nch channels of demodulate() state resident on one GPU."""
+    _destroy = "mi_demod_destroy"
 
     def __init__(self, dev, chans, nstreams=1, max_batches=1, gpu=0):
         self._h = C.c_void_p()
@@ -359,8 +403,8 @@ class Demod:
         axc = np.zeros((self.nstreams, self.nch, nbatches), np.uint8)
         iqo = np.zeros((self.nstreams, self.nch, n, 2), np.float32) if want_iq else None
         stats = (ChannelStats * (self.nstreams * self.nch))() if want_stats else None
-        _check(lib().mi_demod_process(self._h, ptrs, nbatches, wo.ctypes.data_as(C.c_void_p),
-                                      None if iqo is None else iqo.ctypes.data_as(C.c_void_p), axc.ctypes.data_as(C.c_void_p),
+        _check(lib().mi_demod_process(self._h, ptrs, nbatches, _ptr(wo),
+                                      None if iqo is None else _ptr(iqo), _ptr(axc),
                                       None if stats is None else C.cast(stats, C.c_void_p)))
         return wo, axc, iqo, stats
 
@@ -379,8 +423,8 @@ class Demod:
         axc = np.zeros((self.nstreams, self.nch, nbatches), np.uint8)
         iqo = np.zeros((self.nstreams, self.nch, n, 2), np.float32) if want_iq else None
         stats = (ChannelStats * (self.nstreams * self.nch))() if want_stats else None
-        _check(lib().mi_demod_submit(self._h, ptrs, nbatches, wo.ctypes.data_as(C.c_void_p),
-                                     None if iqo is None else iqo.ctypes.data_as(C.c_void_p), axc.ctypes.data_as(C.c_void_p),
+        _check(lib().mi_demod_submit(self._h, ptrs, nbatches, _ptr(wo),
+                                     None if iqo is None else _ptr(iqo), _ptr(axc),
                                      None if stats is None else C.cast(stats, C.c_void_p)))
         if not hasattr(self, "_tickets"):
             self._tickets = []
@@ -412,12 +456,12 @@ class Demod:
             _check(lib().mi_demod_set_active_streams(self._h, None))
             return
         assert len(active) == self.nstreams
-        m = np.array([1 if a else 0 for a in active], np.uint8)
-        _check(lib().mi_demod_set_active_streams(self._h, m.ctypes.data_as(C.c_void_p)))
+        m = _flags(active)
+        _check(lib().mi_demod_set_active_streams(self._h, _ptr(m)))
 
     def get_active_streams(self):
         m = np.zeros(self.nstreams, np.uint8)
-        _check(lib().mi_demod_get_active_streams(self._h, m.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_demod_get_active_streams(self._h, _ptr(m)))
         return [bool(x) for x in m]
 
     def stats(self):
@@ -428,12 +472,12 @@ class Demod:
     def get_state(self):
         n = lib().mi_demod_state_size(self._h)
         buf = np.zeros(n, np.uint8)
-        _check(lib().mi_demod_get_state(self._h, buf.ctypes.data_as(C.c_void_p), n))
+        _check(lib().mi_demod_get_state(self._h, _ptr(buf), n))
         return buf
 
     def set_state(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        _check(lib().mi_demod_set_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
+        _check(lib().mi_demod_set_state(self._h, _ptr(buf), buf.size))
 
     def last_path(self):
         """(1 if the last call ran the time-parallel stage 2 else 0, rows left unverified -- always 0)."""
@@ -453,8 +497,8 @@ class Demod:
         zc = None if cplx is None else np.ascontiguousarray(cplx, dtype=np.float32)
         f = lib().mi_demod_process_planes
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _check(f(self._h, mag.ctypes.data_as(C.c_void_p), None if zc is None else zc.ctypes.data_as(C.c_void_p), nbatches,
-                 wo.ctypes.data_as(C.c_void_p), None if iqo is None else iqo.ctypes.data_as(C.c_void_p), axc.ctypes.data_as(C.c_void_p),
+        _check(f(self._h, _ptr(mag), None if zc is None else _ptr(zc), nbatches,
+                 _ptr(wo), None if iqo is None else _ptr(iqo), _ptr(axc),
                  C.cast(stats, C.c_void_p)))
         return wo, axc, iqo, list(stats)
 
@@ -481,15 +525,15 @@ class Demod:
         _check(lib().mi_demod_tp_debug(self._h, row, None, 0, None, C.byref(nseg)))
         core = np.zeros((nseg.value + 1, 4), np.float32)
         diag = np.zeros(8, np.int32)
-        _check(lib().mi_demod_tp_debug(self._h, row, core.ctypes.data_as(C.c_void_p), nseg.value + 1, diag.ctypes.data_as(C.c_void_p),
+        _check(lib().mi_demod_tp_debug(self._h, row, _ptr(core), nseg.value + 1, _ptr(diag),
                                        C.byref(nseg)))
         return core, diag
 
     def read_planes(self, stream, ch, first, count, want_iq=False):
         mag = np.zeros(count, np.float32)
         iq = np.zeros((count, 2), np.float32) if want_iq else None
-        _check(lib().mi_demod_read_planes(self._h, stream, ch, first, count, mag.ctypes.data_as(C.c_void_p),
-                                          None if iq is None else iq.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_demod_read_planes(self._h, stream, ch, first, count, _ptr(mag),
+                                          None if iq is None else _ptr(iq)))
         return mag, iq
 
     def set_option(self, option, value):
@@ -520,17 +564,6 @@ class Demod:
         _check(lib().mi_demod_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def close(self):
-        if self._h:
-            lib().mi_demod_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def iqgen_cfg(sample_rate=2560000, seed=0xA1B2C3D4, noise_q8_mul=111, gate_samples=None, carriers=()):
     cfg = IqGenCfg()
@@ -546,7 +579,7 @@ def iqgen_cfg(sample_rate=2560000, seed=0xA1B2C3D4, noise_q8_mul=111, gate_sampl
 
 def iqgen_host(cfg, stream_id, first, count):
     out = np.zeros(2 * count, np.uint8)
-    _check(lib().mi_iqgen_host(C.byref(cfg), stream_id, first, count, out.ctypes.data_as(C.c_void_p)))
+    _check(lib().mi_iqgen_host(C.byref(cfg), stream_id, first, count, _ptr(out)))
     return out
 
 
@@ -566,8 +599,9 @@ def jit_counts():
     return a.value, b.value
 
 
-class Gather:
+class Gather(_Handle):
     """mi_gather_*: audio + flags of every rank to rank 0 over RCCL (the C-ABI twin of shard.AudioGather)."""
+    _destroy = "mi_gather_destroy"
 
     @staticmethod
     def unique_id():
@@ -599,11 +633,6 @@ class Gather:
     def sync(self):
         _check(lib().mi_gather_sync(self._h))
 
-    def close(self):
-        if self._h:
-            lib().mi_gather_destroy(self._h)
-            self._h = C.c_void_p()
-
 
 class PinnedBuffer:
     """Page-locked host memory from mi_host_alloc, viewed as a uint8 numpy array (.array); .ptr is its address."""
@@ -631,8 +660,9 @@ class PinnedBuffer:
             self._mem = None
 
 
-class Mixer:
+class Mixer(_Handle):
     """One mixer_t (src/mixer.cpp) over device-resident audio: inputs = [(row, ampfactor, balance), ...]."""
+    _destroy = "mi_mixer_destroy"
 
     def __init__(self, inputs, gpu=0):
         arr = (MixInput * len(inputs))(*[MixInput(int(r), float(a), float(b)) for r, a, b in inputs])
@@ -643,37 +673,27 @@ class Mixer:
     def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_left, d_right, d_axc_out, hip_stream=None):
         _check(lib().mi_mixer_process_device(self._h, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_left, d_right, d_axc_out, hip_stream))
 
-    def close(self):
-        if self._h:
-            lib().mi_mixer_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class OutputGate:
+class OutputGate(_PostStage):
     """mi_outgate: the (row, batch) blocks the reference's outputs consume, packed on the device.  row_rule: one GATE_* per row
     (row = stream * nch + channel); row_has_iq: truth value per row or None; max_blocks: capacity of the destination buffers in
     blocks, 0 = rows * max_batches."""
+    _destroy, _prefix, _launches = "mi_outgate_destroy", "mi_outgate", 3
 
     def __init__(self, row_rule, row_has_iq=None, max_batches=1, max_blocks=0, gpu=0):
         rule = np.ascontiguousarray(row_rule, dtype=np.uint8)
         self.rows, self.max_batches = rule.size, max_batches
         self.max_blocks = min(max_blocks, self.rows * max_batches) if max_blocks else self.rows * max_batches
-        has_iq = None if row_has_iq is None else np.array([1 if x else 0 for x in row_has_iq], np.uint8)
+        has_iq = None if row_has_iq is None else _flags(row_has_iq)
         assert has_iq is None or has_iq.size == self.rows
         self._h = C.c_void_p()
-        _check(lib().mi_outgate_create(rule.ctypes.data_as(C.c_void_p), None if has_iq is None else has_iq.ctypes.data_as(C.c_void_p),
+        _check(lib().mi_outgate_create(_ptr(rule), None if has_iq is None else _ptr(has_iq),
                                        self.rows, max_batches, max_blocks, gpu, C.byref(self._h)))
 
     def set_rules(self, row_rule):
         rule = np.ascontiguousarray(row_rule, dtype=np.uint8)
         assert rule.size == self.rows
-        _check(lib().mi_outgate_set_rules(self._h, rule.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_outgate_set_rules(self._h, _ptr(rule)))
 
     def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_blocks, d_index, d_row_first, d_count, d_iq_out=None,
                        iq_row_stride=0, d_iq_blocks=None, hip_stream=None):
@@ -689,41 +709,14 @@ class OutputGate:
         index = np.empty((self.max_blocks, 2), np.uint32)
         row_first = np.empty(self.rows + 1, np.uint32)
         count = np.zeros(2, np.uint32)
-        _check(lib().mi_outgate_download(self._h, hip_stream, blocks.ctypes.data_as(C.c_void_p), None if iq is None else iq.ctypes.data_as(C.c_void_p),
-                                         index.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_outgate_download(self._h, hip_stream, _ptr(blocks), None if iq is None else _ptr(iq),
+                                         _ptr(index), _ptr(row_first), _ptr(count)))
         k = int(count[1])
         return blocks[:k], None if iq is None else iq[:k], index[:k], row_first, count
 
-    def state(self):
-        """The carried flags, one byte per row (mi_outgate_get_state)."""
-        n = lib().mi_outgate_state_size(self._h)
-        buf = np.zeros(n, np.uint8)
-        _check(lib().mi_outgate_get_state(self._h, buf.ctypes.data_as(C.c_void_p), n))
-        return buf
-
     def set_state(self, buf):
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        _check(lib().mi_outgate_set_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
-
-    def set_timing(self, on=True):
-        _check(lib().mi_outgate_set_timing(self._h, 1 if on else 0))
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of the rank pass, the scan and the block copy of the last call made with set_timing(True)"""
-        ms = (C.c_float * 3)()
-        _check(lib().mi_outgate_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
-        return tuple(ms)
-
-    def close(self):
-        if self._h:
-            lib().mi_outgate_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("set_state", _ptr(buf), buf.size)
 
 
 def gate_plan_host(row_rule, axc, carried=None):
@@ -738,8 +731,8 @@ def gate_plan_host(row_rule, axc, carried=None):
     index = np.empty((rows * nb, 2), np.uint32)
     row_first = np.empty(rows + 1, np.uint32)
     count = np.zeros(2, np.uint32)
-    _check(lib().mi_gate_plan_host(rule.ctypes.data_as(C.c_void_p), rows, axc.ctypes.data_as(C.c_void_p), nb, nb, carried.ctypes.data_as(C.c_void_p),
-                                   index.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+    _check(lib().mi_gate_plan_host(_ptr(rule), rows, _ptr(axc), nb, nb, _ptr(carried),
+                                   _ptr(index), _ptr(row_first), _ptr(count)))
     return index[:int(count[0])], row_first, count, carried
 
 
@@ -750,23 +743,24 @@ def _tx_cfg(cfg):
     return cfg if isinstance(cfg, TxCfg) else TxCfg(*[int(x) for x in cfg])
 
 
-class TxSplit:
+class TxSplit(_PostStage):
     """mi_txsplit: one recording per transmission in signal time (split_on_transmission, src/output.cpp:353-376) on the device.
     row_enabled: truth value per row (row = stream * nch + channel); cfg: (min, idle, max) in batches, 0 = the reference's 8 / 4 /
     28800; max_records: capacity of the record buffer, 0 = rows * (max_batches + 1)."""
+    _destroy, _prefix, _launches = "mi_txsplit_destroy", "mi_txsplit", 4
 
     def __init__(self, row_enabled, max_batches=1, cfg=None, max_records=0, gpu=0):
-        en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+        en = _flags(row_enabled)
         self.rows, self.max_batches = en.size, max_batches
         slots = self.rows * (max_batches + 1)
         self.max_records = min(max_records, slots) if max_records else slots
         self._h = C.c_void_p()
-        _check(lib().mi_txsplit_create(C.byref(_tx_cfg(cfg)), en.ctypes.data_as(C.c_void_p), self.rows, max_batches, max_records, gpu, C.byref(self._h)))
+        _check(lib().mi_txsplit_create(C.byref(_tx_cfg(cfg)), _ptr(en), self.rows, max_batches, max_records, gpu, C.byref(self._h)))
 
     def set_rows(self, row_enabled):
-        en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+        en = _flags(row_enabled)
         assert en.size == self.rows
-        _check(lib().mi_txsplit_set_rows(self._h, en.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_txsplit_set_rows(self._h, _ptr(en)))
 
     def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_records, d_row_first_record, d_count, hip_stream=None):
         """Raw device pointers (ints; d_waveout may be None), strides in floats (audio) and bytes (flags); asynchronous on hip_stream."""
@@ -779,40 +773,13 @@ class TxSplit:
         records = np.zeros(self.max_records, TX_RECORD_DTYPE)
         row_first = np.empty(self.rows + 1, np.uint32)
         count = np.zeros(2, np.uint32)
-        _check(lib().mi_txsplit_download(self._h, hip_stream, records.ctypes.data_as(C.c_void_p), row_first.ctypes.data_as(C.c_void_p),
-                                         count.ctypes.data_as(C.c_void_p)))
+        _check(lib().mi_txsplit_download(self._h, hip_stream, _ptr(records), _ptr(row_first),
+                                         _ptr(count)))
         return records[:int(count[1])], row_first, count
-
-    def state(self):
-        """The state blob, rows * 32 bytes (mi_txsplit_get_state); .view(TX_STATE_DTYPE) names its fields."""
-        n = lib().mi_txsplit_state_size(self._h)
-        buf = np.zeros(n, np.uint8)
-        _check(lib().mi_txsplit_get_state(self._h, buf.ctypes.data_as(C.c_void_p), n))
-        return buf
 
     def set_state(self, buf):
         buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        _check(lib().mi_txsplit_set_state(self._h, buf.ctypes.data_as(C.c_void_p), buf.size))
-
-    def set_timing(self, on=True):
-        _check(lib().mi_txsplit_set_timing(self._h, 1 if on else 0))
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of the walk, the scan, the block statistics and the combine pass of the last call made with set_timing(True)"""
-        ms = (C.c_float * 4)()
-        _check(lib().mi_txsplit_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
-        return tuple(ms)
-
-    def close(self):
-        if self._h:
-            lib().mi_txsplit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("set_state", _ptr(buf), buf.size)
 
 
 def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_records=0, nbatches=None):
@@ -820,7 +787,7 @@ def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_recor
     float32 [rows][row_stride] or None; state: the blob (rows * 32 bytes) or None (a fresh one); nbatches: batches of the call, default
     axc's width; max_records: 0 = rows * (nbatches + 1).  Returns (records [count[1]], row_first_record [rows + 1], count [2], state
     after the call)."""
-    en = np.array([1 if x else 0 for x in row_enabled], np.uint8)
+    en = _flags(row_enabled)
     axc = np.ascontiguousarray(axc, dtype=np.uint8)
     assert axc.ndim == 2 and axc.shape[0] == en.size
     rows, axc_stride = axc.shape
@@ -836,9 +803,9 @@ def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_recor
     records = np.zeros(cap, TX_RECORD_DTYPE)
     row_first = np.empty(rows + 1, np.uint32)
     count = np.zeros(2, np.uint32)
-    _check(lib().mi_tx_plan_host(C.byref(_tx_cfg(cfg)), en.ctypes.data_as(C.c_void_p), rows, axc.ctypes.data_as(C.c_void_p), axc_stride, nb,
-                                 None if waveout is None else waveout.ctypes.data_as(C.c_void_p), row_stride, state.ctypes.data_as(C.c_void_p),
-                                 records.ctypes.data_as(C.c_void_p), cap, row_first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+    _check(lib().mi_tx_plan_host(C.byref(_tx_cfg(cfg)), _ptr(en), rows, _ptr(axc), axc_stride, nb,
+                                 None if waveout is None else _ptr(waveout), row_stride, _ptr(state),
+                                 _ptr(records), cap, _ptr(row_first), _ptr(count)))
     return records[:int(count[1])], row_first, count, state
 
 

@@ -25,19 +25,11 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
-#include "hip_own.hpp"
-#include "plan.hpp"
-
-namespace mi {
-std::string& last_error_ref();
-}
+#include "poststage.hpp"
 
 namespace {
 
-int gfail(int code, const std::string& what) {
-    mi::last_error_ref() = what;
-    return code;
-}
+using mi::fail;
 
 struct Rccl {
     void* lib = nullptr;
@@ -80,7 +72,7 @@ Rccl& rccl() {
 
 int nccl_fail(int rc, const char* where) {
     Rccl& r = rccl();
-    return gfail(MI_ERR_HIP, std::string(where) + ": " + (r.error_string ? r.error_string(rc) : "RCCL error"));
+    return fail(MI_ERR_HIP, std::string(where) + ": " + (r.error_string ? r.error_string(rc) : "RCCL error"));
 }
 
 #define NCCL_TRY(expr)                    \
@@ -93,7 +85,7 @@ int nccl_fail(int rc, const char* where) {
     do {                                                                                \
         const hipError_t e__ = (expr);                                                  \
         if (e__ != hipSuccess)                                                          \
-            return gfail(MI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+            return fail(MI_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
 // ---- the transport under the gather: point-to-point send / recv in groups, RCCL's semantics ----
@@ -158,7 +150,7 @@ struct LoopTransport : Transport {
         m.src = buf, m.bytes = bytes_of(count, type);
         if (hipEventCreateWithFlags(m.ready.put(), hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(m.done.put(), hipEventDisableTiming) != hipSuccess ||
             hipEventRecord(m.ready, s) != hipSuccess)
-            return gfail(MI_ERR_HIP, "loopback send: event");
+            return fail(MI_ERR_HIP, "loopback send: event");
         std::unique_lock<std::mutex> lk(hub->mu);
         hub->box[{rank, peer}].push_back(&m);
         hub->cv.notify_all();
@@ -177,16 +169,16 @@ struct LoopTransport : Transport {
         if (ok)
             (void)hipEventSynchronize(m.done);  // (the event objects die with this frame)
         if (!ok)
-            return gfail(MI_ERR_HIP, "loopback send: no matching recv within 60 s");
+            return fail(MI_ERR_HIP, "loopback send: no matching recv within 60 s");
         if (m.failed || e != hipSuccess)
-            return gfail(MI_ERR_HIP, "loopback send: the receiver's copy failed");
+            return fail(MI_ERR_HIP, "loopback send: the receiver's copy failed");
         return MI_OK;
     }
     int recv(void* buf, size_t count, int type, int peer, hipStream_t s) override {
         std::unique_lock<std::mutex> lk(hub->mu);
         auto& q = hub->box[{peer, rank}];
         if (!hub->cv.wait_for(lk, std::chrono::seconds(60), [&] { return !q.empty(); }))
-            return gfail(MI_ERR_HIP, "loopback recv: no matching send within 60 s");
+            return fail(MI_ERR_HIP, "loopback recv: no matching send within 60 s");
         LoopMsg* m = q.front();
         q.pop_front();
         hipError_t e = (m->bytes == bytes_of(count, type)) ? hipSuccess : hipErrorInvalidValue;  // RCCL would hang or corrupt: the test transport says so
@@ -201,7 +193,7 @@ struct LoopTransport : Transport {
         hub->cv.notify_all();
         lk.unlock();
         if (e != hipSuccess)
-            return gfail(MI_ERR_HIP, std::string("loopback recv: ") + (e == hipErrorInvalidValue ? "send / recv sizes differ" : hipGetErrorString(e)));
+            return fail(MI_ERR_HIP, std::string("loopback recv: ") + (e == hipErrorInvalidValue ? "send / recv sizes differ" : hipGetErrorString(e)));
         return MI_OK;
     }
     int group_start() override { return MI_OK; }
@@ -269,17 +261,17 @@ extern "C" {
 
 int mi_gather_unique_id(mi_gather_id* id) {
     if (!id)
-        return gfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     Rccl& r = rccl();
     if (!r.ok)
-        return gfail(MI_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded");
+        return fail(MI_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded");
     NCCL_TRY(r.get_unique_id(id));
     return MI_OK;
 }
 
 int mi_gather_loopback_id(mi_gather_id* id, uint64_t job) {
     if (!id)
-        return gfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     std::memset(id->internal, 0, sizeof(id->internal));
     std::memcpy(id->internal, kLoopMagic, sizeof(kLoopMagic));
     std::memcpy(id->internal + 8, &job, sizeof(job));
@@ -298,20 +290,20 @@ void mi_gather_destroy(mi_gather* g) {
 
 int mi_gather_create(const mi_gather_id* id, int rank, int world, int gpu, const int* streams_per_rank, int nch, int max_batches, mi_gather** out) {
     if (!out)
-        return gfail(MI_ERR_INVALID, "out is NULL");
+        return fail(MI_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!streams_per_rank || world < 1 || rank < 0 || rank >= world || nch < 1 || max_batches < 1 || (world > 1 && !id))
-        return gfail(MI_ERR_INVALID, "bad gather geometry");
+        return fail(MI_ERR_INVALID, "bad gather geometry");
     mi_gather* g = new (std::nothrow) mi_gather();
     if (!g)
-        return gfail(MI_ERR_NOMEM, "host allocation failed");
+        return fail(MI_ERR_NOMEM, "host allocation failed");
     g->rank = rank, g->world = world, g->gpu = gpu, g->nch = nch, g->max_batches = max_batches;
     g->streams.assign(streams_per_rank, streams_per_rank + world);
     size_t lo = 0;
     for (int r = 0; r < world; ++r) {
         if (streams_per_rank[r] < 0) {
             delete g;
-            return gfail(MI_ERR_INVALID, "negative stream count");
+            return fail(MI_ERR_INVALID, "negative stream count");
         }
         g->row_lo.push_back(lo);
         lo += static_cast<size_t>(streams_per_rank[r]) * nch;
@@ -332,7 +324,7 @@ int mi_gather_create(const mi_gather_id* id, int rank, int world, int gpu, const
     if (e == hipSuccess)
         e = hipEventCreateWithFlags(g->ev_done.put(), hipEventDisableTiming);
     if (e != hipSuccess)
-        return bail(gfail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MI_ERR_NO_DEVICE : MI_ERR_HIP, std::string("mi_gather_create: ") + hipGetErrorString(e)));
+        return bail(fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MI_ERR_NO_DEVICE : MI_ERR_HIP, std::string("mi_gather_create: ") + hipGetErrorString(e)));
     if (world > 1 && std::memcmp(id->internal, kLoopMagic, sizeof(kLoopMagic)) == 0) {
         uint64_t key = 0;
         std::memcpy(&key, id->internal + 8, sizeof(key));
@@ -349,7 +341,7 @@ int mi_gather_create(const mi_gather_id* id, int rank, int world, int gpu, const
     } else if (world > 1) {
         Rccl& r = rccl();
         if (!r.ok)
-            return bail(gfail(MI_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded"));
+            return bail(fail(MI_ERR_UNSUPPORTED, "RCCL (librccl.so.1) could not be loaded"));
         auto t = std::make_unique<RcclTransport>();
         const int rc = r.comm_init_rank(&t->comm, world, *id, rank);
         if (rc != 0)
@@ -363,7 +355,7 @@ int mi_gather_create(const mi_gather_id* id, int rank, int world, int gpu, const
 int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int nbatches, int open_only, float* d_all_waveout, char* d_all_axc,
                     void* hip_stream) {
     if (!g || nbatches < 1 || nbatches > g->max_batches || (g->rows_local && (!d_waveout || !d_axc)) || (g->rank == 0 && (!d_all_waveout || !d_all_axc)))
-        return gfail(MI_ERR_INVALID, "bad argument");
+        return fail(MI_ERR_INVALID, "bad argument");
     G_HIP_TRY(hipSetDevice(g->gpu));
     Transport* const t = g->tr.get();
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
@@ -413,7 +405,7 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
         if (e == hipSuccess)
             e = hipHostMalloc(reinterpret_cast<void**>(flags.put()), max_blocks, hipHostMallocDefault);
         if (e != hipSuccess)
-            return gfail(MI_ERR_NOMEM, std::string("mi_gather_audio: scratch of the open-batches mode: ") + hipGetErrorString(e));
+            return fail(MI_ERR_NOMEM, std::string("mi_gather_audio: scratch of the open-batches mode: ") + hipGetErrorString(e));
         g->d_pack = std::move(pack), g->d_idx = std::move(idx), g->h_flags = std::move(flags);
     }
     auto open_blocks = [&](const char* flags, size_t count, size_t base) {  // indices (relative to `base`) of the blocks that carry a signal
@@ -498,7 +490,7 @@ int mi_gather_audio(mi_gather* g, const float* d_waveout, const char* d_axc, int
 
 int mi_gather_stream_wait(mi_gather* g, void* hip_stream) {
     if (!g)
-        return gfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     G_HIP_TRY(hipSetDevice(g->gpu));
     G_HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), g->ev_done, 0));
     return MI_OK;
@@ -506,7 +498,7 @@ int mi_gather_stream_wait(mi_gather* g, void* hip_stream) {
 
 int mi_gather_sync(mi_gather* g) {
     if (!g)
-        return gfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     G_HIP_TRY(hipSetDevice(g->gpu));
     G_HIP_TRY(hipStreamSynchronize(g->side));
     return MI_OK;

@@ -15,6 +15,7 @@
 #include "hip_own.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "poststage.hpp"
 #include "tuning.hpp"
 
 namespace {
@@ -24,17 +25,14 @@ thread_local std::string g_err;
 }  // namespace
 
 namespace mi {
-std::string& last_error_ref() {  // shared with mixer.hip
+std::string& last_error_ref() {  // declared in poststage.hpp
     return g_err;
 }
 }  // namespace mi
 
 namespace {
 
-int fail(int code, const std::string& what) {
-    g_err = what;
-    return code;
-}
+using mi::fail;
 
 int hip_fail(hipError_t e, const char* where) {
     g_err = std::string(where) + ": " + hipGetErrorString(e);

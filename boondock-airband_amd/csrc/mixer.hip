@@ -10,12 +10,7 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
-#include "hip_own.hpp"
-#include "plan.hpp"
-
-namespace mi {
-std::string& last_error_ref();  // mi_airband.cpp
-}
+#include "poststage.hpp"
 
 struct MixIn {
     int row;
@@ -61,10 +56,8 @@ __global__ __launch_bounds__(256) void k_mix(const MixIn* __restrict__ in, const
         axc_out[batch] = any ? MI_SIGNAL : MI_NO_SIGNAL;
 }
 
-int mfail(int code, const std::string& msg) {
-    mi::last_error_ref() = msg;
-    return code;
-}
+using mi::aligned;
+using mi::fail;
 
 }  // namespace
 
@@ -72,20 +65,17 @@ extern "C" {
 
 int mi_mixer_create(const mi_mix_input* inputs, int ninputs, int gpu, mi_mixer** out) {
     if (!inputs || !out || ninputs < 1)
-        return mfail(MI_ERR_INVALID, "mixer needs at least one input");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return mfail(MI_ERR_NO_DEVICE, "no HIP device: the mixer runs on the GPU only");
-    if (gpu < 0 || gpu >= ndev)
-        return mfail(MI_ERR_INVALID, "gpu index out of range");
+        return fail(MI_ERR_INVALID, "mixer needs at least one input");
+    if (const int rc = mi::check_gpu(gpu, "no HIP device: the mixer runs on the GPU only"))
+        return rc;
     std::vector<MixIn> v(static_cast<size_t>(ninputs));
     int stereo = 0;
     for (int i = 0; i < ninputs; ++i) {
         const mi_mix_input& k = inputs[i];
         if (k.row < 0)
-            return mfail(MI_ERR_INVALID, "mixer input row must be >= 0");
+            return fail(MI_ERR_INVALID, "mixer input row must be >= 0");
         if (!(k.balance >= -1.0f && k.balance <= 1.0f))
-            return mfail(MI_ERR_INVALID, "balance out of allowed range <-1.0;1.0>");  // config.cpp:183-186
+            return fail(MI_ERR_INVALID, "balance out of allowed range <-1.0;1.0>");  // config.cpp:183-186
         const float ampl = fminf(1.0f, 1.0f - k.balance), ampr = fminf(1.0f, 1.0f + k.balance);  // mixer.cpp:80-81
         v[i].row = k.row;
         v[i].ml = k.ampfactor * ampl;
@@ -100,7 +90,7 @@ int mi_mixer_create(const mi_mix_input* inputs, int ninputs, int gpu, mi_mixer**
     if (hipSetDevice(gpu) != hipSuccess || dalloc(m->d_in, v.size()) != hipSuccess ||
         hipMemcpy(m->d_in, v.data(), v.size() * sizeof(MixIn), hipMemcpyHostToDevice) != hipSuccess) {
         delete m;
-        return mfail(MI_ERR_HIP, "mixer: device allocation failed");
+        return fail(MI_ERR_HIP, "mixer: device allocation failed");
     }
     *out = m;
     return MI_OK;
@@ -120,19 +110,18 @@ int mi_mixer_is_stereo(const mi_mixer* m) {
 int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
                             float* d_left, float* d_right, char* d_axc_out, void* hip_stream) {
     if (!m || !d_waveout || !d_axc || !d_left || !d_axc_out || nbatches < 1)
-        return mfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (m->stereo && !d_right)
-        return mfail(MI_ERR_INVALID, "stereo mixer needs a right-channel buffer");
-    if (row_stride % 4 != 0 || reinterpret_cast<uintptr_t>(d_waveout) % 16 != 0 || reinterpret_cast<uintptr_t>(d_left) % 16 != 0 ||
-        (d_right && reinterpret_cast<uintptr_t>(d_right) % 16 != 0))
-        return mfail(MI_ERR_INVALID, "audio buffers must be 16-byte aligned with a row stride that is a multiple of 4 floats");
+        return fail(MI_ERR_INVALID, "stereo mixer needs a right-channel buffer");
+    if (row_stride % 4 != 0 || !aligned(d_waveout, 16) || !aligned(d_left, 16) || (d_right && !aligned(d_right, 16)))
+        return fail(MI_ERR_INVALID, "audio buffers must be 16-byte aligned with a row stride that is a multiple of 4 floats");
     if (hipSetDevice(m->gpu) != hipSuccess)
-        return mfail(MI_ERR_HIP, "hipSetDevice failed");
+        return fail(MI_ERR_HIP, "hipSetDevice failed");
     const size_t total = static_cast<size_t>(nbatches) * (mi::kWaveBatch / 4);
     hipLaunchKernelGGL(k_mix, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), m->d_in.get(), m->n,
                        m->stereo, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_left, d_right, d_axc_out);
     if (hipGetLastError() != hipSuccess)
-        return mfail(MI_ERR_HIP, "mixer kernel launch failed");
+        return fail(MI_ERR_HIP, "mixer kernel launch failed");
     return MI_OK;
 }
 

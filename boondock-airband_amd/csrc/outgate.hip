@@ -5,20 +5,15 @@
 //   continuous outputs  skip nothing                                                       the same lines, continuous == true
 // A post-stage of its own like the mixer (mixer.hip): three small launches on the caller's stream, no atomics -- a block's place is
 // its row's exclusive prefix plus its rank within the row, so the packed order is rows ascending, batches ascending, on every run.
-// Everything moved is a copy: bandwidth-bound, one float4 per lane per access.  mi_gate_plan_host (plan.cpp) is the host twin.
+// Everything moved is a copy: bandwidth-bound, one float4 per lane per access.  mi_gate_plan_host (poststage_host.cpp) is the host twin.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
+#include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/mi_airband.h"
-#include "hip_own.hpp"
-#include "plan.hpp"
-
-namespace mi {
-std::string& last_error_ref();  // mi_airband.cpp
-}
+#include "poststage.hpp"
 
 struct mi_outgate {
     int gpu = 0;
@@ -30,8 +25,7 @@ struct mi_outgate {
     mi::DevBuf<int> d_rank;                           // [rows][nbatches of the call]: place within the row, -1 = does not travel
     mi::DevBuf<uint32_t> d_row_count;                 // [rows]
     mi::PinnedBuf<uint32_t> h_count;                  // [2], landing place of the counts in mi_outgate_download
-    bool timing = false;  // mi_outgate_set_timing: events around each of the three launches
-    mi::Event ev[4];
+    mi::LaunchTiming timing{"output gate", 3};        // mi_outgate_set_timing
     // destinations of the last mi_outgate_process_device (what mi_outgate_download reads)
     const float* last_blocks = nullptr;
     const float* last_iq_blocks = nullptr;
@@ -42,8 +36,9 @@ struct mi_outgate {
 
 namespace {
 
-constexpr int kRowsPerGroup = 4;  // one wave per row, four rows per 256-thread workgroup
-constexpr int kScanTile = 256;
+using mi::aligned;
+using mi::fail;
+using mi::kRowsPerGroup;
 
 // Launch 1.  Lane l of the row's wave takes batch b0 + l of a 64-batch chunk; the predecessor's flag comes from the lane below,
 // lane 0 takes the carried flag (first chunk) or the last lane of the chunk before.
@@ -79,41 +74,7 @@ __global__ __launch_bounds__(256) void k_gate_rank(const uint8_t* __restrict__ r
     }
 }
 
-// Launch 2.  Exclusive scan of the row counts, one workgroup walking tiles of 256 rows, and the two counts.
-__global__ __launch_bounds__(kScanTile) void k_gate_scan(const uint32_t* __restrict__ row_count, const int rows, const uint32_t max_blocks,
-                                                         uint32_t* __restrict__ row_first, uint32_t* __restrict__ count) {
-    __shared__ uint32_t wave_sum[kScanTile / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t running = 0;
-    for (int r0 = 0; r0 < rows; r0 += kScanTile) {
-        const int r = r0 + t;
-        const uint32_t c = r < rows ? row_count[r] : 0u;
-        uint32_t incl = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d)
-                incl += up;
-        }
-        if (lane == 63)
-            wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, tile = 0;
-        for (int w = 0; w < kScanTile / 64; ++w) {
-            const uint32_t s = wave_sum[w];
-            before += w < wave ? s : 0u;
-            tile += s;
-        }
-        if (r < rows)
-            row_first[r] = running + before + incl - c;
-        running += tile;
-        __syncthreads();  // wave_sum is rewritten by the next tile
-    }
-    if (t == 0) {
-        row_first[rows] = running;
-        count[0] = running;
-        count[1] = running < max_blocks ? running : max_blocks;
-    }
-}
+// Launch 2.  mi::launch_row_scan (poststage.hip): exclusive scan of the row counts into row_first, and the two counts.
 
 // Launch 3.  One workgroup per (row, batch) on a 1-D grid; a block that does not travel, or whose place is beyond the capacity,
 // returns at once.  500 float4 of audio, 1000 of raw I/Q where the row has them (k_move_blocks of gather.hip).
@@ -142,20 +103,11 @@ __global__ __launch_bounds__(256) void k_gate_copy(const int* __restrict__ rank,
         *reinterpret_cast<uint2*>(index + k) = make_uint2(row, b);
 }
 
-int ofail(int code, const std::string& msg) {
-    mi::last_error_ref() = msg;
-    return code;
-}
-
 bool rules_valid(const uint8_t* row_rule, int rows) {
     for (int r = 0; r < rows; ++r)
         if (row_rule[r] > MI_GATE_ALL)
             return false;
     return true;
-}
-
-bool aligned(const void* p, uintptr_t a) {
-    return reinterpret_cast<uintptr_t>(p) % a == 0;
 }
 
 }  // namespace
@@ -164,30 +116,22 @@ extern "C" {
 
 int mi_outgate_create(const uint8_t* row_rule, const uint8_t* row_has_iq, int rows, int max_batches, size_t max_blocks, int gpu, mi_outgate** out) {
     if (!row_rule || !out)
-        return ofail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return ofail(MI_ERR_INVALID, "output gate needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+        return fail(MI_ERR_INVALID, "output gate needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
     const size_t all = static_cast<size_t>(rows) * static_cast<size_t>(max_batches);
     if (!rules_valid(row_rule, rows))
-        return ofail(MI_ERR_INVALID, "gate rule out of range 0..3");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return ofail(MI_ERR_NO_DEVICE, "no HIP device: the output gate runs on the GPU only");
-    if (gpu < 0 || gpu >= ndev)
-        return ofail(MI_ERR_INVALID, "gpu index out of range");
-    std::vector<uint8_t> iq(static_cast<size_t>(rows), 0);
-    bool any_iq = false;
-    for (int r = 0; row_has_iq && r < rows; ++r) {
-        iq[static_cast<size_t>(r)] = row_has_iq[r] ? 1 : 0;
-        any_iq = any_iq || row_has_iq[r];
-    }
+        return fail(MI_ERR_INVALID, "gate rule out of range 0..3");
+    if (const int rc = mi::check_gpu(gpu, "no HIP device: the output gate runs on the GPU only"))
+        return rc;
+    const size_t n = static_cast<size_t>(rows);
+    const std::vector<uint8_t> iq = row_has_iq ? mi::as_flags(row_has_iq, n) : std::vector<uint8_t>(n, 0);
     mi_outgate* g = new mi_outgate();
     g->gpu = gpu;
     g->rows = rows;
     g->max_batches = max_batches;
     g->max_blocks = static_cast<uint32_t>(max_blocks && max_blocks < all ? max_blocks : all);  // (no call has more blocks than `all`)
-    g->any_iq = any_iq;
-    const size_t n = static_cast<size_t>(rows);
+    g->any_iq = std::find(iq.begin(), iq.end(), 1) != iq.end();
     if (hipSetDevice(gpu) != hipSuccess || dalloc(g->d_rule, n) != hipSuccess || dalloc(g->d_has_iq, n) != hipSuccess ||
         dalloc(g->d_carried, n) != hipSuccess || dalloc(g->d_rank, all) != hipSuccess || dalloc(g->d_row_count, n) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(g->h_count.put()), 2 * sizeof(uint32_t)) != hipSuccess ||
@@ -195,7 +139,7 @@ int mi_outgate_create(const uint8_t* row_rule, const uint8_t* row_has_iq, int ro
         hipMemcpy(g->d_has_iq, iq.data(), n, hipMemcpyHostToDevice) != hipSuccess || hipMemset(g->d_carried, 0, n) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         delete g;
-        return ofail(MI_ERR_HIP, "output gate: device allocation failed");
+        return fail(MI_ERR_HIP, "output gate: device allocation failed");
     }
     *out = g;
     return MI_OK;
@@ -210,13 +154,12 @@ void mi_outgate_destroy(mi_outgate* g) {
 
 int mi_outgate_set_rules(mi_outgate* g, const uint8_t* row_rule) {
     if (!g || !row_rule)
-        return ofail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (!rules_valid(row_rule, g->rows))
-        return ofail(MI_ERR_INVALID, "gate rule out of range 0..3");
+        return fail(MI_ERR_INVALID, "gate rule out of range 0..3");
     // (a call still queued reads the rules it was made with)
-    if (hipSetDevice(g->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(g->d_rule, row_rule, static_cast<size_t>(g->rows), hipMemcpyHostToDevice) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: uploading the rules failed");
+    if (!mi::sync_copy(g->gpu, g->d_rule, row_rule, static_cast<size_t>(g->rows), hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, "output gate: uploading the rules failed");
     return MI_OK;
 }
 
@@ -224,38 +167,34 @@ int mi_outgate_process_device(mi_outgate* g, const float* d_waveout, size_t row_
                               size_t axc_stride, int nbatches, float* d_blocks, float* d_iq_blocks, mi_gate_block* d_index, uint32_t* d_row_first,
                               uint32_t* d_count, void* hip_stream) {
     if (!g || !d_waveout || !d_axc || !d_blocks || !d_index || !d_row_first || !d_count)
-        return ofail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (nbatches < 1 || nbatches > g->max_batches)
-        return ofail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
+        return fail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
     const size_t n = static_cast<size_t>(nbatches) * mi::kWaveBatch;
     if (row_stride < n || axc_stride < static_cast<size_t>(nbatches) || (d_iq_out && iq_row_stride < 2 * n))
-        return ofail(MI_ERR_INVALID, "a row stride is shorter than the call");
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
     if (d_iq_out && g->any_iq && !d_iq_blocks)
-        return ofail(MI_ERR_INVALID, "rows with raw I/Q need a d_iq_blocks buffer");
+        return fail(MI_ERR_INVALID, "rows with raw I/Q need a d_iq_blocks buffer");
     if (row_stride % 4 != 0 || !aligned(d_waveout, 16) || !aligned(d_blocks, 16) ||
         (d_iq_out && (iq_row_stride % 4 != 0 || !aligned(d_iq_out, 16) || !aligned(d_iq_blocks, 16))) || !aligned(d_index, 8) ||
         !aligned(d_row_first, 4) || !aligned(d_count, 4))
-        return ofail(MI_ERR_INVALID, "audio and I/Q buffers must be 16-byte aligned with row strides that are multiples of 4 floats; index 8-byte aligned");
+        return fail(MI_ERR_INVALID, "audio and I/Q buffers must be 16-byte aligned with row strides that are multiples of 4 floats; index 8-byte aligned");
     if (hipSetDevice(g->gpu) != hipSuccess)
-        return ofail(MI_ERR_HIP, "hipSetDevice failed");
+        return fail(MI_ERR_HIP, "hipSetDevice failed");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
-    auto stamp = [&](int i) {
-        if (g->timing)
-            (void)hipEventRecord(g->ev[i], q);
-    };
-    stamp(0);
+    g->timing.stamp(0, q);
     const unsigned groups = static_cast<unsigned>((g->rows + kRowsPerGroup - 1) / kRowsPerGroup);
     hipLaunchKernelGGL(k_gate_rank, dim3(groups), dim3(256), 0, q, g->d_rule.get(), g->d_carried.get(), d_axc, axc_stride, g->rows, nbatches, g->d_rank.get(),
                        g->d_row_count.get());
-    stamp(1);
-    hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(kScanTile), 0, q, g->d_row_count.get(), g->rows, g->max_blocks, d_row_first, d_count);
-    stamp(2);
+    g->timing.stamp(1, q);
+    mi::launch_row_scan(q, g->d_row_count, g->rows, g->max_blocks, d_row_first, d_count);
+    g->timing.stamp(2, q);
     const float* iq = g->any_iq ? d_iq_out : nullptr;
     hipLaunchKernelGGL(k_gate_copy, dim3(static_cast<unsigned>(g->rows) * static_cast<unsigned>(nbatches)), dim3(256), 0, q, g->d_rank.get(), d_row_first,
                        g->d_has_iq.get(), d_waveout, row_stride, iq, iq_row_stride, nbatches, g->max_blocks, d_blocks, d_iq_blocks, d_index);
-    stamp(3);
+    g->timing.stamp(3, q);
     if (hipGetLastError() != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate kernel launch failed");
+        return fail(MI_ERR_HIP, "output gate kernel launch failed");
     g->last_blocks = d_blocks;
     g->last_iq_blocks = iq ? d_iq_blocks : nullptr;
     g->last_index = d_index;
@@ -266,17 +205,14 @@ int mi_outgate_process_device(mi_outgate* g, const float* d_waveout, size_t row_
 
 int mi_outgate_download(mi_outgate* g, void* hip_stream, float* blocks, float* iq_blocks, mi_gate_block* index, uint32_t* row_first, uint32_t* count) {
     if (!g || !count)
-        return ofail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (!g->last_count)
-        return ofail(MI_ERR_INVALID, "no mi_outgate_process_device call to download");
+        return fail(MI_ERR_INVALID, "no mi_outgate_process_device call to download");
     if (iq_blocks && !g->last_iq_blocks)
-        return ofail(MI_ERR_INVALID, "the last call packed no raw I/Q");
+        return fail(MI_ERR_INVALID, "the last call packed no raw I/Q");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
-    if (hipSetDevice(g->gpu) != hipSuccess || hipMemcpyAsync(g->h_count, g->last_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, q) != hipSuccess ||
-        hipStreamSynchronize(q) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: reading the counts failed");
-    count[0] = g->h_count.get()[0];
-    count[1] = g->h_count.get()[1];
+    if (!mi::land_counts(g->gpu, q, g->h_count, g->last_count, count))
+        return fail(MI_ERR_HIP, "output gate: reading the counts failed");
     const size_t k = count[1];
     bool ok = true;
     if (blocks && k)
@@ -288,35 +224,22 @@ int mi_outgate_download(mi_outgate* g, void* hip_stream, float* blocks, float* i
     if (row_first)
         ok = ok && hipMemcpyAsync(row_first, g->last_row_first, (static_cast<size_t>(g->rows) + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, q) == hipSuccess;
     if (!ok || hipStreamSynchronize(q) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: download failed");
+        return fail(MI_ERR_HIP, "output gate: download failed");
     return MI_OK;
 }
 
 int mi_outgate_set_timing(mi_outgate* g, int on) {
     if (!g)
-        return ofail(MI_ERR_INVALID, "NULL argument");
-    if (on && !g->ev[0]) {
-        if (hipSetDevice(g->gpu) != hipSuccess)
-            return ofail(MI_ERR_HIP, "hipSetDevice failed");
-        for (mi::Event& e : g->ev)
-            if (hipEventCreate(e.put()) != hipSuccess)
-                return ofail(MI_ERR_HIP, "output gate: hipEventCreate failed");
-    }
-    g->timing = on != 0;
-    return MI_OK;
+        return fail(MI_ERR_INVALID, "NULL argument");
+    return g->timing.enable(g->gpu, on != 0);
 }
 
 int mi_outgate_last_launch_ms(mi_outgate* g, float* ms) {
     if (!g || !ms)
-        return ofail(MI_ERR_INVALID, "NULL argument");
-    if (!g->timing || !g->last_count)
-        return ofail(MI_ERR_INVALID, "no timed mi_outgate_process_device call");
-    if (hipSetDevice(g->gpu) != hipSuccess || hipEventSynchronize(g->ev[3]) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: waiting for the timing events failed");
-    for (int i = 0; i < 3; ++i)
-        if (hipEventElapsedTime(ms + i, g->ev[i], g->ev[i + 1]) != hipSuccess)
-            return ofail(MI_ERR_HIP, "output gate: hipEventElapsedTime failed");
-    return MI_OK;
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!g->timing.on || !g->last_count)
+        return fail(MI_ERR_INVALID, "no timed mi_outgate_process_device call");
+    return g->timing.elapsed(g->gpu, ms);
 }
 
 size_t mi_outgate_state_size(const mi_outgate* g) {
@@ -325,22 +248,17 @@ size_t mi_outgate_state_size(const mi_outgate* g) {
 
 int mi_outgate_get_state(mi_outgate* g, void* buf, size_t len) {
     if (!g || !buf || len != static_cast<size_t>(g->rows))
-        return ofail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
-    if (hipSetDevice(g->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(buf, g->d_carried, len, hipMemcpyDeviceToHost) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: reading the state failed");
+        return fail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
+    if (!mi::sync_copy(g->gpu, buf, g->d_carried, len, hipMemcpyDeviceToHost))
+        return fail(MI_ERR_HIP, "output gate: reading the state failed");
     return MI_OK;
 }
 
 int mi_outgate_set_state(mi_outgate* g, const void* buf, size_t len) {
     if (!g || !buf || len != static_cast<size_t>(g->rows))
-        return ofail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
-    std::vector<uint8_t> flags(len);
-    for (size_t i = 0; i < len; ++i)
-        flags[i] = static_cast<const uint8_t*>(buf)[i] ? 1 : 0;
-    if (hipSetDevice(g->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(g->d_carried, flags.data(), len, hipMemcpyHostToDevice) != hipSuccess)
-        return ofail(MI_ERR_HIP, "output gate: writing the state failed");
+        return fail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
+    if (!mi::sync_copy(g->gpu, g->d_carried, mi::as_flags(buf, len).data(), len, hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, "output gate: writing the state failed");
     return MI_OK;
 }
 

@@ -431,160 +431,3 @@ RowClasses classify_rows(const Plan& p, int nstreams, int nch) {
 }
 
 }  // namespace mi
-
-// ---- output gate, host side (include/mi_airband.h "output gate"): the index mi_outgate_process_device computes, from flags the
-// caller already has.  One pass per row in batch order with the row's carried flag as output_t::active (output.cpp:518-520, 560,
-// 568-570); outgate.hip holds the device twin.
-namespace mi {
-std::string& last_error_ref();  // mi_airband.cpp
-}
-
-extern "C" int mi_gate_plan_host(const uint8_t* row_rule, int rows, const char* axc, size_t axc_stride, int nbatches, uint8_t* carried_inout,
-                                 mi_gate_block* index, uint32_t* row_first, uint32_t* count) {
-    auto fail = [](const char* msg) {
-        mi::last_error_ref() = msg;
-        return static_cast<int>(MI_ERR_INVALID);
-    };
-    if (!row_rule || !axc || !carried_inout || !index || !row_first || !count)
-        return fail("NULL argument");
-    if (rows < 1 || nbatches < 1 || axc_stride < static_cast<size_t>(nbatches))
-        return fail("gate plan needs rows >= 1 and 1 <= nbatches <= axc_stride");
-    if (static_cast<uint64_t>(rows) * static_cast<uint64_t>(nbatches) > UINT32_MAX)
-        return fail("gate plan: rows * nbatches does not fit the 32-bit block index");
-    for (int r = 0; r < rows; ++r)
-        if (row_rule[r] > MI_GATE_ALL)
-            return fail("gate rule out of range 0..3");
-    uint32_t k = 0;
-    for (int r = 0; r < rows; ++r) {
-        row_first[r] = k;
-        const uint8_t rule = row_rule[r];
-        if (rule == MI_GATE_NONE)
-            continue;
-        bool active = carried_inout[r] != 0;
-        for (int b = 0; b < nbatches; ++b) {
-            const bool signal = axc[static_cast<size_t>(r) * axc_stride + b] != MI_NO_SIGNAL;
-            if (rule == MI_GATE_ALL || signal || (rule == MI_GATE_OPEN_TRAIL && active)) {
-                index[k].row = static_cast<uint32_t>(r);
-                index[k].batch = static_cast<uint32_t>(b);
-                ++k;
-            }
-            active = signal;
-        }
-        carried_inout[r] = active ? 1 : 0;
-    }
-    row_first[rows] = k;
-    count[0] = count[1] = k;
-    return MI_OK;
-}
-
-// ---- transmission splitter, host side (include/mi_airband.h "transmission splitter"): close_if_necessary's rule in signal time,
-// one row and one batch at a time, and a block's energy in the order the header defines; txsplit.hip holds the device twin.
-namespace {
-
-// sum of x * x over one block: 256 partial sums, each over float4 number t and (t < 244) number 256 + t, then the halving tree
-double tx_block_energy(const float* x, float* peak) {
-    double acc[256];
-    float p = 0.0f;
-    for (int t = 0; t < 256; ++t) {
-        double a = 0.0;
-        for (int f = t; f < mi::kWaveBatch / 4; f += 256)
-            for (int e = 0; e < 4; ++e) {
-                const float v = x[4 * f + e];
-                a += static_cast<double>(v) * static_cast<double>(v);
-                p = std::fabs(v) > p ? std::fabs(v) : p;
-            }
-        acc[t] = a;
-    }
-    for (int d = 128; d >= 1; d >>= 1)
-        for (int t = 0; t < d; ++t)
-            acc[t] += acc[t + d];
-    *peak = p;
-    return acc[0];
-}
-
-}  // namespace
-
-extern "C" int mi_tx_plan_host(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, const char* axc, size_t axc_stride, int nbatches,
-                               const float* waveout, size_t row_stride, void* state_inout, mi_tx_record* records, size_t max_records,
-                               uint32_t* row_first_record, uint32_t* count) {
-    auto fail = [](const char* msg) {
-        mi::last_error_ref() = msg;
-        return static_cast<int>(MI_ERR_INVALID);
-    };
-    if (!row_enabled || !axc || !state_inout || !records || !row_first_record || !count)
-        return fail("NULL argument");
-    if (rows < 1 || nbatches < 1 || axc_stride < static_cast<size_t>(nbatches) || max_records < 1)
-        return fail("tx plan needs rows >= 1, 1 <= nbatches <= axc_stride and max_records >= 1");
-    if (waveout && row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
-        return fail("a row stride is shorter than the call");
-    if (static_cast<uint64_t>(rows) * (static_cast<uint64_t>(nbatches) + 1) > UINT32_MAX)
-        return fail("tx plan: rows * (nbatches + 1) does not fit the 32-bit record count");
-    const mi_tx_cfg c = mi::tx_cfg_or_default(cfg);
-    mi::TxRowState* state = static_cast<mi::TxRowState*>(state_inout);
-    for (int r = 0; r < rows; ++r)
-        if (state[r].open > 1 || state[r].active > 1 || state[r].zero != 0)
-            return fail("tx plan: malformed state blob");
-    constexpr uint32_t kNone = 0xFFFFFFFFu;
-    uint32_t k = 0;
-    for (int r = 0; r < rows; ++r) {
-        row_first_record[r] = k;
-        if (!row_enabled[r])
-            continue;
-        mi::TxRowState s = state[r];
-        mi_tx_record cur{};
-        bool have = false;       // `cur` describes the open file's part in this call
-        uint32_t travelled = 0;  // the row's travelling blocks so far
-        auto begin = [&](uint32_t flags) {
-            cur = mi_tx_record{static_cast<uint32_t>(r), s.seq, travelled, 0, kNone, kNone, flags, 0.0f, 0.0};
-            have = true;
-        };
-        auto flush = [&] {
-            if (k < max_records)
-                records[k] = cur;
-            ++k;
-            have = false;
-        };
-        for (int b = 0; b < nbatches; ++b) {
-            const bool signal = axc[static_cast<size_t>(r) * axc_stride + b] != MI_NO_SIGNAL;
-            if (s.open) {  // close_if_necessary, output.cpp:367-375
-                const uint64_t d = s.clock - s.opened, i = s.clock - s.last_write;
-                if (d > c.max_batches || (d > c.min_batches && i > c.idle_batches)) {
-                    s.open = 0;
-                    if (!have)
-                        begin(1);
-                    cur.close_batch = static_cast<uint32_t>(b);
-                    flush();
-                }
-            }
-            if (signal || s.active) {  // output.cpp:518-520
-                if (!s.open) {         // output_file_ready, :404-414, :454
-                    s.seq += 1;
-                    s.open = 1;
-                    s.opened = s.last_write = s.clock;
-                    begin(0);
-                } else if (!have) {
-                    begin(1);
-                }
-                if (cur.nblocks == 0)
-                    cur.first_batch = static_cast<uint32_t>(b);
-                cur.nblocks += 1;
-                travelled += 1;
-                if (waveout) {
-                    float p;
-                    cur.energy += tx_block_energy(waveout + static_cast<size_t>(r) * row_stride + static_cast<size_t>(b) * mi::kWaveBatch, &p);
-                    cur.peak = p > cur.peak ? p : cur.peak;
-                }
-                s.active = signal ? 1 : 0;  // :560
-                s.last_write = s.clock;     // :561
-            }
-            s.clock += 1;
-        }
-        if (have)
-            flush();
-        state[r] = s;
-    }
-    row_first_record[rows] = k;
-    count[0] = k;
-    count[1] = k < max_records ? k : static_cast<uint32_t>(max_records);
-    return MI_OK;
-}

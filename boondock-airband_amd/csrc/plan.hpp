@@ -16,33 +16,6 @@ constexpr int kAgcExtra = MI_AGC_EXTRA;
 constexpr int kMaxTones = 52;
 constexpr int kSquelchRing = 102;  // Squelch::buffer_size_, squelch.cpp:67
 
-// One row of the transmission splitter's state (include/mi_airband.h "transmission splitter"): the checkpoint blob is an array of
-// these, and txsplit.hip keeps the same array in device memory.
-struct TxRowState {
-    uint64_t clock;       // batches this row has handled
-    uint64_t opened;      // value of clock when the open file was opened
-    uint64_t last_write;  // value of clock at the last write
-    uint32_t seq;         // running file number, 0 before the first file
-    uint8_t open;         // fdata->f != NULL
-    uint8_t active;       // output_t::active
-    uint16_t zero;
-};
-static_assert(sizeof(TxRowState) == MI_TX_STATE_ROW_BYTES && sizeof(mi_tx_record) == 40, "the splitter's blob and record layouts are ABI");
-
-// close_if_necessary's three constants (output.cpp:356-358) in batches: d * WAVE_BATCH > seconds * WAVE_RATE
-constexpr uint32_t kTxMinBatches = 1 * kWaveRate / kWaveBatch;      // 8
-constexpr uint32_t kTxIdleBatches = kWaveRate / 2 / kWaveBatch;     // 4
-constexpr uint32_t kTxMaxBatches = 3600 * kWaveRate / kWaveBatch;   // 28800
-static_assert(1 * kWaveRate % kWaveBatch == 0 && kWaveRate / 2 % kWaveBatch == 0, "the thresholds are whole batches");
-
-inline mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg) {
-    mi_tx_cfg c = cfg ? *cfg : mi_tx_cfg{0, 0, 0};
-    c.min_batches = c.min_batches ? c.min_batches : kTxMinBatches;
-    c.idle_batches = c.idle_batches ? c.idle_batches : kTxIdleBatches;
-    c.max_batches = c.max_batches ? c.max_batches : kTxMaxBatches;
-    return c;
-}
-
 // Per-channel constants, identical for every stream of a handle.  Plain 4-byte fields: the struct is
 // copied verbatim into device memory.
 struct ChanParams {

@@ -1,0 +1,112 @@
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip) and the host twins (poststage_host.cpp)
+// share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "hip_own.hpp"
+#include "plan.hpp"
+
+namespace mi {
+
+std::string& last_error_ref();  // mi_airband.cpp
+
+inline int fail(int code, const std::string& msg) {
+    last_error_ref() = msg;
+    return code;
+}
+
+inline bool aligned(const void* p, uintptr_t a) {
+    return reinterpret_cast<uintptr_t>(p) % a == 0;
+}
+
+// truth values as 0 / 1 bytes
+inline std::vector<uint8_t> as_flags(const void* v, size_t n) {
+    std::vector<uint8_t> f(n);
+    for (size_t i = 0; i < n; ++i)
+        f[i] = static_cast<const uint8_t*>(v)[i] ? 1 : 0;
+    return f;
+}
+
+// MI_OK, or the refusal of a create call on a machine without a device (in the stage's own words) or with fewer than gpu + 1
+inline int check_gpu(int gpu, const char* no_device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(MI_ERR_NO_DEVICE, no_device);
+    if (gpu < 0 || gpu >= ndev)
+        return fail(MI_ERR_INVALID, "gpu index out of range");
+    return MI_OK;
+}
+
+// Events around each launch of a call: event i before launch i, the last one after the last launch.
+struct LaunchTiming {
+    const char* stage;  // leads the error texts
+    int launches;
+    bool on = false;
+    Event ev[5];
+    LaunchTiming(const char* stage_, int launches_) : stage(stage_), launches(launches_) {}
+    void stamp(int i, hipStream_t q) {
+        if (on)
+            (void)hipEventRecord(ev[i], q);
+    }
+    int enable(int gpu, bool want) {
+        if (want && !ev[0]) {
+            if (hipSetDevice(gpu) != hipSuccess)
+                return fail(MI_ERR_HIP, "hipSetDevice failed");
+            for (int i = 0; i <= launches; ++i)
+                if (hipEventCreate(ev[i].put()) != hipSuccess)
+                    return fail(MI_ERR_HIP, std::string(stage) + ": hipEventCreate failed");
+        }
+        on = want;
+        return MI_OK;
+    }
+    int elapsed(int gpu, float* ms) {  // ms[launches] of the last stamped call
+        if (hipSetDevice(gpu) != hipSuccess || hipEventSynchronize(ev[launches]) != hipSuccess)
+            return fail(MI_ERR_HIP, std::string(stage) + ": waiting for the timing events failed");
+        for (int i = 0; i < launches; ++i)
+            if (hipEventElapsedTime(ms + i, ev[i], ev[i + 1]) != hipSuccess)
+                return fail(MI_ERR_HIP, std::string(stage) + ": hipEventElapsedTime failed");
+        return MI_OK;
+    }
+};
+
+// The two counts of the last call, landed through pinned memory on the caller's stream: what a download starts with.
+inline bool land_counts(int gpu, hipStream_t q, uint32_t* h_count, const uint32_t* d_count, uint32_t* count) {
+    if (hipSetDevice(gpu) != hipSuccess || hipMemcpyAsync(h_count, d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, q) != hipSuccess ||
+        hipStreamSynchronize(q) != hipSuccess)
+        return false;
+    count[0] = h_count[0];
+    count[1] = h_count[1];
+    return true;
+}
+
+// State and settings in or out between calls: whatever is queued on the device finishes first.
+inline bool sync_copy(int gpu, void* dst, const void* src, size_t len, hipMemcpyKind kind) {
+    return hipSetDevice(gpu) == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(dst, src, len, kind) == hipSuccess;
+}
+
+constexpr int kRowsPerGroup = 4;  // one wave per row, four rows per 256-thread workgroup
+constexpr int kScanTile = 256;
+
+// k_row_scan (poststage.hip), one workgroup: row_first[0 .. rows] = exclusive scan of row_count[0 .. rows - 1], count[0] = the total,
+// count[1] = min(total, cap)
+void launch_row_scan(hipStream_t stream, const uint32_t* row_count, int rows, uint32_t cap, uint32_t* row_first, uint32_t* count);
+
+// One row of the transmission splitter's state (include/mi_airband.h "transmission splitter"): the checkpoint blob is an array of
+// these, and txsplit.hip keeps the same array in device memory.
+struct TxRowState {
+    uint64_t clock;       // batches this row has handled
+    uint64_t opened;      // value of clock when the open file was opened
+    uint64_t last_write;  // value of clock at the last write
+    uint32_t seq;         // running file number, 0 before the first file
+    uint8_t open;         // fdata->f != NULL
+    uint8_t active;       // output_t::active
+    uint16_t zero;
+};
+static_assert(sizeof(TxRowState) == MI_TX_STATE_ROW_BYTES && sizeof(mi_tx_record) == 40, "the splitter's blob and record layouts are ABI");
+
+mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg);  // poststage_host.cpp
+
+}  // namespace mi

@@ -6,7 +6,7 @@
 // restated on the jitter-free schedule (batch b of a row at t0 + b * WAVE_BATCH / WAVE_RATE), so every time is a count of batches:
 // the rule, the thresholds, the record, the order of `energy` and the state blob are in include/mi_airband.h.  A post-stage of its
 // own like the gate (outgate.hip), whose MI_GATE_OPEN_TRAIL rule lets the same blocks travel: four small launches on the caller's
-// stream, no atomics.  mi_tx_plan_host (plan.cpp) is the host twin.
+// stream, no atomics.  mi_tx_plan_host (poststage_host.cpp) is the host twin.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -14,12 +14,7 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
-#include "hip_own.hpp"
-#include "plan.hpp"
-
-namespace mi {
-std::string& last_error_ref();  // mi_airband.cpp
-}
+#include "poststage.hpp"
 
 struct mi_txsplit {
     int gpu = 0;
@@ -35,8 +30,7 @@ struct mi_txsplit {
     mi::DevBuf<double> d_block_sum;        // [rows][nbatches]: sum of x * x of the row's travelling block number `rank`
     mi::DevBuf<float> d_block_peak;        // the same for max |x|
     mi::PinnedBuf<uint32_t> h_count;       // [2], landing place of the counts in mi_txsplit_download
-    bool timing = false;                   // mi_txsplit_set_timing: events around each of the four launches
-    mi::Event ev[5];
+    mi::LaunchTiming timing{"transmission splitter", 4};  // mi_txsplit_set_timing
     // destinations of the last mi_txsplit_process_device (what mi_txsplit_download reads)
     const mi_tx_record* last_records = nullptr;
     const uint32_t* last_row_first = nullptr;
@@ -45,8 +39,10 @@ struct mi_txsplit {
 
 namespace {
 
-constexpr int kRowsPerGroup = 4;  // one wave per row, four rows per 256-thread workgroup
-constexpr int kScanTile = 256;
+using mi::aligned;
+using mi::as_flags;
+using mi::fail;
+using mi::kRowsPerGroup;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 __device__ inline uint32_t uniform(uint32_t v) {
@@ -166,41 +162,7 @@ __global__ __launch_bounds__(256) void k_tx_walk(const uint8_t* __restrict__ ena
     }
 }
 
-// Launch 2.  Exclusive scan of the rows' record counts, one workgroup walking tiles of 256 rows, and the two counts (k_gate_scan).
-__global__ __launch_bounds__(kScanTile) void k_tx_scan(const uint32_t* __restrict__ row_count, const int rows, const uint32_t max_records,
-                                                       uint32_t* __restrict__ row_first, uint32_t* __restrict__ count) {
-    __shared__ uint32_t wave_sum[kScanTile / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t running = 0;
-    for (int r0 = 0; r0 < rows; r0 += kScanTile) {
-        const int r = r0 + t;
-        const uint32_t c = r < rows ? row_count[r] : 0u;
-        uint32_t incl = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d)
-                incl += up;
-        }
-        if (lane == 63)
-            wave_sum[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, tile = 0;
-        for (int w = 0; w < kScanTile / 64; ++w) {
-            const uint32_t s = wave_sum[w];
-            before += w < wave ? s : 0u;
-            tile += s;
-        }
-        if (r < rows)
-            row_first[r] = running + before + incl - c;
-        running += tile;
-        __syncthreads();  // wave_sum is rewritten by the next tile
-    }
-    if (t == 0) {
-        row_first[rows] = running;
-        count[0] = running;
-        count[1] = running < max_records ? running : max_records;
-    }
-}
+// Launch 2.  mi::launch_row_scan (poststage.hip): exclusive scan of the rows' record counts, and the two counts.
 
 // Launch 3.  One workgroup per (row, batch) on a 1-D grid; a block that does not travel returns at once.  Thread t squares float4
 // number t and (t < 244) number 256 + t in double, which is exact, and adds the eight in sequence; the 256 sums are halved through
@@ -287,37 +249,18 @@ __global__ __launch_bounds__(256) void k_tx_combine(const mi_tx_record* __restri
     dst[4] = make_uint2(static_cast<uint32_t>(e), static_cast<uint32_t>(e >> 32));
 }
 
-int tfail(int code, const std::string& msg) {
-    mi::last_error_ref() = msg;
-    return code;
-}
-
-bool aligned(const void* p, uintptr_t a) {
-    return reinterpret_cast<uintptr_t>(p) % a == 0;
-}
-
-std::vector<uint8_t> as_flags(const uint8_t* v, int n) {
-    std::vector<uint8_t> f(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i)
-        f[static_cast<size_t>(i)] = v[i] ? 1 : 0;
-    return f;
-}
-
 }  // namespace
 
 extern "C" {
 
 int mi_txsplit_create(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_records, int gpu, mi_txsplit** out) {
     if (!row_enabled || !out)
-        return tfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (rows < 1 || rows >= (1 << 20) || max_batches < 1 ||
         static_cast<uint64_t>(rows) * (static_cast<uint64_t>(max_batches) + 1) >= (1ull << 24))
-        return tfail(MI_ERR_INVALID, "transmission splitter needs 1 <= rows < 2^20, max_batches >= 1 and rows * (max_batches + 1) < 2^24");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return tfail(MI_ERR_NO_DEVICE, "no HIP device: the transmission splitter runs on the GPU only");
-    if (gpu < 0 || gpu >= ndev)
-        return tfail(MI_ERR_INVALID, "gpu index out of range");
+        return fail(MI_ERR_INVALID, "transmission splitter needs 1 <= rows < 2^20, max_batches >= 1 and rows * (max_batches + 1) < 2^24");
+    if (const int rc = mi::check_gpu(gpu, "no HIP device: the transmission splitter runs on the GPU only"))
+        return rc;
     mi_txsplit* t = new mi_txsplit();
     t->gpu = gpu;
     t->rows = rows;
@@ -325,12 +268,12 @@ int mi_txsplit_create(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows
     t->cfg = mi::tx_cfg_or_default(cfg);
     const size_t n = static_cast<size_t>(rows), all = n * static_cast<size_t>(max_batches), slots = n * (static_cast<size_t>(max_batches) + 1);
     t->max_records = static_cast<uint32_t>(max_records && max_records < slots ? max_records : slots);  // (no call has more records than `slots`)
-    if (hipSetDevice(gpu) != hipSuccess || dalloc_copy(t->d_enabled, as_flags(row_enabled, rows)) != hipSuccess ||
+    if (hipSetDevice(gpu) != hipSuccess || dalloc_copy(t->d_enabled, as_flags(row_enabled, static_cast<size_t>(rows))) != hipSuccess ||
         dalloc_zero(t->d_state, n) != hipSuccess || dalloc(t->d_rank, all) != hipSuccess || dalloc(t->d_row_rec, slots) != hipSuccess ||
         dalloc(t->d_row_rec_count, n) != hipSuccess || dalloc(t->d_block_sum, all) != hipSuccess || dalloc(t->d_block_peak, all) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(t->h_count.put()), 2 * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         delete t;
-        return tfail(MI_ERR_HIP, "transmission splitter: device allocation failed");
+        return fail(MI_ERR_HIP, "transmission splitter: device allocation failed");
     }
     *out = t;
     return MI_OK;
@@ -345,50 +288,45 @@ void mi_txsplit_destroy(mi_txsplit* t) {
 
 int mi_txsplit_set_rows(mi_txsplit* t, const uint8_t* row_enabled) {
     if (!t || !row_enabled)
-        return tfail(MI_ERR_INVALID, "NULL argument");
-    const std::vector<uint8_t> flags = as_flags(row_enabled, t->rows);
+        return fail(MI_ERR_INVALID, "NULL argument");
+    const std::vector<uint8_t> flags = as_flags(row_enabled, static_cast<size_t>(t->rows));
     // (a call still queued reads the rows it was made with)
-    if (hipSetDevice(t->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(t->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: uploading the rows failed");
+    if (!mi::sync_copy(t->gpu, t->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, "transmission splitter: uploading the rows failed");
     return MI_OK;
 }
 
 int mi_txsplit_process_device(mi_txsplit* t, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
                               mi_tx_record* d_records, uint32_t* d_row_first_record, uint32_t* d_count, void* hip_stream) {
     if (!t || !d_axc || !d_records || !d_row_first_record || !d_count)
-        return tfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (nbatches < 1 || nbatches > t->max_batches)
-        return tfail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
+        return fail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
     if (axc_stride < static_cast<size_t>(nbatches) || (d_waveout && row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch))
-        return tfail(MI_ERR_INVALID, "a row stride is shorter than the call");
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
     if ((d_waveout && (row_stride % 4 != 0 || !aligned(d_waveout, 16))) || !aligned(d_records, 8) || !aligned(d_row_first_record, 4) ||
         !aligned(d_count, 4))
-        return tfail(MI_ERR_INVALID, "the audio buffer must be 16-byte aligned with a row stride that is a multiple of 4 floats; records 8-byte aligned");
+        return fail(MI_ERR_INVALID, "the audio buffer must be 16-byte aligned with a row stride that is a multiple of 4 floats; records 8-byte aligned");
     if (hipSetDevice(t->gpu) != hipSuccess)
-        return tfail(MI_ERR_HIP, "hipSetDevice failed");
+        return fail(MI_ERR_HIP, "hipSetDevice failed");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
-    auto stamp = [&](int i) {
-        if (t->timing)
-            (void)hipEventRecord(t->ev[i], q);
-    };
     const unsigned rows = static_cast<unsigned>(t->rows), nb = static_cast<unsigned>(nbatches);
-    stamp(0);
+    t->timing.stamp(0, q);
     hipLaunchKernelGGL(k_tx_walk, dim3((rows + kRowsPerGroup - 1) / kRowsPerGroup), dim3(256), 0, q, t->d_enabled.get(), t->d_state.get(), d_axc, axc_stride,
                        t->rows, nbatches, t->cfg.min_batches, t->cfg.idle_batches, t->cfg.max_batches, t->d_rank.get(), t->d_row_rec.get(),
                        t->d_row_rec_count.get());
-    stamp(1);
-    hipLaunchKernelGGL(k_tx_scan, dim3(1), dim3(kScanTile), 0, q, t->d_row_rec_count.get(), t->rows, t->max_records, d_row_first_record, d_count);
-    stamp(2);
+    t->timing.stamp(1, q);
+    mi::launch_row_scan(q, t->d_row_rec_count, t->rows, t->max_records, d_row_first_record, d_count);
+    t->timing.stamp(2, q);
     if (d_waveout)
         hipLaunchKernelGGL(k_tx_block_stats, dim3(rows * nb), dim3(256), 0, q, t->d_rank.get(), d_waveout, row_stride, nbatches, t->d_block_sum.get(),
                            t->d_block_peak.get());
-    stamp(3);
+    t->timing.stamp(3, q);
     hipLaunchKernelGGL(k_tx_combine, dim3((rows * (nb + 1) + 255) / 256), dim3(256), 0, q, t->d_row_rec.get(), t->d_row_rec_count.get(), d_row_first_record,
                        t->d_block_sum.get(), t->d_block_peak.get(), t->rows, nbatches, d_waveout ? 1 : 0, t->max_records, d_records);
-    stamp(4);
+    t->timing.stamp(4, q);
     if (hipGetLastError() != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter kernel launch failed");
+        return fail(MI_ERR_HIP, "transmission splitter kernel launch failed");
     t->last_records = d_records;
     t->last_row_first = d_row_first_record;
     t->last_count = d_count;
@@ -397,15 +335,12 @@ int mi_txsplit_process_device(mi_txsplit* t, const float* d_waveout, size_t row_
 
 int mi_txsplit_download(mi_txsplit* t, void* hip_stream, mi_tx_record* records, uint32_t* row_first_record, uint32_t* count) {
     if (!t || !count)
-        return tfail(MI_ERR_INVALID, "NULL argument");
+        return fail(MI_ERR_INVALID, "NULL argument");
     if (!t->last_count)
-        return tfail(MI_ERR_INVALID, "no mi_txsplit_process_device call to download");
+        return fail(MI_ERR_INVALID, "no mi_txsplit_process_device call to download");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
-    if (hipSetDevice(t->gpu) != hipSuccess || hipMemcpyAsync(t->h_count, t->last_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, q) != hipSuccess ||
-        hipStreamSynchronize(q) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: reading the counts failed");
-    count[0] = t->h_count.get()[0];
-    count[1] = t->h_count.get()[1];
+    if (!mi::land_counts(t->gpu, q, t->h_count, t->last_count, count))
+        return fail(MI_ERR_HIP, "transmission splitter: reading the counts failed");
     const size_t k = count[1];
     bool ok = true;
     if (records && k)
@@ -414,35 +349,22 @@ int mi_txsplit_download(mi_txsplit* t, void* hip_stream, mi_tx_record* records, 
         ok = ok && hipMemcpyAsync(row_first_record, t->last_row_first, (static_cast<size_t>(t->rows) + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, q) ==
                        hipSuccess;
     if (!ok || hipStreamSynchronize(q) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: download failed");
+        return fail(MI_ERR_HIP, "transmission splitter: download failed");
     return MI_OK;
 }
 
 int mi_txsplit_set_timing(mi_txsplit* t, int on) {
     if (!t)
-        return tfail(MI_ERR_INVALID, "NULL argument");
-    if (on && !t->ev[0]) {
-        if (hipSetDevice(t->gpu) != hipSuccess)
-            return tfail(MI_ERR_HIP, "hipSetDevice failed");
-        for (mi::Event& e : t->ev)
-            if (hipEventCreate(e.put()) != hipSuccess)
-                return tfail(MI_ERR_HIP, "transmission splitter: hipEventCreate failed");
-    }
-    t->timing = on != 0;
-    return MI_OK;
+        return fail(MI_ERR_INVALID, "NULL argument");
+    return t->timing.enable(t->gpu, on != 0);
 }
 
 int mi_txsplit_last_launch_ms(mi_txsplit* t, float* ms) {
     if (!t || !ms)
-        return tfail(MI_ERR_INVALID, "NULL argument");
-    if (!t->timing || !t->last_count)
-        return tfail(MI_ERR_INVALID, "no timed mi_txsplit_process_device call");
-    if (hipSetDevice(t->gpu) != hipSuccess || hipEventSynchronize(t->ev[4]) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: waiting for the timing events failed");
-    for (int i = 0; i < 4; ++i)
-        if (hipEventElapsedTime(ms + i, t->ev[i], t->ev[i + 1]) != hipSuccess)
-            return tfail(MI_ERR_HIP, "transmission splitter: hipEventElapsedTime failed");
-    return MI_OK;
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!t->timing.on || !t->last_count)
+        return fail(MI_ERR_INVALID, "no timed mi_txsplit_process_device call");
+    return t->timing.elapsed(t->gpu, ms);
 }
 
 size_t mi_txsplit_state_size(const mi_txsplit* t) {
@@ -451,24 +373,22 @@ size_t mi_txsplit_state_size(const mi_txsplit* t) {
 
 int mi_txsplit_get_state(mi_txsplit* t, void* buf, size_t len) {
     if (!t || !buf || len != mi_txsplit_state_size(t))
-        return tfail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
-    if (hipSetDevice(t->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(buf, t->d_state, len, hipMemcpyDeviceToHost) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: reading the state failed");
+        return fail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
+    if (!mi::sync_copy(t->gpu, buf, t->d_state, len, hipMemcpyDeviceToHost))
+        return fail(MI_ERR_HIP, "transmission splitter: reading the state failed");
     return MI_OK;
 }
 
 int mi_txsplit_set_state(mi_txsplit* t, const void* buf, size_t len) {
     if (!t || !buf || len != mi_txsplit_state_size(t))
-        return tfail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
+        return fail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
     std::vector<mi::TxRowState> rows(static_cast<size_t>(t->rows));
     std::memcpy(rows.data(), buf, len);
     for (const mi::TxRowState& s : rows)
         if (s.open > 1 || s.active > 1 || s.zero != 0)
-            return tfail(MI_ERR_INVALID, "transmission splitter state: malformed blob");
-    if (hipSetDevice(t->gpu) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(t->d_state, rows.data(), len, hipMemcpyHostToDevice) != hipSuccess)
-        return tfail(MI_ERR_HIP, "transmission splitter: writing the state failed");
+            return fail(MI_ERR_INVALID, "transmission splitter state: malformed blob");
+    if (!mi::sync_copy(t->gpu, t->d_state, rows.data(), len, hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, "transmission splitter: writing the state failed");
     return MI_OK;
 }
 

@@ -1,0 +1,155 @@
+"""What the post-stages refuse, and in which words, without a GPU: the output gate, the transmission splitter, the mixer and the two host
+twins.  Every code and text below was copied from the sources as they stood before the stages came to share one error helper and one set
+of argument checks; a call that is refused must be refused with the same code and the same bytes of mi_last_error() after it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+INVALID, NO_DEVICE = -1, -2
+NULL = b"NULL argument"
+GATE_GEOMETRY = b"output gate needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24"
+GATE_RULE = b"gate rule out of range 0..3"
+GATE_STATE = b"output gate state: NULL argument or wrong length"
+TX_GEOMETRY = b"transmission splitter needs 1 <= rows < 2^20, max_batches >= 1 and rows * (max_batches + 1) < 2^24"
+TX_STATE = b"transmission splitter state: NULL argument or wrong length"
+STRIDE = b"a row stride is shorter than the call"
+WAVE_BATCH = 2000
+
+
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def refused(pkg, rc, code, text):
+    assert rc == code
+    assert pkg.lib().mi_last_error() == text
+
+
+@pytest.fixture()
+def L(pkg):
+    return pkg.lib()
+
+
+def test_output_gate(pkg, L):
+    out = C.c_void_p()
+    rule, some = np.ones(4, np.uint8), np.zeros(64, np.uint8)
+    create = L.mi_outgate_create
+    refused(pkg, create(None, None, 4, 1, 0, 0, C.byref(out)), INVALID, NULL)
+    refused(pkg, create(ptr(rule), None, 4, 1, 0, 0, None), INVALID, NULL)
+    for rows, max_batches in ((0, 1), (-1, 1), (1 << 20, 1), (4, 0), (4, -1), (1 << 12, 1 << 12), ((1 << 20) - 1, 17)):
+        refused(pkg, create(ptr(rule), None, rows, max_batches, 0, 0, C.byref(out)), INVALID, GATE_GEOMETRY)
+    for bad in (4, 255):
+        refused(pkg, create(ptr(np.array([0, 3, bad, 1], np.uint8)), None, 4, 1, 0, 0, C.byref(out)), INVALID, GATE_RULE)
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, create(ptr(rule), None, 4, 1, 0, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the output gate runs on the GPU only")
+        refused(pkg, create(ptr(rule), ptr(rule), 4, 2, 3, -1, C.byref(out)), NO_DEVICE, b"no HIP device: the output gate runs on the GPU only")
+        assert not out.value
+    # every other entry point refuses a NULL handle, and a NULL argument, before it looks at anything else
+    refused(pkg, L.mi_outgate_set_rules(None, ptr(rule)), INVALID, NULL)
+    refused(pkg, L.mi_outgate_process_device(None, ptr(some), 0, None, 0, ptr(some), 0, 1, ptr(some), None, ptr(some), ptr(some), ptr(some), None),
+            INVALID, NULL)
+    refused(pkg, L.mi_outgate_download(None, None, None, None, None, None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_outgate_set_timing(None, 1), INVALID, NULL)
+    refused(pkg, L.mi_outgate_last_launch_ms(None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_outgate_get_state(None, ptr(some), 4), INVALID, GATE_STATE)
+    refused(pkg, L.mi_outgate_set_state(None, ptr(some), 4), INVALID, GATE_STATE)
+    assert L.mi_outgate_state_size(None) == 0
+    L.mi_outgate_destroy(None)
+
+
+def test_transmission_splitter(pkg, L):
+    out = C.c_void_p()
+    en, some = np.ones(4, np.uint8), np.zeros(64, np.uint8)
+    cfg = pkg.TxCfg(0, 0, 0)
+    create = L.mi_txsplit_create
+    refused(pkg, create(C.byref(cfg), None, 4, 1, 0, 0, C.byref(out)), INVALID, NULL)
+    refused(pkg, create(C.byref(cfg), ptr(en), 4, 1, 0, 0, None), INVALID, NULL)
+    for rows, max_batches in ((0, 1), (-1, 1), (1 << 20, 1), (4, 0), (4, -1), (1 << 12, (1 << 12) - 1), ((1 << 20) - 1, 16)):
+        refused(pkg, create(None, ptr(en), rows, max_batches, 0, 0, C.byref(out)), INVALID, TX_GEOMETRY)
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, create(None, ptr(en), 4, 1, 0, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the transmission splitter runs on the GPU only")
+        refused(pkg, create(C.byref(cfg), ptr(en), 4, 2, 3, -1, C.byref(out)), NO_DEVICE,
+                b"no HIP device: the transmission splitter runs on the GPU only")
+        assert not out.value
+    refused(pkg, L.mi_txsplit_set_rows(None, ptr(en)), INVALID, NULL)
+    refused(pkg, L.mi_txsplit_process_device(None, ptr(some), 0, ptr(some), 0, 1, ptr(some), ptr(some), ptr(some), None), INVALID, NULL)
+    refused(pkg, L.mi_txsplit_download(None, None, None, None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_txsplit_set_timing(None, 1), INVALID, NULL)
+    refused(pkg, L.mi_txsplit_last_launch_ms(None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_txsplit_get_state(None, ptr(some), 32), INVALID, TX_STATE)
+    refused(pkg, L.mi_txsplit_set_state(None, ptr(some), 32), INVALID, TX_STATE)
+    assert L.mi_txsplit_state_size(None) == 0
+    L.mi_txsplit_destroy(None)
+
+
+def test_mixer(pkg, L):
+    out = C.c_void_p()
+    one = (pkg.MixInput * 1)(pkg.MixInput(0, 1.0, 0.0))
+    some = np.zeros(64, np.uint8)
+    refused(pkg, L.mi_mixer_create(None, 1, 0, C.byref(out)), INVALID, b"mixer needs at least one input")
+    refused(pkg, L.mi_mixer_create(one, 1, 0, None), INVALID, b"mixer needs at least one input")
+    refused(pkg, L.mi_mixer_create(one, 0, 0, C.byref(out)), INVALID, b"mixer needs at least one input")
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, L.mi_mixer_create(one, 1, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the mixer runs on the GPU only")
+        bad = (pkg.MixInput * 1)(pkg.MixInput(-1, 1.0, 2.0))  # (its inputs are looked at after the device)
+        refused(pkg, L.mi_mixer_create(bad, 1, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the mixer runs on the GPU only")
+        assert not out.value
+    refused(pkg, L.mi_mixer_process_device(None, ptr(some), 0, ptr(some), 0, 1, ptr(some), None, ptr(some), None), INVALID, NULL)
+    assert L.mi_mixer_is_stereo(None) == 0
+    L.mi_mixer_destroy(None)
+
+
+def test_gate_plan_host(pkg, L):
+    rows, nb = 3, 5
+    rule, axc, carried = np.ones(rows, np.uint8), np.full((rows, nb), ord("*"), np.uint8), np.zeros(rows, np.uint8)
+    index, first, count = np.zeros((rows * nb, 2), np.uint32), np.zeros(rows + 1, np.uint32), np.zeros(2, np.uint32)
+    good = [ptr(rule), rows, ptr(axc), nb, nb, ptr(carried), ptr(index), ptr(first), ptr(count)]
+    assert L.mi_gate_plan_host(*good) == 0 and count[0] == rows * nb
+    for i in (0, 2, 5, 6, 7, 8):
+        refused(pkg, L.mi_gate_plan_host(*[None if j == i else a for j, a in enumerate(good)]), INVALID, NULL)
+    geometry = b"gate plan needs rows >= 1 and 1 <= nbatches <= axc_stride"
+    for r, stride, n in ((0, nb, nb), (-1, nb, nb), (rows, nb, 0), (rows, nb, -1), (rows, nb - 1, nb)):  # (the last: row stride too short)
+        refused(pkg, L.mi_gate_plan_host(ptr(rule), r, ptr(axc), stride, n, ptr(carried), ptr(index), ptr(first), ptr(count)), INVALID, geometry)
+    refused(pkg, L.mi_gate_plan_host(ptr(rule), 1 << 20, ptr(axc), 1 << 12, 1 << 12, ptr(carried), ptr(index), ptr(first), ptr(count)), INVALID,
+            b"gate plan: rows * nbatches does not fit the 32-bit block index")
+    for bad in (4, 255):
+        worse = np.array([1, 1, bad], np.uint8)
+        refused(pkg, L.mi_gate_plan_host(*([ptr(worse)] + good[1:])), INVALID, GATE_RULE)
+
+
+def test_tx_plan_host(pkg, L):
+    rows, nb = 3, 5
+    en, axc = np.ones(rows, np.uint8), np.full((rows, nb), ord("*"), np.uint8)
+    wave = np.zeros((rows, nb * WAVE_BATCH), np.float32)
+    state = np.zeros(rows, pkg.TX_STATE_DTYPE)
+    cap = rows * (nb + 1)
+    records, first, count = np.zeros(cap, pkg.TX_RECORD_DTYPE), np.zeros(rows + 1, np.uint32), np.zeros(2, np.uint32)
+
+    def call(**over):
+        a = dict(cfg=None, en=ptr(en), rows=rows, axc=ptr(axc), axc_stride=nb, nb=nb, wave=ptr(wave), row_stride=nb * WAVE_BATCH, state=ptr(state),
+                 records=ptr(records), cap=cap, first=ptr(first), count=ptr(count))
+        a.update(over)
+        return L.mi_tx_plan_host(*a.values())
+
+    assert call() == 0 and count[0] == rows
+    state[:] = 0
+    for name in ("en", "axc", "state", "records", "first", "count"):
+        refused(pkg, call(**{name: None}), INVALID, NULL)
+    geometry = b"tx plan needs rows >= 1, 1 <= nbatches <= axc_stride and max_records >= 1"
+    for over in (dict(rows=0), dict(rows=-1), dict(nb=0), dict(nb=-1), dict(axc_stride=nb - 1), dict(cap=0)):
+        refused(pkg, call(**over), INVALID, geometry)
+    refused(pkg, call(row_stride=nb * WAVE_BATCH - 1), INVALID, STRIDE)
+    assert call(wave=None, row_stride=0) == 0  # (no audio, no stride to check)
+    state[:] = 0
+    refused(pkg, call(rows=1 << 20, nb=1 << 12, axc_stride=1 << 12, wave=None), INVALID,
+            b"tx plan: rows * (nbatches + 1) does not fit the 32-bit record count")
+    for field, value in (("open", 2), ("active", 2), ("zero", 1)):
+        state[:] = 0
+        state[field][rows - 1] = value
+        before = state.copy()
+        refused(pkg, call(), INVALID, b"tx plan: malformed state blob")
+        assert np.array_equal(state, before)

@@ -10,26 +10,14 @@ and, from the gate's per-launch events, where its time sits (rank pass, scan, bl
 """
 import argparse
 import ctypes as C
-import importlib.util
 import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WAVE_BATCH = 2000
+from rate_common import WAVE_BATCH, draw, load_package, timed as timed_on
+
 D2H, D2D = 2, 3  # hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice
-
-
-def load_package():
-    path = os.path.join(ROOT, "boondock-airband_amd", "__init__.py")
-    spec = importlib.util.spec_from_file_location("boondock_airband_amd", path, submodule_search_locations=[os.path.dirname(path)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["boondock_airband_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def hip_runtime():
@@ -73,17 +61,7 @@ def main():
     h_count = np.zeros(2, np.uint32)
 
     def timed(fn):
-        """mean ms per repetition by HIP events on the stream"""
-        for _ in range(args.warmup):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record()
-            for _ in range(args.reps):
-                fn()
-            b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / args.reps
+        return timed_on(torch, stream, fn, args.warmup, args.reps)
 
     def check(rc):
         if rc != 0:
@@ -98,7 +76,7 @@ def main():
           f"({nbytes / d2h_ms / 1e6:.1f} GB/s)")
     print("  open   blocks   gate ms   (rank / scan / copy)        vs d2d   download ms   vs d2h")
     for frac in args.fractions:
-        flags = np.where(rng.random((rows, nb)) < frac, ord("*"), ord(" ")).astype(np.uint8)
+        flags = draw(rng, rows, nb, frac)
         axc = torch.from_numpy(flags).cuda()
         gate = pkg.OutputGate(np.full(rows, pkg.GATE_OPEN, np.uint8), None, max_batches=nb)
         torch.cuda.synchronize()

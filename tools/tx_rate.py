@@ -8,40 +8,11 @@ Flags are transmissions of a geometric length (mean --burst batches) placed so t
 carries from one repetition to the next as in a replay.  Prints one table and one JSON line.
 """
 import argparse
-import importlib.util
 import json
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WAVE_BATCH = 2000
-
-
-def load_package():
-    path = os.path.join(ROOT, "boondock-airband_amd", "__init__.py")
-    spec = importlib.util.spec_from_file_location("boondock_airband_amd", path, submodule_search_locations=[os.path.dirname(path)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["boondock_airband_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def draw(rng, rows, nb, frac, burst):
-    """flags [rows][nb]: a two-state chain whose open runs have mean length `burst` and whose open share is `frac`"""
-    if frac >= 1.0:
-        return np.full((rows, nb), ord("*"), np.uint8)
-    p_close = 1.0 / burst
-    p_open = min(1.0, p_close * frac / (1.0 - frac))
-    flags = np.full((rows, nb), ord(" "), np.uint8)
-    for r in range(rows):
-        on = rng.random() < frac
-        for b in range(nb):
-            if on:
-                flags[r, b] = ord("*")
-            on = (rng.random() >= p_close) if on else (rng.random() < p_open)
-    return flags
+from rate_common import WAVE_BATCH, draw, load_package, timed as timed_on
 
 
 def main():
@@ -69,17 +40,7 @@ def main():
     count = torch.empty(2, dtype=torch.int32, device="cuda")
 
     def timed(fn):
-        """mean ms per repetition by HIP events on the stream"""
-        for _ in range(args.warmup):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(stream):
-            a.record()
-            for _ in range(args.reps):
-                fn()
-            b.record()
-        b.synchronize()
-        return a.elapsed_time(b) / args.reps
+        return timed_on(torch, stream, fn, args.warmup, args.reps)
 
     result = dict(tool="tx_rate", device=torch.cuda.get_device_name(0), hip=torch.version.hip, rows=rows, batches=nb, reps=args.reps, cases=[])
     print(f"{result['device']}, HIP {result['hip']}: {rows} rows x {nb} batches, {args.reps} repetitions")
