@@ -130,6 +130,8 @@ ABI_SYMBOLS = [
     "mi_outgate_get_state", "mi_outgate_set_state", "mi_outgate_set_timing", "mi_outgate_last_launch_ms", "mi_gate_plan_host",
     "mi_txsplit_create", "mi_txsplit_destroy", "mi_txsplit_set_rows", "mi_txsplit_process_device", "mi_txsplit_download", "mi_txsplit_state_size",
     "mi_txsplit_get_state", "mi_txsplit_set_state", "mi_txsplit_set_timing", "mi_txsplit_last_launch_ms", "mi_tx_plan_host",
+    "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
+    "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
 
@@ -218,6 +220,16 @@ def lib():
         L.mi_txsplit_set_timing.argtypes = [vp, C.c_int]
         L.mi_txsplit_last_launch_ms.argtypes = [vp, vp]
         L.mi_tx_plan_host.argtypes = [C.POINTER(TxCfg), vp, C.c_int, vp, sz, C.c_int, vp, sz, vp, vp, sz, vp, vp]
+        L.mi_survey_create.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mi_survey_destroy.argtypes = [vp]
+        L.mi_survey_destroy.restype = None
+        L.mi_survey_set_streams.argtypes = [vp, vp]
+        L.mi_survey_bytes_needed.argtypes = [vp, C.c_int]
+        L.mi_survey_bytes_needed.restype = sz
+        L.mi_survey_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp]
+        L.mi_survey_set_timing.argtypes = [vp, C.c_int]
+        L.mi_survey_last_launch_ms.argtypes = [vp, vp]
+        L.mi_survey_bin_range.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mi_plan_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(ChannelCfg), C.c_int, C.POINTER(vp)]
         L.mi_plan_destroy.argtypes = [vp]
         L.mi_plan_destroy.restype = None
@@ -807,6 +819,49 @@ def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_recor
                                  None if waveout is None else _ptr(waveout), row_stride, _ptr(state),
                                  _ptr(records), cap, _ptr(row_first), _ptr(count)))
     return records[:int(count[1])], row_first, count, state
+
+
+class Survey(_Handle):
+    """mi_survey: per-bin mean and peak magnitude of every cell of windows_per_cell consecutive windows (0 = WAVE_BATCH), over the full
+    FFT of the windows stage 1 runs -- the pass that comes before a channel plan.  Stateless between calls; no state blob."""
+    _destroy = "mi_survey_destroy"
+
+    def __init__(self, dev, nstreams=1, max_cells=1, windows_per_cell=0, gpu=0):
+        self.nstreams, self.max_cells = nstreams, max_cells
+        self.windows_per_cell = windows_per_cell or WAVE_BATCH
+        self.fft_size = 1 << dev.fft_size_log
+        self._h = C.c_void_p()
+        _check(lib().mi_survey_create(C.byref(dev), nstreams, max_cells, windows_per_cell, gpu, C.byref(self._h)))
+
+    def set_streams(self, enabled=None):
+        """enabled: truth value per stream, or None = all.  A disabled stream is neither read nor written."""
+        en = None if enabled is None else _flags(enabled)
+        assert en is None or en.size == self.nstreams
+        _check(lib().mi_survey_set_streams(self._h, None if en is None else _ptr(en)))
+
+    def bytes_needed(self, ncells):
+        return lib().mi_survey_bytes_needed(self._h, ncells)
+
+    def process_device(self, d_iq, stream_stride, ncells, d_mean, d_peak, hip_stream=None):
+        """Raw device pointers (ints): d_mean and d_peak float32 [nstreams][ncells][fft_size]; asynchronous on hip_stream."""
+        _check(lib().mi_survey_process_device(self._h, d_iq, stream_stride, ncells, d_mean, d_peak, hip_stream))
+
+    def set_timing(self, on=True):
+        _check(lib().mi_survey_set_timing(self._h, 1 if on else 0))
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of the two launches of the last call made with set_timing(True): the windows, the fold"""
+        ms = (C.c_float * 2)()
+        _check(lib().mi_survey_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
+        return tuple(ms)
+
+
+def survey_bin_range(dev, bin):
+    """mi_survey_bin_range: (lo_hz, hi_hz), a closed range of integer frequencies inside the band that the plan's bin rule maps to
+    `bin` (the bin's longest piece; see include/mi_airband.h).  No GPU."""
+    lo, hi = C.c_int(), C.c_int()
+    _check(lib().mi_survey_bin_range(C.byref(dev), bin, C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
 
 
 # ---- the BASELINE.json channel plans (SURVEY 8d) ----

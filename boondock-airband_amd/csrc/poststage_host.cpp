@@ -1,6 +1,8 @@
 // poststage_host.cpp -- the host twins of the output gate and the transmission splitter: what the device stages compute, from flags
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
-// device walk and with the Python model, which are the other two statements of the same rule.
+// device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
+// too: mi_survey_bin_range, the plan's bin rule read backwards.
+#include <algorithm>
 #include <cmath>
 
 #include "poststage.hpp"
@@ -58,6 +60,36 @@ extern "C" int mi_gate_plan_host(const uint8_t* row_rule, int rows, const char* 
     }
     row_first[rows] = k;
     count[0] = count[1] = k;
+    return MI_OK;
+}
+
+// ---- band survey, host side (include/mi_airband.h "band survey"): the frequencies the plan's bin rule sends to one FFT bin.
+// plan.cpp states the rule as the reference does (config.cpp:669-670), in double: with d = freq + sample_rate - centerfreq and the
+// INTEGER quotient q = sample_rate / fft_size, B = ceil(d / q - 1.0) and bin = B % fft_size.  d / q misses an integer by at least 1 / q
+// where it is not one, far more than a double's rounding, so B = ceil(d / q) - 1 in integers: B's frequencies are d = B q + 1 .. (B + 1) q.
+extern "C" int mi_survey_bin_range(const mi_device_cfg* dev, int bin, int* lo_hz, int* hi_hz) {
+    if (!dev || !lo_hz || !hi_hz)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (dev->fft_size_log < 8 || dev->fft_size_log > 13)
+        return fail(MI_ERR_INVALID, "fft_size must be a power of two in 2^8..2^13");
+    if (dev->sample_rate <= mi::kWaveRate)
+        return fail(MI_ERR_INVALID, "sample_rate must be greater than WAVE_RATE");
+    const int64_t n = int64_t{1} << dev->fft_size_log, sr = dev->sample_rate, q = sr / n;
+    if (bin < 0 || bin >= n)
+        return fail(MI_ERR_INVALID, "bin outside 0 .. fft_size - 1");
+    const int64_t d_first = sr - sr / 2, d_last = sr + (sr + 1) / 2 - 1;  // the band [centerfreq - sample_rate / 2, centerfreq + sample_rate / 2)
+    int64_t best_lo = 0, best_len = 0;
+    for (int64_t b = bin; b * q + 1 <= d_last; b += n) {  // the band holds fft_size + 1 values of B or a few more: at most two pieces
+        const int64_t lo = std::max(b * q + 1, d_first), hi = std::min((b + 1) * q, d_last);
+        if (hi - lo + 1 > best_len) {
+            best_lo = lo;
+            best_len = hi - lo + 1;
+        }
+    }
+    if (best_len < 1)  // (every residue occurs among fft_size consecutive values of B, and the band is at least that wide)
+        return fail(MI_ERR_INVALID, "no frequency of the band maps to this bin");
+    *lo_hz = static_cast<int>(best_lo - sr + dev->centerfreq);
+    *hi_hz = static_cast<int>(best_lo + best_len - 1 - sr + dev->centerfreq);
     return MI_OK;
 }
 

@@ -536,6 +536,56 @@ int mi_tx_plan_host(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, 
                     const float* waveout, size_t row_stride, void* state_inout, mi_tx_record* records, size_t max_records,
                     uint32_t* row_first_record, uint32_t* count /* [2] */);
 
+/* ---------------- band survey: per-bin mean and peak magnitude per cell, the pass that comes before a channel plan ----------------
+ * The demodulator evaluates only the bins its plan picks; the survey looks at every bin of the full fft_size-point FFT, for a caller
+ * who holds a wide-band capture and no channel list yet.  It reads the device-resident IQ mi_demod_process_device reads and runs the
+ * same windows -- the plan's Blackman-7 window, the device's sample conversion (fullscale as in stage 1), hop_bytes apart, fft_size
+ * long -- and reduces every run of windows_per_cell consecutive windows (a cell) to two floats per bin:
+ *   peak[stream][cell][bin] = the maximum over the cell's windows of sqrtf(re * re + im * im)
+ *   mean[stream][cell][bin] = (float)(S / windows_per_cell), S = the sum of the same float magnitudes accumulated in float64
+ * A window's spectrum is the documented FFT, so a magnitude has the bits stage 1 would give the bin.
+ * Window placement: cell c of stream s covers windows c * wpc .. (c + 1) * wpc - 1, counted from d_iq + s * stream_stride_bytes.  The
+ *   stage keeps no state between calls.  A caller who wants the cells aligned with the demodulator's audio batches offsets the
+ *   pointer: the first call of a demod handle runs MI_AGC_EXTRA more windows (mi_demod_bytes_needed), so batch b of that handle's
+ *   audio is made of the windows MI_AGC_EXTRA + b * MI_WAVE_BATCH .. of the capture -- hand the survey d_iq + MI_AGC_EXTRA * hop_bytes.
+ * Bin order: FFT order 0 .. fft_size - 1, the index mi_plan_channel().bin reports (bin 0 = centerfreq, the upper half = below it).
+ * Supported: fft_size_log 8 .. 13, all four sample formats, any hop the plan derives (160, 128, 150, ...); d_iq and the stream stride
+ *   aligned to one complex sample.  Stateless, no option or environment switch; nothing is shared with a demod handle.
+ * Disabled streams (mi_survey_set_streams; the companion of mi_demod_set_active_streams, as MI_GATE_NONE is): a disabled stream's IQ
+ *   is not read and its regions of d_mean / d_peak are not written.  NULL enables all (the default).  Completes queued work first.
+ * Execution: asynchronous on `hip_stream`, no host synchronisation; two kernels (the windows; the fold of a cell's partial sums).  The
+ *   partial sums live in the handle: calls of one handle go to one stream, or are ordered by the caller.
+ * Determinism: no floating-point atomics; the partial sums of a cell are combined in a fixed order (csrc/survey.hip), so two runs give
+ *   the same bytes.  With f32 input, NaN and Inf are unspecified.
+ * MI_ERR_NO_DEVICE without a GPU; MI_ERR_INVALID for bad arguments, d_mean / d_peak not 16-byte aligned, ncells outside
+ * 1 .. max_cells, or a mask that enables no stream (the mask then stays as it was). */
+typedef struct mi_survey mi_survey;
+/* 1 <= nstreams < 2^16, 1 <= max_cells < 2^24; windows_per_cell 0 = MI_WAVE_BATCH (one audio batch), at most 2^20 */
+int mi_survey_create(const mi_device_cfg* dev, int nstreams, int max_cells, int windows_per_cell, int gpu, mi_survey** out);
+void mi_survey_destroy(mi_survey* s);
+int mi_survey_set_streams(mi_survey* s, const uint8_t* stream_enabled /* [nstreams] or NULL = all */);
+/* contiguous bytes a call over ncells cells reads per stream: (ncells * wpc - 1) * hop_bytes + 2 * bytes_per_sample * fft_size */
+size_t mi_survey_bytes_needed(const mi_survey* s, int ncells);
+/* d_mean, d_peak: device [nstreams][ncells][fft_size] each, 16-byte aligned */
+int mi_survey_process_device(mi_survey* s, const void* d_iq, size_t stream_stride_bytes, int ncells, float* d_mean, float* d_peak,
+                             void* hip_stream);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {windows, fold}.  tools/survey_rate.py. */
+int mi_survey_set_timing(mi_survey* s, int on);
+int mi_survey_last_launch_ms(mi_survey* s, float* ms /* [2] */);
+/* From a bin back to frequencies a plan can be given: no GPU and no HIP call.  The plan's bin rule (config.cpp:669-670) is
+ * bin = ceil((freq + sample_rate - centerfreq) / (sample_rate / fft_size) - 1.0) % fft_size with the INTEGER quotient
+ * q = sample_rate / fft_size: the unwrapped index B owns the q frequencies B q + 1 .. (B + 1) q above centerfreq - sample_rate, upper
+ * end included, lower end not.  A frequency exactly on an FFT bin's centre therefore lands in the bin BELOW it, which is why this
+ * returns a range and not "the bin's frequency".  [*lo_hz, *hi_hz] is a closed range of integer frequencies inside the band
+ * [centerfreq - sample_rate / 2, centerfreq + sample_rate / 2) that all map to `bin`, and *lo_hz - 1 and *hi_hz + 1 do not (where they
+ * lie in the band).  The band is half open at the other end than the rule, and wider than fft_size * q where the quotient truncates,
+ * so it holds fft_size + 1 values of B or a few more: a bin next to fft_size / 2 can own a second, shorter piece at the opposite
+ * edge of the band (at 2.56 MS/s and fft 256 the one frequency centerfreq - 1280000 maps to bin 127, whose range lies at the top of
+ * the band).  The range returned is the bin's longest piece, the lower one of two equal ones; the ranges of all bins are disjoint,
+ * and what they leave uncovered is those second pieces at the band's edges, fewer than 2 q + fft_size frequencies in all.
+ * MI_ERR_INVALID: bin outside 0 .. fft_size - 1, or a device configuration the plan refuses. */
+int mi_survey_bin_range(const mi_device_cfg* dev, int bin, int* lo_hz, int* hi_hz);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which

@@ -1,0 +1,303 @@
+"""The band survey on the GPU (mi_survey_*, csrc/survey.hip) against the oracle model of tests/survey_model.py.
+
+Pass criteria, the same in every case:
+  peak  equals the model bit for bit (a max is order-free);
+  mean  is within one float32 step of the model's float64 mean.  Derived, not measured: a float64 sum of at most 2000 floats errs by
+        under 2000 x 2^-53 relative whatever its order, so its float32 rounding is the correctly rounded value or that value's neighbour.
+Every output buffer holds a sentinel before a call and is longer than the call writes: the floats behind the last cell, and the regions
+of a disabled stream, must still hold it afterwards.  mi_survey_bytes_needed is checked against its formula in every case, and the
+capture handed over is exactly that long per stream."""
+import functools
+
+import numpy as np
+import pytest
+
+import survey_model as sv
+
+pytestmark = pytest.mark.gpu
+
+SENT = int(np.uint32(0xDEADBEEF).view(np.int32))
+GUARD = 64  # floats allocated behind the last cell
+SAMPLE_BYTES = {sv.SFMT_U8: 2, sv.SFMT_S8: 2, sv.SFMT_S16: 4, sv.SFMT_F32: 8}  # one complex sample
+
+
+def device(pkg, rate, log2n, sfmt=sv.SFMT_U8, fullscale=127.5):
+    return pkg.device_cfg(sample_rate=rate, centerfreq=sv.CENTRE, fft_size_log=log2n, sfmt=sfmt, fullscale=fullscale)
+
+
+class Run:
+    """one handle and one capture in device memory: streams `stride` bytes apart from a base that is only sample-aligned"""
+
+    def __init__(self, pkg, dev, raws, wpc, ncells, enabled=None, poison=None):
+        import torch
+        self.torch, self.dev, self.ncells, self.n = torch, dev, ncells, 1 << dev.fft_size_log
+        self.ns = len(raws)
+        sb = SAMPLE_BYTES[dev.sfmt]
+        self.survey = pkg.Survey(dev, nstreams=self.ns, max_cells=ncells, windows_per_cell=wpc)
+        need = self.survey.bytes_needed(ncells)
+        hop_bytes = sv.hop_samples(dev.sample_rate) * sb
+        assert need == (ncells * (wpc or 2000) - 1) * hop_bytes + sb * self.n, "mi_survey_bytes_needed against its formula"
+        self.stride = (need + 15) // 16 * 16 + 3 * sb  # no multiple of 16: the streams' bases differ in alignment
+        off = sb
+        host = np.zeros(off + (self.ns - 1) * self.stride + need, np.uint8)
+        for s, raw in enumerate(raws):
+            b = np.ascontiguousarray(raw).view(np.uint8)
+            assert b.size >= need
+            host[off + s * self.stride:off + s * self.stride + need] = b[:need] if poison is None or s not in poison else poison[s]
+        self.buf = torch.from_numpy(host).cuda()
+        self.d_iq = self.buf.data_ptr() + off
+        if enabled is not None:
+            self.survey.set_streams(enabled)
+        self.enabled = [True] * self.ns if enabled is None else [bool(e) for e in enabled]
+
+    def outputs(self):
+        return [self.torch.full((self.ns * self.ncells * self.n + GUARD,), SENT, dtype=self.torch.int32, device="cuda") for _ in range(2)]
+
+    def call(self, stream=None, out=None):
+        mean, peak = out or self.outputs()
+        self.survey.process_device(self.d_iq, self.stride, self.ncells, mean.data_ptr(), peak.data_ptr(), hip_stream=stream)
+        return mean, peak
+
+    def host(self, out):
+        """(mean, peak) float32 [ns][ncells][n] and the int32 views of the whole buffers"""
+        raw = [t.cpu().numpy() for t in out]
+        shaped = [r[:self.ns * self.ncells * self.n].view(np.float32).reshape(self.ns, self.ncells, self.n) for r in raw]
+        return shaped[0], shaped[1], raw
+
+    def close(self):
+        self.survey.close()
+
+
+def check(what, run, out, models):
+    """models[s] = (mean float64, peak float32) of stream s, or None for a disabled stream"""
+    mean, peak, raw = run.host(out)
+    for r in raw:
+        assert (r[run.ns * run.ncells * run.n:] == SENT).all(), f"{what}: floats behind the last cell were written"
+    for s, m in enumerate(models):
+        if m is None:
+            assert not run.enabled[s]
+            assert (mean[s].view(np.int32) == SENT).all() and (peak[s].view(np.int32) == SENT).all(), f"{what}: a disabled stream's region was written"
+            continue
+        want_mean, want_peak = m
+        bad = np.argwhere(peak[s].view(np.int32) != want_peak.view(np.int32))
+        ulps = sv.ulps_from_rounded(mean[s], want_mean)
+        print(f"{what}: stream {s}: {run.ncells} cells x {run.n} bins, peak differs in {len(bad)}, mean at most {int(ulps.max())} float32 steps "
+              f"from the rounded float64 mean ({int((ulps > 0).sum())} of {ulps.size} not equal to it)")
+        assert len(bad) == 0, f"{what}: stream {s}: peak differs from the model in {len(bad)} places, first (cell, bin) {tuple(bad[0])}: " \
+                              f"{peak[s][tuple(bad[0])]!r} vs {want_peak[tuple(bad[0])]!r}"
+        assert ulps.max() <= 1, f"{what}: stream {s}: mean {int(ulps.max())} float32 steps from the model at (cell, bin) " \
+                                f"{np.unravel_index(int(ulps.argmax()), ulps.shape)}"
+    return mean, peak
+
+
+CARRIERS = [(-700000, 0), (25000, 0), (901000, 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def noise_case(rate, log2n, sfmt, fullscale, wpc, ncells, nstreams):
+    """(dev fields, raws, models): noise plus three carriers per stream (another seed each), in the case's format"""
+    from conftest import load_package
+    pkg = load_package()
+    dev = device(pkg, rate, log2n, sfmt, fullscale)
+    raws = [sv.as_format(sv.noise_and_carriers(pkg, rate, sv.samples_needed(dev, wpc * ncells), CARRIERS, stream=s, seed=0x5EED + 7 * s), sfmt)
+            for s in range(nstreams)]
+    for r in raws:
+        r.setflags(write=False)
+    return raws, [sv.survey_model(dev, r, wpc, ncells) for r in raws]
+
+
+def noise_run(pkg, what, rate, log2n, sfmt, fullscale, wpc, ncells, nstreams, disabled=()):
+    dev = device(pkg, rate, log2n, sfmt, fullscale)
+    raws, models = noise_case(rate, log2n, sfmt, fullscale, wpc, ncells, nstreams)
+    enabled = None if not disabled else [s not in disabled for s in range(nstreams)]
+    # a disabled stream's IQ region holds full-scale garbage: read, it would change what the stream's neighbours or its own region hold
+    poison = {s: np.uint8(0xFF) for s in disabled}
+    run = Run(pkg, dev, raws, wpc, ncells, enabled, poison)
+    out = run.call()
+    run.torch.cuda.synchronize()
+    got = check(what, run, out, [None if s in disabled else models[s] for s in range(nstreams)])
+    run.close()
+    return got
+
+
+def test_fft256_u8_two_streams(pkg):
+    """case 1: the default cell (windows_per_cell = 0 = 2000), eight FFTs side by side in a workgroup, four tiles a cell"""
+    dev = device(pkg, 2560000, 8)
+    raws, models = noise_case(2560000, 8, sv.SFMT_U8, 127.5, 2000, 2, 2)
+    run = Run(pkg, dev, raws, 0, 2, None)
+    out = run.call()
+    run.torch.cuda.synchronize()
+    check("fft 256 u8", run, out, models)
+    run.close()
+
+
+def test_fft512_u8_stream_1_disabled(pkg):
+    """case 2: three streams, three cells of 2000; stream 1 sits out -- its output regions and the floats behind the last cell keep the
+    sentinel, and its IQ region holds a pattern no result shows"""
+    noise_run(pkg, "fft 512 u8, stream 1 disabled", 2560000, 9, sv.SFMT_U8, 127.5, 2000, 3, 3, disabled=(1,))
+
+
+def test_fft2048_s16_hop128_cell70(pkg):
+    """case 3: a cell that is no multiple of the tile (70 = 32 + 32 + 6 windows) and an FFT that spans waves"""
+    noise_run(pkg, "fft 2048 s16 hop 128", 2048000, 11, sv.SFMT_S16, 32767.0, 70, 5, 1)
+
+
+def test_fft1024_s8_hop150_cell33(pkg):
+    """case 4: hop 150 samples = 300 bytes, window starts that are only 4-byte aligned"""
+    noise_run(pkg, "fft 1024 s8 hop 150", 2400000, 10, sv.SFMT_S8, 127.5, 33, 3, 1)
+
+
+def test_fft8192_f32_fullscale2_cell33(pkg):
+    """case 5: 1024 lanes to an FFT, tiles of 16, 16 and 1 windows"""
+    noise_run(pkg, "fft 8192 f32", 2560000, 13, sv.SFMT_F32, 2.0, 33, 2, 1)
+
+
+def test_fft4096_u8_cell33(pkg):
+    """case 6"""
+    noise_run(pkg, "fft 4096 u8", 2560000, 12, sv.SFMT_U8, 127.5, 33, 2, 1)
+
+
+def test_constant_input_mean_equals_peak(pkg):
+    """case 7: every byte pair equal, so all 2000 windows are identical: 2000 x m is exact in float64 and mean == peak bit for bit in
+    every bin -- a dropped or doubled window shows here that a tolerance would hide."""
+    dev = device(pkg, 2560000, 9)
+    raw = np.full(2 * sv.samples_needed(dev, 2000), 201, np.uint8)
+    run = Run(pkg, dev, [raw], 2000, 1)
+    out = run.call()
+    run.torch.cuda.synchronize()
+    one = sv.magnitudes(dev, raw, 0, 1)[0]
+    mean, peak = check("constant input", run, out, [(one.astype(np.float64)[None, :], one[None, :])])
+    assert one.max() > 0
+    assert np.array_equal(mean.view(np.int32), peak.view(np.int32)), "mean != peak on identical windows"
+    run.close()
+
+
+WPC8, CELLS8 = 50, 3
+
+
+@pytest.mark.parametrize("start", [0, WPC8 - 1, WPC8, WPC8 * CELLS8 - 1], ids=["window0", "last-of-cell0", "first-of-cell1", "last-of-call"])
+def test_cell_boundaries(pkg, start):
+    """case 8: mid-scale IQ with one full-scale burst exactly one window long, starting with window `start`.  At hop 160 and fft 256
+    the burst's samples lie in windows start - 1, start and start + 1: the cells of those windows see it, with the model's exact
+    peaks, and no other cell does."""
+    dev = device(pkg, 2560000, 8)
+    hop, n = 160, 256
+    nwin = WPC8 * CELLS8
+    quiet = np.full(2 * sv.samples_needed(dev, nwin), 128, np.uint8)
+    raw = quiet.copy()
+    raw[2 * start * hop:2 * (start * hop + n)] = 255
+    model_quiet = sv.survey_model(dev, quiet, WPC8, CELLS8)
+    model = sv.survey_model(dev, raw, WPC8, CELLS8)
+    touched = {w // WPC8 for w in (start - 1, start, start + 1) if 0 <= w < nwin}
+    seen_model = {c for c in range(CELLS8) if not np.array_equal(model[1][c], model_quiet[1][c])}
+    assert seen_model == touched, (seen_model, touched)
+    run = Run(pkg, dev, [raw], WPC8, CELLS8)
+    out = run.call()
+    run.torch.cuda.synchronize()
+    _, peak = check(f"burst at window {start}", run, out, [model])
+    seen = {c for c in range(CELLS8) if not np.array_equal(peak[0, c], model_quiet[1][c])}
+    assert seen == touched, (seen, touched)
+    for c in touched:
+        assert peak[0, c].max() > 4 * model_quiet[1][c].max()
+    run.close()
+
+
+def test_it_does_its_job(pkg):
+    """case 9: one always-on carrier and one that is on in cell 1 only, over a sigma = 2 LSB floor.  The strongest bin of `mean` is the
+    always-on carrier's FFT bin in each cell; the gated carrier's bin rises from cell 0 to cell 1 by more than the model says minus one
+    float32 step; and mi_survey_bin_range of the strongest bin, given to mi_plan_create, comes back as that bin."""
+    rate, log2n, wpc = 2560000, 9, 2000
+    n, hop = 1 << log2n, 160
+    dev = device(pkg, rate, log2n)
+    always, gated = 301000, -452500  # Hz from the centre: FFT bins round(f / 5000) = 60 and 512 - 90 (-90.5 lies between 421 and 422)
+    u8 = sv.noise_and_carriers(pkg, rate, sv.samples_needed(dev, 2 * wpc), [(always, 0), (always, 1), (gated, 0)], gate_samples=wpc * hop)
+    model = sv.survey_model(dev, u8, wpc, 2)
+    run = Run(pkg, dev, [u8], wpc, 2)
+    out = run.call()
+    run.torch.cuda.synchronize()
+    mean, _ = check("two carriers", run, out, [model])
+    b_always = round(always * n / rate) % n
+    assert [int(mean[0, c].argmax()) for c in range(2)] == [b_always, b_always]
+    b_gated = int(model[0][1, n // 2:].argmax()) + n // 2  # the model's strongest bin below the centre in cell 1
+    assert b_gated in (421, 422)
+    rise_model = model[0][1, b_gated] - model[0][0, b_gated]
+    step = float(np.spacing(np.float32(model[0][1, b_gated])))
+    rise = float(mean[0, 1, b_gated]) - float(mean[0, 0, b_gated])
+    print(f"gated carrier, bin {b_gated}: mean {mean[0, 0, b_gated]:.4f} -> {mean[0, 1, b_gated]:.4f}, the model's rise {rise_model:.4f}")
+    assert rise_model > 5 * model[0][0, b_gated] and rise > rise_model - step
+    lo, hi = pkg.survey_bin_range(dev, b_always)
+    assert lo <= sv.CENTRE + always <= hi
+    p = pkg.Plan(dev, [pkg.channel_cfg(lo), pkg.channel_cfg(hi), pkg.channel_cfg((lo + hi) // 2)])
+    assert [p.channel(i).bin for i in range(3)] == [b_always] * 3
+    p.close()
+    run.close()
+
+
+def test_side_stream_two_calls_and_timing(pkg):
+    """case 10: two calls into different output buffers on a side stream without a host wait in between, then one synchronisation: both
+    byte-identical to each other and to a run on the NULL stream; per-launch times are finite and positive."""
+    import torch
+    dev = device(pkg, 2560000, 8)
+    raws, models = noise_case(2560000, 8, sv.SFMT_U8, 127.5, 2000, 2, 2)
+    run = Run(pkg, dev, raws, 2000, 2)
+    base = run.call()  # hip_stream None: the NULL stream
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    a, b = run.outputs(), run.outputs()
+    torch.cuda.synchronize()
+    run.call(side.cuda_stream, a)
+    run.call(side.cuda_stream, b)
+    side.synchronize()
+    check("NULL stream", run, base, models)
+    for t_base, t_a, t_b in zip(base, a, b):
+        assert torch.equal(t_base, t_a) and torch.equal(t_a, t_b)
+    with pytest.raises(pkg.MiError):
+        run.survey.last_launch_ms()  # no timed call yet
+    run.survey.set_timing(True)
+    run.call(side.cuda_stream, a)
+    ms = run.survey.last_launch_ms()
+    print(f"fft 256, 2 streams x 2 cells of 2000: windows {ms[0]:.4f} ms, fold {ms[1]:.4f} ms")
+    assert len(ms) == 2 and all(np.isfinite(m) and m > 0 for m in ms)
+    run.survey.set_timing(False)
+    assert torch.equal(a[0], base[0]) and torch.equal(a[1], base[1])
+    run.close()
+
+
+def test_refusals_on_the_device(pkg):
+    """case 11"""
+    import torch
+    dev = device(pkg, 2560000, 8)
+    for log2n in (7, 14):
+        with pytest.raises(pkg.MiError) as e:
+            pkg.Survey(device(pkg, 2560000, log2n), nstreams=1, max_cells=1)
+        assert e.value.code == pkg.MI_ERR_INVALID and "fft_size" in str(e.value)
+    for gpu in (-1, torch.cuda.device_count()):
+        with pytest.raises(pkg.MiError) as e:
+            pkg.Survey(dev, nstreams=1, max_cells=1, gpu=gpu)
+        assert e.value.code == pkg.MI_ERR_INVALID and "gpu index out of range" in str(e.value)
+    wpc, max_cells = 10, 2
+    raw = np.full(2 * sv.samples_needed(dev, wpc * (max_cells + 1)), 128, np.uint8)
+    run = Run(pkg, dev, [raw, raw], wpc, max_cells)
+    mean, peak = run.outputs()
+
+    def refused(text, fn):
+        with pytest.raises(pkg.MiError) as e:
+            fn()
+        assert e.value.code == pkg.MI_ERR_INVALID and text in str(e.value), str(e.value)
+
+    s = run.survey
+    refused("16-byte aligned", lambda: s.process_device(run.d_iq, run.stride, 1, mean.data_ptr() + 4, peak.data_ptr()))
+    refused("16-byte aligned", lambda: s.process_device(run.d_iq, run.stride, 1, mean.data_ptr(), peak.data_ptr() + 8))
+    refused("ncells outside 1 .. max_cells", lambda: s.process_device(run.d_iq, run.stride, 0, mean.data_ptr(), peak.data_ptr()))
+    refused("ncells outside 1 .. max_cells", lambda: s.process_device(run.d_iq, run.stride, max_cells + 1, mean.data_ptr(), peak.data_ptr()))
+    refused("one complex sample", lambda: s.process_device(run.d_iq + 1, run.stride, 1, mean.data_ptr(), peak.data_ptr()))
+    refused("NULL argument", lambda: s.process_device(None, run.stride, 1, mean.data_ptr(), peak.data_ptr()))
+    refused("no stream enabled", lambda: s.set_streams([0, 0]))
+    torch.cuda.synchronize()
+    assert (mean.cpu().numpy() == SENT).all() and (peak.cpu().numpy() == SENT).all(), "a refused call wrote"
+    # the refused mask left the old one in place: both streams still take part
+    run.call(out=(mean, peak))
+    torch.cuda.synchronize()
+    m = mean.cpu().numpy()[:2 * max_cells * 256]
+    assert (m != SENT).all()
+    run.close()
