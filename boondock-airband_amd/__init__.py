@@ -120,6 +120,25 @@ TX_STATE_DTYPE = np.dtype([("clock", "<u8"), ("opened", "<u8"), ("last_write", "
                            ("zero", "<u2")])  # one row of the splitter's state blob, MI_TX_STATE_ROW_BYTES = 32
 TX_NONE = 0xFFFFFFFF  # first_batch of a record without blocks, close_batch of a file still open
 
+
+class OccCfg(C.Structure):  # mi_occ_cfg: 0 = 250 permille / ratio 3.0 / 1 cell
+    _fields_ = [("floor_permille", C.c_uint32), ("ratio", C.c_float), ("min_cells", C.c_uint32)]
+
+
+class OccBin(C.Structure):  # mi_occ_bin
+    _fields_ = [("floor", C.c_float), ("threshold", C.c_float), ("active_cells", C.c_uint32), ("first_cell", C.c_uint32), ("last_cell", C.c_uint32),
+                ("runs", C.c_uint32), ("max_mean", C.c_float), ("max_peak", C.c_float)]
+
+
+class OccCandidate(C.Structure):  # mi_occ_candidate
+    _fields_ = [("stream", C.c_uint32), ("best_bin", C.c_uint32), ("lo_bin", C.c_uint32), ("hi_bin", C.c_uint32), ("nbins", C.c_uint32),
+                ("active_cells", C.c_uint32), ("first_cell", C.c_uint32), ("last_cell", C.c_uint32), ("max_mean", C.c_float), ("max_peak", C.c_float)]
+
+
+OCC_BIN_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in OccBin._fields_])  # the same 32 bytes as a numpy record
+OCC_CAND_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in OccCandidate._fields_])  # the same 40 bytes
+OCC_NONE = 0xFFFFFFFF  # first_cell / last_cell of a bin without an active cell
+
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
@@ -132,6 +151,8 @@ ABI_SYMBOLS = [
     "mi_txsplit_get_state", "mi_txsplit_set_state", "mi_txsplit_set_timing", "mi_txsplit_last_launch_ms", "mi_tx_plan_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
+    "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
+    "mi_occupancy_set_timing", "mi_occupancy_last_launch_ms", "mi_occupancy_plan_host",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
 
@@ -230,6 +251,15 @@ def lib():
         L.mi_survey_set_timing.argtypes = [vp, C.c_int]
         L.mi_survey_last_launch_ms.argtypes = [vp, vp]
         L.mi_survey_bin_range.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.mi_occupancy_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(OccCfg), C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_occupancy_destroy.argtypes = [vp]
+        L.mi_occupancy_destroy.restype = None
+        L.mi_occupancy_set_streams.argtypes = [vp, vp]
+        L.mi_occupancy_process_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+        L.mi_occupancy_download.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mi_occupancy_set_timing.argtypes = [vp, C.c_int]
+        L.mi_occupancy_last_launch_ms.argtypes = [vp, vp]
+        L.mi_occupancy_plan_host.argtypes = [C.POINTER(DeviceCfg), C.POINTER(OccCfg), vp, C.c_int, vp, vp, C.c_int, vp, vp, sz, vp, vp]
         L.mi_plan_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(ChannelCfg), C.c_int, C.POINTER(vp)]
         L.mi_plan_destroy.argtypes = [vp]
         L.mi_plan_destroy.restype = None
@@ -862,6 +892,81 @@ def survey_bin_range(dev, bin):
     lo, hi = C.c_int(), C.c_int()
     _check(lib().mi_survey_bin_range(C.byref(dev), bin, C.byref(lo), C.byref(hi)))
     return lo.value, hi.value
+
+
+def _occ_cfg(cfg):
+    """None, an OccCfg or (floor_permille, ratio, min_cells) -> a pointer to an OccCfg, or None (all defaults)"""
+    if cfg is None:
+        return None
+    return C.byref(cfg if isinstance(cfg, OccCfg) else OccCfg(int(cfg[0]), float(cfg[1]), int(cfg[2])))
+
+
+class Occupancy(_Handle):
+    """mi_occupancy: the channel finder -- from the survey's planes to one OCC_BIN_DTYPE record per (stream, bin) and to channel
+    candidates (OCC_CAND_DTYPE), the maximal runs of occupied bins in frequency order.  cfg: (floor_permille, ratio, min_cells), 0 = the
+    default 250 / 3.0 / 1; max_candidates: capacity of the candidate buffer, 0 = nstreams * fft_size / 2.  Stateless between calls."""
+    _destroy = "mi_occupancy_destroy"
+
+    def __init__(self, dev, nstreams=1, max_cells=1, cfg=None, max_candidates=0, gpu=0):
+        self.nstreams, self.max_cells = nstreams, max_cells
+        self.fft_size = 1 << dev.fft_size_log
+        most = nstreams * self.fft_size // 2
+        self.max_candidates = min(max_candidates, most) if max_candidates else most
+        self._h = C.c_void_p()
+        _check(lib().mi_occupancy_create(C.byref(dev), _occ_cfg(cfg), nstreams, max_cells, max_candidates, gpu, C.byref(self._h)))
+
+    def set_streams(self, enabled=None):
+        """enabled: truth value per stream, or None = all.  A disabled stream is not read, gets no bin record and no candidate."""
+        en = None if enabled is None else _flags(enabled)
+        assert en is None or en.size == self.nstreams
+        _check(lib().mi_occupancy_set_streams(self._h, None if en is None else _ptr(en)))
+
+    def process_device(self, d_mean, d_peak, ncells, d_bins, d_cands, d_stream_first, d_count, hip_stream=None):
+        """Raw device pointers (ints): d_mean and d_peak float32 [nstreams][ncells][fft_size] as Survey.process_device wrote them;
+        asynchronous on hip_stream."""
+        _check(lib().mi_occupancy_process_device(self._h, d_mean, d_peak, ncells, d_bins, d_cands, d_stream_first, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (bins [nstreams][fft_size] of OCC_BIN_DTYPE, candidates [k] of
+        OCC_CAND_DTYPE, stream_first [nstreams + 1], count [2]) with k = count[1], the number of candidates stored."""
+        bins = np.zeros((self.nstreams, self.fft_size), OCC_BIN_DTYPE)
+        cands = np.zeros(self.max_candidates, OCC_CAND_DTYPE)
+        first = np.empty(self.nstreams + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_occupancy_download(self._h, hip_stream, _ptr(bins), _ptr(cands), _ptr(first), _ptr(count)))
+        return bins, cands[:int(count[1])], first, count
+
+    def set_timing(self, on=True):
+        _check(lib().mi_occupancy_set_timing(self._h, 1 if on else 0))
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of the four launches of the last call made with set_timing(True): bin records, run starts, scan, candidates"""
+        ms = (C.c_float * 4)()
+        _check(lib().mi_occupancy_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
+        return tuple(ms)
+
+
+def occupancy_plan_host(dev, mean, peak, cfg=None, enabled=None, max_candidates=0, bins=None, cands=None):
+    """mi_occupancy_plan_host: the finder on the host, no GPU.  mean, peak: float32 [nstreams][ncells][fft_size]; enabled: truth value per
+    stream or None = all.  bins / cands: arrays to write into (a test's sentinel-filled ones), default fresh zeros.  Returns (bins
+    [nstreams][fft_size], cands -- the whole buffer if one was given, else the count[1] stored --, stream_first [nstreams + 1], count [2])."""
+    mean = np.ascontiguousarray(mean, dtype=np.float32)
+    peak = np.ascontiguousarray(peak, dtype=np.float32)
+    n = 1 << dev.fft_size_log
+    assert mean.ndim == 3 and mean.shape == peak.shape
+    ns, ncells = mean.shape[0], mean.shape[1]
+    en = None if enabled is None else _flags(enabled)
+    assert en is None or en.size == ns
+    cap = max_candidates or ns * n // 2
+    given = cands is not None
+    bins = np.zeros((ns, n), OCC_BIN_DTYPE) if bins is None else bins
+    cands = np.zeros(cap, OCC_CAND_DTYPE) if cands is None else cands
+    assert bins.dtype == OCC_BIN_DTYPE and bins.size >= ns * n and cands.dtype == OCC_CAND_DTYPE and cands.size >= min(cap, ns * n // 2)
+    first = np.empty(ns + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_occupancy_plan_host(C.byref(dev), _occ_cfg(cfg), None if en is None else _ptr(en), ns, _ptr(mean), _ptr(peak), ncells, _ptr(bins),
+                                        _ptr(cands), max_candidates, _ptr(first), _ptr(count)))
+    return bins, (cands if given else cands[:int(count[1])]), first, count
 
 
 # ---- the BASELINE.json channel plans (SURVEY 8d) ----

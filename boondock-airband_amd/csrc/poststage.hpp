@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,5 +108,11 @@ struct TxRowState {
 static_assert(sizeof(TxRowState) == MI_TX_STATE_ROW_BYTES && sizeof(mi_tx_record) == 40, "the splitter's blob and record layouts are ABI");
 
 mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg);  // poststage_host.cpp
+
+static_assert(sizeof(mi_occ_bin) == 32 && sizeof(mi_occ_candidate) == 40, "the channel finder's record layouts are ABI");
+
+// The channel finder's settings with the defaults filled in and its view of the device configuration (poststage_host.cpp): MI_OK, or
+// the refusal with its message set.  *log2n: the one field the arithmetic uses.
+int occ_settings(const mi_device_cfg* dev, const mi_occ_cfg* cfg, mi_occ_cfg* out, int* log2n);
 
 }  // namespace mi

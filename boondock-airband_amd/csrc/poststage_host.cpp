@@ -1,7 +1,7 @@
 // poststage_host.cpp -- the host twins of the output gate and the transmission splitter: what the device stages compute, from flags
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
-// too: mi_survey_bin_range, the plan's bin rule read backwards.
+// too: mi_survey_bin_range, the plan's bin rule read backwards; and the channel finder's twin, mi_occupancy_plan_host.
 #include <algorithm>
 #include <cmath>
 
@@ -198,5 +198,123 @@ extern "C" int mi_tx_plan_host(const mi_tx_cfg* cfg, const uint8_t* row_enabled,
     row_first_record[rows] = k;
     count[0] = k;
     count[1] = k < max_records ? k : static_cast<uint32_t>(max_records);
+    return MI_OK;
+}
+
+// ---- channel finder, host side (include/mi_airband.h "channel finder"): the settings both halves share, and the twin of
+// occupancy.hip -- the floor by std::nth_element on a copy of the column, everything else one pass in cell or position order.
+namespace mi {
+
+int occ_settings(const mi_device_cfg* dev, const mi_occ_cfg* cfg, mi_occ_cfg* out, int* log2n) {
+    mi_occ_cfg c = cfg ? *cfg : mi_occ_cfg{0, 0.0f, 0};
+    if (c.floor_permille > 1000)
+        return fail(MI_ERR_INVALID, "channel finder: floor_permille must be at most 1000");
+    if (!std::isfinite(c.ratio) || c.ratio < 0.0f)
+        return fail(MI_ERR_INVALID, "channel finder: ratio must be finite and not negative (0 = the default 3.0)");
+    c.floor_permille = c.floor_permille ? c.floor_permille : 250;
+    c.ratio = c.ratio != 0.0f ? c.ratio : 3.0f;  // the amplitude ratio of 9.54 dB, the reference's default squelch SNR
+    c.min_cells = c.min_cells ? c.min_cells : 1;
+    // the device configuration as the plan sees it: built for one channel at the centre frequency, as the band survey does
+    mi_channel_cfg ch{};
+    ch.freq = dev->centerfreq;
+    ch.modulation = MI_MOD_AM;
+    ch.squelch_snr_db = -1.0f;
+    ch.ampfactor = 1.0f;
+    ch.tau = -1;
+    Plan plan;
+    const char* msg = "";
+    if (const int rc = build_plan(*dev, &ch, 1, plan, &msg))
+        return fail(rc, msg);
+    *out = c;
+    *log2n = plan.log2n;
+    return MI_OK;
+}
+
+}  // namespace mi
+
+extern "C" int mi_occupancy_plan_host(const mi_device_cfg* dev, const mi_occ_cfg* cfg, const uint8_t* stream_enabled, int nstreams, const float* mean,
+                                      const float* peak, int ncells, mi_occ_bin* bins, mi_occ_candidate* cands, size_t max_candidates,
+                                      uint32_t* stream_first, uint32_t* count) {
+    if (!dev || !mean || !peak || !bins || !cands || !stream_first || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (nstreams < 1 || nstreams > 65535 || ncells < 1 || ncells >= (1 << 24))
+        return fail(MI_ERR_INVALID, "channel finder needs 1 <= nstreams < 2^16 and 1 <= ncells < 2^24");
+    mi_occ_cfg c;
+    int log2n = 0;
+    if (const int rc = mi::occ_settings(dev, cfg, &c, &log2n))
+        return rc;
+    bool any = false;
+    for (int s = 0; s < nstreams; ++s)
+        any = any || !stream_enabled || stream_enabled[s];
+    if (!any)
+        return fail(MI_ERR_INVALID, "channel finder: no stream enabled");
+    const size_t n = size_t{1} << log2n, cells = static_cast<size_t>(ncells);
+    const size_t most = static_cast<size_t>(nstreams) * n / 2;
+    const size_t cap = max_candidates && max_candidates < most ? max_candidates : most;
+    const size_t kth = static_cast<size_t>(static_cast<uint64_t>(ncells - 1) * c.floor_permille / 1000);
+    constexpr uint32_t kNone = 0xFFFFFFFFu;
+    std::vector<float> col(cells);
+    uint32_t k = 0;
+    for (int s = 0; s < nstreams; ++s) {
+        stream_first[s] = k;
+        if (stream_enabled && !stream_enabled[s])
+            continue;
+        const float* m = mean + static_cast<size_t>(s) * cells * n;
+        const float* pk = peak + static_cast<size_t>(s) * cells * n;
+        mi_occ_bin* sb = bins + static_cast<size_t>(s) * n;
+        for (size_t b = 0; b < n; ++b) {
+            for (size_t cell = 0; cell < cells; ++cell)
+                col[cell] = m[cell * n + b];
+            std::nth_element(col.begin(), col.begin() + static_cast<std::ptrdiff_t>(kth), col.end());
+            mi_occ_bin r{col[kth], 0.0f, 0, kNone, kNone, 0, 0.0f, 0.0f};
+            r.threshold = r.floor * c.ratio;
+            bool before = false;
+            for (size_t cell = 0; cell < cells; ++cell) {
+                const float v = m[cell * n + b];
+                const bool active = v > r.threshold;
+                if (active) {
+                    r.active_cells += 1;
+                    r.first_cell = r.first_cell == kNone ? static_cast<uint32_t>(cell) : r.first_cell;
+                    r.last_cell = static_cast<uint32_t>(cell);
+                    r.runs += before ? 0 : 1;
+                    r.max_mean = v > r.max_mean ? v : r.max_mean;
+                    r.max_peak = pk[cell * n + b] > r.max_peak ? pk[cell * n + b] : r.max_peak;
+                }
+                before = active;
+            }
+            sb[b] = r;
+        }
+        // candidates: maximal runs of occupied positions, position p = (bin + n / 2) % n
+        mi_occ_candidate cur{};
+        bool open = false;
+        for (size_t p = 0; p <= n; ++p) {
+            const size_t b = (p + n / 2) % n;
+            const bool occupied = p < n && sb[b].active_cells >= c.min_cells;
+            if (occupied && !open) {
+                cur = mi_occ_candidate{static_cast<uint32_t>(s), static_cast<uint32_t>(b), static_cast<uint32_t>(b), 0, 0, 0, 0, 0, 0.0f, 0.0f};
+                open = true;
+            } else if (occupied && sb[b].max_mean > sb[cur.best_bin].max_mean) {
+                cur.best_bin = static_cast<uint32_t>(b);
+            }
+            if (occupied) {
+                cur.hi_bin = static_cast<uint32_t>(b);
+                cur.nbins += 1;
+            } else if (open) {
+                const mi_occ_bin& best = sb[cur.best_bin];
+                cur.active_cells = best.active_cells;
+                cur.first_cell = best.first_cell;
+                cur.last_cell = best.last_cell;
+                cur.max_mean = best.max_mean;
+                cur.max_peak = best.max_peak;
+                if (k < cap)
+                    cands[k] = cur;
+                ++k;
+                open = false;
+            }
+        }
+    }
+    stream_first[nstreams] = k;
+    count[0] = k;
+    count[1] = k < cap ? k : static_cast<uint32_t>(cap);
     return MI_OK;
 }

@@ -586,6 +586,86 @@ int mi_survey_last_launch_ms(mi_survey* s, float* ms /* [2] */);
  * MI_ERR_INVALID: bin outside 0 .. fft_size - 1, or a device configuration the plan refuses. */
 int mi_survey_bin_range(const mi_device_cfg* dev, int bin, int* lo_hz, int* hi_hz);
 
+/* ---------------- channel finder: occupancy and channel candidates from the survey's planes ----------------
+ * The link between the band survey and a channel plan: which bins carry something, and when.  It reads the two planes
+ * mi_survey_process_device wrote -- d_mean, d_peak [nstreams][ncells][fft_size] float32, FFT bin order -- and keeps no state between
+ * calls: one call looks at the ncells cells it is given.  Values are non-negative and finite, as the survey emits them; a set sign
+ * bit, NaN and Inf are unspecified.  With N = fft_size, per (stream, bin):
+ *   floor      the element at index k = (ncells - 1) * floor_permille / 1000 (integer division) of the bin's `mean` over the call's
+ *              cells sorted ascending: an exact order statistic, not an estimate
+ *   threshold  floor * ratio, one float32 multiply
+ *   cell c is active iff mean[c][bin] > threshold
+ *   mi_occ_bin: the floor, the threshold, the number of active cells, the first and the last of them (0xFFFFFFFF when none), the
+ *              number of maximal runs of consecutive active cells ("transmissions" at cell resolution), and the maxima of mean and of
+ *              peak over the active cells (0.0f when none)
+ * Per stream, the candidates.  Bins are walked in frequency order: position p = (bin + N / 2) % N, so position 0 is bin N / 2, the
+ * bottom of the band, bins N - 1 and 0 are neighbours in the middle, and the band does not wrap.  A bin is occupied iff
+ * active_cells >= min_cells; a candidate is a maximal run of occupied positions (the Blackman-7 main lobe spreads one strong
+ * carrier over up to about 13 bins, which is why the clustering is done here).  mi_occ_candidate: the stream, best_bin = the run's
+ * bin with the largest max_mean (ties: the lowest position), lo_bin / hi_bin = the FFT-order bins at the run's lowest and highest
+ * position, nbins, and best_bin's active_cells, first_cell, last_cell, max_mean and max_peak.  Candidates are stored streams
+ * ascending, positions ascending within a stream.  mi_survey_bin_range(best_bin) gives frequencies mi_plan_create maps to that bin.
+ * Configuration (mi_occ_cfg, a field that is 0 takes its default): floor_permille 250 (at most 1000); ratio 3.0f, the amplitude ratio
+ * of the reference's default squelch SNR of 9.54 dB (squelch.cpp constructor defaults) -- a caller's setting, not a tolerance, and
+ * not validated on a real band; min_cells 1 (at most max_cells).
+ * Disabled streams (mi_occupancy_set_streams, the companion of mi_survey_set_streams): a disabled stream's planes are not read, its
+ *   mi_occ_bin region is not written and it has no candidates (its d_stream_first entries repeat).  NULL enables all (the default).
+ *   A mask that enables no stream is refused and the mask stays as it was.  Completes queued work first.
+ * Execution: asynchronous on `hip_stream`, no host synchronisation; four kernels (bin records; run starts; scan; candidates).  The
+ *   run starts of a call live in the handle: calls of one handle go to one stream, or are ordered by the caller.
+ * Determinism: no floating-point atomics (integer counts in LDS only, which are order-free): every output byte is the same on every
+ *   run, and equals mi_occupancy_plan_host's.
+ * Only fft_size_log of the device configuration enters the arithmetic; the rest is checked as the plan checks it.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, floor_permille > 1000, a ratio that is negative or
+ * not finite, min_cells > max_cells, misaligned buffers, ncells outside 1 .. max_cells, or a device configuration the plan refuses. */
+typedef struct { uint32_t floor_permille; float ratio; uint32_t min_cells; } mi_occ_cfg; /* 0 = 250 / 3.0f / 1 */
+typedef struct {
+    float floor, threshold;
+    uint32_t active_cells;
+    uint32_t first_cell, last_cell; /* 0xFFFFFFFF when no cell is active */
+    uint32_t runs;                  /* maximal runs of consecutive active cells */
+    float max_mean, max_peak;       /* over the active cells; 0.0f when none */
+} mi_occ_bin;                       /* 32 bytes */
+typedef struct {
+    uint32_t stream;
+    uint32_t best_bin;                            /* largest max_mean of the run; ties: the lowest position */
+    uint32_t lo_bin, hi_bin;                      /* FFT-order bins at the run's lowest and highest position */
+    uint32_t nbins;
+    uint32_t active_cells, first_cell, last_cell; /* best_bin's */
+    float max_mean, max_peak;                     /* best_bin's */
+} mi_occ_candidate;                               /* 40 bytes */
+typedef struct mi_occupancy mi_occupancy;
+/* cfg NULL = all defaults; 1 <= nstreams < 2^16, 1 <= max_cells < 2^24; max_candidates: capacity of the caller's candidate buffer,
+ * 0 = nstreams * fft_size / 2, the most that alternating bins can give */
+int mi_occupancy_create(const mi_device_cfg* dev, const mi_occ_cfg* cfg, int nstreams, int max_cells, size_t max_candidates, int gpu,
+                        mi_occupancy** out);
+void mi_occupancy_destroy(mi_occupancy* o);
+int mi_occupancy_set_streams(mi_occupancy* o, const uint8_t* stream_enabled /* [nstreams] or NULL = all */);
+/* One call over ncells (1 .. max_cells) cells.  d_mean, d_peak: device [nstreams][ncells][fft_size], 16-byte aligned.  Outputs, all
+ * in device memory:
+ *   d_bins          [nstreams][fft_size]  in FFT bin order (16-byte aligned)
+ *   d_cands         [max_candidates]      (8-byte aligned)
+ *   d_stream_first  [nstreams + 1]        exclusive prefix of the streams' candidate counts
+ *   d_count         [2]                   candidates found, and min(that, max_candidates) = the number stored
+ * Nothing is written at or beyond max_candidates. */
+int mi_occupancy_process_device(mi_occupancy* o, const float* d_mean, const float* d_peak, int ncells, mi_occ_bin* d_bins,
+                                mi_occ_candidate* d_cands, uint32_t* d_stream_first, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_occupancy_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] candidates; bins holds nstreams * fft_size records (a disabled stream's are copied as they lie in d_bins),
+ * stream_first nstreams + 1.  bins, cands and stream_first may each be NULL.  The one place that synchronises. */
+int mi_occupancy_download(mi_occupancy* o, void* hip_stream, mi_occ_bin* bins, mi_occ_candidate* cands, uint32_t* stream_first,
+                          uint32_t* count /* [2] */);
+/* (diagnostic) as mi_outgate_set_timing; ms[4] = {bin records, run starts, scan, candidates}.  tools/occupancy_rate.py. */
+int mi_occupancy_set_timing(mi_occupancy* o, int on);
+int mi_occupancy_last_launch_ms(mi_occupancy* o, float* ms /* [4] */);
+/* The host twin: no GPU and no HIP call; the same bytes in every output, and nothing written in a disabled stream's region of bins.
+ * stream_enabled [nstreams] or NULL = all; mean, peak [nstreams][ncells][fft_size]; bins [nstreams][fft_size]; cands holds
+ * max_candidates entries (0 = nstreams * fft_size / 2), of which count[1] are written.  There is no max_cells here, so min_cells is
+ * not bounded: a min_cells above ncells leaves no bin occupied, as it does on the device. */
+int mi_occupancy_plan_host(const mi_device_cfg* dev, const mi_occ_cfg* cfg, const uint8_t* stream_enabled, int nstreams, const float* mean,
+                           const float* peak, int ncells, mi_occ_bin* bins, mi_occ_candidate* cands, size_t max_candidates,
+                           uint32_t* stream_first, uint32_t* count /* [2] */);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
