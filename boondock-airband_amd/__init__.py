@@ -139,6 +139,27 @@ OCC_BIN_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in OccBin._fields_])  # the 
 OCC_CAND_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in OccCandidate._fields_])  # the same 40 bytes
 OCC_NONE = 0xFFFFFFFF  # first_cell / last_cell of a bin without an active cell
 
+
+class ProbeTarget(C.Structure):  # mi_probe_target
+    _fields_ = [("stream", C.c_uint32), ("bin", C.c_uint32)]
+
+
+class ProbeCell(C.Structure):  # mi_probe_cell
+    _fields_ = [("s1", C.c_double), ("s2", C.c_double), ("r_re", C.c_double), ("r_im", C.c_double), ("windows", C.c_uint32), ("pairs", C.c_uint32)]
+
+
+class ProbeFeatures(C.Structure):  # mi_probe_features
+    _fields_ = [("s1", C.c_double), ("s2", C.c_double), ("r_re", C.c_double), ("r_im", C.c_double), ("n", C.c_uint64), ("pairs", C.c_uint64),
+                ("cv2", C.c_double), ("coherence", C.c_double), ("dphi", C.c_double), ("carrier_hz", C.c_double)]
+
+
+class ProbeRule(C.Structure):  # mi_probe_rule: 0 = the default
+    _fields_ = [("coherence_max", C.c_double), ("cv2_min", C.c_double)]
+
+
+PROBE_TARGET_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ProbeTarget._fields_])  # the same 8 bytes as a numpy record
+PROBE_CELL_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ProbeCell._fields_])  # the same 40 bytes
+
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
@@ -153,6 +174,8 @@ ABI_SYMBOLS = [
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
     "mi_occupancy_set_timing", "mi_occupancy_last_launch_ms", "mi_occupancy_plan_host",
+    "mi_probe_create", "mi_probe_destroy", "mi_probe_set_targets", "mi_probe_bytes_needed", "mi_probe_process_device", "mi_probe_download",
+    "mi_probe_set_timing", "mi_probe_last_launch_ms", "mi_probe_targets_from_candidates", "mi_probe_features_host", "mi_probe_classify_host",
     "mi_gather_unique_id", "mi_gather_loopback_id", "mi_gather_create", "mi_gather_destroy", "mi_gather_audio", "mi_gather_stream_wait", "mi_gather_sync",
 ]
 
@@ -260,6 +283,19 @@ def lib():
         L.mi_occupancy_set_timing.argtypes = [vp, C.c_int]
         L.mi_occupancy_last_launch_ms.argtypes = [vp, vp]
         L.mi_occupancy_plan_host.argtypes = [C.POINTER(DeviceCfg), C.POINTER(OccCfg), vp, C.c_int, vp, vp, C.c_int, vp, vp, sz, vp, vp]
+        L.mi_probe_create.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mi_probe_destroy.argtypes = [vp]
+        L.mi_probe_destroy.restype = None
+        L.mi_probe_set_targets.argtypes = [vp, vp, C.c_int]
+        L.mi_probe_bytes_needed.argtypes = [vp, C.c_int]
+        L.mi_probe_bytes_needed.restype = sz
+        L.mi_probe_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp]
+        L.mi_probe_download.argtypes = [vp, vp, vp]
+        L.mi_probe_set_timing.argtypes = [vp, C.c_int]
+        L.mi_probe_last_launch_ms.argtypes = [vp, vp]
+        L.mi_probe_targets_from_candidates.argtypes = [vp, sz, vp]
+        L.mi_probe_features_host.argtypes = [C.POINTER(DeviceCfg), C.c_int, vp, C.c_int, vp, C.POINTER(ProbeFeatures)]
+        L.mi_probe_classify_host.argtypes = [C.POINTER(ProbeFeatures), C.POINTER(ProbeRule), C.POINTER(C.c_int)]
         L.mi_plan_create.argtypes = [C.POINTER(DeviceCfg), C.POINTER(ChannelCfg), C.c_int, C.POINTER(vp)]
         L.mi_plan_destroy.argtypes = [vp]
         L.mi_plan_destroy.restype = None
@@ -967,6 +1003,85 @@ def occupancy_plan_host(dev, mean, peak, cfg=None, enabled=None, max_candidates=
     _check(lib().mi_occupancy_plan_host(C.byref(dev), _occ_cfg(cfg), None if en is None else _ptr(en), ns, _ptr(mean), _ptr(peak), ncells, _ptr(bins),
                                         _ptr(cands), max_candidates, _ptr(first), _ptr(count)))
     return bins, (cands if given else cands[:int(count[1])]), first, count
+
+
+def _probe_targets(targets):
+    """a PROBE_TARGET_DTYPE array, or (stream, bin) pairs -> a contiguous PROBE_TARGET_DTYPE array"""
+    if isinstance(targets, np.ndarray) and targets.dtype == PROBE_TARGET_DTYPE:
+        return np.ascontiguousarray(targets)
+    return np.array([(int(s), int(b)) for s, b in targets], PROBE_TARGET_DTYPE)
+
+
+class Probe(_Handle):
+    """mi_probe: the channel probe -- for a list of targets (stream, bin), one PROBE_CELL_DTYPE record per (target, cell) with the
+    float64 sums of the bin's envelope and of z_w * conj(z_(w-1)) over the cell's windows.  The windows are the survey's.  Stateless
+    between calls; the target list stays until it is replaced."""
+    _destroy = "mi_probe_destroy"
+
+    def __init__(self, dev, nstreams=1, max_cells=1, windows_per_cell=0, max_targets=1, gpu=0):
+        self.nstreams, self.max_cells, self.max_targets = nstreams, max_cells, max_targets
+        self.windows_per_cell = windows_per_cell or WAVE_BATCH
+        self.fft_size = 1 << dev.fft_size_log
+        self.ntargets = self._last = 0
+        self._h = C.c_void_p()
+        _check(lib().mi_probe_create(C.byref(dev), nstreams, max_cells, windows_per_cell, max_targets, gpu, C.byref(self._h)))
+
+    def set_targets(self, targets):
+        """targets: (stream, bin) pairs or a PROBE_TARGET_DTYPE array, strictly ascending.  A refused list leaves the old one."""
+        t = _probe_targets(targets)
+        _check(lib().mi_probe_set_targets(self._h, _ptr(t), t.size))
+        self.ntargets = t.size
+
+    def bytes_needed(self, ncells):
+        return lib().mi_probe_bytes_needed(self._h, ncells)
+
+    def process_device(self, d_iq, stream_stride, ncells, d_cells, hip_stream=None):
+        """Raw device pointers (ints): d_cells [ntargets][ncells] of 40-byte records; asynchronous on hip_stream."""
+        _check(lib().mi_probe_process_device(self._h, d_iq, stream_stride, ncells, d_cells, hip_stream))
+        self._last = (self.ntargets, ncells)
+
+    def download(self, hip_stream=None):
+        """The records of the last process_device (enqueued on hip_stream): PROBE_CELL_DTYPE [ntargets][ncells]."""
+        cells = np.zeros(self._last or (0, 0), PROBE_CELL_DTYPE)
+        _check(lib().mi_probe_download(self._h, hip_stream, _ptr(cells)))
+        return cells
+
+    def set_timing(self, on=True):
+        _check(lib().mi_probe_set_timing(self._h, 1 if on else 0))
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of the two launches of the last call made with set_timing(True): the windows, the reduction"""
+        ms = (C.c_float * 2)()
+        _check(lib().mi_probe_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
+        return tuple(ms)
+
+
+def probe_targets_from_candidates(cands):
+    """mi_probe_targets_from_candidates: OCC_CAND_DTYPE [n] -> PROBE_TARGET_DTYPE [n], best_bin of each, sorted by (stream, bin).  No GPU."""
+    cands = np.ascontiguousarray(cands, dtype=OCC_CAND_DTYPE)
+    out = np.zeros(cands.size, PROBE_TARGET_DTYPE)
+    _check(lib().mi_probe_targets_from_candidates(_ptr(cands), cands.size, _ptr(out)))
+    return out
+
+
+def probe_features_host(dev, bin, cells, mask=None):
+    """mi_probe_features_host: the ProbeFeatures of one target from its PROBE_CELL_DTYPE [ncells] records; mask: truth value per cell or
+    None = all.  No GPU."""
+    cells = np.ascontiguousarray(cells, dtype=PROBE_CELL_DTYPE)
+    assert cells.ndim == 1
+    m = None if mask is None else _flags(mask)
+    assert m is None or m.size == cells.size
+    f = ProbeFeatures()
+    _check(lib().mi_probe_features_host(C.byref(dev), bin, _ptr(cells), cells.size, None if m is None else _ptr(m), C.byref(f)))
+    return f
+
+
+def probe_classify_host(features, rule=None):
+    """mi_probe_classify_host: MOD_AM or MOD_NFM; rule: None, a ProbeRule or (coherence_max, cv2_min), 0 = the default.  No GPU."""
+    r = None if rule is None else C.byref(rule if isinstance(rule, ProbeRule) else ProbeRule(float(rule[0]), float(rule[1])))
+    mod = C.c_int(-1)
+    _check(lib().mi_probe_classify_host(C.byref(features), r, C.byref(mod)))
+    return mod.value
 
 
 # ---- the BASELINE.json channel plans (SURVEY 8d) ----

@@ -1,4 +1,4 @@
-// fft_radix8.hpp -- the device pieces channelize.hip (stage 1) and survey.hip (the band survey) share: the geometry of an N-point
+// fft_radix8.hpp -- the device pieces channelize.hip (stage 1), survey.hip (the band survey) and probe.hip (the channel probe) share: the geometry of an N-point
 // FFT done by N/8 lanes, the butterflies of the documented FFT spec taken three radix-2 DIT stages at a time, the LDS
 // exchange between passes, and the sample conversion x window.  Internal linkage: every .hip that includes it gets its own copy.
 //
@@ -145,6 +145,30 @@ __device__ __forceinline__ void later_passes(float2 (&x)[8], const float2 (&twr)
                 xch[xpad(P::pos(tau, gi, ri))] = x[gi * P::G + ri];
         fft_sync<L>();
         later_passes<L, K + 1>(x, twr, xch, tau);
+    }
+}
+
+// The passes behind pass 0 with the lane's twiddles fetched where they are used: for the instantiations that cannot keep four passes
+// of them beside what they accumulate (N >= 4096: 1024 lanes a workgroup, 128 registers a lane).  Same butterflies.
+template <int L, int K>
+__device__ __forceinline__ void later_passes_tw(float2 (&x)[8], const float2* __restrict__ tw, float2* __restrict__ xch, int tau) {
+    if constexpr (K < FftGeom<L>::NPASS) {
+        using P = Pass<L, K>;
+        float2 r[7];
+        P::load_tw(tau, tw, r);
+#pragma unroll
+        for (int gi = 0; gi < P::GROUPS; ++gi)
+#pragma unroll
+            for (int ri = 0; ri < P::G; ++ri)
+                x[gi * P::G + ri] = xch[xpad(P::pos(tau, gi, ri))];
+        P::run(x, r);
+#pragma unroll
+        for (int gi = 0; gi < P::GROUPS; ++gi)
+#pragma unroll
+            for (int ri = 0; ri < P::G; ++ri)
+                xch[xpad(P::pos(tau, gi, ri))] = x[gi * P::G + ri];
+        fft_sync<L>();
+        later_passes_tw<L, K + 1>(x, tw, xch, tau);
     }
 }
 

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,7 +109,13 @@ static_assert(sizeof(TxRowState) == MI_TX_STATE_ROW_BYTES && sizeof(mi_tx_record
 
 mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg);  // poststage_host.cpp
 
+// The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
+// finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is
+// used.  MI_OK, or the plan's refusal with its message set.
+int device_plan(const mi_device_cfg& dev, Plan& p);
+
 static_assert(sizeof(mi_occ_bin) == 32 && sizeof(mi_occ_candidate) == 40, "the channel finder's record layouts are ABI");
+static_assert(sizeof(mi_probe_target) == 8 && sizeof(mi_probe_cell) == 40, "the channel probe's record layouts are ABI");
 
 // The channel finder's settings with the defaults filled in and its view of the device configuration (poststage_host.cpp): MI_OK, or
 // the refusal with its message set.  *log2n: the one field the arithmetic uses.

@@ -1,7 +1,8 @@
 // poststage_host.cpp -- the host twins of the output gate and the transmission splitter: what the device stages compute, from flags
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
-// too: mi_survey_bin_range, the plan's bin rule read backwards; and the channel finder's twin, mi_occupancy_plan_host.
+// too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
+// (target list, features, classification).
 #include <algorithm>
 #include <cmath>
 
@@ -21,6 +22,18 @@ mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg) {
     c.idle_batches = c.idle_batches ? c.idle_batches : kTxIdleBatches;
     c.max_batches = c.max_batches ? c.max_batches : kTxMaxBatches;
     return c;
+}
+
+int device_plan(const mi_device_cfg& dev, Plan& p) {
+    mi_channel_cfg ch{};
+    ch.freq = dev.centerfreq;
+    ch.modulation = MI_MOD_AM;
+    ch.squelch_snr_db = -1.0f;
+    ch.ampfactor = 1.0f;
+    ch.tau = -1;
+    const char* msg = "";
+    const int rc = build_plan(dev, &ch, 1, p, &msg);
+    return rc == MI_OK ? MI_OK : fail(rc, msg);
 }
 
 }  // namespace mi
@@ -214,17 +227,9 @@ int occ_settings(const mi_device_cfg* dev, const mi_occ_cfg* cfg, mi_occ_cfg* ou
     c.floor_permille = c.floor_permille ? c.floor_permille : 250;
     c.ratio = c.ratio != 0.0f ? c.ratio : 3.0f;  // the amplitude ratio of 9.54 dB, the reference's default squelch SNR
     c.min_cells = c.min_cells ? c.min_cells : 1;
-    // the device configuration as the plan sees it: built for one channel at the centre frequency, as the band survey does
-    mi_channel_cfg ch{};
-    ch.freq = dev->centerfreq;
-    ch.modulation = MI_MOD_AM;
-    ch.squelch_snr_db = -1.0f;
-    ch.ampfactor = 1.0f;
-    ch.tau = -1;
     Plan plan;
-    const char* msg = "";
-    if (const int rc = build_plan(*dev, &ch, 1, plan, &msg))
-        return fail(rc, msg);
+    if (const int rc = device_plan(*dev, plan))
+        return rc;
     *out = c;
     *log2n = plan.log2n;
     return MI_OK;
@@ -316,5 +321,76 @@ extern "C" int mi_occupancy_plan_host(const mi_device_cfg* dev, const mi_occ_cfg
     stream_first[nstreams] = k;
     count[0] = k;
     count[1] = k < cap ? k : static_cast<uint32_t>(cap);
+    return MI_OK;
+}
+
+// ---- channel probe, host side (include/mi_airband.h "channel probe"): the target list from the finder's candidates, and from the
+// cells of one target to the features a channel plan asks for.  probe.hip makes the cells.
+extern "C" int mi_probe_targets_from_candidates(const mi_occ_candidate* cands, size_t n, mi_probe_target* out) {
+    if (!cands || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    for (size_t i = 0; i < n; ++i)
+        out[i] = mi_probe_target{cands[i].stream, cands[i].best_bin};
+    std::sort(out, out + n, [](const mi_probe_target& a, const mi_probe_target& b) { return a.stream != b.stream ? a.stream < b.stream : a.bin < b.bin; });
+    return MI_OK;
+}
+
+extern "C" int mi_probe_features_host(const mi_device_cfg* dev, int bin, const mi_probe_cell* cells, int ncells, const uint8_t* cell_mask,
+                                      mi_probe_features* out) {
+    if (!dev || !cells || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (ncells < 1)
+        return fail(MI_ERR_INVALID, "channel probe: ncells must be at least 1");
+    mi::Plan plan;
+    if (const int rc = mi::device_plan(*dev, plan))
+        return rc;
+    int lo = 0, hi = 0;
+    if (const int rc = mi_survey_bin_range(dev, bin, &lo, &hi))
+        return rc;
+    mi_probe_features f{};
+    for (int c = 0; c < ncells; ++c) {
+        if (cell_mask && !cell_mask[c])
+            continue;
+        f.s1 += cells[c].s1;
+        f.s2 += cells[c].s2;
+        f.r_re += cells[c].r_re;
+        f.r_im += cells[c].r_im;
+        f.n += cells[c].windows;
+        f.pairs += cells[c].pairs;
+    }
+    if (f.n == 0 || f.s1 == 0.0) {
+        *out = mi_probe_features{};
+        return MI_OK;
+    }
+    const double n = static_cast<double>(f.n);
+    f.cv2 = n * f.s2 / (f.s1 * f.s1) - 1.0;
+    f.coherence = std::hypot(f.r_re, f.r_im) / f.s2;
+    f.dphi = std::atan2(f.r_im, f.r_re);
+    const double two_pi = 6.283185307179586476925286766559;
+    const double fw = static_cast<double>(dev->sample_rate) / static_cast<double>(plan.hop_samples());  // windows per second
+    const double f0 = f.dphi / two_pi * fw;
+    const double mid = (static_cast<double>(lo) + static_cast<double>(hi)) / 2.0;
+    const double centre = static_cast<double>(dev->centerfreq);
+    f.carrier_hz = centre + f0 + fw * std::nearbyint((mid - centre - f0) / fw);
+    *out = f;
+    return MI_OK;
+}
+
+namespace mi {
+// The geometric middles between the nearest AM and NFM values measured over the synthetic captures of DESIGN.md section 5g.
+constexpr double kProbeCoherenceMax = 0.9314, kProbeCv2Min = 0.1005;
+}  // namespace mi
+
+extern "C" int mi_probe_classify_host(const mi_probe_features* f, const mi_probe_rule* rule, int* modulation) {
+    if (!f || !modulation)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (f->n == 0)
+        return fail(MI_ERR_INVALID, "channel probe: no window selected, nothing to classify");
+    mi_probe_rule r = rule ? *rule : mi_probe_rule{0.0, 0.0};
+    if (!(r.coherence_max >= 0.0) || !(r.cv2_min >= 0.0) || !std::isfinite(r.coherence_max) || !std::isfinite(r.cv2_min))
+        return fail(MI_ERR_INVALID, "channel probe: the rule's thresholds must be finite and not negative (0 = the default)");
+    r.coherence_max = r.coherence_max != 0.0 ? r.coherence_max : mi::kProbeCoherenceMax;
+    r.cv2_min = r.cv2_min != 0.0 ? r.cv2_min : mi::kProbeCv2Min;
+    *modulation = (f->coherence < r.coherence_max || f->cv2 < r.cv2_min) ? MI_MOD_NFM : MI_MOD_AM;
     return MI_OK;
 }

@@ -1,0 +1,440 @@
+// probe.hip -- the channel probe: for a caller-given list of targets {stream, bin}, envelope and phase statistics of that bin over
+// each run of windows_per_cell consecutive windows (a cell).  It is the step between the channel finder and a channel plan: the
+// survey's planes keep magnitudes, and what tells an AM carrier from a constant-envelope NFM one, and where in its bin a carrier
+// sits, is the phase and how the envelope moves from window to window.  Definition: include/mi_airband.h "channel probe".
+//
+// A post-stage of its own like the band survey (survey.hip): its own handle, two launches on the caller's stream, no atomics.
+//   k_probe         one workgroup = one tile of consecutive windows of one stream that has targets.  The windows are the survey's and
+//                   stage 1's: the same span load, conversion x window and radix-8 passes (fft_radix8.hpp), so a bin's value has
+//                   the bits of the oracle's ao_fft_forward.  Behind the last pass, where k_survey takes all bins, lane tau of an
+//                   FFT takes the bins of the stream's targets tau, tau + N/8, ... (a stream has at most N) from the natural-order
+//                   spectrum in the exchange slot and stores {re, im} at z[target][window], the scratch plane in the handle.  Tiles
+//                   cut the call's windows, not the cells: the plane makes a window's predecessor a plain load, whatever tile or
+//                   cell it lies in.  A tile is walked TW windows of span at a time, as in k_survey.
+//   k_probe_reduce  one workgroup of 256 lanes = one (target, cell).
+// Order of the four float64 sums of a (target, cell) (fixed, so two runs give the same bytes): lane t adds the terms of the cell's
+// windows t, t + 256, t + 512, ... in turn; the 256 lanes' sums are then added by the halving tree -- lane t takes lane t + d for
+// d = 128, 64, ... 1.  The term of window w in r_re and r_im is formed from z[w] and z[w - 1]; window 0 of the call has none.
+//
+// Compile with -ffp-contract=off (the FFT spec; the float64 terms are sums of exact products and do not depend on it).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "../../include/mi_airband.h"
+#include "fft_radix8.hpp"
+#include "poststage.hpp"
+
+namespace mi {
+namespace {
+
+// a stream that has targets: its slice of the sorted target list
+struct ProbeStream {
+    int stream, first, count;
+};
+
+}  // namespace
+}  // namespace mi
+
+struct mi_probe {
+    int gpu = 0;
+    int nstreams = 0;
+    int max_cells = 0;
+    int max_targets = 0;
+    uint32_t wpc = 0;           // windows per cell
+    int log2n = 0, fft_size = 0, sfmt = 0, sample_bytes = 0;  // sample_bytes: one complex sample
+    bool conv_arith = false;
+    float conv_scale = 0.0f;
+    size_t hop_bytes = 0;
+    int ntargets = 0;  // 0 until mi_probe_set_targets
+    int nactive = 0;   // streams that have a target
+    mi::DevBuf<float> d_window, d_tw, d_levels;
+    mi::DevBuf<mi_probe_target> d_targets;  // [max_targets], the first ntargets
+    mi::DevBuf<mi::ProbeStream> d_active;   // [nstreams], the first nactive
+    mi::DevBuf<float2> d_z;                 // [max_targets][max_cells * wpc], the scratch plane
+    mi::LaunchTiming timing{"channel probe", 2};  // mi_probe_set_timing
+    bool timed = false;  // the last call was stamped
+    // the last mi_probe_process_device (what mi_probe_download reads)
+    const mi_probe_cell* last_cells = nullptr;
+    size_t last_records = 0;
+};
+
+namespace mi {
+namespace {
+
+constexpr int kProbeTilePieces = 2;  // a tile is this many TW-window pieces: enough workgroups for one stream, lane setup paid once per tile
+constexpr int kReduceBlock = 256;
+
+struct ProbeArgs {
+    const unsigned char* iq;  // stream s at iq + s*stream_stride
+    size_t stream_stride;
+    size_t valid_bytes;       // readable bytes per stream starting at its base
+    uint32_t hop_bytes;
+    uint32_t nwindows;        // of the call, per stream
+    uint32_t tile_windows;    // kProbeTilePieces * TW, set by the launcher
+    const float* window;
+    const float* tw;
+    const float* levels;
+    float conv_scale;
+    const ProbeStream* active;        // [gridDim.z]
+    const mi_probe_target* targets;
+    float2* z;                        // [targets][zstride]
+    size_t zstride;
+};
+
+template <int L, int SFMT>
+__global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) {
+    using Gm = FftGeom<L>;
+    constexpr int N = Gm::N, TPF = Gm::TPF, F = Gm::F, TW = Gm::TW, XN = Gm::XN, BLOCK = Gm::BLOCK;
+    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));  // bytes per complex sample
+    constexpr bool kTwInRegs = L <= 11;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int tid = threadIdx.x;
+    const ProbeStream as = a.active[blockIdx.z];
+    const unsigned wfirst = blockIdx.x * a.tile_windows;                         // first window of the tile, counted from the stream's base
+    const int nt = static_cast<int>(min(a.tile_windows, a.nwindows - wfirst));   // its windows: the last tile of the call may be short
+
+    const unsigned span_alloc = (static_cast<unsigned>(TW - 1) * a.hop_bytes + N * BPS2 + 16 + 15) & ~15u;
+    unsigned char* span = lds;
+    float* lut = reinterpret_cast<float*>(lds + span_alloc);
+    float2* xch_all = reinterpret_cast<float2*>(lds + span_alloc + 1024);
+    if constexpr (SFMT == MI_SFMT_U8 || SFMT == MI_SFMT_S8) {
+        for (int i = tid; i < 256; i += BLOCK)
+            lut[i] = a.levels[i];
+    }
+
+    // ---- per-lane constants: window coefficients of the 8 samples this lane converts, twiddles ----
+    const int f = tid / TPF;
+    const int tau = tid - f * TPF;
+    float2* xch = xch_all + f * XN;
+    const int nrev = (L > 3) ? static_cast<int>(__brev(static_cast<unsigned>(tau)) >> (32 - (L - 3))) : 0;
+    int nidx[8];
+    float wreg[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int rev3 = ((r & 1) << 2) | (r & 2) | ((r >> 2) & 1);
+        nidx[r] = rev3 * TPF + nrev;  // natural sample index = bitrev_L(8 tau + r)
+        wreg[r] = a.window[nidx[r]];
+    }
+    const float2* tw = reinterpret_cast<const float2*>(a.tw);
+    const float2 w8 = tw[N / 8], w83 = tw[3 * N / 8];
+    [[maybe_unused]] float2 twr[kTwInRegs ? Gm::NPASS : 1][7];
+    if constexpr (kTwInRegs)
+        load_all_tw<L, 1>(tau, tw, twr);
+    // the lane's targets are numbers tau, tau + TPF, ... of the stream's slice (count <= N = 8 TPF, so at most 8): their bins are read
+    // where they are used, a few cached loads beside a whole FFT: eight more registers a lane would add to what N = 8192 spills
+    const mi_probe_target* tg = a.targets + as.first;
+    float2* zrows = a.z + static_cast<size_t>(as.first) * a.zstride;
+
+    const unsigned char* gbase = a.iq + static_cast<size_t>(as.stream) * a.stream_stride;
+    for (int s0 = 0; s0 < nt; s0 += TW) {  // the tile, TW windows of span at a time
+        const int nw = min(TW, nt - s0);
+        if (s0)
+            __syncthreads();  // every FFT of the piece before has converted its samples
+        // ---- HBM -> LDS: the byte span of this piece, each byte read once, 16 B per lane ----
+        const long long b0 = (static_cast<long long>(wfirst) + s0) * static_cast<long long>(a.hop_bytes);
+        const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(gbase + b0) & 15);
+        const unsigned need = static_cast<unsigned>(nw - 1) * a.hop_bytes + N * BPS2;
+        const unsigned nchunks = (mis + need + 15) >> 4;
+        for (unsigned c = tid; c < nchunks; c += BLOCK) {
+            const long long off = b0 - mis + 16ll * c;
+            uint4 v;
+            if (off >= 0 && off + 16 <= static_cast<long long>(a.valid_bytes)) {
+                v = *reinterpret_cast<const uint4*>(gbase + off);
+            } else {  // the 16-byte lines around the first and the last byte of the call: nothing outside them is touched
+                unsigned char tmp[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const long long o = off + i;
+                    tmp[i] = (o >= 0 && o < static_cast<long long>(a.valid_bytes)) ? gbase[o] : 0;
+                }
+                v = *reinterpret_cast<uint4*>(tmp);
+            }
+            *reinterpret_cast<uint4*>(span + 16 * c) = v;
+        }
+        __syncthreads();
+
+        // ---- FFTs: F windows at a time ----
+        for (int it = 0; it * F < nw; ++it) {
+            const int wi = it * F + f;
+            const bool active = wi < nw;
+            float2 x[8];
+            const int wbyte = static_cast<int>(mis) + (active ? wi : 0) * static_cast<int>(a.hop_bytes);
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                x[r] = fetch_sample<SFMT>(span, wbyte + nidx[r] * BPS2, lut, a.conv_scale, wreg[r]);
+            pass0(x, w8, w83);
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                xch[xpad(tau * 8 + r)] = x[r];
+            fft_sync<L>();
+            if constexpr (kTwInRegs)
+                later_passes<L, 1>(x, twr, xch, tau);
+            else
+                later_passes_tw<L, 1>(x, tw, xch, tau);
+            // natural-order spectrum now sits in xch: the targets' bins, as stage 1 takes a picked one (rtl_airband.cpp:505-511)
+            if (active) {
+                const size_t w = static_cast<size_t>(wfirst) + static_cast<size_t>(s0 + wi);  // < nwindows <= zstride
+                for (int k = tau; k < as.count; k += TPF)
+                    zrows[static_cast<size_t>(k) * a.zstride + w] = xch[xpad(static_cast<int>(tg[k].bin))];
+            }
+            fft_sync<L>();  // the slot is rewritten by the next window's pass 0
+        }
+    }
+}
+
+// One workgroup = one (target, cell): blockIdx.x = target * ncells + cell.  The order of the sums is the file's head comment.
+__global__ __launch_bounds__(kReduceBlock) void k_probe_reduce(const float2* __restrict__ z, const size_t zstride, const uint32_t wpc,
+                                                              const uint32_t ncells, mi_probe_cell* __restrict__ cells) {
+    __shared__ double sh[4][kReduceBlock];
+    const int t = threadIdx.x;
+    const uint32_t target = blockIdx.x / ncells, cell = blockIdx.x - target * ncells;
+    const float2* row = z + static_cast<size_t>(target) * zstride;
+    const size_t w0 = static_cast<size_t>(cell) * wpc;
+    double s1 = 0.0, s2 = 0.0, rr = 0.0, ri = 0.0;
+    for (uint32_t i = t; i < wpc; i += kReduceBlock) {
+        const size_t w = w0 + i;
+        const float2 c = row[w];
+        const float m = sqrtf(c.x * c.x + c.y * c.y);
+        const double md = static_cast<double>(m);
+        s1 += md;
+        s2 += md * md;
+        if (w > 0) {
+            const float2 p = row[w - 1];
+            const double cr = c.x, ci = c.y, pr = p.x, pi = p.y;
+            rr += cr * pr + ci * pi;
+            ri += ci * pr - cr * pi;
+        }
+    }
+    sh[0][t] = s1, sh[1][t] = s2, sh[2][t] = rr, sh[3][t] = ri;
+    __syncthreads();
+    for (int d = kReduceBlock / 2; d >= 1; d >>= 1) {
+        if (t < d) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                sh[k][t] += sh[k][t + d];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        mi_probe_cell r;
+        r.s1 = sh[0][0], r.s2 = sh[1][0], r.r_re = sh[2][0], r.r_im = sh[3][0];
+        r.windows = wpc;
+        r.pairs = wpc - (cell == 0 ? 1u : 0u);
+        cells[blockIdx.x] = r;
+    }
+}
+
+template <int L, int SFMT>
+hipError_t launch_probe_one(ProbeArgs a, int nactive, hipStream_t s) {
+    using Gm = FftGeom<L>;
+    a.tile_windows = kProbeTilePieces * Gm::TW;
+    const unsigned tiles = (a.nwindows + a.tile_windows - 1) / a.tile_windows;
+    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
+    const unsigned span_alloc = (static_cast<unsigned>(Gm::TW - 1) * a.hop_bytes + Gm::N * BPS2 + 16 + 15) & ~15u;
+    const size_t lds = span_alloc + 1024 + static_cast<size_t>(Gm::F) * Gm::XN * 8;
+    if (lds > 160 * 1024)
+        return hipErrorInvalidValue;
+    auto kern = k_probe<L, SFMT>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(kern, dim3(tiles, 1, nactive), dim3(Gm::BLOCK), lds, s, a);
+    return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_probe_fmt(const ProbeArgs& a, int sfmt, bool conv_arith, int nactive, hipStream_t s) {
+    switch (sfmt) {
+        case MI_SFMT_U8:
+            return conv_arith ? launch_probe_one<L, kSfmtU8Arith>(a, nactive, s) : launch_probe_one<L, MI_SFMT_U8>(a, nactive, s);
+        case MI_SFMT_S8: return launch_probe_one<L, MI_SFMT_S8>(a, nactive, s);
+        case MI_SFMT_S16: return launch_probe_one<L, MI_SFMT_S16>(a, nactive, s);
+        case MI_SFMT_F32: return launch_probe_one<L, MI_SFMT_F32>(a, nactive, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_probe(const ProbeArgs& a, int log2n, int sfmt, bool conv_arith, int nactive, hipStream_t s) {
+    switch (log2n) {
+        case 8: return launch_probe_fmt<8>(a, sfmt, conv_arith, nactive, s);
+        case 9: return launch_probe_fmt<9>(a, sfmt, conv_arith, nactive, s);
+        case 10: return launch_probe_fmt<10>(a, sfmt, conv_arith, nactive, s);
+        case 11: return launch_probe_fmt<11>(a, sfmt, conv_arith, nactive, s);
+        case 12: return launch_probe_fmt<12>(a, sfmt, conv_arith, nactive, s);
+        case 13: return launch_probe_fmt<13>(a, sfmt, conv_arith, nactive, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+}  // namespace mi
+
+using mi::aligned;
+using mi::fail;
+
+extern "C" {
+
+int mi_probe_create(const mi_device_cfg* dev, int nstreams, int max_cells, int windows_per_cell, int max_targets, int gpu, mi_probe** out) {
+    if (!dev || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (nstreams < 1 || nstreams > 65535 || max_cells < 1 || max_cells >= (1 << 24) || windows_per_cell < 0 || windows_per_cell > (1 << 20))
+        return fail(MI_ERR_INVALID, "channel probe needs 1 <= nstreams < 2^16, 1 <= max_cells < 2^24 and 0 <= windows_per_cell <= 2^20");
+    mi::Plan plan;
+    if (const int rc = mi::device_plan(*dev, plan))
+        return rc;
+    if (plan.hop_bytes == 0 || plan.hop_bytes > (1u << 20))
+        return fail(MI_ERR_INVALID, "channel probe: the hop (sample_rate / 8000 samples) is out of range");
+    const uint64_t wpc = static_cast<uint64_t>(windows_per_cell ? windows_per_cell : MI_WAVE_BATCH);
+    if (max_targets < 1 || static_cast<int64_t>(max_targets) > static_cast<int64_t>(nstreams) * plan.fft_size ||
+        static_cast<uint64_t>(max_targets) * static_cast<uint64_t>(max_cells) >= (uint64_t{1} << 31))
+        return fail(MI_ERR_INVALID, "channel probe needs 1 <= max_targets <= nstreams * fft_size and max_targets * max_cells < 2^31");
+    if (static_cast<uint64_t>(max_cells) * wpc >= (uint64_t{1} << 32))
+        return fail(MI_ERR_INVALID, "channel probe: max_cells * windows_per_cell does not fit the 32-bit window count");
+    if (const int rc = mi::check_gpu(gpu, "no HIP device: the channel probe runs on the GPU only"))
+        return rc;
+    mi_probe* p = new (std::nothrow) mi_probe();
+    if (!p)
+        return fail(MI_ERR_NOMEM, "host allocation failed");
+    p->gpu = gpu;
+    p->nstreams = nstreams;
+    p->max_cells = max_cells;
+    p->max_targets = max_targets;
+    p->wpc = static_cast<uint32_t>(wpc);
+    p->log2n = plan.log2n;
+    p->fft_size = plan.fft_size;
+    p->sfmt = plan.dev.sfmt;
+    p->sample_bytes = 2 * plan.bytes_per_sample;
+    p->conv_arith = plan.conv_arith;
+    p->conv_scale = plan.conv_scale;
+    p->hop_bytes = plan.hop_bytes;
+    const size_t zlen = static_cast<size_t>(max_targets) * static_cast<size_t>(max_cells) * p->wpc;
+    if (hipSetDevice(gpu) != hipSuccess || dalloc_copy(p->d_window, plan.window) != hipSuccess || dalloc_copy(p->d_tw, plan.tw) != hipSuccess ||
+        dalloc_copy(p->d_levels, plan.levels) != hipSuccess || dalloc(p->d_targets, static_cast<size_t>(max_targets)) != hipSuccess ||
+        dalloc(p->d_active, static_cast<size_t>(nstreams)) != hipSuccess || dalloc(p->d_z, zlen) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        delete p;
+        return fail(MI_ERR_HIP, "channel probe: device allocation failed");
+    }
+    *out = p;
+    return MI_OK;
+}
+
+void mi_probe_destroy(mi_probe* p) {
+    if (!p)
+        return;
+    (void)hipSetDevice(p->gpu);
+    delete p;
+}
+
+int mi_probe_set_targets(mi_probe* p, const mi_probe_target* targets, int ntargets) {
+    if (!p || !targets)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (ntargets < 1 || ntargets > p->max_targets)
+        return fail(MI_ERR_INVALID, "channel probe: ntargets outside 1 .. max_targets");
+    std::vector<mi::ProbeStream> active;
+    for (int i = 0; i < ntargets; ++i) {
+        const mi_probe_target& t = targets[i];
+        if (t.stream >= static_cast<uint32_t>(p->nstreams) || t.bin >= static_cast<uint32_t>(p->fft_size))
+            return fail(MI_ERR_INVALID, "channel probe: a target's stream or bin is out of range");
+        if (i && (t.stream < targets[i - 1].stream || (t.stream == targets[i - 1].stream && t.bin <= targets[i - 1].bin)))
+            return fail(MI_ERR_INVALID, "channel probe: the targets must be strictly ascending by (stream, bin)");
+        if (active.empty() || active.back().stream != static_cast<int>(t.stream))
+            active.push_back(mi::ProbeStream{static_cast<int>(t.stream), i, 0});
+        active.back().count += 1;
+    }
+    // (a call still queued reads the lists it was made with)
+    if (!mi::sync_copy(p->gpu, p->d_targets, targets, static_cast<size_t>(ntargets) * sizeof(mi_probe_target), hipMemcpyHostToDevice) ||
+        hipMemcpy(p->d_active, active.data(), active.size() * sizeof(mi::ProbeStream), hipMemcpyHostToDevice) != hipSuccess) {
+        p->ntargets = 0;  // the device lists may be torn: a call is refused until a list has been set
+        return fail(MI_ERR_HIP, "channel probe: uploading the target list failed");
+    }
+    p->ntargets = ntargets;
+    p->nactive = static_cast<int>(active.size());
+    return MI_OK;
+}
+
+size_t mi_probe_bytes_needed(const mi_probe* p, int ncells) {
+    if (!p || ncells < 1)
+        return 0;
+    return (static_cast<size_t>(ncells) * p->wpc - 1) * p->hop_bytes + static_cast<size_t>(p->sample_bytes) * static_cast<size_t>(p->fft_size);
+}
+
+int mi_probe_process_device(mi_probe* p, const void* d_iq, size_t stream_stride_bytes, int ncells, mi_probe_cell* d_cells, void* hip_stream) {
+    if (!p || !d_iq || !d_cells)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (p->ntargets < 1)
+        return fail(MI_ERR_INVALID, "channel probe: no target list set (mi_probe_set_targets)");
+    if (ncells < 1 || ncells > p->max_cells)
+        return fail(MI_ERR_INVALID, "ncells outside 1 .. max_cells");
+    if (!aligned(d_cells, 8))
+        return fail(MI_ERR_INVALID, "channel probe: d_cells must be 8-byte aligned");
+    if (!aligned(d_iq, static_cast<uintptr_t>(p->sample_bytes)) || stream_stride_bytes % static_cast<size_t>(p->sample_bytes) != 0)
+        return fail(MI_ERR_INVALID, "channel probe: d_iq and the stream stride must be aligned to one complex sample");
+    if (hipSetDevice(p->gpu) != hipSuccess)
+        return fail(MI_ERR_HIP, "hipSetDevice failed");
+    hipStream_t q = static_cast<hipStream_t>(hip_stream);
+    mi::ProbeArgs a{};
+    a.iq = static_cast<const unsigned char*>(d_iq);
+    a.stream_stride = stream_stride_bytes;
+    a.valid_bytes = mi_probe_bytes_needed(p, ncells);
+    a.hop_bytes = static_cast<uint32_t>(p->hop_bytes);
+    a.nwindows = static_cast<uint32_t>(ncells) * p->wpc;
+    a.window = p->d_window;
+    a.tw = p->d_tw;
+    a.levels = p->d_levels;
+    a.conv_scale = p->conv_scale;
+    a.active = p->d_active;
+    a.targets = p->d_targets;
+    a.z = p->d_z;
+    a.zstride = static_cast<size_t>(p->max_cells) * p->wpc;
+    p->timing.stamp(0, q);
+    if (mi::launch_probe(a, p->log2n, p->sfmt, p->conv_arith, p->nactive, q) != hipSuccess)
+        return fail(MI_ERR_HIP, "channel probe kernel launch failed");
+    p->timing.stamp(1, q);
+    const size_t records = static_cast<size_t>(p->ntargets) * static_cast<size_t>(ncells);  // < 2^31 (mi_probe_create)
+    hipLaunchKernelGGL(mi::k_probe_reduce, dim3(static_cast<unsigned>(records)), dim3(mi::kReduceBlock), 0, q, p->d_z.get(), a.zstride, p->wpc,
+                       static_cast<uint32_t>(ncells), d_cells);
+    p->timing.stamp(2, q);
+    if (hipGetLastError() != hipSuccess)
+        return fail(MI_ERR_HIP, "channel probe kernel launch failed");
+    p->timed = p->timing.on;
+    p->last_cells = d_cells;
+    p->last_records = records;
+    return MI_OK;
+}
+
+int mi_probe_download(mi_probe* p, void* hip_stream, mi_probe_cell* cells) {
+    if (!p || !cells)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!p->last_cells)
+        return fail(MI_ERR_INVALID, "no mi_probe_process_device call to download");
+    hipStream_t q = static_cast<hipStream_t>(hip_stream);
+    if (hipSetDevice(p->gpu) != hipSuccess ||
+        hipMemcpyAsync(cells, p->last_cells, p->last_records * sizeof(mi_probe_cell), hipMemcpyDeviceToHost, q) != hipSuccess ||
+        hipStreamSynchronize(q) != hipSuccess)
+        return fail(MI_ERR_HIP, "channel probe: download failed");
+    return MI_OK;
+}
+
+int mi_probe_set_timing(mi_probe* p, int on) {
+    if (!p)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    return p->timing.enable(p->gpu, on != 0);
+}
+
+int mi_probe_last_launch_ms(mi_probe* p, float* ms) {
+    if (!p || !ms)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!p->timing.on || !p->timed)
+        return fail(MI_ERR_INVALID, "no timed mi_probe_process_device call");
+    return p->timing.elapsed(p->gpu, ms);
+}
+
+}  // extern "C"

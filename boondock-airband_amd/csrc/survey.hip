@@ -67,30 +67,6 @@ struct SurveyArgs {
     float* pmax;
 };
 
-// The passes behind pass 0 with the lane's twiddles fetched where they are used: the instantiations that cannot keep four passes
-// of them beside the 24 accumulator registers (N >= 4096: 1024 lanes a workgroup, 128 registers a lane).  Same butterflies.
-template <int L, int K>
-__device__ __forceinline__ void later_passes_tw(float2 (&x)[8], const float2* __restrict__ tw, float2* __restrict__ xch, int tau) {
-    if constexpr (K < FftGeom<L>::NPASS) {
-        using P = Pass<L, K>;
-        float2 r[7];
-        P::load_tw(tau, tw, r);
-#pragma unroll
-        for (int gi = 0; gi < P::GROUPS; ++gi)
-#pragma unroll
-            for (int ri = 0; ri < P::G; ++ri)
-                x[gi * P::G + ri] = xch[xpad(P::pos(tau, gi, ri))];
-        P::run(x, r);
-#pragma unroll
-        for (int gi = 0; gi < P::GROUPS; ++gi)
-#pragma unroll
-            for (int ri = 0; ri < P::G; ++ri)
-                xch[xpad(P::pos(tau, gi, ri))] = x[gi * P::G + ri];
-        fft_sync<L>();
-        later_passes_tw<L, K + 1>(x, tw, xch, tau);
-    }
-}
-
 template <int L>
 constexpr size_t survey_lds_bytes(unsigned span_alloc) {
     using Gm = FftGeom<L>;
@@ -313,20 +289,6 @@ int kernel_tw(int log2n) {  // FftGeom<L>::TW
     return log2n <= 10 ? 64 : (log2n == 11 ? 32 : (log2n == 12 ? 16 : 8));
 }
 static_assert(FftGeom<10>::TW == 64 && FftGeom<11>::TW == 32 && FftGeom<12>::TW == 16 && FftGeom<13>::TW == 8, "kernel_tw restates FftGeom::TW");
-
-// The device configuration as the plan sees it: window, twiddles, level table, hop.  The survey has no channels; the plan is built
-// for one at the centre frequency and only its device-wide part is used.
-int device_plan(const mi_device_cfg& dev, Plan& p) {
-    mi_channel_cfg ch{};
-    ch.freq = dev.centerfreq;
-    ch.modulation = MI_MOD_AM;
-    ch.squelch_snr_db = -1.0f;
-    ch.ampfactor = 1.0f;
-    ch.tau = -1;
-    const char* msg = "";
-    const int rc = build_plan(dev, &ch, 1, p, &msg);
-    return rc == MI_OK ? MI_OK : fail(rc, msg);
-}
 
 }  // namespace
 }  // namespace mi

@@ -666,6 +666,90 @@ int mi_occupancy_plan_host(const mi_device_cfg* dev, const mi_occ_cfg* cfg, cons
                            const float* peak, int ncells, mi_occ_bin* bins, mi_occ_candidate* cands, size_t max_candidates,
                            uint32_t* stream_first, uint32_t* count /* [2] */);
 
+/* ---------------- channel probe: per-candidate envelope and phase statistics, the step between the finder and a channel plan ----------------
+ * The finder says which bins carry something and when; a mi_channel_cfg also needs a modulation and, for NFM, a carrier frequency
+ * inside the bin.  The survey's planes keep magnitudes only; the probe keeps, for a caller-given list of targets {stream, bin}, the
+ * complex value of that bin in every window and reduces it per cell.  It reads the device-resident IQ the survey reads and runs the
+ * same windows (the plan's window, the device's conversion, hop_bytes apart, fft_size long, windows_per_cell to a cell; cell c of a
+ * stream covers windows c * wpc .. (c + 1) * wpc - 1 counted from d_iq + s * stream_stride_bytes).
+ * Arithmetic.  For target k and window w, re and im are the float32 parts of bin bin_k of the documented FFT: the bits
+ * the survey and stage 1 give.  m_w = sqrtf(re * re + im * im) in float32, each operation rounded.  Per (target, cell), over the
+ * cell's windows, in float64:
+ *   s1   = sum of (double)m_w
+ *   s2   = sum of (double)m_w * (double)m_w                                  (each product is exact)
+ *   r_re = sum of (double)re_w * (double)re_p + (double)im_w * (double)im_p  (p = w - 1; exact products, their sum rounded once)
+ *   r_im = sum of (double)im_w * (double)re_p - (double)re_w * (double)im_p  (the same)
+ *   so r_re + j r_im = sum of z_w * conj(z_p): its angle is the mean phase advance of the bin per hop.
+ * A pair (w, p) belongs to the cell of w.  The first window of the call has no predecessor and contributes no pair: cell 0 has
+ * wpc - 1 pairs, every other cell wpc.  `windows` = wpc and `pairs` say over how many terms the sums run.  The stage keeps no state
+ * between calls.  Order of the sums: fixed, documented in csrc/probe.hip; no floating-point atomics, so two runs give the same bytes.
+ * It is not window order: a float64 model that adds in window order differs by the reordering of at most wpc terms.
+ * Targets (mi_probe_set_targets): 1 .. max_targets of them, strictly ascending by (stream, bin) -- a duplicate is refused as an
+ *   unsorted list is --, stream < nstreams, bin < fft_size.  The list is copied to the device; queued work completes first; after a
+ *   refusal the old list stays.  Targets of one stream share one pass over that stream's IQ; a stream with no target is not read.
+ *   mi_probe_targets_from_candidates (host only) makes the list from the finder's candidates: best_bin of each, sorted.
+ * Output: d_cells [ntargets][ncells] of mi_probe_cell, 8-byte aligned, in the order of the target list.
+ * Execution: asynchronous on `hip_stream`, no host synchronisation; two kernels (the windows; the reduction of each (target, cell)).
+ *   Between them the bins' values lie in a scratch plane in the handle, 8 bytes per (target, window): calls of one handle go to one
+ *   stream, or are ordered by the caller.  mi_probe_download is the one place that synchronises.
+ * Supported: what the survey supports.  With f32 input, NaN and Inf are unspecified.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, a refused target list, a call before any list was
+ * set, d_cells not 8-byte aligned, ncells outside 1 .. max_cells, or a device configuration the plan refuses. */
+typedef struct { uint32_t stream, bin; } mi_probe_target; /* 8 bytes */
+typedef struct {
+    double s1, s2, r_re, r_im;
+    uint32_t windows, pairs;
+} mi_probe_cell; /* 40 bytes */
+typedef struct mi_probe mi_probe;
+/* 1 <= nstreams < 2^16, 1 <= max_cells < 2^24, windows_per_cell 0 = MI_WAVE_BATCH, at most 2^20 (the survey's limits);
+ * 1 <= max_targets <= nstreams * fft_size, max_targets * max_cells < 2^31.  Allocates the scratch plane:
+ * 8 * max_targets * max_cells * windows_per_cell bytes. */
+int mi_probe_create(const mi_device_cfg* dev, int nstreams, int max_cells, int windows_per_cell, int max_targets, int gpu, mi_probe** out);
+void mi_probe_destroy(mi_probe* p);
+int mi_probe_set_targets(mi_probe* p, const mi_probe_target* targets, int ntargets);
+/* contiguous bytes a call over ncells cells reads per stream: mi_survey_bytes_needed's formula */
+size_t mi_probe_bytes_needed(const mi_probe* p, int ncells);
+int mi_probe_process_device(mi_probe* p, const void* d_iq, size_t stream_stride_bytes, int ncells, mi_probe_cell* d_cells, void* hip_stream);
+/* The records of the last mi_probe_process_device, which must have been enqueued on `hip_stream`: waits for it and copies
+ * ntargets * ncells records of that call. */
+int mi_probe_download(mi_probe* p, void* hip_stream, mi_probe_cell* cells);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {windows, reduce}.  tools/probe_rate.py. */
+int mi_probe_set_timing(mi_probe* p, int on);
+int mi_probe_last_launch_ms(mi_probe* p, float* ms /* [2] */);
+/* Host only, no HIP call: out[i] = {cands[i].stream, cands[i].best_bin}, then sorted by (stream, bin).  The finder stores its
+ * candidates by stream and by position (bin N / 2 first), so the order changes within a stream. */
+int mi_probe_targets_from_candidates(const mi_occ_candidate* cands, size_t n, mi_probe_target* out /* [n] */);
+
+/* From the cells of one target to what a channel plan asks for: no GPU and no HIP call.
+ * mi_probe_features_host adds the sums of the selected cells (cell_mask[c] != 0; NULL = all) in cell order -- S1, S2, R_re, R_im, the
+ * window count n and the pair count -- and derives, in float64:
+ *   cv2        = n * S2 / (S1 * S1) - 1    the squared coefficient of variation of the envelope: about 0 for a constant envelope
+ *   coherence  = hypot(R_re, R_im) / S2    how steadily the phase advances from window to window; at most about 1
+ *   dphi       = atan2(R_im, R_re)         the mean phase advance per hop, in (-pi, pi]
+ *   carrier_hz : with hop = the plan's hop in samples (sample_rate / MI_WAVE_RATE rounded to the nearest integer) and the window rate
+ *                fw = (double)sample_rate / hop (MI_WAVE_RATE exactly where sample_rate == hop * MI_WAVE_RATE, else not: 2.4 MS/s has
+ *                hop 150 and fw = 16000, 2.5 MS/s has hop 156 and fw = 16025.64...), a carrier at centerfreq + f advances the bin's
+ *                phase by 2 pi f / fw per hop, so f is known modulo fw: f0 = dphi / (2 pi) * fw.  With [lo, hi] =
+ *                mi_survey_bin_range(dev, bin) and mid = (lo + hi) / 2.0,
+ *                  carrier_hz = centerfreq + f0 + fw * nearbyint((mid - centerfreq - f0) / fw)
+ *                the frequency congruent to f0 nearest to the middle of the bin's range.  Unambiguous while a bin is narrower than fw
+ *                (fft_size > hop).  It is an estimate of the power-weighted mean frequency in the bin, not a bound.
+ * A caller masks cells with the finder's threshold: cell c is selected iff mean[c][bin] > mi_occ_bin.threshold.  If no cell is
+ * selected, or S1 == 0, every field is 0.  MI_ERR_INVALID: NULL arguments, ncells < 1, bin out of range, a configuration the plan refuses.
+ * mi_probe_classify_host: *modulation = MI_MOD_NFM iff coherence < rule.coherence_max or cv2 < rule.cv2_min, else MI_MOD_AM; with
+ * n == 0 it is refused (nothing to classify).  rule NULL or a field that is 0 takes its default, coherence_max 0.9314 and cv2_min
+ * 0.1005: the geometric middles between the two classes' nearest values over synthetic captures (DESIGN.md 5g has the table).  They
+ * are a caller's settings like the finder's ratio, measured on mi_iqgen signals only: they have NOT been tried on a real band. */
+typedef struct {
+    double s1, s2, r_re, r_im;  /* totals over the selected cells */
+    uint64_t n, pairs;          /* windows and pairs in them */
+    double cv2, coherence, dphi, carrier_hz;
+} mi_probe_features;            /* 80 bytes */
+typedef struct { double coherence_max, cv2_min; } mi_probe_rule; /* 0 = the default */
+int mi_probe_features_host(const mi_device_cfg* dev, int bin, const mi_probe_cell* cells, int ncells, const uint8_t* cell_mask /* [ncells] or NULL = all */,
+                           mi_probe_features* out);
+int mi_probe_classify_host(const mi_probe_features* f, const mi_probe_rule* rule /* NULL = defaults */, int* modulation);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
