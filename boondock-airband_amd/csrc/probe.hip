@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/mi_airband.h"
@@ -66,6 +67,40 @@ namespace {
 
 constexpr int kProbeTilePieces = 2;  // a tile is this many TW-window pieces: enough workgroups for one stream, lane setup paid once per tile
 constexpr int kReduceBlock = 256;
+constexpr size_t kProbeLdsLimit = 160 * 1024;  // what one workgroup may ask for on gfx950: the CU's whole LDS
+
+// bytes per complex sample of a kernel instance's format
+constexpr int probe_bps2(int sfmt) {
+    return sfmt == MI_SFMT_S16 ? 4 : (sfmt == MI_SFMT_F32 ? 8 : 2);
+}
+
+// The span of one TW-window piece in LDS: its bytes, up to 15 in front of them (the piece starts at a 16-byte line) and a line's
+// rounding.  k_probe lays its LDS out with it and probe_lds_bytes sizes the launch with it.
+template <int L>
+__host__ __device__ constexpr unsigned probe_span_alloc(int bps2, unsigned hop_bytes) {
+    return (static_cast<unsigned>(FftGeom<L>::TW - 1) * hop_bytes + static_cast<unsigned>(FftGeom<L>::N * bps2) + 16 + 15) & ~15u;
+}
+
+template <int L>
+constexpr size_t probe_lds_bytes_of(int bps2, unsigned hop_bytes) {
+    return static_cast<size_t>(probe_span_alloc<L>(bps2, hop_bytes)) + 1024 + static_cast<size_t>(FftGeom<L>::F) * FftGeom<L>::XN * 8;
+}
+
+// The dynamic LDS a k_probe workgroup needs: span + level table + F exchange slots.  mi_probe_create refuses a geometry whose need
+// exceeds kProbeLdsLimit and launch_probe_one launches with it: one function, so the two cannot drift.  hop_bytes <= 2^20
+// (mi_probe_create), so nothing here wraps.  0: no such kernel instance.
+size_t probe_lds_bytes(int log2n, int sfmt, unsigned hop_bytes) {
+    const int bps2 = probe_bps2(sfmt);
+    switch (log2n) {
+        case 8: return probe_lds_bytes_of<8>(bps2, hop_bytes);
+        case 9: return probe_lds_bytes_of<9>(bps2, hop_bytes);
+        case 10: return probe_lds_bytes_of<10>(bps2, hop_bytes);
+        case 11: return probe_lds_bytes_of<11>(bps2, hop_bytes);
+        case 12: return probe_lds_bytes_of<12>(bps2, hop_bytes);
+        case 13: return probe_lds_bytes_of<13>(bps2, hop_bytes);
+    }
+    return 0;
+}
 
 struct ProbeArgs {
     const unsigned char* iq;  // stream s at iq + s*stream_stride
@@ -88,7 +123,7 @@ template <int L, int SFMT>
 __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) {
     using Gm = FftGeom<L>;
     constexpr int N = Gm::N, TPF = Gm::TPF, F = Gm::F, TW = Gm::TW, XN = Gm::XN, BLOCK = Gm::BLOCK;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));  // bytes per complex sample
+    constexpr int BPS2 = probe_bps2(SFMT);  // bytes per complex sample
     constexpr bool kTwInRegs = L <= 11;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -97,7 +132,7 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) 
     const unsigned wfirst = blockIdx.x * a.tile_windows;                         // first window of the tile, counted from the stream's base
     const int nt = static_cast<int>(min(a.tile_windows, a.nwindows - wfirst));   // its windows: the last tile of the call may be short
 
-    const unsigned span_alloc = (static_cast<unsigned>(TW - 1) * a.hop_bytes + N * BPS2 + 16 + 15) & ~15u;
+    const unsigned span_alloc = probe_span_alloc<L>(BPS2, a.hop_bytes);
     unsigned char* span = lds;
     float* lut = reinterpret_cast<float*>(lds + span_alloc);
     float2* xch_all = reinterpret_cast<float2*>(lds + span_alloc + 1024);
@@ -233,10 +268,8 @@ hipError_t launch_probe_one(ProbeArgs a, int nactive, hipStream_t s) {
     using Gm = FftGeom<L>;
     a.tile_windows = kProbeTilePieces * Gm::TW;
     const unsigned tiles = (a.nwindows + a.tile_windows - 1) / a.tile_windows;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
-    const unsigned span_alloc = (static_cast<unsigned>(Gm::TW - 1) * a.hop_bytes + Gm::N * BPS2 + 16 + 15) & ~15u;
-    const size_t lds = span_alloc + 1024 + static_cast<size_t>(Gm::F) * Gm::XN * 8;
-    if (lds > 160 * 1024)
+    const size_t lds = probe_lds_bytes(L, SFMT, a.hop_bytes);
+    if (lds > kProbeLdsLimit)  // (mi_probe_create has refused such a geometry)
         return hipErrorInvalidValue;
     auto kern = k_probe<L, SFMT>;
     if (lds > 48 * 1024) {
@@ -290,7 +323,11 @@ int mi_probe_create(const mi_device_cfg* dev, int nstreams, int max_cells, int w
     if (const int rc = mi::device_plan(*dev, plan))
         return rc;
     if (plan.hop_bytes == 0 || plan.hop_bytes > (1u << 20))
-        return fail(MI_ERR_INVALID, "channel probe: the hop (sample_rate / 8000 samples) is out of range");
+        return fail(MI_ERR_INVALID, "channel probe: the hop (sample_rate / 16000 samples) is out of range");
+    if (const size_t lds = mi::probe_lds_bytes(plan.log2n, plan.dev.sfmt, static_cast<unsigned>(plan.hop_bytes)); lds > mi::kProbeLdsLimit)
+        return fail(MI_ERR_INVALID, "channel probe: a workgroup would need " + std::to_string(lds) + " bytes of LDS at this fft_size, sample format and hop (" +
+                                        std::to_string(plan.hop_bytes) + " bytes), over the limit of " + std::to_string(mi::kProbeLdsLimit) +
+                                        " (160 KiB): lower the sample rate");
     const uint64_t wpc = static_cast<uint64_t>(windows_per_cell ? windows_per_cell : MI_WAVE_BATCH);
     if (max_targets < 1 || static_cast<int64_t>(max_targets) > static_cast<int64_t>(nstreams) * plan.fft_size ||
         static_cast<uint64_t>(max_targets) * static_cast<uint64_t>(max_cells) >= (uint64_t{1} << 31))

@@ -67,19 +67,49 @@ struct SurveyArgs {
     float* pmax;
 };
 
+constexpr size_t kSurveyLdsLimit = 160 * 1024;  // what one workgroup may ask for on gfx950: the CU's whole LDS
+
+// bytes per complex sample of a kernel instance's format
+constexpr int survey_bps2(int sfmt) {
+    return sfmt == MI_SFMT_S16 ? 4 : (sfmt == MI_SFMT_F32 ? 8 : 2);
+}
+
+// The span of one TW-window piece in LDS: its bytes, up to 15 in front of them (the piece starts at a 16-byte line) and a line's
+// rounding.  k_survey lays its LDS out with it and survey_lds_bytes sizes the launch with it.
 template <int L>
-constexpr size_t survey_lds_bytes(unsigned span_alloc) {
+__host__ __device__ constexpr unsigned survey_span_alloc(int bps2, unsigned hop_bytes) {
+    return (static_cast<unsigned>(FftGeom<L>::TW - 1) * hop_bytes + static_cast<unsigned>(FftGeom<L>::N * bps2) + 16 + 15) & ~15u;
+}
+
+template <int L>
+constexpr size_t survey_lds_bytes_of(int bps2, unsigned hop_bytes) {
     using Gm = FftGeom<L>;
-    const size_t work = span_alloc + 1024 + static_cast<size_t>(Gm::F) * Gm::XN * 8;
+    const size_t work = static_cast<size_t>(survey_span_alloc<L>(bps2, hop_bytes)) + 1024 + static_cast<size_t>(Gm::F) * Gm::XN * 8;
     const size_t fold = Gm::F > 1 ? static_cast<size_t>(Gm::F) * Gm::N * 12 : 0;  // the groups' partials lie over the working set
     return work > fold ? work : fold;
+}
+
+// The dynamic LDS a k_survey workgroup needs.  mi_survey_create refuses a geometry whose need exceeds kSurveyLdsLimit and
+// launch_survey_one launches with it: one function, so the two cannot drift.  hop_bytes <= 2^20 (mi_survey_create), so nothing here
+// wraps.  0: no such kernel instance.
+size_t survey_lds_bytes(int log2n, int sfmt, unsigned hop_bytes) {
+    const int bps2 = survey_bps2(sfmt);
+    switch (log2n) {
+        case 8: return survey_lds_bytes_of<8>(bps2, hop_bytes);
+        case 9: return survey_lds_bytes_of<9>(bps2, hop_bytes);
+        case 10: return survey_lds_bytes_of<10>(bps2, hop_bytes);
+        case 11: return survey_lds_bytes_of<11>(bps2, hop_bytes);
+        case 12: return survey_lds_bytes_of<12>(bps2, hop_bytes);
+        case 13: return survey_lds_bytes_of<13>(bps2, hop_bytes);
+    }
+    return 0;
 }
 
 template <int L, int SFMT>
 __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_survey(const SurveyArgs a) {
     using Gm = FftGeom<L>;
     constexpr int N = Gm::N, TPF = Gm::TPF, F = Gm::F, TW = Gm::TW, XN = Gm::XN, BLOCK = Gm::BLOCK;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));  // bytes per complex sample
+    constexpr int BPS2 = survey_bps2(SFMT);  // bytes per complex sample
     constexpr bool kTwInRegs = L <= 11;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -90,7 +120,7 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_survey(const SurveyArgs a
     const int nt = static_cast<int>(min(a.tile_windows, a.wpc - t0));                // its windows: the last tile of a cell may be short
     const long long wfirst = static_cast<long long>(cell) * a.wpc + t0;             // ... counted from the stream's base
 
-    const unsigned span_alloc = (static_cast<unsigned>(TW - 1) * a.hop_bytes + N * BPS2 + 16 + 15) & ~15u;
+    const unsigned span_alloc = survey_span_alloc<L>(BPS2, a.hop_bytes);
     unsigned char* span = lds;
     float* lut = reinterpret_cast<float*>(lds + span_alloc);
     float2* xch_all = reinterpret_cast<float2*>(lds + span_alloc + 1024);
@@ -246,10 +276,8 @@ __global__ __launch_bounds__(64) void k_survey_fold(const double* __restrict__ p
 template <int L, int SFMT>
 hipError_t launch_survey_one(const SurveyArgs& a, int ncells, int nenabled, hipStream_t s) {
     using Gm = FftGeom<L>;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
-    const unsigned span_alloc = (static_cast<unsigned>(Gm::TW - 1) * a.hop_bytes + Gm::N * BPS2 + 16 + 15) & ~15u;
-    const size_t lds = survey_lds_bytes<L>(span_alloc);
-    if (lds > 160 * 1024)
+    const size_t lds = survey_lds_bytes(L, SFMT, a.hop_bytes);
+    if (lds > kSurveyLdsLimit)  // (mi_survey_create has refused such a geometry)
         return hipErrorInvalidValue;
     auto kern = k_survey<L, SFMT>;
     if (lds > 48 * 1024) {
@@ -308,7 +336,11 @@ int mi_survey_create(const mi_device_cfg* dev, int nstreams, int max_cells, int 
     if (const int rc = mi::device_plan(*dev, plan))
         return rc;
     if (plan.hop_bytes == 0 || plan.hop_bytes > (1u << 20))
-        return fail(MI_ERR_INVALID, "band survey: the hop (sample_rate / 8000 samples) is out of range");
+        return fail(MI_ERR_INVALID, "band survey: the hop (sample_rate / 16000 samples) is out of range");
+    if (const size_t lds = mi::survey_lds_bytes(plan.log2n, plan.dev.sfmt, static_cast<unsigned>(plan.hop_bytes)); lds > mi::kSurveyLdsLimit)
+        return fail(MI_ERR_INVALID, "band survey: a workgroup would need " + std::to_string(lds) + " bytes of LDS at this fft_size, sample format and hop (" +
+                                        std::to_string(plan.hop_bytes) + " bytes), over the limit of " + std::to_string(mi::kSurveyLdsLimit) +
+                                        " (160 KiB): lower the sample rate");
     if (const int rc = mi::check_gpu(gpu, "no HIP device: the band survey runs on the GPU only"))
         return rc;
     mi_survey* s = new (std::nothrow) mi_survey();

@@ -551,14 +551,19 @@ int mi_tx_plan_host(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows, 
  * Bin order: FFT order 0 .. fft_size - 1, the index mi_plan_channel().bin reports (bin 0 = centerfreq, the upper half = below it).
  * Supported: fft_size_log 8 .. 13, all four sample formats, any hop the plan derives (160, 128, 150, ...); d_iq and the stream stride
  *   aligned to one complex sample.  Stateless, no option or environment switch; nothing is shared with a demod handle.
+ * The hop is bounded by the LDS: a workgroup keeps a piece of 64 windows (32 at fft 2048, 16 at 4096, 8 at 8192) of IQ there beside
+ *   its exchange slots, and may ask for 160 KiB (163 840 bytes) at most.  mi_survey_create refuses a configuration that needs more, with
+ *   MI_ERR_INVALID and both figures in mi_last_error(), before it looks for a device.  The need grows with hop_bytes: at fft 256
+ *   the largest hop is 568 samples with s16 (9.088 MS/s; a 10 MS/s capture is refused), 1141 with u8 / s8, 282 with f32 (4.512 MS/s);
+ *   fft 1024 allows the least (1129 / 556 / 270), the sizes above it more, their pieces being shorter.
  * Disabled streams (mi_survey_set_streams; the companion of mi_demod_set_active_streams, as MI_GATE_NONE is): a disabled stream's IQ
  *   is not read and its regions of d_mean / d_peak are not written.  NULL enables all (the default).  Completes queued work first.
  * Execution: asynchronous on `hip_stream`, no host synchronisation; two kernels (the windows; the fold of a cell's partial sums).  The
  *   partial sums live in the handle: calls of one handle go to one stream, or are ordered by the caller.
  * Determinism: no floating-point atomics; the partial sums of a cell are combined in a fixed order (csrc/survey.hip), so two runs give
  *   the same bytes.  With f32 input, NaN and Inf are unspecified.
- * MI_ERR_NO_DEVICE without a GPU; MI_ERR_INVALID for bad arguments, d_mean / d_peak not 16-byte aligned, ncells outside
- * 1 .. max_cells, or a mask that enables no stream (the mask then stays as it was). */
+ * MI_ERR_NO_DEVICE without a GPU; MI_ERR_INVALID for bad arguments, a hop over the LDS bound, d_mean / d_peak not 16-byte aligned,
+ * ncells outside 1 .. max_cells, or a mask that enables no stream (the mask then stays as it was). */
 typedef struct mi_survey mi_survey;
 /* 1 <= nstreams < 2^16, 1 <= max_cells < 2^24; windows_per_cell 0 = MI_WAVE_BATCH (one audio batch), at most 2^20 */
 int mi_survey_create(const mi_device_cfg* dev, int nstreams, int max_cells, int windows_per_cell, int gpu, mi_survey** out);
@@ -692,7 +697,9 @@ int mi_occupancy_plan_host(const mi_device_cfg* dev, const mi_occ_cfg* cfg, cons
  * Execution: asynchronous on `hip_stream`, no host synchronisation; two kernels (the windows; the reduction of each (target, cell)).
  *   Between them the bins' values lie in a scratch plane in the handle, 8 bytes per (target, window): calls of one handle go to one
  *   stream, or are ordered by the caller.  mi_probe_download is the one place that synchronises.
- * Supported: what the survey supports.  With f32 input, NaN and Inf are unspecified.
+ * Supported: what the survey supports, its bound on the hop included: the windows kernel keeps the same piece of IQ in LDS, and
+ *   mi_probe_create refuses a configuration whose workgroup would need more than 160 KiB in the survey's way (at fft 256: hop 568
+ *   samples with s16, 1141 with u8 / s8, 282 with f32).  With f32 input, NaN and Inf are unspecified.
  * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, a refused target list, a call before any list was
  * set, d_cells not 8-byte aligned, ncells outside 1 .. max_cells, or a device configuration the plan refuses. */
 typedef struct { uint32_t stream, bin; } mi_probe_target; /* 8 bytes */

@@ -52,6 +52,41 @@ def hop_samples(sample_rate):
     return int(round(sample_rate / WAVE_RATE))  # rtl_airband.cpp:416
 
 
+# ------------------------------------------------------------------ the LDS a workgroup of k_survey / k_probe asks for
+# Restated from FftGeom (csrc/fft_radix8.hpp) and from survey_lds_bytes / probe_lds_bytes (csrc/survey.hip, csrc/probe.hip), the one
+# function per stage that both its create and its launcher call.  mi_survey_create and mi_probe_create refuse a geometry that needs
+# more than LDS_LIMIT; tests/test_poststage_refusals.py pins these formulas to the library on both sides of the limit.
+
+LDS_LIMIT = 160 * 1024
+COMPLEX_BYTES = {SFMT_U8: 2, SFMT_S8: 2, SFMT_S16: 4, SFMT_F32: 8}
+
+
+def fft_geom(log2n):
+    """FftGeom<log2n>: dict of N, TPF (lanes per FFT), BLOCK, F (FFTs side by side in a workgroup), TW (windows per piece), XN"""
+    n = 1 << log2n
+    tpf = n // 8
+    block = max(256, tpf)
+    return dict(N=n, TPF=tpf, BLOCK=block, F=block // tpf, TW=64 if log2n <= 10 else {11: 32, 12: 16, 13: 8}[log2n], XN=n + n // 8)
+
+
+def lds_bytes(stage, log2n, sfmt, hop_samples_):
+    """stage "survey" or "probe": span of TW windows + 1 KB level table + F exchange slots; the survey's fold region lies over them"""
+    g = fft_geom(log2n)
+    span = ((g["TW"] - 1) * hop_samples_ * COMPLEX_BYTES[sfmt] + g["N"] * COMPLEX_BYTES[sfmt] + 16 + 15) & ~15
+    work = span + 1024 + g["F"] * g["XN"] * 8
+    fold = g["F"] * g["N"] * 12 if stage == "survey" and g["F"] > 1 else 0
+    return max(work, fold)
+
+
+def largest_hop(stage, log2n, sfmt):
+    """the largest hop in samples whose LDS need does not exceed LDS_LIMIT (the need grows with the hop)"""
+    hop = 1
+    while lds_bytes(stage, log2n, sfmt, hop + 1) <= LDS_LIMIT:
+        hop += 1
+    assert lds_bytes(stage, log2n, sfmt, hop) <= LDS_LIMIT < lds_bytes(stage, log2n, sfmt, hop + 1)
+    return hop
+
+
 def window(n):
     w = np.zeros(n, np.float32)
     _oracle().ao_window(w, n)

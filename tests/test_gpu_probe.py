@@ -35,12 +35,14 @@ class Run:
     """one handle and one capture in device memory: streams `stride` bytes apart from a base that is only sample-aligned.  raws[s] None:
     the stream has no target, lies last, and its region is 64 bytes of 0xFF -- shorter than any window"""
 
-    def __init__(self, pkg, dev, raws, wpc, ncells, targets, max_targets=None):
+    def __init__(self, pkg, dev, raws, wpc, ncells, targets, max_targets=None, handle_wpc=None):
+        """handle_wpc: what the handle is created with where that is not wpc itself (0 = the default cell, which wpc then states)"""
         import torch
         self.torch, self.dev, self.wpc, self.ncells, self.n = torch, dev, wpc, ncells, 1 << dev.fft_size_log
         self.ns = len(raws)
         sb = SAMPLE_BYTES[dev.sfmt]
-        self.probe = pkg.Probe(dev, nstreams=self.ns, max_cells=ncells, windows_per_cell=wpc, max_targets=max_targets or len(targets))
+        self.probe = pkg.Probe(dev, nstreams=self.ns, max_cells=ncells, windows_per_cell=wpc if handle_wpc is None else handle_wpc,
+                               max_targets=max_targets or len(targets))
         need = self.probe.bytes_needed(ncells)
         hop_bytes = sv.hop_samples(dev.sample_rate) * sb
         assert need == (ncells * wpc - 1) * hop_bytes + sb * self.n, "mi_probe_bytes_needed against the survey's formula"
@@ -118,10 +120,10 @@ def noise_raws(rate, log2n, sfmt, nwin, nstreams):
     return tuple(raws)
 
 
-def noise_run(pkg, what, rate, log2n, sfmt, fullscale, wpc, ncells, nstreams, targets, idle_last=False, max_targets=None):
+def noise_run(pkg, what, rate, log2n, sfmt, fullscale, wpc, ncells, nstreams, targets, idle_last=False, max_targets=None, handle_wpc=None):
     dev = device(pkg, rate, log2n, sfmt, fullscale)
     raws = list(noise_raws(rate, log2n, sfmt, wpc * ncells, nstreams))
-    run = Run(pkg, dev, raws + ([None] if idle_last else []), wpc, ncells, targets, max_targets)
+    run = Run(pkg, dev, raws + ([None] if idle_last else []), wpc, ncells, targets, max_targets, handle_wpc)
     out = run.call()
     run.torch.cuda.synchronize()
     cells = run.host(out)
@@ -244,9 +246,22 @@ def test_constant_input(pkg):
     term of r_re and of s2 is one value, and n equal terms add exactly in any order while n <= 2^29: the sums are n times the term, bit
     for bit -- a dropped or doubled window or pair shows here that a tolerance would hide.  Over cells 1 .. the coherence is 1 up to the
     float32 rounding of m (R_re holds re^2 + im^2 in float64, S2 the square of the float32 m)."""
+    constant_input_case(pkg, 67, 3)
+
+
+def test_constant_input_long_cells(pkg):
+    """test_constant_input with cells of 600 windows, two of them: three trips of k_probe_reduce's strided loop, the last one partial
+    (lanes 0 .. 87 add three terms, the others two).  The same equalities, bit for bit: a term that a later trip drops, doubles or takes
+    from the neighbouring cell changes n.  n * m is exact for any float32 m; m * m and re^2 + im^2 have up to 48 bits, so for them
+    "n equal terms add exactly" rests on the capture and the cell length: with every byte 201, adding 600 (in cell 0, 599) times the
+    term in the kernel's order -- lane t the terms t, t + 256, t + 512, then the halving tree -- on the host in float64 gives n * term
+    bit for bit in every sum this case asserts (worked out when the case was written; at 2000 windows s2 would round on the way)."""
+    constant_input_case(pkg, 600, 2)
+
+
+def constant_input_case(pkg, wpc, ncells):
     import torch
     dev = device(pkg, 2560000, 9)
-    wpc, ncells = 67, 3
     raw = np.full(2 * sv.samples_needed(dev, wpc * ncells), 201, np.uint8)
     run = Run(pkg, dev, [raw], wpc, ncells, [(0, 0), (0, 1)])
     out = run.call()
@@ -259,10 +274,160 @@ def test_constant_input(pkg):
     c = cells[0]
     assert (c["r_im"] == 0.0).all()
     assert c["s1"].tolist() == [wpc * m] * ncells and c["s2"].tolist() == [wpc * (m * m)] * ncells
-    assert c["r_re"].tolist() == [p * (z[0] * z[0] + z[1] * z[1]) for p in (wpc - 1, wpc, wpc)]
-    f = pkg.probe_features_host(dev, 0, c, [0, 1, 1])
-    assert f.n == 2 * wpc and f.pairs == 2 * wpc and f.dphi == 0.0 and abs(f.coherence - 1.0) < 2.0 ** -22 and abs(f.cv2) < 1e-12
+    assert c["r_re"].tolist() == [p * (z[0] * z[0] + z[1] * z[1]) for p in [wpc - 1] + [wpc] * (ncells - 1)]
+    f = pkg.probe_features_host(dev, 0, c, [0] + [1] * (ncells - 1))
+    later = (ncells - 1) * wpc
+    assert f.n == later and f.pairs == later and f.dphi == 0.0 and abs(f.coherence - 1.0) < 2.0 ** -22 and abs(f.cv2) < 1e-12
     run.close()
+
+
+# ---- cells longer than k_probe_reduce's block: lane t adds the windows t, t + 256, ... of a cell, so from 257 windows on a lane adds more than one
+
+@pytest.mark.parametrize("wpc", [256, 257, 600])
+def test_fft256_long_cells(pkg, wpc):
+    """cells of 256 windows (every lane one term, none a second), 257 (lane 0 alone takes a second term, the cell's last window) and
+    600 (three trips, the last of 88 lanes), two cells each, so that a later trip of cell 0 that strays reads cell 1's windows and
+    cell 1's first pair reaches back into cell 0; bins 0, N / 2, N - 1 and an inner one"""
+    run, *_ = noise_run(pkg, f"fft 256 u8, cells of {wpc}", 2560000, 8, sv.SFMT_U8, 127.5, wpc, 2, 1, [(0, b) for b in (0, 77, 128, 255)])
+    run.close()
+
+
+def test_fft256_default_cell_is_2000_windows(pkg):
+    """windows_per_cell = 0 is MI_WAVE_BATCH = 2000 windows, what a caller gets who asks for nothing: eight trips of the strided loop,
+    the last of 208 lanes.  mi_probe_bytes_needed (checked in Run against the formula) and every record's `windows` say 2000."""
+    run, _, _, cells = noise_run(pkg, "fft 256 u8, the default cell", 2560000, 8, sv.SFMT_U8, 127.5, 2000, 2, 1, [(0, 5), (0, 186)], handle_wpc=0)
+    assert run.probe.windows_per_cell == 2000 and run.probe.bytes_needed(2) == (2 * 2000 - 1) * 160 * 2 + 2 * 256
+    assert (cells["windows"] == 2000).all() and cells["pairs"].tolist() == [[1999, 2000]] * 2
+    run.close()
+
+
+# ---- cells of one window: every sum is one term, so nothing is reordered and the device gives the model's bits
+
+ONE_LOG2N, ONE_CELLS, ONE_BINS = 9, 140, (0, 1, 180, 256, 511)  # (bin 180 holds the carrier at +901 kHz)
+
+
+def test_single_window_cells_are_bit_exact(pkg):
+    """fft 512, 140 cells of one window -- tiles 128 + 12, so cell 128's predecessor lies in another tile.  Each of s1, s2, r_re and
+    r_im is 0.0 + one term: (double)m and its square with m = sqrtf(re * re + im * im) in float32, and cr * pr + ci * pi and
+    ci * pr - cr * pi of float32 values in float64 -- exact products, one rounding.  The expected values are stated here from the
+    oracle's spectra in exactly these forms and compared byte for byte; tests/probe_model.py forms them the same way and must agree
+    byte for byte too.  Cell 0 has no pair and r_re = r_im = 0.0; every other cell has one, and its predecessor lies in the cell before.
+    The same capture through a survey of one-window cells: its peak is the float32 m that s1 holds, bit for bit."""
+    import torch
+    n = 1 << ONE_LOG2N
+    dev = device(pkg, 2560000, ONE_LOG2N)
+    raw, = noise_raws(2560000, ONE_LOG2N, sv.SFMT_U8, ONE_CELLS, 1)
+    run = Run(pkg, dev, [raw], 1, ONE_CELLS, [(0, b) for b in ONE_BINS])
+    out = run.call()
+    torch.cuda.synchronize()
+    cells = run.host(out)
+
+    z = sv.spectra(dev, raw, 0, ONE_CELLS)[:, list(ONE_BINS), :]  # float32 [window][target][2]
+    re, im = np.ascontiguousarray(z[..., 0].T), np.ascontiguousarray(z[..., 1].T)  # [target][window]
+    m = np.sqrt(re * re + im * im)
+    assert m.dtype == np.float32 and (m > 0).all()
+    md, cr, ci = m.astype(np.float64), re.astype(np.float64), im.astype(np.float64)
+    pr, pi = np.roll(cr, 1, axis=1), np.roll(ci, 1, axis=1)
+    want = np.zeros((len(ONE_BINS), ONE_CELLS), pm.CELL_DTYPE)
+    want["s1"] = 0.0 + md
+    want["s2"] = 0.0 + md * md
+    want["r_re"] = 0.0 + (cr * pr + ci * pi)
+    want["r_im"] = 0.0 + (ci * pr - cr * pi)
+    want["r_re"][:, 0] = want["r_im"][:, 0] = 0.0
+    want["windows"] = 1
+    want["pairs"] = 1
+    want["pairs"][:, 0] = 0
+    model, _ = pm.probe_model(dev, raw, 1, ONE_CELLS, list(ONE_BINS))
+    assert model.tobytes() == want.tobytes(), "tests/probe_model.py forms a term otherwise than this test states it"
+    for name in ("windows", "pairs", "s1", "s2", "r_re", "r_im"):
+        bad = np.argwhere(cells[name].view(np.uint64 if name[0] in "sr" else np.uint32) != want[name].view(np.uint64 if name[0] in "sr" else np.uint32))
+        print(f"one-window cells: {name}: {len(bad)} of {want[name].size} records differ from the expected bits")
+        assert len(bad) == 0, f"{name} differs first at (target, cell) {tuple(bad[0])}: {cells[name][tuple(bad[0])]!r} vs {want[name][tuple(bad[0])]!r}"
+    assert cells.tobytes() == want.tobytes()
+    assert (cells["pairs"][:, 0] == 0).all() and (cells["r_re"][:, 0] == 0.0).all() and (cells["r_im"][:, 0] == 0.0).all()
+    assert (cells["pairs"][:, 1:] == 1).all() and (cells["r_re"][:, 1:] != 0.0).all()
+    run.close()
+
+    survey = pkg.Survey(dev, nstreams=1, max_cells=ONE_CELLS, windows_per_cell=1)
+    assert survey.bytes_needed(ONE_CELLS) == raw.size
+    iq = torch.from_numpy(np.array(raw)).cuda()
+    mean = torch.zeros((ONE_CELLS, n), dtype=torch.float32, device="cuda")
+    peak = torch.zeros_like(mean)
+    survey.process_device(iq.data_ptr(), raw.size, ONE_CELLS, mean.data_ptr(), peak.data_ptr())
+    torch.cuda.synchronize()
+    peak_h = peak.cpu().numpy()[:, list(ONE_BINS)].T  # [target][cell]
+    assert np.array_equal(peak_h.view(np.uint32), cells["s1"].astype(np.float32).view(np.uint32)), "the survey's peak is not the probe's m"
+    assert np.array_equal(cells["s1"].astype(np.float32).astype(np.float64), cells["s1"]), "s1 of one window is a float32 value"
+    survey.close()
+
+
+def test_two_window_cells(pkg):
+    """cells of two windows, 70 of them: every sum has two terms (cell 0's pair sums one), the tile edge at window 128 is a cell edge"""
+    run, *_ = noise_run(pkg, "fft 512 u8, cells of 2", 2560000, ONE_LOG2N, sv.SFMT_U8, 127.5, 2, ONE_CELLS // 2, 1, [(0, b) for b in ONE_BINS])
+    run.close()
+
+
+# ---- the FFT sizes between 512 and 8192, each with its own tile length, and the fourth format at the largest size
+
+PROBE_TILE_PIECES = 2  # kProbeTilePieces (csrc/probe.hip): a tile of k_probe is this many pieces of FftGeom::TW windows
+SIZES_WPC, SIZES_CELLS = 70, 3
+
+
+def tiles_of(log2n, wpc, ncells):
+    """(tile length, length of the last tile, cells whose windows lie in more than one tile) of a call of k_probe"""
+    tile = PROBE_TILE_PIECES * sv.fft_geom(log2n)["TW"]
+    nwin = wpc * ncells
+    return tile, nwin - (nwin - 1) // tile * tile, [c for c in range(ncells) if c * wpc // tile != ((c + 1) * wpc - 1) // tile]
+
+
+def sizes_case(pkg, what, rate, log2n, sfmt, fullscale, nstreams, targets, want_tiles):
+    assert tiles_of(log2n, SIZES_WPC, SIZES_CELLS) == want_tiles
+    tile, last, straddling = want_tiles
+    assert last < tile and straddling, "the case needs a short last tile and a cell that straddles two tiles"
+    run, *_ = noise_run(pkg, what, rate, log2n, sfmt, fullscale, SIZES_WPC, SIZES_CELLS, nstreams, targets)
+    run.close()
+
+
+def test_fft1024_s16_hop128_every_bin_of_a_stream(pkg):
+    """log2n 10: two FFTs to a workgroup, each over two waves, so the exchange is fenced by the workgroup's barrier.  210 windows =
+    a tile of 128 and a short one of 82 (a whole piece and 18 windows); cell 1 (windows 70 .. 139) straddles the two.  Stream 0 has all
+    1024 bins as targets: 128 lanes to an FFT, so every lane walks 8 of them; stream 1 has three."""
+    targets = [(0, b) for b in range(1024)] + [(1, 0), (1, 513), (1, 1023)]
+    sizes_case(pkg, "fft 1024 s16 hop 128, 1027 targets", 2048000, 10, sv.SFMT_S16, 32767.0, 2, targets, (128, 82, [1]))
+
+
+def test_fft2048_s8_hop150(pkg):
+    """log2n 11: the last size with the twiddles in registers, pieces of 32 windows.  210 windows = three tiles of 64 and a short one of
+    18; every one of the three cells straddles a tile edge (64, 128, 192).  Hop 150: window starts that are only 4-byte aligned."""
+    sizes_case(pkg, "fft 2048 s8 hop 150", 2400000, 11, sv.SFMT_S8, 127.5, 1, [(0, b) for b in (0, 1, 375, 1024, 1450, 2047)], (64, 18, [0, 1, 2]))
+
+
+def test_fft4096_u8(pkg):
+    """log2n 12: the first size that fetches its twiddles pass by pass, pieces of 16 windows.  210 windows = six tiles of 32 and a short
+    one of 18; every cell straddles tile edges."""
+    sizes_case(pkg, "fft 4096 u8", 2560000, 12, sv.SFMT_U8, 127.5, 1, [(0, b) for b in (0, 40, 1442, 2048, 2976, 4095)], (32, 18, [0, 1, 2]))
+
+
+def test_fft8192_f32(pkg):
+    """log2n 13 with 8-byte samples: the largest LDS the probe asks for at 2.56 MS/s (64 KB of span and 7 hops, 72 KB of exchange
+    slot).  210 windows = thirteen tiles of 16 and a short one of 2."""
+    assert sv.lds_bytes("probe", 13, sv.SFMT_F32, 160) == 149264 == max(sv.lds_bytes("probe", l, f, 160) for l in range(8, 14) for f in sv.COMPLEX_BYTES)
+    sizes_case(pkg, "fft 8192 f32", 2560000, 13, sv.SFMT_F32, 2.0, 1, [(0, b) for b in (0, 80, 2883, 4096, 8191)], (16, 2, [0, 1, 2]))
+
+
+# ---- the largest hop whose span still fits the LDS
+
+def test_fft256_s16_largest_accepted_hop(pkg):
+    """mi_probe_create accepts a geometry whose workgroup needs at most 160 KiB of LDS.  At fft 256 with s16 the largest such hop is
+    568 samples (9.088 MS/s): 163 632 of 163 840 bytes.  The handle is made, the kernel launches with that much, and the records
+    agree with the model; one hop more is refused at create."""
+    hop = sv.largest_hop("probe", 8, sv.SFMT_S16)
+    assert hop == 568 and sv.lds_bytes("probe", 8, sv.SFMT_S16, hop) == 163632
+    run, *_ = noise_run(pkg, f"fft 256 s16 hop {hop}", hop * sv.WAVE_RATE, 8, sv.SFMT_S16, 32767.0, 70, 2, 1, [(0, b) for b in (0, 20, 128, 255)])
+    run.close()
+    with pytest.raises(pkg.MiError) as e:
+        pkg.Probe(device(pkg, (hop + 1) * sv.WAVE_RATE, 8, sv.SFMT_S16, 32767.0), max_cells=2, windows_per_cell=70, max_targets=4)
+    assert e.value.code == pkg.MI_ERR_INVALID and "over the limit of 163840" in str(e.value), str(e.value)
 
 
 # ---- end to end: survey -> finder -> targets -> probe -> features -> classification -> plan, on one device-generated capture

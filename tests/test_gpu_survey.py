@@ -157,6 +157,18 @@ def test_fft4096_u8_cell33(pkg):
     noise_run(pkg, "fft 4096 u8", 2560000, 12, sv.SFMT_U8, 127.5, 33, 2, 1)
 
 
+def test_fft256_s16_largest_accepted_hop(pkg):
+    """mi_survey_create accepts a geometry whose workgroup needs at most 160 KiB of LDS.  At fft 256 with s16 the largest such hop is
+    568 samples (9.088 MS/s): 163 632 of 163 840 bytes, the working set (the fold region of 24 KB lies over it).  The handle is made, the
+    kernel launches with that much and agrees with the model: two cells of 70 windows, tiles 64 + 6; one hop more is refused at create."""
+    hop = sv.largest_hop("survey", 8, sv.SFMT_S16)
+    assert hop == 568 and sv.lds_bytes("survey", 8, sv.SFMT_S16, hop) == 163632
+    noise_run(pkg, f"fft 256 s16 hop {hop}", hop * sv.WAVE_RATE, 8, sv.SFMT_S16, 32767.0, 70, 2, 1)
+    with pytest.raises(pkg.MiError) as e:
+        pkg.Survey(device(pkg, (hop + 1) * sv.WAVE_RATE, 8, sv.SFMT_S16, 32767.0), max_cells=2, windows_per_cell=70)
+    assert e.value.code == pkg.MI_ERR_INVALID and "over the limit of 163840" in str(e.value), str(e.value)
+
+
 def test_constant_input_mean_equals_peak(pkg):
     """case 7: every byte pair equal, so all 2000 windows are identical: 2000 x m is exact in float64 and mean == peak bit for bit in
     every bin -- a dropped or doubled window shows here that a tolerance would hide."""

@@ -103,6 +103,65 @@ def test_mixer(pkg, L):
     L.mi_mixer_destroy(None)
 
 
+STAGES = {"probe": ("channel probe", "mi_probe_create", "mi_probe_destroy", b"no HIP device: the channel probe runs on the GPU only"),
+          "survey": ("band survey", "mi_survey_create", "mi_survey_destroy", b"no HIP device: the band survey runs on the GPU only")}
+
+
+def stage_create(pkg, L, stage, dev, out):
+    if stage == "probe":
+        return L.mi_probe_create(C.byref(dev), 1, 1, 1, 1, 0, C.byref(out))
+    return L.mi_survey_create(C.byref(dev), 1, 1, 1, 0, C.byref(out))
+
+
+def lds_refusal(stage, log2n, sfmt, hop):
+    """the words of the refusal, with the need that tests/survey_model.py restates from the stage's one LDS function"""
+    import survey_model as sv
+    return (f"{STAGES[stage][0]}: a workgroup would need {sv.lds_bytes(stage, log2n, sfmt, hop)} bytes of LDS at this fft_size, sample format and hop "
+            f"({hop * sv.COMPLEX_BYTES[sfmt]} bytes), over the limit of {sv.LDS_LIMIT} (160 KiB): lower the sample rate").encode()
+
+
+@pytest.mark.parametrize("stage", ["probe", "survey"])
+def test_lds_limit_refused_at_create(pkg, L, stage):
+    """A workgroup of k_probe / k_survey keeps TW windows of span in LDS, so the need grows with the hop, and a geometry that needs more
+    than 160 KiB can never launch: create refuses it, before it looks for a device, with the need and the limit in the message.
+    The largest accepted hop comes from the stage's formula as tests/survey_model.py restates it: at fft 256 with s16 it is 568 samples
+    (9 088 000 S/s, 163 632 bytes) and 569 (9 104 000 S/s, 163 888 bytes) is refused, for both stages (the survey's fold region, 24 KB at
+    most, is the smaller one anywhere near the limit); with f32 it is 282 samples (4 512 000 S/s).  The rate just under the limit passes the check: without a
+    device the refusal is then the missing device's, with one the handle is made.  The messages state the hop as sample_rate / 16000."""
+    import survey_model as sv
+    _, _, destroy, no_device = STAGES[stage]
+    out = C.c_void_p()
+    hop = sv.largest_hop(stage, 8, sv.SFMT_S16)
+    assert hop == 568 and sv.lds_bytes(stage, 8, sv.SFMT_S16, hop) == 163632 and sv.lds_bytes(stage, 8, sv.SFMT_S16, hop + 1) == 163888
+    # every FFT size (each has its own piece length TW, exchange slots and, in the survey, fold region) and every format
+    cases = [(8, sv.SFMT_S16, 32767.0), (8, sv.SFMT_F32, 2.0), (9, sv.SFMT_U8, 127.5), (10, sv.SFMT_S16, 32767.0), (11, sv.SFMT_S8, 127.5),
+             (12, sv.SFMT_U8, 127.5), (13, sv.SFMT_U8, 127.5), (13, sv.SFMT_F32, 2.0)]
+    for log2n, sfmt, fullscale in cases:
+        hop = sv.largest_hop(stage, log2n, sfmt)
+        over = pkg.device_cfg(sample_rate=(hop + 1) * sv.WAVE_RATE, fft_size_log=log2n, sfmt=sfmt, fullscale=fullscale)
+        assert sv.hop_samples(over.sample_rate) == hop + 1
+        refused(pkg, stage_create(pkg, L, stage, over, out), INVALID, lds_refusal(stage, log2n, sfmt, hop + 1))
+        assert not out.value
+        # the last rate that still rounds to the largest accepted hop
+        under = pkg.device_cfg(sample_rate=hop * sv.WAVE_RATE + sv.WAVE_RATE // 2 - 1, fft_size_log=log2n, sfmt=sfmt, fullscale=fullscale)
+        assert sv.hop_samples(under.sample_rate) == hop
+        rc = stage_create(pkg, L, stage, under, out)
+        if pkg.device_count() < 1:
+            refused(pkg, rc, NO_DEVICE, no_device)
+            assert not out.value
+        else:
+            assert rc == 0 and out.value
+            getattr(L, destroy)(out)
+            out = C.c_void_p()
+    assert sv.largest_hop(stage, 8, sv.SFMT_F32) == 282
+    # far over the limit, and the hop check that stands before it: f32 at 2.1 GS/s is a hop of 131 250 samples = 1 050 000 bytes > 2^20
+    far = pkg.device_cfg(sample_rate=10000000, fft_size_log=8, sfmt=sv.SFMT_S16, fullscale=32767.0)
+    refused(pkg, stage_create(pkg, L, stage, far, out), INVALID, lds_refusal(stage, 8, sv.SFMT_S16, 625))
+    wide = pkg.device_cfg(sample_rate=2100000000, fft_size_log=8, sfmt=sv.SFMT_F32, fullscale=2.0)
+    refused(pkg, stage_create(pkg, L, stage, wide, out), INVALID, f"{STAGES[stage][0]}: the hop (sample_rate / 16000 samples) is out of range".encode())
+    assert not out.value
+
+
 def test_gate_plan_host(pkg, L):
     rows, nb = 3, 5
     rule, axc, carried = np.ones(rows, np.uint8), np.full((rows, nb), ord("*"), np.uint8), np.zeros(rows, np.uint8)
