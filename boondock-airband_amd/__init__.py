@@ -121,6 +121,29 @@ TX_STATE_DTYPE = np.dtype([("clock", "<u8"), ("opened", "<u8"), ("last_write", "
 TX_NONE = 0xFFFFFFFF  # first_batch of a record without blocks, close_batch of a file still open
 
 
+class TonesCfg(C.Structure):  # mi_tones_cfg: 0 = 6400 samples
+    _fields_ = [("window_samples", C.c_uint32)]
+
+
+class ToneRecord(C.Structure):  # mi_tone_record
+    _fields_ = [("row", C.c_uint32), ("seq", C.c_uint32), ("end_batch", C.c_uint32), ("end_sample", C.c_uint32), ("best", C.c_uint32),
+                ("second", C.c_uint32), ("best_power", C.c_float), ("second_power", C.c_float), ("mean_power", C.c_float), ("zero", C.c_uint32)]
+
+
+class TonesRule(C.Structure):  # mi_tones_rule: 0 = 2 windows / 500 permille
+    _fields_ = [("min_windows", C.c_uint32), ("min_share_permille", C.c_uint32)]
+
+
+class TonesVote(C.Structure):  # mi_tones_vote
+    _fields_ = [("windows", C.c_uint32), ("votes", C.c_uint32), ("tone", C.c_uint32), ("freq_hz", C.c_float), ("share", C.c_double),
+                ("found", C.c_uint32), ("zero", C.c_uint32)]
+
+
+TONES_STANDARD, TONES_LANES = 51, 64  # MI_TONES_STANDARD, MI_TONES_LANES
+TONE_RECORD_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ToneRecord._fields_])  # the same 40 bytes as a numpy record
+TONES_STATE_DTYPE = np.dtype([("count", "<u4"), ("seq", "<u4"), ("q1", "<f4", (TONES_LANES,)), ("q2", "<f4", (TONES_LANES,))])  # MI_TONES_STATE_ROW_BYTES = 520
+
+
 class OccCfg(C.Structure):  # mi_occ_cfg: 0 = 250 permille / ratio 3.0 / 1 cell
     _fields_ = [("floor_permille", C.c_uint32), ("ratio", C.c_float), ("min_cells", C.c_uint32)]
 
@@ -170,6 +193,9 @@ ABI_SYMBOLS = [
     "mi_outgate_get_state", "mi_outgate_set_state", "mi_outgate_set_timing", "mi_outgate_last_launch_ms", "mi_gate_plan_host",
     "mi_txsplit_create", "mi_txsplit_destroy", "mi_txsplit_set_rows", "mi_txsplit_process_device", "mi_txsplit_download", "mi_txsplit_state_size",
     "mi_txsplit_get_state", "mi_txsplit_set_state", "mi_txsplit_set_timing", "mi_txsplit_last_launch_ms", "mi_tx_plan_host",
+    "mi_tones_create", "mi_tones_destroy", "mi_tones_set_rows", "mi_tones_process_device", "mi_tones_download", "mi_tones_state_size",
+    "mi_tones_get_state", "mi_tones_set_state", "mi_tones_set_timing", "mi_tones_last_launch_ms", "mi_tones_plan_host", "mi_tones_table",
+    "mi_tones_vote_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -264,6 +290,21 @@ def lib():
         L.mi_txsplit_set_timing.argtypes = [vp, C.c_int]
         L.mi_txsplit_last_launch_ms.argtypes = [vp, vp]
         L.mi_tx_plan_host.argtypes = [C.POINTER(TxCfg), vp, C.c_int, vp, sz, C.c_int, vp, sz, vp, vp, sz, vp, vp]
+        L.mi_tones_create.argtypes = [C.POINTER(TonesCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_tones_destroy.argtypes = [vp]
+        L.mi_tones_destroy.restype = None
+        L.mi_tones_set_rows.argtypes = [vp, vp]
+        L.mi_tones_process_device.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp, vp, vp, vp]
+        L.mi_tones_download.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mi_tones_state_size.argtypes = [vp]
+        L.mi_tones_state_size.restype = sz
+        L.mi_tones_get_state.argtypes = [vp, vp, sz]
+        L.mi_tones_set_state.argtypes = [vp, vp, sz]
+        L.mi_tones_set_timing.argtypes = [vp, C.c_int]
+        L.mi_tones_last_launch_ms.argtypes = [vp, vp]
+        L.mi_tones_plan_host.argtypes = [C.POINTER(TonesCfg), vp, C.c_int, vp, sz, C.c_int, vp, sz, vp, vp, vp, sz, vp, vp]
+        L.mi_tones_table.argtypes = [C.c_uint32, vp, vp, vp]
+        L.mi_tones_vote_host.argtypes = [vp, sz, C.POINTER(TonesRule), C.POINTER(TonesVote)]
         L.mi_survey_create.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.mi_survey_destroy.argtypes = [vp]
         L.mi_survey_destroy.restype = None
@@ -372,7 +413,7 @@ class _PostStage(_Handle):
 
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
-        fields .view(TX_STATE_DTYPE) names."""
+        fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE)."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -383,7 +424,7 @@ class _PostStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass"""
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
         return tuple(ms)
@@ -885,6 +926,101 @@ def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_recor
                                  None if waveout is None else _ptr(waveout), row_stride, _ptr(state),
                                  _ptr(records), cap, _ptr(row_first), _ptr(count)))
     return records[:int(count[1])], row_first, count, state
+
+
+def _tones_cfg(window):
+    """None or 0 (the default 6400), a window in samples or a TonesCfg -> TonesCfg"""
+    return window if isinstance(window, TonesCfg) else TonesCfg(int(window or 0))
+
+
+def tones_max_windows(window, nbatches):
+    """the most windows one row completes in a call of nbatches batches"""
+    w = window or 6400
+    return (w - 1 + WAVE_BATCH * nbatches) // w
+
+
+class Tones(_PostStage):
+    """mi_tones: the CTCSS tone finder -- the reference's 51 standard tones (src/ctcss.cpp:101-103), one Goertzel detector each, over
+    every window of `window` samples (0 = 6400, 800 .. 64000) of the rows' audio; a MI_NO_SIGNAL batch resets a row's window.
+    row_enabled: truth value per row (row = stream * nch + channel); max_records: capacity of the record buffer, 0 = rows * the most
+    windows a row completes in max_batches batches.  state() gives rows * 520 bytes, whose fields .view(TONES_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_tones_destroy", "mi_tones", 3
+
+    def __init__(self, row_enabled, max_batches=1, window=0, max_records=0, gpu=0):
+        en = _flags(row_enabled)
+        self.rows, self.max_batches, self.window = en.size, max_batches, _tones_cfg(window).window_samples or 6400
+        most = self.rows * tones_max_windows(self.window, max_batches)
+        self.max_records = min(max_records, most) if max_records else most
+        self._h = C.c_void_p()
+        _check(lib().mi_tones_create(C.byref(_tones_cfg(window)), _ptr(en), self.rows, max_batches, max_records, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_tones_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_records, d_row_first_record, d_count, d_powers=None,
+                       hip_stream=None):
+        """Raw device pointers (ints; d_powers may be None), strides in floats (audio) and bytes (flags); asynchronous on hip_stream."""
+        self._with_powers = d_powers is not None
+        _check(lib().mi_tones_process_device(self._h, d_waveout, row_stride, d_axc, axc_stride, nbatches, d_records, d_powers, d_row_first_record,
+                                             d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (records [k] of TONE_RECORD_DTYPE, powers [k][64] or None where
+        the call stored none, row_first_record [rows + 1], count [2]) with k = count[1], the number of records stored."""
+        records = np.zeros(self.max_records, TONE_RECORD_DTYPE)
+        powers = np.zeros((self.max_records, TONES_LANES), np.float32) if getattr(self, "_with_powers", False) else None
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_tones_download(self._h, hip_stream, _ptr(records), None if powers is None else _ptr(powers), _ptr(row_first), _ptr(count)))
+        k = int(count[1])
+        return records[:k], None if powers is None else powers[:k], row_first, count
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        self._call("set_state", _ptr(buf), buf.size)
+
+
+def tones_plan_host(row_enabled, axc, waveout, state=None, window=0, max_records=0, nbatches=None, want_powers=True):
+    """mi_tones_plan_host: the tone finder's records (and powers) from flags and audio on the host, no GPU.  axc: uint8 [rows][axc_stride];
+    waveout: float32 [rows][row_stride]; state: the blob (rows * 520 bytes) or None (a fresh one); nbatches: batches of the call, default
+    axc's width; max_records: 0 = every record of the call.  Returns (records [count[1]], powers [count[1]][64] or None,
+    row_first_record [rows + 1], count [2], state after the call)."""
+    en = _flags(row_enabled)
+    axc = np.ascontiguousarray(axc, dtype=np.uint8)
+    waveout = np.ascontiguousarray(waveout, dtype=np.float32)
+    assert axc.ndim == 2 and axc.shape[0] == en.size and waveout.ndim == 2 and waveout.shape[0] == en.size
+    rows, axc_stride = axc.shape
+    nb = axc_stride if nbatches is None else nbatches
+    cfg = _tones_cfg(window)
+    state = np.zeros(rows * TONES_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * TONES_STATE_DTYPE.itemsize
+    cap = max_records or max(1, rows * tones_max_windows(cfg.window_samples, nb))
+    records = np.zeros(cap, TONE_RECORD_DTYPE)
+    powers = np.zeros((cap, TONES_LANES), np.float32) if want_powers else None
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_tones_plan_host(C.byref(cfg), _ptr(en), rows, _ptr(axc), axc_stride, nb, _ptr(waveout), waveout.shape[1], _ptr(state),
+                                    _ptr(records), None if powers is None else _ptr(powers), cap, _ptr(row_first), _ptr(count)))
+    k = int(count[1])
+    return records[:k], None if powers is None else powers[:k], row_first, count, state
+
+
+def tones_table(window=0):
+    """mi_tones_table: (freq [51], coeff [51], alias_of [51]) of the tone table at `window` samples (0 = 6400)"""
+    freq, coeff, alias = np.zeros(TONES_STANDARD, np.float32), np.zeros(TONES_STANDARD, np.float32), np.zeros(TONES_STANDARD, np.uint32)
+    _check(lib().mi_tones_table(int(window or 0), _ptr(freq), _ptr(coeff), _ptr(alias)))
+    return freq, coeff, alias
+
+
+def tones_vote_host(records, min_windows=0, min_share_permille=0):
+    """mi_tones_vote_host: one row's records (TONE_RECORD_DTYPE) -> TonesVote; 0 = the defaults, 2 windows and 500 permille"""
+    records = np.ascontiguousarray(records, dtype=TONE_RECORD_DTYPE)
+    out = TonesVote()
+    _check(lib().mi_tones_vote_host(_ptr(records) if records.size else None, records.size, C.byref(TonesRule(min_windows, min_share_permille)),
+                                    C.byref(out)))
+    return out
 
 
 class Survey(_Handle):

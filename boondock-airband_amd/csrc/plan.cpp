@@ -12,6 +12,13 @@
 #include <string>
 
 namespace mi {
+
+const float kStandardToneHz[kStandardTones] = {67.0f,  69.3f,  71.9f,  74.4f,  77.0f,  79.7f,  82.5f,  85.4f,  88.5f,  91.5f,  94.8f,
+                                               97.4f,  100.0f, 103.5f, 107.2f, 110.9f, 114.8f, 118.8f, 123.0f, 127.3f, 131.8f, 136.5f,
+                                               141.3f, 146.2f, 150.0f, 151.4f, 156.7f, 159.8f, 162.2f, 165.5f, 167.9f, 171.3f, 173.8f,
+                                               177.3f, 179.9f, 183.5f, 186.2f, 189.9f, 192.8f, 196.6f, 199.5f, 203.5f, 206.5f, 210.7f,
+                                               218.1f, 225.7f, 229.1f, 233.6f, 241.8f, 250.3f, 254.1f};  // ctcss.cpp:101-103
+
 namespace {
 
 // ToneDetector::ToneDetector, ctcss.cpp:31-42 (omega is a float; cos(float) is the float overload)
@@ -24,11 +31,6 @@ float goertzel_coeff(float tone_freq, float sample_rate, int window_size) {
 // CTCSS::CTCSS + ToneDetectorSet::add, ctcss.cpp:61-73,105-122: target tone first, then every standard
 // tone at least 5 Hz away, dropping tones whose coefficient duplicates an earlier one.
 int goertzel_bank(float ctcss_freq, float sample_rate, int window_size, float* coeffs) {
-    static const float standard_tones[] = {67.0f,  69.3f,  71.9f,  74.4f,  77.0f,  79.7f,  82.5f,  85.4f,  88.5f,  91.5f,  94.8f,
-                                           97.4f,  100.0f, 103.5f, 107.2f, 110.9f, 114.8f, 118.8f, 123.0f, 127.3f, 131.8f, 136.5f,
-                                           141.3f, 146.2f, 150.0f, 151.4f, 156.7f, 159.8f, 162.2f, 165.5f, 167.9f, 171.3f, 173.8f,
-                                           177.3f, 179.9f, 183.5f, 186.2f, 189.9f, 192.8f, 196.6f, 199.5f, 203.5f, 206.5f, 210.7f,
-                                           218.1f, 225.7f, 229.1f, 233.6f, 241.8f, 250.3f, 254.1f};  // ctcss.cpp:101-103
     int n = 0;
     auto add = [&](float f) {
         const float c = goertzel_coeff(f, sample_rate, window_size);
@@ -38,7 +40,7 @@ int goertzel_bank(float ctcss_freq, float sample_rate, int window_size, float* c
         coeffs[n++] = c;
     };
     add(ctcss_freq);
-    for (float t : standard_tones) {
+    for (float t : kStandardToneHz) {
         if (std::abs(ctcss_freq - t) < 5)
             continue;
         add(t);
@@ -94,6 +96,10 @@ float alpha_for_tau(int tau_us) {
 }
 
 }  // namespace
+
+float tone_coeff(float tone_freq, float sample_rate, int window_size) {
+    return goertzel_coeff(tone_freq, sample_rate, window_size);
+}
 
 int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, Plan& p, const char** msg) {
     *msg = "";

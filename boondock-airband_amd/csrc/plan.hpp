@@ -116,6 +116,12 @@ struct RowClasses {
 };
 RowClasses classify_rows(const Plan& p, int nstreams, int nch);
 
+// CTCSS::standard_tones (ctcss.cpp:101-103) in table order and ToneDetector's coefficient (ctcss.cpp:31-42): what the plan's detector
+// sets and the tone finder (tones.hip, poststage_host.cpp) are built from
+constexpr int kStandardTones = 51;
+extern const float kStandardToneHz[kStandardTones];
+float tone_coeff(float tone_freq, float sample_rate, int window_size);
+
 // returns MI_OK or a negative mi_status; msg receives the reason
 int build_plan(const mi_device_cfg& dev, const mi_channel_cfg* chans, int nch, Plan& out, const char** msg);
 

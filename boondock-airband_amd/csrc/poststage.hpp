@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,6 +108,26 @@ struct TxRowState {
 static_assert(sizeof(TxRowState) == MI_TX_STATE_ROW_BYTES && sizeof(mi_tx_record) == 40, "the splitter's blob and record layouts are ABI");
 
 mi_tx_cfg tx_cfg_or_default(const mi_tx_cfg* cfg);  // poststage_host.cpp
+
+// One row of the tone finder's state (include/mi_airband.h "CTCSS tone finder"): the checkpoint blob is an array of these, and
+// tones.hip keeps the same array in device memory.
+struct TonesRowState {
+    uint32_t count;  // samples in the running window, < window
+    uint32_t seq;    // windows completed since creation / set_state
+    float q1[MI_TONES_LANES], q2[MI_TONES_LANES];
+};
+static_assert(sizeof(TonesRowState) == MI_TONES_STATE_ROW_BYTES && sizeof(mi_tone_record) == 40 && sizeof(mi_tones_vote) == 32,
+              "the tone finder's blob and record layouts are ABI");
+
+// What both halves of the tone finder share (poststage_host.cpp).  tones_window: the window with the default filled in, or 0 with
+// the refusal's message set.  tones_max_windows: the most windows one row completes in a call.  tones_coeffs: coeff[64], lanes 51 ..
+// 63 zero.  tones_state_ok: every row's count < window and padding lanes all-zero bits.
+uint32_t tones_window(const mi_tones_cfg* cfg);
+inline uint64_t tones_max_windows(uint32_t window, uint64_t nbatches) {
+    return (window - 1 + static_cast<uint64_t>(kWaveBatch) * nbatches) / window;
+}
+void tones_coeffs(uint32_t window, float* coeff);
+bool tones_state_ok(const TonesRowState* state, size_t rows, uint32_t window);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

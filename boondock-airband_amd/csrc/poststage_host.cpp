@@ -2,9 +2,10 @@
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
-// (target list, features, classification).
+// (target list, features, classification); and the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "poststage.hpp"
 
@@ -392,5 +393,178 @@ extern "C" int mi_probe_classify_host(const mi_probe_features* f, const mi_probe
     r.coherence_max = r.coherence_max != 0.0 ? r.coherence_max : mi::kProbeCoherenceMax;
     r.cv2_min = r.cv2_min != 0.0 ? r.cv2_min : mi::kProbeCv2Min;
     *modulation = (f->coherence < r.coherence_max || f->cv2 < r.cv2_min) ? MI_MOD_NFM : MI_MOD_AM;
+    return MI_OK;
+}
+
+// ---- CTCSS tone finder, host side (include/mi_airband.h "CTCSS tone finder"): the settings both halves share, the twin of tones.hip
+// -- one row, one batch and one sample at a time, the 64 lanes in the inner loop --, the tone table and the vote.
+namespace mi {
+
+constexpr uint32_t kTonesDefaultWindow = static_cast<uint32_t>(kWaveRate * 0.4);  // Squelch::set_ctcss_freq's slow window, squelch.cpp:115
+
+uint32_t tones_window(const mi_tones_cfg* cfg) {
+    const uint32_t w = cfg && cfg->window_samples ? cfg->window_samples : kTonesDefaultWindow;
+    if (w < 800 || w > 64000) {
+        fail(MI_ERR_INVALID, "tone finder: window_samples outside 800 .. 64000 (0 = the default 6400)");
+        return 0;
+    }
+    return w;
+}
+
+void tones_coeffs(uint32_t window, float* coeff) {
+    for (int t = 0; t < MI_TONES_LANES; ++t)
+        coeff[t] = t < kStandardTones ? tone_coeff(kStandardToneHz[t], static_cast<float>(kWaveRate), static_cast<int>(window)) : 0.0f;
+}
+
+bool tones_state_ok(const TonesRowState* state, size_t rows, uint32_t window) {
+    for (size_t r = 0; r < rows; ++r) {
+        if (state[r].count >= window)
+            return false;
+        for (int t = kStandardTones; t < MI_TONES_LANES; ++t) {
+            uint32_t a, b;
+            std::memcpy(&a, &state[r].q1[t], 4);
+            std::memcpy(&b, &state[r].q2[t], 4);
+            if (a | b)
+                return false;
+        }
+    }
+    return true;
+}
+
+}  // namespace mi
+static_assert(mi::kTonesDefaultWindow == 6400 && mi::kStandardTones == MI_TONES_STANDARD, "the default window and the table's length are ABI");
+
+extern "C" int mi_tones_plan_host(const mi_tones_cfg* cfg, const uint8_t* row_enabled, int rows, const char* axc, size_t axc_stride, int nbatches,
+                                  const float* waveout, size_t row_stride, void* state_inout, mi_tone_record* records, float* powers,
+                                  size_t max_records, uint32_t* row_first_record, uint32_t* count) {
+    if (!row_enabled || !axc || !waveout || !state_inout || !records || !row_first_record || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || axc_stride < static_cast<size_t>(nbatches) || max_records < 1)
+        return fail(MI_ERR_INVALID, "tone plan needs rows >= 1, 1 <= nbatches <= axc_stride and max_records >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    const uint32_t window = mi::tones_window(cfg);
+    if (!window)
+        return MI_ERR_INVALID;
+    if (static_cast<uint64_t>(rows) * mi::tones_max_windows(window, static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "tone plan: the windows of the call do not fit the 32-bit record count");
+    mi::TonesRowState* state = static_cast<mi::TonesRowState*>(state_inout);
+    if (!mi::tones_state_ok(state, static_cast<size_t>(rows), window))
+        return fail(MI_ERR_INVALID, "tone plan: malformed state blob (count >= window or a padding lane not zero)");
+    float coeff[MI_TONES_LANES];
+    mi::tones_coeffs(window, coeff);
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first_record[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::TonesRowState s = state[r];
+        for (int b = 0; b < nbatches; ++b) {
+            if (axc[static_cast<size_t>(r) * axc_stride + b] == MI_NO_SIGNAL) {  // CTCSS::reset, ctcss.cpp:165-172
+                s.count = 0;
+                for (int t = 0; t < MI_TONES_LANES; ++t)
+                    s.q1[t] = s.q2[t] = 0.0f;
+                continue;
+            }
+            const float* x = waveout + static_cast<size_t>(r) * row_stride + static_cast<size_t>(b) * mi::kWaveBatch;
+            for (int i = 0; i < mi::kWaveBatch; ++i) {
+                const float v = x[i];
+                for (int t = 0; t < mi::kStandardTones; ++t) {  // ToneDetector::process_sample, ctcss.cpp:44-49
+                    const float q0 = coeff[t] * s.q1[t] - s.q2[t] + v;
+                    s.q2[t] = s.q1[t];
+                    s.q1[t] = q0;
+                }
+                if (++s.count < window)
+                    continue;
+                float p[MI_TONES_LANES] = {};
+                for (int t = 0; t < mi::kStandardTones; ++t)  // ToneDetector::relative_power, ctcss.cpp:51-55
+                    p[t] = s.q1[t] * s.q1[t] + s.q2[t] * s.q2[t] - s.q1[t] * s.q2[t] * coeff[t];
+                float total = 0.0f, bp = p[0], sp = 0.0f;
+                uint32_t best = 0, second = 0xFFFFFFFFu;
+                for (int t = 0; t < mi::kStandardTones; ++t) {
+                    total += p[t];
+                    if (t == 0)
+                        continue;
+                    if (p[t] > bp) {
+                        second = best;
+                        sp = bp;
+                        best = static_cast<uint32_t>(t);
+                        bp = p[t];
+                    } else if (second == 0xFFFFFFFFu || p[t] > sp) {
+                        second = static_cast<uint32_t>(t);
+                        sp = p[t];
+                    }
+                }
+                if (k < max_records) {
+                    records[k] = mi_tone_record{static_cast<uint32_t>(r), s.seq, static_cast<uint32_t>(b), static_cast<uint32_t>(i), best, second,
+                                                bp, sp, total / 51.0f, 0};
+                    if (powers)
+                        std::memcpy(powers + static_cast<size_t>(k) * MI_TONES_LANES, p, sizeof(p));
+                }
+                ++k;
+                s.count = 0;
+                s.seq += 1;
+                for (int t = 0; t < MI_TONES_LANES; ++t)
+                    s.q1[t] = s.q2[t] = 0.0f;
+            }
+        }
+        state[r] = s;
+    }
+    row_first_record[rows] = k;
+    count[0] = k;
+    count[1] = k < max_records ? k : static_cast<uint32_t>(max_records);
+    return MI_OK;
+}
+
+extern "C" int mi_tones_table(uint32_t window, float* freq, float* coeff, uint32_t* alias_of) {
+    const mi_tones_cfg cfg{window};
+    const uint32_t w = mi::tones_window(&cfg);
+    if (!w)
+        return MI_ERR_INVALID;
+    float c[MI_TONES_LANES];
+    mi::tones_coeffs(w, c);
+    for (int t = 0; t < mi::kStandardTones; ++t) {
+        if (freq)
+            freq[t] = mi::kStandardToneHz[t];
+        if (coeff)
+            coeff[t] = c[t];
+        if (alias_of) {
+            int first = t;
+            for (int u = t - 1; u >= 0; --u)
+                first = c[u] == c[t] ? u : first;
+            alias_of[t] = static_cast<uint32_t>(first);
+        }
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_tones_vote_host(const mi_tone_record* records, size_t n, const mi_tones_rule* rule, mi_tones_vote* out) {
+    if ((!records && n) || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi_tones_rule r = rule ? *rule : mi_tones_rule{0, 0};
+    if (r.min_share_permille > 1000)
+        return fail(MI_ERR_INVALID, "tone vote: min_share_permille must be at most 1000");
+    if (n > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "tone vote: more than 2^32 - 1 records");
+    r.min_windows = r.min_windows ? r.min_windows : 2;
+    r.min_share_permille = r.min_share_permille ? r.min_share_permille : 500;
+    uint32_t votes[MI_TONES_STANDARD] = {};
+    for (size_t i = 0; i < n; ++i) {
+        if (records[i].best >= MI_TONES_STANDARD)
+            return fail(MI_ERR_INVALID, "tone vote: a record's best is not an index into the tone table");
+        if (records[i].best_power > records[i].mean_power)  // ctcss.cpp:150
+            votes[records[i].best] += 1;
+    }
+    uint32_t tone = 0;
+    for (uint32_t t = 1; t < MI_TONES_STANDARD; ++t)
+        tone = votes[t] > votes[tone] ? t : tone;
+    mi_tones_vote v{static_cast<uint32_t>(n), votes[tone], 0, 0.0f, 0.0, 0, 0};
+    if (v.votes) {
+        v.tone = tone;
+        v.freq_hz = mi::kStandardToneHz[tone];
+        v.share = static_cast<double>(v.votes) / static_cast<double>(v.windows);
+    }
+    v.found = v.windows >= r.min_windows && static_cast<uint64_t>(v.votes) * 1000 >= static_cast<uint64_t>(r.min_share_permille) * v.windows ? 1 : 0;
+    *out = v;
     return MI_OK;
 }

@@ -757,6 +757,98 @@ int mi_probe_features_host(const mi_device_cfg* dev, int bin, const mi_probe_cel
                            mi_probe_features* out);
 int mi_probe_classify_host(const mi_probe_features* f, const mi_probe_rule* rule /* NULL = defaults */, int* modulation);
 
+/* ---------------- CTCSS tone finder: all 51 standard tones per window, on the device ----------------
+ * The demodulator answers "is THIS tone present?" (Squelch::set_ctcss_freq, src/ctcss.cpp:105-163): one Goertzel detector for the
+ * target, one for every standard tone at least 5 Hz away, and the target must be the strongest.  The finder answers "which tone?":
+ * the whole bank of the reference's 51 CTCSS::standard_tones (ctcss.cpp:101-103) over the audio mi_demod_process_device wrote, one
+ * record per row and window of window_samples samples.  A post-stage like the gate and the splitter: rows of d_waveout plus d_axc,
+ * state carried in the handle, a host twin, every byte the same on every run, no host synchronisation.
+ *
+ * Tone table: the 51 tones in the reference's table order, index 0 = 67.0 Hz .. 50 = 254.1 Hz.  Coefficient of tone t at window W:
+ * ToneDetector's (ctcss.cpp:31-42) at sample rate MI_WAVE_RATE: k = (int)(0.5 + W * freq / 16000), omega = (float)(2 pi k / W),
+ * coeff = (float)(2 cos(omega)) -- the value mi_plan_ctcss_coeffs gives for a channel with that ctcss_freq.  Below W = 6400 tones
+ * share a k and so a coefficient: mi_tones_table reports the aliases (11 distinct coefficients at 800, 25 at 2000, 37 at 3200, 51
+ * at 6400 and above).  Aliased tones have equal powers; the lowest index of the group is the one `best` and `second` name.
+ *
+ * Per row the state is { uint32 count; uint32 seq; float q1[64]; float q2[64] }, lane t < 51 = tone t, lanes 51 .. 63 zero.  For
+ * each batch b of an enabled row, in order:
+ *   axc[row][b] == MI_NO_SIGNAL:  count = 0 and q1 = q2 = 0 -- CTCSS::reset on the way to CLOSED (squelch.cpp:287, ctcss.cpp:165-172),
+ *                                 restated at batch resolution
+ *   otherwise:  each of the batch's 2000 samples x in order:  for every tone  q0 = coeff * q1 - q2 + x; q2 = q1; q1 = q0;  count++;
+ *               when count == window:  p[t] = q1 * q1 + q2 * q2 - q1 * q2 * coeff for every tone, one record is emitted, then
+ *               q1 = q2 = 0, count = 0, seq++
+ * Every operation is float32 and rounds on its own (no fused multiply-add).  In a record, mean_power is the sequential float32 sum
+ * p[0] + p[1] + .. + p[50] in index order divided by 51.0f; best is the index of the largest p, the lowest index on ties; second the
+ * same over the other 50.  Records are stored rows ascending, seq ascending within a row.  A disabled row produces no record and
+ * every byte of its state stays.  Inputs are the demodulator's audio (finite, |x| <= 1); NaN and Inf are unspecified.
+ *
+ * State blob: rows * MI_TONES_STATE_ROW_BYTES bytes, per row little-endian in the layout above. */
+enum { MI_TONES_STANDARD = 51, MI_TONES_LANES = 64, MI_TONES_STATE_ROW_BYTES = 520 };
+typedef struct { uint32_t window_samples; } mi_tones_cfg; /* 0 = 6400 = (int)(MI_WAVE_RATE * 0.4), squelch.cpp:115; 800 .. 64000 */
+typedef struct {
+    uint32_t row, seq;              /* seq: the row's window number since creation / set_state, 0-based; a reset does not reset it */
+    uint32_t end_batch, end_sample; /* call-relative batch and offset (0 .. 1999) of the window's last sample */
+    uint32_t best, second;          /* indices into the tone table; ties: the lowest index */
+    float best_power, second_power, mean_power;
+    uint32_t zero;
+} mi_tone_record;                   /* 40 bytes */
+typedef struct mi_tones mi_tones;
+
+/* cfg NULL = the default window.  row_enabled [rows] as for mi_txsplit_create; 1 <= rows < 2^20, 1 <= max_batches <= 2^20 and
+ * rows * ((window - 1 + 2000 * max_batches) / window) < 2^24: the second factor is the most windows one row can complete in a call.
+ * max_records: capacity of the caller's record (and powers) buffer, 0 = that product. */
+int mi_tones_create(const mi_tones_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_records, int gpu, mi_tones** out);
+void mi_tones_destroy(mi_tones* t);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_tones_set_rows(mi_tones* t, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the buffers mi_demod_process_device wrote; alignment and strides as for
+ * mi_outgate_process_device (d_waveout is required).  Outputs in device memory:
+ *   d_records           [max_records]      rows ascending, seq ascending within a row (8-byte aligned)
+ *   d_powers            [max_records][64]  or NULL (not wanted): p[0 .. 50] of record k, entries 51 .. 63 zero (4-byte aligned)
+ *   d_row_first_record  [rows + 1]         exclusive prefix of the rows' record counts
+ *   d_count             [2]                number of records, and min(that, max_records) = the number stored
+ * Nothing is written at or beyond max_records.  Asynchronous on `hip_stream`, no host synchronisation; three kernels (walk, scan,
+ * bank) without atomics, so every byte is the same on every run. */
+int mi_tones_process_device(mi_tones* t, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
+                            mi_tone_record* d_records, float* d_powers, uint32_t* d_row_first_record, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_tones_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] records (and their powers, if the call had a d_powers and powers is not NULL; with powers not NULL after
+ * a call without d_powers it is refused).  records, powers and row_first_record may each be NULL.  The one place that synchronises. */
+int mi_tones_download(mi_tones* t, void* hip_stream, mi_tone_record* records, float* powers, uint32_t* row_first_record, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_TONES_STATE_ROW_BYTES bytes in the layout above (mi_tones_plan_host reads and writes the same
+ * bytes).  set_state refuses a blob with count >= window or a padding lane that is not zero.  Both complete queued work first. */
+size_t mi_tones_state_size(const mi_tones* t);
+int mi_tones_get_state(mi_tones* t, void* buf, size_t len);
+int mi_tones_set_state(mi_tones* t, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[3] = {walk, scan, bank}.  tools/tones_rate.py. */
+int mi_tones_set_timing(mi_tones* t, int on);
+int mi_tones_last_launch_ms(mi_tones* t, float* ms /* [3] */);
+/* The host twin: no GPU and no HIP call; the same state blob byte for byte, the same records and powers.  axc [rows][axc_stride];
+ * waveout [rows][row_stride]; state_inout rows * MI_TONES_STATE_ROW_BYTES bytes, read and updated; records holds max_records
+ * entries (max_records >= 1) and powers, if not NULL, max_records * 64 floats, of which min(count[0], max_records) = count[1] are
+ * written. */
+int mi_tones_plan_host(const mi_tones_cfg* cfg, const uint8_t* row_enabled, int rows, const char* axc, size_t axc_stride, int nbatches,
+                       const float* waveout, size_t row_stride, void* state_inout, mi_tone_record* records, float* powers, size_t max_records,
+                       uint32_t* row_first_record, uint32_t* count /* [2] */);
+/* The tone table at `window` (0 = the default): freq[t], coeff[t] and alias_of[t] = the lowest index with the same coefficient
+ * (t itself where the tone has a coefficient of its own).  Each output may be NULL. */
+int mi_tones_table(uint32_t window, float* freq /* [51] */, float* coeff /* [51] */, uint32_t* alias_of /* [51] */);
+/* From one row's records to a ctcss_freq.  A window votes for its `best` iff best_power > mean_power (the reference's second
+ * condition, ctcss.cpp:150; the first, "the target is the strongest", holds for `best` by construction).  out describes the tone
+ * with the most votes, the lowest index on ties (tone = freq_hz = share = 0 without any vote): windows = n, votes = that tone's,
+ * share = votes / (double)windows, found iff windows >= min_windows and votes * 1000 >= min_share_permille * windows.
+ * rule NULL or a field that is 0 takes its default, min_windows 2 and min_share_permille 500; min_share_permille <= 1000.  On noise
+ * alone the strongest of 51 powers is several times their mean, so one window is no detection: the vote is.  The defaults are a
+ * caller's settings like the finder's ratio, not tolerances; they have been tried on synthetic signals only. */
+typedef struct { uint32_t min_windows, min_share_permille; } mi_tones_rule;
+typedef struct {
+    uint32_t windows, votes, tone;
+    float freq_hz;
+    double share;
+    uint32_t found, zero;
+} mi_tones_vote;                    /* 32 bytes */
+int mi_tones_vote_host(const mi_tone_record* records, size_t n, const mi_tones_rule* rule /* NULL = defaults */, mi_tones_vote* out);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
