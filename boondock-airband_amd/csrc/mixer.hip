@@ -113,6 +113,8 @@ int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stri
         return fail(MI_ERR_INVALID, "NULL argument");
     if (m->stereo && !d_right)
         return fail(MI_ERR_INVALID, "stereo mixer needs a right-channel buffer");
+    if (axc_stride < static_cast<size_t>(nbatches) || row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
     if (row_stride % 4 != 0 || !aligned(d_waveout, 16) || !aligned(d_left, 16) || (d_right && !aligned(d_right, 16)))
         return fail(MI_ERR_INVALID, "audio buffers must be 16-byte aligned with a row stride that is a multiple of 4 floats");
     if (hipSetDevice(m->gpu) != hipSuccess)

@@ -395,7 +395,8 @@ void mi_mixer_destroy(mi_mixer* m);
 int mi_mixer_is_stereo(const mi_mixer* m);
 /* d_waveout/d_axc: device buffers as written by mi_demod_process_device (nbatches batches); d_left / d_right:
  * [nbatches * WAVE_BATCH] (d_right may be NULL for a mono mixer, must not be for a stereo one); d_axc_out: [nbatches].
- * Enqueued on `hip_stream`, asynchronous. */
+ * A row_stride below nbatches * WAVE_BATCH or an axc_stride below nbatches is refused with MI_ERR_INVALID, as every other
+ * post-stage refuses it.  Enqueued on `hip_stream`, asynchronous. */
 int mi_mixer_process_device(mi_mixer* m, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
                             float* d_left, float* d_right, char* d_axc_out, void* hip_stream);
 

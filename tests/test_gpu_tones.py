@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 from common import AGC_EXTRA
-from test_tones_model import E2E_BATCHES, STAR, case, e2e_setup, e2e_verdict
-from tones_model import LANES, NO_SIGNAL, NTONES, RECORD, WAVE_BATCH, fresh_state, run_in_calls, tones_model
+from test_tones_model import E2E_BATCHES, LONG_NB, LONG_WINDOWS, STAR, assert_long_call_conditions, case, e2e_setup, e2e_verdict
+from tones_model import (LANES, LONG_PRELUDE, NO_SIGNAL, NTONES, RECORD, WAVE_BATCH, fresh_state, long_call_masks, long_call_planes, run_in_calls,
+                         tones_model)
 
 gpu = pytest.mark.gpu
 SENT_BYTE = 0xA5
@@ -61,7 +62,8 @@ def check(what, got, dest, rows, want_rec, want_pw, want_first):
 
 
 def run_calls(pkg, axc, wave, window, cuts, what, masks=None, cap=0, powers=True, pad=0, stream=None, twin_at=None):
-    """One finder over consecutive calls of the lengths `cuts`, each over buffers laid out for `pad` more batches than the call:
+    """One finder over consecutive calls of the lengths `cuts`, each over buffers laid out for `pad` more batches than the call (their
+    flags the opposite of the row's last, so a walk or a twin that read them would reset or run on where the model does not):
     records, powers and the state after every call against the model, and the state against the host twin run from the same blob.
     masks: the enabled rows of each call (set_rows in between).  twin_at: that call is made by the host twin from the device's state
     blob, whose state goes back to the device."""
@@ -78,6 +80,7 @@ def run_calls(pkg, axc, wave, window, cuts, what, masks=None, cap=0, powers=True
         a = np.full((rows, lay), NO_SIGNAL, np.uint8)
         w = np.full((rows, lay * WAVE_BATCH), np.float32(0.5))
         a[:, :n], w[:, :n * WAVE_BATCH] = axc[:, done:done + n], wave[:, done * WAVE_BATCH:(done + n) * WAVE_BATCH]
+        a[:, n:] = np.where(a[:, n - 1:n] == NO_SIGNAL, STAR, NO_SIGNAL)  # behind the call: the opposite of the row's last flag
         want_rec, want_pw, want_first, after = tones_model(a[:, :n], w[:, :n * WAVE_BATCH], state, en, window)
         before = tn.state()
         assert before.tobytes() == state.tobytes(), f"{what}, call {i}: state before"
@@ -144,6 +147,51 @@ def test_capped_records_padded_strides_and_a_side_stream(pkg, powers):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     run_calls(pkg, axc, wave, 800, (5, 7), f"cap {cap}, powers {powers}", cap=cap, powers=powers, pad=3, stream=side)
+
+
+def long_case(nb, window):
+    """long_call_planes, with the conditions that make it worth running checked from the model before the device sees it"""
+    axc, wave = long_call_planes(nb, window)
+    masks = long_call_masks()
+    calls = run_in_calls(axc, wave, (LONG_PRELUDE, nb), window, masks=masks)[0]
+    assert_long_call_conditions(nb, window, calls)
+    return axc, wave, masks, calls
+
+
+@gpu
+@pytest.mark.parametrize("window", LONG_WINDOWS)
+@pytest.mark.parametrize("nb", LONG_NB)
+def test_calls_past_64_batches_equal_model_and_twin(pkg, nb, window):
+    """A 3-batch call, then one of 64, 65, 128 or 130 batches in the carried state: k_tones_walk takes each row in two or three trips
+    of 64 flags and carries count, window start, carried-state mark and record count from trip to trip.  Nine rows (tones_model.py,
+    long_call_planes): all signal -- whole trips, more than 64 windows a stretch at window 800, a window across the trip boundary at
+    64000 --, all silent, a reset on the last lane of trip 0 and on the first of trip 1, a run from lane 62 to lane 2 of the next
+    trip, a silent first trip, two drawn rows and one the long call disables."""
+    axc, wave, masks, calls = long_case(nb, window)
+    total, state = run_calls(pkg, axc, wave, window, (LONG_PRELUDE, nb), f"long call of {nb}, window {window}", masks=masks)
+    assert total == sum(len(c[1]) for c in calls) and state.tobytes() == calls[1][4].tobytes()
+
+
+@gpu
+def test_long_call_with_half_its_records_stored(pkg):
+    """130 batches at window 800 with room for half the long call's records: the walk writes no piece and the bank no record at or
+    behind the capacity, row_first_record and count[0] still count them all, and every row's tail still writes its state"""
+    axc, wave, masks, calls = long_case(130, 800)
+    cap = len(calls[1][1]) // 2
+    assert cap > len(calls[0][1]) and cap > 129
+    for powers in (True, False):
+        run_calls(pkg, axc, wave, 800, (LONG_PRELUDE, 130), f"long call, cap {cap}, powers {powers}", masks=masks, cap=cap, powers=powers)
+
+
+@gpu
+def test_long_call_padded_strides_on_a_side_stream(pkg):
+    """65 batches in buffers laid out for 68, enqueued on a side stream behind the uploads: lane 0 of the second trip reads batch 64 of
+    its own row, not what lies behind the call"""
+    import torch
+    axc, wave, masks, _ = long_case(65, 800)
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    run_calls(pkg, axc, wave, 800, (LONG_PRELUDE, 65), "long call, padded, side stream", masks=masks, pad=3, stream=side)
 
 
 @gpu

@@ -1,40 +1,12 @@
 """The mixer restatement (src/mixer.cpp:56-98, 133-140, 190-213).  mixer.cpp cannot be built here (it needs the
 reference's umbrella header with lame / shout / libconfig), so parity is unpinned by the reference; the restatement is
-checked against the arithmetic written out in numpy, operation for operation."""
+checked against the arithmetic written out in numpy (mixer_model.py), operation for operation."""
 import numpy as np
+import pytest
 
 import libs
 from common import WAVE_BATCH
-
-
-def numpy_mixer(inputs, wave, axc, nb):
-    stereo = any(b != 0.0 for _, _, b in inputs)
-    left = np.zeros(nb * WAVE_BATCH, np.float32)
-    right = np.zeros(nb * WAVE_BATCH, np.float32)
-    out = np.full(nb, ord(" "), np.uint8)
-    for b in range(nb):
-        sl = slice(b * WAVE_BATCH, (b + 1) * WAVE_BATCH)
-        for row, amp, bal in inputs:
-            if axc[row, b] == ord(" "):
-                continue
-            ampl = np.float32(min(np.float32(1.0), np.float32(1.0) - np.float32(bal)))
-            ampr = np.float32(min(np.float32(1.0), np.float32(1.0) + np.float32(bal)))
-            ml, mr = np.float32(amp) * ampl, np.float32(amp) * ampr
-            if ml != 0:
-                left[sl] = left[sl] + wave[row, sl] * ml
-            if stereo and mr != 0:
-                right[sl] = right[sl] + wave[row, sl] * mr
-            out[b] = ord("*")
-    return left, (right if stereo else None), out
-
-
-def case(seed, rows=6, nb=5):
-    rng = np.random.default_rng(seed)
-    wave = rng.uniform(-1, 1, (rows, nb * WAVE_BATCH + 100)).astype(np.float32)
-    axc = np.where(rng.random((rows, nb)) < 0.6, ord("*"), ord(" ")).astype(np.uint8)
-    axc[1, 2] = ord("<")  # AFC indicators count as signal (output.cpp:564)
-    axc[:, 3] = ord(" ")  # a batch nobody talks in
-    return wave, axc
+from mixer_model import INF_ROW, LISTS, LONE_BATCH, NO_SIGNAL, ROWS, SILENT_BATCH, assert_mix_conditions, case, mixer_planes, numpy_mixer
 
 
 def test_mono_mixer_sums_in_input_order():
@@ -59,3 +31,21 @@ def test_stereo_mixer_balance():
     for b in np.nonzero(only0)[0]:
         sl = slice(b * WAVE_BATCH, (b + 1) * WAVE_BATCH)
         assert np.array_equal(l[sl], wave[0, sl]) and not r[sl].any()
+
+
+@pytest.mark.parametrize("name", list(LISTS))
+@pytest.mark.parametrize("nb,pad", [(6, 0), (6, 3), (1, 0), (2, 3)])
+def test_oracle_reads_only_what_the_reference_copies(name, nb, pad):
+    """mixer_planes: NaN in every NO_SIGNAL batch, in the row no input lists and behind the call, +Inf on a row whose multiplier is
+    0.0f in one channel.  ao_mixer_run equals the numpy mixer byte for byte (NaN != NaN, so bytes), no NaN comes out, and Inf comes
+    out of the one channel its row feeds: `mult == 0.0f` skipped the input, it did not multiply it."""
+    wave, axc = mixer_planes(ROWS, nb, pad)
+    assert np.isnan(wave[:, nb * WAVE_BATCH:]).all() and np.isnan(wave[ROWS - 1]).all() and (axc[ROWS - 1] != NO_SIGNAL).all()
+    assert np.isinf(wave[INF_ROW, :WAVE_BATCH]).any() and {ord("<"), ord(">")} <= set(axc[:, :nb].reshape(-1).tolist())
+    assert nb <= LONE_BATCH or ((axc[:ROWS - 1, LONE_BATCH] != NO_SIGNAL).sum() == 1 and (axc[:ROWS - 1, SILENT_BATCH] == NO_SIGNAL).all())
+    inputs = LISTS[name]
+    l, r, out = libs.oracle_mixer(inputs, wave, axc, nb)
+    el, er, eout = numpy_mixer(inputs, wave, axc, nb)
+    assert (r is None) == (er is None)
+    assert l.tobytes() == el.tobytes() and out.tobytes() == eout.tobytes() and (r is None or r.tobytes() == er.tobytes())
+    assert_mix_conditions(name, axc, nb, l, r, out)

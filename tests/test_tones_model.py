@@ -11,9 +11,9 @@ import pytest
 
 import libs
 from common import bytes_for_batches, oracle_run
-from tones_model import (DEFAULT_WINDOW, LANES, NO_SIGNAL, NTONES, RECORD, STANDARD_TONES, STATE, WAVE_BATCH, WAVE_RATE, alias_of, coeffs, detector_set,
-                         draw_audio, draw_flags, fresh_state, full_scale_audio, has_tone, run_in_calls, silence, tone_audio, tones_model, two_tone_audio,
-                         vote)
+from tones_model import (DEFAULT_WINDOW, LANES, LONG_PRELUDE, LONG_ROWS, NO_SIGNAL, NTONES, RECORD, STANDARD_TONES, STATE, WAVE_BATCH, WAVE_RATE,
+                         alias_of, coeffs, detector_set, draw_audio, draw_flags, fresh_state, full_scale_audio, has_tone, long_call_masks,
+                         long_call_planes, run_in_calls, silence, tone_audio, tones_model, two_tone_audio, vote)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TONES_SYMBOLS = {"mi_tones_create", "mi_tones_destroy", "mi_tones_set_rows", "mi_tones_process_device", "mi_tones_download", "mi_tones_state_size",
@@ -140,12 +140,13 @@ def case(rows, nb, window, seed=0, p_open=0.85):
     return axc, draw_audio(rng, rows, nb * WAVE_BATCH)
 
 
-def assert_twin_equals_model(pkg, axc, wave, window, cuts, what, enabled=None):
+def assert_twin_equals_model(pkg, axc, wave, window, cuts, what, enabled=None, masks=None, calls=None):
+    """masks: the enabled rows of each call; calls: the model's run_in_calls over the same arguments, where the caller has it already"""
     rows = axc.shape[0]
-    en = np.ones(rows, np.uint8) if enabled is None else enabled
-    calls, want_state = run_in_calls(axc, wave, cuts, window, en)
+    masks = [np.ones(rows, np.uint8) if enabled is None else enabled] * len(cuts) if masks is None else masks
+    calls, want_state = run_in_calls(axc, wave, cuts, window, masks=masks) if calls is None else calls
     state, total = None, 0
-    for n, (done, want_rec, want_pw, want_first, want_after) in zip(cuts, calls):
+    for n, en, (done, want_rec, want_pw, want_first, want_after) in zip(cuts, masks, calls):
         rec, pw, first, count, state = pkg.tones_plan_host(en, axc[:, done:done + n], wave[:, done * WAVE_BATCH:(done + n) * WAVE_BATCH], state, window)
         assert tuple(count) == (len(want_rec), len(want_rec)), f"{what} at batch {done}: counts {count} vs {len(want_rec)}"
         assert np.array_equal(first, want_first), f"{what} at batch {done}: row_first_record"
@@ -173,6 +174,51 @@ def test_plan_host_equals_the_model(pkg, rows, window):
     if window == 2000:
         rec = tones_model(axc, wave, window=window)[0]
         assert (rec["end_sample"] == WAVE_BATCH - 1).all() and list(rec["seq"][rec["row"] == 0]) == list(range(16))
+
+
+LONG_NB = [64, 65, 128, 130]
+LONG_WINDOWS = [800, 2000, 6400, 64000]
+
+
+def assert_long_call_conditions(nb, window, calls):
+    """What makes long_call_planes worth running, from the model's two calls alone (here and before the device runs them)"""
+    prelude, (_, rec, _, first, after) = calls[0][4], calls[1]
+    of = lambda name: rec[first[LONG_ROWS[name]]:first[LONG_ROWS[name] + 1]]
+    ends = lambda name: [(int(x["seq"]), int(x["end_batch"]), int(x["end_sample"])) for x in of(name)]
+    assert (prelude["count"] == LONG_PRELUDE * WAVE_BATCH % window).all() and (prelude["seq"] == LONG_PRELUDE * WAVE_BATCH // window).all()
+    a = of("A")
+    assert len(a) == (int(prelude[0]["count"]) + nb * WAVE_BATCH) // window
+    if window == 800:
+        assert len(a) >= 129, "three trips of the walk's window loop"
+    if window == 64000 and nb >= 128:
+        end = a["end_batch"].astype(np.int64) * WAVE_BATCH + a["end_sample"]
+        assert ((end - window < 64 * WAVE_BATCH) & (64 * WAVE_BATCH <= end)).any(), "a window across the boundary of the walk's trips"
+    b = LONG_ROWS["B"]
+    assert len(of("B")) == 0 and after[b]["count"] == 0 and not after[b]["q1"].any() and not after[b]["q2"].any()
+    assert prelude[b]["q1"].any() == (LONG_PRELUDE * WAVE_BATCH % window != 0), "where the prelude leaves a count, the reset has something to clear"
+    c, d = LONG_ROWS["C"], LONG_ROWS["D"]
+    rowless = lambda x: np.rec.fromarrays([x[n] for n in RECORD.names[1:]]).tobytes()
+    assert len(of("C")) and len(of("D")) and rowless(of("C")) != rowless(of("D"))
+    # ... and not by their audio alone: the windows end elsewhere, or (no window ends behind batch 63) the counts left differ
+    assert ends("C") != ends("D") or (window > 2000 and after[c]["count"] != after[d]["count"])
+    e = LONG_ROWS["E"]
+    assert int(after[e]["count"]) == ((min(nb, 67) - 62) * WAVE_BATCH % window if nb <= 67 else 0)
+    assert bool(after[e]["q1"].any()) == bool(after[e]["count"])
+    i = LONG_ROWS["I"]
+    assert len(of("I")) == 0 and after[i].tobytes() == prelude[i].tobytes() and len(prelude[i].tobytes()) == 520 and any(prelude[i].tobytes())
+
+
+@pytest.mark.parametrize("window", LONG_WINDOWS)
+@pytest.mark.parametrize("nb", LONG_NB)
+def test_plan_host_equals_the_model_past_64_batches(pkg, nb, window):
+    """long_call_planes as a 3-batch call and one of 64, 65, 128 or 130 on one state: the rows the device's walk takes in more than one
+    64-batch trip -- whole trips of signal, a reset on either side of the trip boundary, a run across it, a silent first trip -- with
+    the conditions that make them so asserted from the model"""
+    axc, wave = long_call_planes(nb, window)
+    cuts, masks = (LONG_PRELUDE, nb), long_call_masks()
+    calls = run_in_calls(axc, wave, cuts, window, masks=masks)
+    assert_long_call_conditions(nb, window, calls[0])
+    assert_twin_equals_model(pkg, axc, wave, window, cuts, f"long call of {nb}, window {window}", masks=masks, calls=calls)
 
 
 def test_reset_one_batch_before_a_window_completes(pkg):

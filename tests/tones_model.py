@@ -152,13 +152,15 @@ def tones_model(axc, wave, state=None, enabled=None, window=DEFAULT_WINDOW):
     return records, powers, row_first, state
 
 
-def run_in_calls(axc, wave, cuts, window=DEFAULT_WINDOW, enabled=None, state=None):
-    """the model over consecutive calls of the lengths `cuts` (sum = axc's width), state carried.
+def run_in_calls(axc, wave, cuts, window=DEFAULT_WINDOW, enabled=None, state=None, masks=None):
+    """the model over consecutive calls of the lengths `cuts` (sum = axc's width), state carried.  masks: the enabled rows of each
+    call, in place of one `enabled` for all of them.
     Returns ([(first batch, records, powers, row_first_record, state after)], state after the last)"""
-    assert sum(cuts) == axc.shape[1]
+    assert sum(cuts) == axc.shape[1] and (masks is None or len(masks) == len(cuts))
     done, calls = 0, []
-    for n in cuts:
-        rec, pw, first, state = tones_model(axc[:, done:done + n], wave[:, done * WAVE_BATCH:(done + n) * WAVE_BATCH], state, enabled, window)
+    for i, n in enumerate(cuts):
+        en = enabled if masks is None else masks[i]
+        rec, pw, first, state = tones_model(axc[:, done:done + n], wave[:, done * WAVE_BATCH:(done + n) * WAVE_BATCH], state, en, window)
         calls.append((done, rec, pw, first, state))
         done += n
     return calls, state
@@ -242,3 +244,41 @@ def draw_audio(rng, rows, floats):
         elif kind == 3:
             wave[r] = full_scale_audio(rng, floats)
     return wave
+
+
+# ---------------- designed planes for calls longer than one 64-batch trip of the walk ----------------
+
+LONG_PRELUDE = 3  # batches of the call before the long one, all signal: the long call begins in the carried state
+LONG_ROWS = {name: r for r, name in enumerate("ABCDHEFGI")}  # (draw_audio's silent row, 4, is H: every designed row has audio)
+
+
+def long_call_planes(nb, window, seed=0):
+    """(axc [9][LONG_PRELUDE + nb], wave) for two calls (LONG_PRELUDE, nb) on one handle, one row per flag pattern (LONG_ROWS), batch
+    numbers those of the long call:
+      A  every batch signals                              E  NO_SIGNAL except batches 62..66 (clipped to nb)
+      B  every batch is NO_SIGNAL                         F  batches 0..63 NO_SIGNAL, the rest signal (B where nb == 64)
+      C  signal except batch 63                           G, H  draw_flags at p_open 0.85 and 0.5
+      D  signal except batch 64 (A where nb == 64)        I  drawn flags; the row the long call disables (long_call_masks)"""
+    assert nb >= 64
+    rng = np.random.default_rng([seed, nb, window])
+    rows = len(LONG_ROWS)
+    long = np.full((rows, nb), SYMBOLS[0], np.uint8)
+    long[LONG_ROWS["B"]] = NO_SIGNAL
+    long[LONG_ROWS["C"], 63] = NO_SIGNAL
+    if nb > 64:
+        long[LONG_ROWS["D"], 64] = NO_SIGNAL
+    long[LONG_ROWS["E"]] = NO_SIGNAL
+    long[LONG_ROWS["E"], 62:min(nb, 67)] = SYMBOLS[0]
+    long[LONG_ROWS["F"], :64] = NO_SIGNAL
+    long[LONG_ROWS["G"]] = draw_flags(rng, 1, nb, 0.85)[0]
+    long[LONG_ROWS["H"]] = draw_flags(rng, 1, nb, 0.5)[0]
+    long[LONG_ROWS["I"]] = draw_flags(rng, 1, nb, 0.85)[0]
+    axc = np.concatenate([np.full((rows, LONG_PRELUDE), SYMBOLS[0], np.uint8), long], axis=1)
+    return axc, draw_audio(rng, rows, (LONG_PRELUDE + nb) * WAVE_BATCH)
+
+
+def long_call_masks():
+    """the enabled rows of the two calls: all of them, then all but I"""
+    second = np.ones(len(LONG_ROWS), np.uint8)
+    second[LONG_ROWS["I"]] = 0
+    return [np.ones(len(LONG_ROWS), np.uint8), second]
