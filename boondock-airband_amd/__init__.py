@@ -144,6 +144,15 @@ TONE_RECORD_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ToneRecord._fields_])
 TONES_STATE_DTYPE = np.dtype([("count", "<u4"), ("seq", "<u4"), ("q1", "<f4", (TONES_LANES,)), ("q2", "<f4", (TONES_LANES,))])  # MI_TONES_STATE_ROW_BYTES = 520
 
 
+class PcmCfg(C.Structure):  # mi_pcm_cfg: 0 = 8000 / PCM_S16
+    _fields_ = [("rate", C.c_uint32), ("format", C.c_uint32)]
+
+
+PCM_S16, PCM_IMA4 = 1, 2  # MI_PCM_*
+PCM_TAPS, PCM_HISTORY = 63, 62  # MI_PCM_TAPS, MI_PCM_HISTORY
+PCM_STATE_DTYPE = np.dtype([("x", "<f4", (PCM_HISTORY,))])  # one row of the PCM stage's state blob, MI_PCM_STATE_ROW_BYTES = 248
+
+
 class OccCfg(C.Structure):  # mi_occ_cfg: 0 = 250 permille / ratio 3.0 / 1 cell
     _fields_ = [("floor_permille", C.c_uint32), ("ratio", C.c_float), ("min_cells", C.c_uint32)]
 
@@ -196,6 +205,8 @@ ABI_SYMBOLS = [
     "mi_tones_create", "mi_tones_destroy", "mi_tones_set_rows", "mi_tones_process_device", "mi_tones_download", "mi_tones_state_size",
     "mi_tones_get_state", "mi_tones_set_state", "mi_tones_set_timing", "mi_tones_last_launch_ms", "mi_tones_plan_host", "mi_tones_table",
     "mi_tones_vote_host",
+    "mi_pcm_create", "mi_pcm_destroy", "mi_pcm_set_rows", "mi_pcm_process_device", "mi_pcm_download", "mi_pcm_state_size", "mi_pcm_get_state",
+    "mi_pcm_set_state", "mi_pcm_set_timing", "mi_pcm_last_launch_ms", "mi_pcm_block_bytes", "mi_pcm_taps", "mi_pcm_plan_host", "mi_pcm_wav_header",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -305,6 +316,23 @@ def lib():
         L.mi_tones_plan_host.argtypes = [C.POINTER(TonesCfg), vp, C.c_int, vp, sz, C.c_int, vp, sz, vp, vp, vp, sz, vp, vp]
         L.mi_tones_table.argtypes = [C.c_uint32, vp, vp, vp]
         L.mi_tones_vote_host.argtypes = [vp, sz, C.POINTER(TonesRule), C.POINTER(TonesVote)]
+        L.mi_pcm_create.argtypes = [C.POINTER(PcmCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_pcm_destroy.argtypes = [vp]
+        L.mi_pcm_destroy.restype = None
+        L.mi_pcm_set_rows.argtypes = [vp, vp]
+        L.mi_pcm_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp]
+        L.mi_pcm_download.argtypes = [vp, vp, vp, vp]
+        L.mi_pcm_state_size.argtypes = [vp]
+        L.mi_pcm_state_size.restype = sz
+        L.mi_pcm_get_state.argtypes = [vp, vp, sz]
+        L.mi_pcm_set_state.argtypes = [vp, vp, sz]
+        L.mi_pcm_set_timing.argtypes = [vp, C.c_int]
+        L.mi_pcm_last_launch_ms.argtypes = [vp, vp]
+        L.mi_pcm_block_bytes.argtypes = [C.POINTER(PcmCfg)]
+        L.mi_pcm_block_bytes.restype = sz
+        L.mi_pcm_taps.argtypes = [vp]
+        L.mi_pcm_plan_host.argtypes = [C.POINTER(PcmCfg), vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp]
+        L.mi_pcm_wav_header.argtypes = [C.POINTER(PcmCfg), C.c_uint64, vp, sz, C.POINTER(sz)]
         L.mi_survey_create.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.mi_survey_destroy.argtypes = [vp]
         L.mi_survey_destroy.restype = None
@@ -413,7 +441,8 @@ class _PostStage(_Handle):
 
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
-        fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE)."""
+        fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
+        .view(PCM_STATE_DTYPE)."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -424,7 +453,7 @@ class _PostStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank"""
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
         return tuple(ms)
@@ -1005,6 +1034,91 @@ def tones_plan_host(row_enabled, axc, waveout, state=None, window=0, max_records
                                     _ptr(records), None if powers is None else _ptr(powers), cap, _ptr(row_first), _ptr(count)))
     k = int(count[1])
     return records[:k], None if powers is None else powers[:k], row_first, count, state
+
+
+def _pcm_cfg(rate=0, fmt=0):
+    """a rate (0 = 8000) and a format (0 = PCM_S16), or a PcmCfg -> PcmCfg"""
+    return rate if isinstance(rate, PcmCfg) else PcmCfg(int(rate or 0), int(fmt or 0))
+
+
+def pcm_block_bytes(rate=0, fmt=0):
+    """mi_pcm_block_bytes: bytes of one encoded block -- 2000 / 4000 as PCM_S16, 640 / 1280 as PCM_IMA4 at 8000 / 16000"""
+    n = lib().mi_pcm_block_bytes(C.byref(_pcm_cfg(rate, fmt)))
+    if not n:
+        raise MiError(MI_ERR_INVALID, lib().mi_last_error().decode())
+    return n
+
+
+class Pcm(_PostStage):
+    """mi_pcm: the blocks the output gate lets travel as int16 or WAV-container IMA ADPCM at 8000 (through the 63-tap decimating
+    filter) or 16000 samples a second, encoded on the device from the gate's index and counts where it left them.  row_enabled: truth
+    value per row (a disabled row's carried samples stay); max_blocks: capacity of the destination in blocks, 0 = rows * max_batches.
+    state() gives rows * 248 bytes, .view(PCM_STATE_DTYPE): the 62 samples a row carries into its next call."""
+    _destroy, _prefix, _launches = "mi_pcm_destroy", "mi_pcm", 2
+
+    def __init__(self, row_enabled, max_batches=1, rate=0, fmt=0, max_blocks=0, gpu=0):
+        en = _flags(row_enabled)
+        cfg = _pcm_cfg(rate, fmt)
+        self.rows, self.max_batches, self.block_bytes = en.size, max_batches, pcm_block_bytes(cfg)
+        self.max_blocks = min(max_blocks, self.rows * max_batches) if max_blocks else self.rows * max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_pcm_create(C.byref(cfg), _ptr(en), self.rows, max_batches, max_blocks, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_pcm_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_waveout, row_stride, nbatches, d_index, d_count, d_out, hip_stream=None):
+        """Raw device pointers (ints), the stride in floats; d_index and d_count as OutputGate.process_device left them; asynchronous
+        on hip_stream."""
+        _check(lib().mi_pcm_process_device(self._h, d_waveout, row_stride, nbatches, d_index, d_count, d_out, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (blocks [k][block_bytes] uint8, count [2]) with k = count[1],
+        the number of blocks stored; count[0] is the gate's number of travelling blocks."""
+        blocks = np.empty((self.max_blocks, self.block_bytes), np.uint8)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_pcm_download(self._h, hip_stream, _ptr(blocks), _ptr(count)))
+        return blocks[:int(count[1])], count
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        self._call("set_state", _ptr(buf), buf.size)
+
+
+def pcm_plan_host(row_enabled, waveout, index, state=None, rate=0, fmt=0, nbatches=None):
+    """mi_pcm_plan_host: the PCM stage's blocks from audio and an index on the host, no GPU.  waveout: float32 [rows][row_stride];
+    index: [k][2] = (row, batch), as gate_plan_host gives it; state: the blob (rows * 248 bytes) or None (a fresh one); nbatches:
+    batches of the call, default row_stride // WAVE_BATCH.  Returns (blocks [k][block_bytes] uint8, state after the call)."""
+    en = _flags(row_enabled)
+    waveout = np.ascontiguousarray(waveout, dtype=np.float32)
+    assert waveout.ndim == 2 and waveout.shape[0] == en.size
+    rows, row_stride = waveout.shape
+    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
+    index = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1, 2)
+    cfg = _pcm_cfg(rate, fmt)
+    state = np.zeros(rows * PCM_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * PCM_STATE_DTYPE.itemsize
+    blocks = np.zeros((len(index), pcm_block_bytes(cfg)), np.uint8)
+    _check(lib().mi_pcm_plan_host(C.byref(cfg), _ptr(en), rows, nb, _ptr(waveout), row_stride, _ptr(index) if len(index) else None, len(index),
+                                  _ptr(state), _ptr(blocks) if len(index) else None))
+    return blocks, state
+
+
+def pcm_taps():
+    """mi_pcm_taps: the 63 float32 taps of the 2:1 decimating filter"""
+    h = np.zeros(PCM_TAPS, np.float32)
+    _check(lib().mi_pcm_taps(_ptr(h)))
+    return h
+
+
+def pcm_wav_header(nblocks, rate=0, fmt=0):
+    """mi_pcm_wav_header: the bytes that, in front of `nblocks` encoded blocks, make a complete WAV file (44 as PCM_S16, 60 as PCM_IMA4)"""
+    buf = np.zeros(64, np.uint8)
+    n = C.c_size_t(0)
+    _check(lib().mi_pcm_wav_header(C.byref(_pcm_cfg(rate, fmt)), int(nblocks), _ptr(buf), buf.size, C.byref(n)))
+    return buf[:n.value].tobytes()
 
 
 def tones_table(window=0):

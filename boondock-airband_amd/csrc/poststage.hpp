@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,6 +128,34 @@ inline uint64_t tones_max_windows(uint32_t window, uint64_t nbatches) {
 }
 void tones_coeffs(uint32_t window, float* coeff);
 bool tones_state_ok(const TonesRowState* state, size_t rows, uint32_t window);
+
+// The PCM stage (include/mi_airband.h "PCM stage").  One row of its state: the checkpoint blob is an array of these, and pcm.hip
+// keeps the same array in device memory.
+struct PcmRowState {
+    float x[MI_PCM_HISTORY];  // the last 62 samples of the row's last batch, oldest first
+};
+// The settings with the defaults filled in and what follows from them.
+struct PcmGeometry {
+    uint32_t rate, format;
+    uint32_t samples;      // S, samples per block
+    uint32_t block_bytes;  // 2 S, or 16 S / 25
+};
+// Taps whose value is not exactly zero, in the order the sum takes them: h[0], h[2], .. h[30], h[31], h[32], .. h[62].  pcm.hip sums
+// only these: a zero tap's product is +-0, and adding it changes no finite sum that started from +0.0f.
+constexpr int kPcmLiveTaps = 33;
+struct PcmLiveTaps {
+    float h[kPcmLiveTaps];
+};
+static_assert(sizeof(PcmRowState) == MI_PCM_STATE_ROW_BYTES && MI_PCM_HISTORY == MI_PCM_TAPS - 1 && sizeof(mi_pcm_cfg) == 8 &&
+                  sizeof(mi_gate_block) == 8 && kWaveBatch % (2 * MI_PCM_IMA_SAMPLES) == 0 && kWaveBatch % 8 == 0,
+              "the PCM stage's blob and block layouts are ABI");
+constexpr int kImaSteps = 89;
+extern const int kImaStepTable[kImaSteps];  // poststage_host.cpp
+
+// pcm_geometry: MI_OK, or the refusal with its message set.  pcm_taps: h[63].  (poststage_host.cpp)
+int pcm_geometry(const mi_pcm_cfg* cfg, PcmGeometry* out);
+void pcm_taps(float* h);
+PcmLiveTaps pcm_live_taps();
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

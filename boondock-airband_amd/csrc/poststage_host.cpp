@@ -2,7 +2,8 @@
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
-// (target list, features, classification); and the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote.
+// (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; and the PCM
+// stage's twin mi_pcm_plan_host with its taps and WAV headers.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -566,5 +567,230 @@ extern "C" int mi_tones_vote_host(const mi_tone_record* records, size_t n, const
     }
     v.found = v.windows >= r.min_windows && static_cast<uint64_t>(v.votes) * 1000 >= static_cast<uint64_t>(r.min_share_permille) * v.windows ? 1 : 0;
     *out = v;
+    return MI_OK;
+}
+
+// ---- PCM stage, host side (include/mi_airband.h "PCM stage"): the settings and taps both halves share, the twin of pcm.hip -- one
+// block, one output sample and one tap at a time, all 63 taps in the sum --, and the WAV headers.
+namespace mi {
+
+const int kImaStepTable[kImaSteps] = {
+    7,     8,     9,     10,    11,    12,    13,    14,    16,    17,    19,    21,    23,    25,    28,    31,    34,    37,
+    41,    45,    50,    55,    60,    66,    73,    80,    88,    97,    107,   118,   130,   143,   157,   173,   190,   209,
+    230,   253,   279,   307,   337,   371,   408,   449,   494,   544,   598,   658,   724,   796,   876,   963,   1060,  1166,
+    1282,  1411,  1552,  1707,  1878,  2066,  2272,  2499,  2749,  3024,  3327,  3660,  4026,  4428,  4871,  5358,  5894,  6484,
+    7132,  7845,  8630,  9493,  10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767};
+
+int pcm_geometry(const mi_pcm_cfg* cfg, PcmGeometry* out) {
+    PcmGeometry g{cfg && cfg->rate ? cfg->rate : 8000u, cfg && cfg->format ? cfg->format : static_cast<uint32_t>(MI_PCM_S16), 0, 0};
+    if (g.rate != 8000 && g.rate != static_cast<uint32_t>(kWaveRate))
+        return fail(MI_ERR_INVALID, "PCM stage: rate must be 8000 or 16000 (0 = 8000)");
+    if (g.format != MI_PCM_S16 && g.format != MI_PCM_IMA4)
+        return fail(MI_ERR_INVALID, "PCM stage: format must be MI_PCM_S16 or MI_PCM_IMA4 (0 = MI_PCM_S16)");
+    g.samples = g.rate == 8000 ? kWaveBatch / 2 : kWaveBatch;
+    g.block_bytes = g.format == MI_PCM_S16 ? 2 * g.samples : MI_PCM_IMA_BYTES * g.samples / MI_PCM_IMA_SAMPLES;
+    *out = g;
+    return MI_OK;
+}
+
+// The design in float64.  The lower half and the centre come from the formula; the upper half is its mirror image, so that the
+// symmetry holds bit for bit whatever cos() does with the two arguments.
+void pcm_taps(float* h) {
+    const double pi = 3.14159265358979323846;
+    double g[MI_PCM_TAPS];
+    for (int k = 0; k <= MI_PCM_HISTORY / 2; ++k) {
+        const int c = k - MI_PCM_HISTORY / 2;
+        if (c % 2 == 0 && c != 0) {
+            g[k] = 0.0;
+        } else {
+            const double t = c / 2.0, sinc = c == 0 ? 1.0 : std::sin(pi * t) / (pi * t);
+            g[k] = 0.5 * sinc * (0.42 - 0.5 * std::cos(2.0 * pi * k / MI_PCM_HISTORY) + 0.08 * std::cos(4.0 * pi * k / MI_PCM_HISTORY));
+        }
+        g[MI_PCM_HISTORY - k] = g[k];
+    }
+    double sum = 0.0;
+    for (int k = 0; k < MI_PCM_TAPS; ++k)
+        sum += g[k];
+    for (int k = 0; k < MI_PCM_TAPS; ++k)
+        h[k] = (k - MI_PCM_HISTORY / 2) % 2 == 0 && k != MI_PCM_HISTORY / 2 ? 0.0f : static_cast<float>(g[k] / sum);
+}
+
+PcmLiveTaps pcm_live_taps() {
+    float h[MI_PCM_TAPS];
+    pcm_taps(h);
+    PcmLiveTaps live;
+    int n = 0;
+    for (int k = 0; k < MI_PCM_TAPS; ++k)
+        if (k % 2 == 0 || k == MI_PCM_HISTORY / 2)
+            live.h[n++] = h[k];
+    return live;
+}
+
+namespace {
+
+int16_t pcm_quantise(float y) {
+    float v = y * 32767.0f;
+    v = v < -32767.0f ? -32767.0f : v;
+    v = v > 32767.0f ? 32767.0f : v;
+    return static_cast<int16_t>(std::nearbyintf(v));  // (the default rounding mode: to nearest, ties to even)
+}
+
+void put16(uint8_t* p, uint32_t v) {
+    p[0] = static_cast<uint8_t>(v);
+    p[1] = static_cast<uint8_t>(v >> 8);
+}
+
+void put32(uint8_t* p, uint32_t v) {
+    put16(p, v);
+    put16(p + 2, v >> 16);
+}
+
+// one sub-block: 25 samples -> 16 bytes
+void ima_subblock(const int16_t* s, uint8_t* out) {
+    static const int kIndexStep[8] = {-1, -1, -1, -1, 2, 4, 6, 8};
+    const int d = s[1] > s[0] ? s[1] - s[0] : s[0] - s[1];
+    int index = kImaSteps - 1;
+    for (int i = 0; i < kImaSteps; ++i)
+        if (7 * kImaStepTable[i] >= 4 * d) {
+            index = i;
+            break;
+        }
+    put16(out, static_cast<uint16_t>(s[0]));
+    out[2] = static_cast<uint8_t>(index);
+    out[3] = 0;
+    int p = s[0];
+    for (int n = 1; n < MI_PCM_IMA_SAMPLES; ++n) {
+        int step = kImaStepTable[index], diff = s[n] - p, code = 0;
+        const int sign = diff < 0 ? 8 : 0;
+        diff = diff < 0 ? -diff : diff;
+        int vp = step >> 3;
+        if (diff >= step) {
+            code |= 4;
+            diff -= step;
+            vp += step;
+        }
+        step >>= 1;
+        if (diff >= step) {
+            code |= 2;
+            diff -= step;
+            vp += step;
+        }
+        step >>= 1;
+        if (diff >= step) {
+            code |= 1;
+            vp += step;
+        }
+        p = sign ? p - vp : p + vp;
+        p = p < -32768 ? -32768 : (p > 32767 ? 32767 : p);
+        index += kIndexStep[code];
+        index = index < 0 ? 0 : (index > kImaSteps - 1 ? kImaSteps - 1 : index);
+        const uint8_t nibble = static_cast<uint8_t>(code | sign);
+        uint8_t* byte = out + 4 + (n - 1) / 2;
+        *byte = (n - 1) % 2 == 0 ? nibble : static_cast<uint8_t>(*byte | (nibble << 4));
+    }
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" size_t mi_pcm_block_bytes(const mi_pcm_cfg* cfg) {
+    mi::PcmGeometry g;
+    return mi::pcm_geometry(cfg, &g) == MI_OK ? g.block_bytes : 0;
+}
+
+extern "C" int mi_pcm_taps(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::pcm_taps(out);
+    return MI_OK;
+}
+
+extern "C" int mi_pcm_plan_host(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* waveout, size_t row_stride,
+                                const mi_gate_block* index, size_t nblocks, void* state_inout, void* out) {
+    if (!row_enabled || !waveout || !state_inout || (nblocks && (!index || !out)))
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::PcmGeometry g;
+    if (const int rc = mi::pcm_geometry(cfg, &g))
+        return rc;
+    if (rows < 1 || nbatches < 1)
+        return fail(MI_ERR_INVALID, "pcm plan needs rows >= 1 and nbatches >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::PcmRowState* state = static_cast<mi::PcmRowState*>(state_inout);
+    float h[MI_PCM_TAPS];
+    mi::pcm_taps(h);
+    std::vector<float> x(MI_PCM_HISTORY + mi::kWaveBatch);
+    std::vector<int16_t> s(mi::kWaveBatch);
+    for (size_t k = 0; k < nblocks; ++k) {
+        uint8_t* dst = static_cast<uint8_t*>(out) + k * g.block_bytes;
+        const uint32_t row = index[k].row, batch = index[k].batch;
+        if (row >= static_cast<uint32_t>(rows) || batch >= static_cast<uint32_t>(nbatches)) {
+            std::memset(dst, 0, g.block_bytes);
+            continue;
+        }
+        // x[62 + n] = sample n of the block, x[0 .. 61] = the 62 before it
+        const float* blk = waveout + static_cast<size_t>(row) * row_stride + static_cast<size_t>(batch) * mi::kWaveBatch;
+        std::memcpy(x.data(), batch ? blk - MI_PCM_HISTORY : state[row].x, MI_PCM_HISTORY * sizeof(float));
+        std::memcpy(x.data() + MI_PCM_HISTORY, blk, mi::kWaveBatch * sizeof(float));
+        for (uint32_t m = 0; m < g.samples; ++m) {
+            float y = x[MI_PCM_HISTORY + m];
+            if (g.rate == 8000) {
+                y = 0.0f;
+                for (int t = 0; t < MI_PCM_TAPS; ++t)
+                    y = y + h[t] * x[MI_PCM_HISTORY + 2 * m - t];
+            }
+            s[m] = mi::pcm_quantise(y);
+        }
+        if (g.format == MI_PCM_S16) {
+            for (uint32_t m = 0; m < g.samples; ++m)
+                mi::put16(dst + 2 * m, static_cast<uint16_t>(s[m]));
+        } else {
+            for (uint32_t j = 0; j < g.samples / MI_PCM_IMA_SAMPLES; ++j)
+                mi::ima_subblock(s.data() + j * MI_PCM_IMA_SAMPLES, dst + j * MI_PCM_IMA_BYTES);
+        }
+    }
+    for (int r = 0; r < rows; ++r)  // (after every block: batch 0 of a row reads the samples the call found)
+        if (row_enabled[r])
+            std::memcpy(state[r].x, waveout + static_cast<size_t>(r) * row_stride + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_PCM_HISTORY,
+                        MI_PCM_HISTORY * sizeof(float));
+    return MI_OK;
+}
+
+extern "C" int mi_pcm_wav_header(const mi_pcm_cfg* cfg, uint64_t nblocks, void* buf, size_t cap, size_t* len) {
+    if (!buf || !len)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::PcmGeometry g;
+    if (const int rc = mi::pcm_geometry(cfg, &g))
+        return rc;
+    const bool ima = g.format == MI_PCM_IMA4;
+    const size_t need = ima ? 60 : 44;
+    if (cap < need)
+        return fail(MI_ERR_INVALID, "PCM stage: the WAV header needs 44 bytes (S16) or 60 (IMA4)");
+    if (nblocks > (UINT32_MAX - need) / g.block_bytes || nblocks > UINT32_MAX / g.samples)
+        return fail(MI_ERR_INVALID, "PCM stage: a WAV file holds less than 2^32 bytes and samples");
+    const uint32_t data = static_cast<uint32_t>(nblocks * g.block_bytes);
+    uint8_t* b = static_cast<uint8_t*>(buf);
+    std::memcpy(b, "RIFF", 4);
+    mi::put32(b + 4, static_cast<uint32_t>(need) - 8 + data);
+    std::memcpy(b + 8, "WAVEfmt ", 8);
+    mi::put32(b + 16, ima ? 20 : 16);
+    mi::put16(b + 20, ima ? 0x0011 : 0x0001);
+    mi::put16(b + 22, 1);
+    mi::put32(b + 24, g.rate);
+    mi::put32(b + 28, ima ? g.rate * MI_PCM_IMA_BYTES / MI_PCM_IMA_SAMPLES : 2 * g.rate);
+    mi::put16(b + 32, ima ? MI_PCM_IMA_BYTES : 2);
+    mi::put16(b + 34, ima ? 4 : 16);
+    uint8_t* d = b + 36;
+    if (ima) {
+        mi::put16(b + 36, 2);
+        mi::put16(b + 38, MI_PCM_IMA_SAMPLES);
+        std::memcpy(b + 40, "fact", 4);
+        mi::put32(b + 44, 4);
+        mi::put32(b + 48, static_cast<uint32_t>(nblocks * g.samples));
+        d = b + 52;
+    }
+    std::memcpy(d, "data", 4);
+    mi::put32(d + 4, data);
+    *len = need;
     return MI_OK;
 }

@@ -850,6 +850,91 @@ typedef struct {
 } mi_tones_vote;                    /* 32 bytes */
 int mi_tones_vote_host(const mi_tone_record* records, size_t n, const mi_tones_rule* rule /* NULL = defaults */, mi_tones_vote* out);
 
+/* ---------------- PCM stage: the gate's blocks as 8 kHz int16 or IMA ADPCM, on the device ----------------
+ * The reference hands its audio to LAME (airlame_init, src/output.cpp:147-171: in MI_WAVE_RATE 16000, out MP3_RATE 8000;
+ * lame_encode_buffer_ieee_float at :478 and :534).  MP3 stays with the host.  This stage is the arithmetic between
+ * the gate and a file whose every byte can be defined: a 2:1 decimating FIR, an int16 quantiser and WAV-container IMA ADPCM, which
+ * any player opens.  A post-stage like the gate and the splitter: it reads the audio mi_demod_process_device wrote and the index and
+ * counts mi_outgate_process_device left in device memory, and writes one encoded block per travelling block.  Block k of the output
+ * encodes block k of the index for k < min(d_count[1], max_blocks); nothing is written at or beyond that.  An index entry with
+ * row >= rows or batch >= nbatches cannot be reported by the device: its block is all zero bytes and nothing is read out of range.
+ *
+ * cfg.rate is 0 or 8000 (the default, MP3_RATE) or 16000; cfg.format is 0 or MI_PCM_S16 (the default) or MI_PCM_IMA4.  Samples per
+ * block S = 1000 at 8000, 2000 at 16000; block bytes 2 S for S16 and 16 * S / 25 for IMA4 (640 or 1280): mi_pcm_block_bytes.
+ *
+ * Stream model.  A row's audio is one running sequence x over all batches of all calls the row was enabled in (the demodulator writes
+ * every batch, whether it travels or not); samples before the handle's first call are 0.
+ *   rate 16000:  y[n] = x[n]
+ *   rate 8000:   output m (0 .. 999) of batch b is  y = sum over k = 0 .. 62 of h[k] * x[2000 b + 2 m - k]  in float32, every product
+ *                and every sum rounded on its own, k ascending, starting from 0.0f.  Indices below 0 reach into batch b - 1 of the
+ *                same row in the same call; for b = 0 into the 62 samples the handle carries for the row.
+ * Taps h (mi_pcm_taps), designed in float64 and cast to float32 once, with c = k - 31: c even and not 0 gives exactly 0.0f; otherwise
+ * g[k] = 0.5 * sinc(c / 2) * (0.42 - 0.5 cos(2 pi k / 62) + 0.08 cos(4 pi k / 62)) with sinc(t) = sin(pi t) / (pi t), sinc(0) = 1, and
+ * h[k] = (float)(g[k] / sum g), with g[62 - k] taken from g[k] for k < 31 so that h is symmetric bit for bit: a half-band low-pass under a Blackman window, flat to 3 kHz and below -70 dB from 4.7 kHz.
+ * Quantiser: v = y * 32767.0f (one float32 multiply), clamped to [-32767, 32767], rounded to nearest, ties to even.  NaN and Inf are
+ * unspecified; the demodulator's audio is finite with |x| <= 1.
+ *
+ * MI_PCM_S16: the block is S little-endian int16.
+ * MI_PCM_IMA4: the block is S / 25 sub-blocks of 16 bytes, each a complete mono block of WAV format 0x0011 with nBlockAlign 16 and
+ * wSamplesPerBlock 25, so sub-blocks do not depend on each other.  Over samples s[0 .. 24]: header int16 LE s[0]; uint8 index0;
+ * uint8 0, where with d = |s[1] - s[0]| index0 is the smallest i in 0 .. 88 with 7 * T[i] >= 4 * d, or 88 if there is none (T: the
+ * standard 89-entry IMA step table); then 12 bytes with the codes of s[1] .. s[24], two a byte, the earlier sample in the LOW nibble.
+ * The encoder step is the standard one, predictor p starting at s[0], index i at index0:
+ *   step = T[i]; diff = s - p; sign = diff < 0 ? 8 : 0; diff = |diff|; vp = step >> 3; code = 0
+ *   if diff >= step: code |= 4, diff -= step, vp += step;   step >>= 1
+ *   if diff >= step: code |= 2, diff -= step, vp += step;   step >>= 1
+ *   if diff >= step: code |= 1, vp += step
+ *   p = sign ? p - vp : p + vp, clamped to [-32768, 32767];  i += {-1,-1,-1,-1,2,4,6,8}[code], clamped to 0 .. 88;  nibble = code | sign
+ *
+ * State: per row the last 62 samples of the last batch of the last call the row was enabled in, zeros at first; the blob is
+ * rows * MI_PCM_STATE_ROW_BYTES bytes of little-endian float32, oldest sample first.  A disabled row's carried samples keep their
+ * bytes; blocks of a disabled row that the index names anyway are encoded from whatever is there (a caller gives such rows
+ * MI_GATE_NONE).  At rate 16000 the state is carried all the same, so that a checkpoint does not depend on the rate.
+ * The defaults and the filter have been tried on synthetic signals only. */
+enum { MI_PCM_S16 = 1, MI_PCM_IMA4 = 2, MI_PCM_TAPS = 63, MI_PCM_HISTORY = 62, MI_PCM_STATE_ROW_BYTES = 248, MI_PCM_IMA_SAMPLES = 25, MI_PCM_IMA_BYTES = 16 };
+typedef struct { uint32_t rate; uint32_t format; } mi_pcm_cfg; /* 0 = 8000 / MI_PCM_S16 */
+typedef struct mi_pcm mi_pcm;
+
+/* cfg NULL = the defaults.  row_enabled [rows] as for mi_txsplit_create; rows and max_batches within the gate's limits (1 <= rows <
+ * 2^20, rows * max_batches < 2^24); max_blocks: capacity of the caller's d_out in blocks, 0 = rows * max_batches. */
+int mi_pcm_create(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_blocks, int gpu, mi_pcm** out);
+void mi_pcm_destroy(mi_pcm* p);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_pcm_set_rows(mi_pcm* p, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches: d_waveout [rows][row_stride] with alignment and strides as for
+ * mi_outgate_process_device; d_index (8-byte aligned) and d_count [2] in device memory exactly as mi_outgate_process_device left
+ * them; d_out [max_blocks][mi_pcm_block_bytes] (16-byte aligned).  Asynchronous on `hip_stream`, no host synchronisation; two
+ * kernels without atomics -- the encoder, then the copy of the enabled rows' new tails into the carried state -- so every byte is
+ * the same on every run. */
+int mi_pcm_process_device(mi_pcm* p, const float* d_waveout, size_t row_stride, int nbatches, const mi_gate_block* d_index,
+                          const uint32_t* d_count, void* d_out, void* hip_stream);
+/* Results of the last mi_pcm_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the two counts it
+ * was given and copies exactly min(count[1], max_blocks) blocks; on return count[0] is the gate's count[0] and count[1] the number
+ * of blocks copied.  out may be NULL.  The one place that synchronises. */
+int mi_pcm_download(mi_pcm* p, void* hip_stream, void* out, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_PCM_STATE_ROW_BYTES bytes in the layout above (mi_pcm_plan_host reads and writes the same bytes).
+ * Both complete queued work first. */
+size_t mi_pcm_state_size(const mi_pcm* p);
+int mi_pcm_get_state(mi_pcm* p, void* buf, size_t len);
+int mi_pcm_set_state(mi_pcm* p, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {encode, tails}.  tools/pcm_rate.py. */
+int mi_pcm_set_timing(mi_pcm* p, int on);
+int mi_pcm_last_launch_ms(mi_pcm* p, float* ms /* [2] */);
+/* Bytes of one encoded block under cfg (NULL = the defaults), 0 for a rate or format outside the sets above.  Host only. */
+size_t mi_pcm_block_bytes(const mi_pcm_cfg* cfg);
+/* The 63 taps h[0 .. 62].  Host only. */
+int mi_pcm_taps(float* out /* [MI_PCM_TAPS] */);
+/* The host twin: no GPU and no HIP call; the same bytes and the same state blob.  waveout [rows][row_stride]; index [nblocks] from
+ * the host (any order, repeats allowed); out holds nblocks blocks, all of which are written; state_inout rows *
+ * MI_PCM_STATE_ROW_BYTES bytes, read and updated. */
+int mi_pcm_plan_host(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* waveout, size_t row_stride,
+                     const mi_gate_block* index, size_t nblocks, void* state_inout, void* out);
+/* The header of a WAV file of nblocks blocks: header followed by the blocks of one record of the splitter is a complete file.  S16:
+ * the 44-byte PCM header.  IMA4: RIFF / WAVE with a 20-byte `fmt ` body (wFormatTag 0x0011, 1 channel, nAvgBytesPerSec = rate * 16 /
+ * 25, nBlockAlign 16, wBitsPerSample 4, cbSize 2, wSamplesPerBlock 25), a `fact` chunk with the sample count, then `data`: 60 bytes.
+ * *len = the header's length; MI_ERR_INVALID if cap is below it or the file would pass 2^32 - 1 bytes. */
+int mi_pcm_wav_header(const mi_pcm_cfg* cfg, uint64_t nblocks, void* buf, size_t cap, size_t* len);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
