@@ -153,6 +153,29 @@ PCM_TAPS, PCM_HISTORY = 63, 62  # MI_PCM_TAPS, MI_PCM_HISTORY
 PCM_STATE_DTYPE = np.dtype([("x", "<f4", (PCM_HISTORY,))])  # one row of the PCM stage's state blob, MI_PCM_STATE_ROW_BYTES = 248
 
 
+class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
+    _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
+
+
+class AspecRecord(C.Structure):  # mi_aspec_record
+    _fields_ = [("row", C.c_uint32), ("batch", C.c_uint32), ("peak_bin", C.c_uint32), ("peak_power", C.c_float), ("band_power", C.c_double),
+                ("line_power", C.c_double)]
+
+
+class AspecRule(C.Structure):  # mi_aspec_rule: 0 = 8 blocks / ratio 16.0
+    _fields_ = [("min_blocks", C.c_uint32), ("ratio", C.c_float)]
+
+
+class AspecNotch(C.Structure):  # mi_aspec_notch
+    _fields_ = [("found", C.c_uint32), ("bin", C.c_uint32), ("freq_hz", C.c_double), ("peak", C.c_double), ("floor", C.c_double),
+                ("votes", C.c_uint32), ("blocks", C.c_uint32)]
+
+
+ASPEC_FFT, ASPEC_BINS, ASPEC_LINE_HALF = 2048, 1024, 2  # MI_ASPEC_*
+ASPEC_NONE = 0xFFFFFFFF  # peak_bin of an index entry that is not of the call
+ASPEC_RECORD_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in AspecRecord._fields_])  # the same 32 bytes as a numpy record
+
+
 class OccCfg(C.Structure):  # mi_occ_cfg: 0 = 250 permille / ratio 3.0 / 1 cell
     _fields_ = [("floor_permille", C.c_uint32), ("ratio", C.c_float), ("min_cells", C.c_uint32)]
 
@@ -207,6 +230,8 @@ ABI_SYMBOLS = [
     "mi_tones_vote_host",
     "mi_pcm_create", "mi_pcm_destroy", "mi_pcm_set_rows", "mi_pcm_process_device", "mi_pcm_download", "mi_pcm_state_size", "mi_pcm_get_state",
     "mi_pcm_set_state", "mi_pcm_set_timing", "mi_pcm_last_launch_ms", "mi_pcm_block_bytes", "mi_pcm_taps", "mi_pcm_plan_host", "mi_pcm_wav_header",
+    "mi_aspec_create", "mi_aspec_destroy", "mi_aspec_process_device", "mi_aspec_download", "mi_aspec_set_timing", "mi_aspec_last_launch_ms",
+    "mi_aspec_window", "mi_aspec_band", "mi_aspec_plan_host", "mi_aspec_notch_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -333,6 +358,17 @@ def lib():
         L.mi_pcm_taps.argtypes = [vp]
         L.mi_pcm_plan_host.argtypes = [C.POINTER(PcmCfg), vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp]
         L.mi_pcm_wav_header.argtypes = [C.POINTER(PcmCfg), C.c_uint64, vp, sz, C.POINTER(sz)]
+        L.mi_aspec_create.argtypes = [C.POINTER(AspecCfg), C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_aspec_destroy.argtypes = [vp]
+        L.mi_aspec_destroy.restype = None
+        L.mi_aspec_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mi_aspec_download.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.mi_aspec_set_timing.argtypes = [vp, C.c_int]
+        L.mi_aspec_last_launch_ms.argtypes = [vp, vp]
+        L.mi_aspec_window.argtypes = [vp]
+        L.mi_aspec_band.argtypes = [C.POINTER(AspecCfg), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.mi_aspec_plan_host.argtypes = [C.POINTER(AspecCfg), C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.mi_aspec_notch_host.argtypes = [vp, C.c_uint32, vp, sz, C.POINTER(AspecCfg), C.POINTER(AspecRule), C.POINTER(AspecNotch)]
         L.mi_survey_create.argtypes = [C.POINTER(DeviceCfg), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.mi_survey_destroy.argtypes = [vp]
         L.mi_survey_destroy.restype = None
@@ -442,7 +478,7 @@ class _PostStage(_Handle):
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
-        .view(PCM_STATE_DTYPE)."""
+        .view(PCM_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -453,7 +489,7 @@ class _PostStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy"""
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
         return tuple(ms)
@@ -1119,6 +1155,97 @@ def pcm_wav_header(nblocks, rate=0, fmt=0):
     n = C.c_size_t(0)
     _check(lib().mi_pcm_wav_header(C.byref(_pcm_cfg(rate, fmt)), int(nblocks), _ptr(buf), buf.size, C.byref(n)))
     return buf[:n.value].tobytes()
+
+
+def _aspec_cfg(lo_hz=0, hi_hz=0):
+    """a band in Hz (0 = 60 / 3800), or an AspecCfg -> AspecCfg"""
+    return lo_hz if isinstance(lo_hz, AspecCfg) else AspecCfg(int(lo_hz or 0), int(hi_hz or 0))
+
+
+def aspec_band(lo_hz=0, hi_hz=0):
+    """mi_aspec_band: (lo_bin, hi_bin) of the band, 8 and 486 at the defaults; bin j is j * 7.8125 Hz"""
+    lo, hi = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().mi_aspec_band(C.byref(_aspec_cfg(lo_hz, hi_hz)), C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
+def aspec_window():
+    """mi_aspec_window: the 2000 float32 coefficients of the stage's Hann window"""
+    w = np.zeros(WAVE_BATCH, np.float32)
+    _check(lib().mi_aspec_window(_ptr(w)))
+    return w
+
+
+class Aspec(_PostStage):
+    """mi_aspec: the audio spectrum stage -- a 2048-point power spectrum (1024 bins of 7.8125 Hz) of every block the output gate lets
+    travel, one ASPEC_RECORD_DTYPE record per block (strongest band bin, band and line power), optionally the power rows and one mean
+    spectrum per row, from which aspec_notch_host reads a notch frequency.  Stateless: there is no state blob and no row mask.
+    max_blocks: capacity of the destinations in blocks, 0 = rows * max_batches."""
+    _destroy, _prefix, _launches = "mi_aspec_destroy", "mi_aspec", 2
+
+    def __init__(self, rows, max_batches=1, lo_hz=0, hi_hz=0, max_blocks=0, gpu=0):
+        self.rows, self.max_batches = int(rows), max_batches
+        self.max_blocks = min(max_blocks, self.rows * max_batches) if max_blocks else self.rows * max_batches
+        self._h = C.c_void_p()
+        self._wrote = (False, False)
+        _check(lib().mi_aspec_create(C.byref(_aspec_cfg(lo_hz, hi_hz)), self.rows, max_batches, max_blocks, gpu, C.byref(self._h)))
+
+    def process_device(self, d_waveout, row_stride, nbatches, d_index, d_row_first, d_count, d_records, d_power=None, d_row_mean=None,
+                       d_row_blocks=None, hip_stream=None):
+        """Raw device pointers (ints; d_power, d_row_mean with d_row_blocks, and d_row_first without a row mean may be None), the
+        stride in floats; d_index, d_row_first and d_count as OutputGate.process_device left them; asynchronous on hip_stream."""
+        _check(lib().mi_aspec_process_device(self._h, d_waveout, row_stride, nbatches, d_index, d_row_first, d_count, d_records, d_power, d_row_mean,
+                                             d_row_blocks, hip_stream))
+        self._wrote = (d_power is not None, d_row_mean is not None)
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (records [k] of ASPEC_RECORD_DTYPE, power [k][1024] or None,
+        row_mean [rows][1024] or None, row_blocks [rows] or None, count [2]) with k = count[1], the number of blocks stored; None
+        where the call wrote none."""
+        records = np.zeros(self.max_blocks, ASPEC_RECORD_DTYPE)
+        power = np.zeros((self.max_blocks, ASPEC_BINS), np.float32) if self._wrote[0] else None
+        mean = np.zeros((self.rows, ASPEC_BINS), np.float32) if self._wrote[1] else None
+        blocks = np.zeros(self.rows, np.uint32) if self._wrote[1] else None
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_aspec_download(self._h, hip_stream, _ptr(records), None if power is None else _ptr(power), None if mean is None else _ptr(mean),
+                                       None if blocks is None else _ptr(blocks), _ptr(count)))
+        k = int(count[1])
+        return records[:k], None if power is None else power[:k], mean, blocks, count
+
+
+def aspec_plan_host(rows, waveout, index, row_first=None, lo_hz=0, hi_hz=0, nbatches=None, want_power=True):
+    """mi_aspec_plan_host: the stage's records, power rows and row means from audio and an index on the host, no GPU.  waveout:
+    float32 [rows][row_stride]; index: [k][2] = (row, batch), any order; row_first: [rows + 1] as gate_plan_host gives it, or None (no
+    row mean); nbatches: batches of the call, default row_stride // WAVE_BATCH.  Returns (records [k], power [k][1024] or None,
+    row_mean [rows][1024] or None, row_blocks [rows] or None)."""
+    waveout = np.ascontiguousarray(waveout, dtype=np.float32)
+    assert waveout.ndim == 2 and waveout.shape[0] == rows
+    row_stride = waveout.shape[1]
+    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
+    index = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1, 2)
+    k = len(index)
+    records = np.zeros(k, ASPEC_RECORD_DTYPE)
+    power = np.zeros((k, ASPEC_BINS), np.float32) if want_power else None
+    first = None if row_first is None else np.ascontiguousarray(row_first, dtype=np.uint32)
+    assert first is None or first.size == rows + 1
+    mean = None if first is None else np.zeros((rows, ASPEC_BINS), np.float32)
+    blocks = None if first is None else np.zeros(rows, np.uint32)
+    _check(lib().mi_aspec_plan_host(C.byref(_aspec_cfg(lo_hz, hi_hz)), rows, nb, _ptr(waveout), row_stride, _ptr(index) if k else None, k,
+                                    None if first is None else _ptr(first), _ptr(records) if k else None, _ptr(power) if want_power and k else None,
+                                    None if mean is None else _ptr(mean), None if blocks is None else _ptr(blocks)))
+    return records, power, mean, blocks
+
+
+def aspec_notch_host(row_mean, row_blocks, records=None, lo_hz=0, hi_hz=0, min_blocks=0, ratio=0.0):
+    """mi_aspec_notch_host: an AspecNotch (found, bin, freq_hz, peak, floor, votes, blocks) from one row's mean spectrum [1024], its
+    block count and its records (or None); min_blocks 0 = 8, ratio 0 = 16.0.  freq_hz is what a channel's notch takes when found."""
+    mean = np.ascontiguousarray(row_mean, dtype=np.float32)
+    assert mean.shape == (ASPEC_BINS,)
+    recs = np.zeros(0, ASPEC_RECORD_DTYPE) if records is None else np.ascontiguousarray(records, dtype=ASPEC_RECORD_DTYPE)
+    out = AspecNotch()
+    _check(lib().mi_aspec_notch_host(_ptr(mean), int(row_blocks), _ptr(recs) if len(recs) else None, len(recs), C.byref(_aspec_cfg(lo_hz, hi_hz)),
+                                     C.byref(AspecRule(int(min_blocks or 0), float(ratio or 0.0))), C.byref(out)))
+    return out
 
 
 def tones_table(window=0):

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -156,6 +156,19 @@ extern const int kImaStepTable[kImaSteps];  // poststage_host.cpp
 int pcm_geometry(const mi_pcm_cfg* cfg, PcmGeometry* out);
 void pcm_taps(float* h);
 PcmLiveTaps pcm_live_taps();
+
+// The audio spectrum stage (include/mi_airband.h "audio spectrum stage"), what aspec.hip and its twin share (poststage_host.cpp).
+// aspec_band: MI_OK with the two bins, or the refusal with its message set.  aspec_window: w[2000].  aspec_twiddles: the plan's table
+// at fft_size_log 11, 1024 x {re, im}.
+static_assert(sizeof(mi_aspec_record) == 32 && sizeof(mi_aspec_cfg) == 8 && sizeof(mi_aspec_notch) == 40 && MI_ASPEC_FFT == 1 << MI_ASPEC_FFT_LOG &&
+                  MI_ASPEC_BINS == MI_ASPEC_FFT / 2 && kWaveBatch <= MI_ASPEC_FFT,
+              "the audio spectrum stage's record layouts are ABI");
+struct AspecBand {
+    uint32_t lo, hi;
+};
+int aspec_band(const mi_aspec_cfg* cfg, AspecBand* out);
+void aspec_window(float* w);
+int aspec_twiddles(std::vector<float>& tw);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

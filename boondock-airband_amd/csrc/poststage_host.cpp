@@ -2,8 +2,9 @@
 // (and audio) the caller already has.  Plain C++, no device needed.  Each twin states its rule on its own: tests compare it with the
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
-// (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; and the PCM
-// stage's twin mi_pcm_plan_host with its taps and WAV headers.
+// (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; the PCM
+// stage's twin mi_pcm_plan_host with its taps and WAV headers; and the audio spectrum stage's twin mi_aspec_plan_host with its window,
+// band and the notch vote.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -792,5 +793,237 @@ extern "C" int mi_pcm_wav_header(const mi_pcm_cfg* cfg, uint64_t nblocks, void* 
     std::memcpy(d, "data", 4);
     mi::put32(d + 4, data);
     *len = need;
+    return MI_OK;
+}
+
+// ---- audio spectrum stage, host side (include/mi_airband.h "audio spectrum stage"): the band, the window and the twiddles both
+// halves share, the twin of aspec.hip -- the FFT spec of DESIGN.md 2 stage by stage, one butterfly at a time --, and the vote that
+// reads a notch frequency off a row's mean spectrum.
+namespace mi {
+
+int aspec_band(const mi_aspec_cfg* cfg, AspecBand* out) {
+    const uint64_t lo_hz = cfg && cfg->lo_hz ? cfg->lo_hz : 60u, hi_hz = cfg && cfg->hi_hz ? cfg->hi_hz : 3800u;
+    const uint64_t lo = (lo_hz * MI_ASPEC_FFT + (kWaveRate - 1)) / kWaveRate, hi = hi_hz * MI_ASPEC_FFT / kWaveRate;
+    if (lo < 1 || lo > hi || hi > MI_ASPEC_BINS - 1)
+        return fail(MI_ERR_INVALID, "audio spectrum stage: the band needs 1 <= lo_bin <= hi_bin <= 1023 (lo_hz 0 = 60, hi_hz 0 = 3800)");
+    out->lo = static_cast<uint32_t>(lo);
+    out->hi = static_cast<uint32_t>(hi);
+    return MI_OK;
+}
+
+// The lower half comes from the formula; the upper half is its mirror image, so that the symmetry holds bit for bit whatever cos()
+// does with the two arguments.
+void aspec_window(float* w) {
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < kWaveBatch / 2; ++i)
+        w[i] = w[kWaveBatch - 1 - i] = static_cast<float>(0.5 - 0.5 * std::cos(2.0 * pi * i / (kWaveBatch - 1)));
+}
+
+int aspec_twiddles(std::vector<float>& tw) {
+    mi_device_cfg dev{};
+    dev.sample_rate = 2560000;
+    dev.centerfreq = 120000000;
+    dev.fft_size_log = MI_ASPEC_FFT_LOG;
+    dev.sfmt = MI_SFMT_U8;
+    dev.fullscale = 127.5f;
+    dev.tau = -1;
+    Plan p;
+    if (const int rc = device_plan(dev, p))
+        return rc;
+    tw = p.tw;
+    return MI_OK;
+}
+
+namespace {
+
+// X = the FFT spec at N = 2048, in place over z[2048][2]: bit reversal, then stages s = 1 .. 11 of butterflies (a, b) -> (a + t, a - t)
+// with t = w b, w = tw[j N / 2^s]; t = b for w = 1, (b.im, -b.re) for w = -j, else the two explicit fma.
+void aspec_fft(const float* tw, float* z) {
+    constexpr uint32_t n = MI_ASPEC_FFT;
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t r = 0;
+        for (int b = 0; b < MI_ASPEC_FFT_LOG; ++b)
+            r |= ((i >> b) & 1u) << (MI_ASPEC_FFT_LOG - 1 - b);
+        if (r > i) {
+            std::swap(z[2 * i], z[2 * r]);
+            std::swap(z[2 * i + 1], z[2 * r + 1]);
+        }
+    }
+    for (int s = 1; s <= MI_ASPEC_FFT_LOG; ++s) {
+        const uint32_t half = 1u << (s - 1), step = n >> s;
+        for (uint32_t base = 0; base < n; base += 2 * half)
+            for (uint32_t j = 0; j < half; ++j) {
+                float* a = z + 2 * (base + j);
+                float* b = z + 2 * (base + j + half);
+                const uint32_t e = j * step;
+                float tr, ti;
+                if (e == 0) {
+                    tr = b[0];
+                    ti = b[1];
+                } else if (e == n / 4) {
+                    tr = b[1];
+                    ti = -b[0];
+                } else {
+                    const float wr = tw[2 * e], wi = tw[2 * e + 1];
+                    tr = std::fmaf(-b[1], wi, b[0] * wr);
+                    ti = std::fmaf(b[1], wr, b[0] * wi);
+                }
+                const float ar = a[0], ai = a[1];
+                a[0] = ar + tr;
+                a[1] = ai + ti;
+                b[0] = ar - tr;
+                b[1] = ai - ti;
+            }
+    }
+}
+
+constexpr int kAspecThreads = 256;  // the lanes of aspec.hip's workgroup: the order of band_power is stated over them
+
+// the record of one block from its P[0 .. 1023]
+void aspec_reduce(const float* pw, const AspecBand& band, mi_aspec_record* rec) {
+    double acc[kAspecThreads];
+    for (uint32_t t = 0; t < kAspecThreads; ++t) {
+        acc[t] = 0.0;
+        for (uint32_t bin = t; bin < MI_ASPEC_BINS; bin += kAspecThreads)
+            if (bin >= band.lo && bin <= band.hi)
+                acc[t] += static_cast<double>(pw[bin]);
+    }
+    for (uint32_t d = kAspecThreads / 2; d >= 1; d /= 2)
+        for (uint32_t t = 0; t < d; ++t)
+            acc[t] += acc[t + d];
+    uint32_t peak = band.lo;
+    for (uint32_t bin = band.lo + 1; bin <= band.hi; ++bin)
+        if (pw[bin] > pw[peak])
+            peak = bin;
+    const uint32_t first = peak - band.lo < MI_ASPEC_LINE_HALF ? band.lo : peak - MI_ASPEC_LINE_HALF;
+    const uint32_t last = band.hi - peak < MI_ASPEC_LINE_HALF ? band.hi : peak + MI_ASPEC_LINE_HALF;
+    double line = 0.0;
+    for (uint32_t bin = first; bin <= last; ++bin)
+        line += static_cast<double>(pw[bin]);
+    rec->peak_bin = peak;
+    rec->peak_power = pw[peak];
+    rec->band_power = acc[0];
+    rec->line_power = line;
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" int mi_aspec_window(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::aspec_window(out);
+    return MI_OK;
+}
+
+extern "C" int mi_aspec_band(const mi_aspec_cfg* cfg, uint32_t* lo_bin, uint32_t* hi_bin) {
+    if (!lo_bin || !hi_bin)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::AspecBand band;
+    if (const int rc = mi::aspec_band(cfg, &band))
+        return rc;
+    *lo_bin = band.lo;
+    *hi_bin = band.hi;
+    return MI_OK;
+}
+
+extern "C" int mi_aspec_plan_host(const mi_aspec_cfg* cfg, int rows, int nbatches, const float* waveout, size_t row_stride, const mi_gate_block* index,
+                                  size_t nblocks, const uint32_t* row_first, mi_aspec_record* records, float* power, float* row_mean,
+                                  uint32_t* row_blocks) {
+    if (!waveout || (nblocks && (!index || !records)))
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::AspecBand band;
+    if (const int rc = mi::aspec_band(cfg, &band))
+        return rc;
+    if (rows < 1 || nbatches < 1)
+        return fail(MI_ERR_INVALID, "audio spectrum plan needs rows >= 1 and nbatches >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    if ((row_mean != nullptr) != (row_blocks != nullptr) || (row_mean && (!row_first || (nblocks && !power))))
+        return fail(MI_ERR_INVALID, "audio spectrum stage: a row mean needs the power rows, the row starts and the row counts");
+    std::vector<float> tw, w(mi::kWaveBatch), z(2 * MI_ASPEC_FFT), pw(MI_ASPEC_BINS);
+    if (const int rc = mi::aspec_twiddles(tw))
+        return rc;
+    mi::aspec_window(w.data());
+    for (size_t k = 0; k < nblocks; ++k) {
+        const uint32_t row = index[k].row, batch = index[k].batch;
+        mi_aspec_record rec{row, batch, 0xFFFFFFFFu, 0.0f, 0.0, 0.0};
+        if (row >= static_cast<uint32_t>(rows) || batch >= static_cast<uint32_t>(nbatches)) {
+            std::fill(pw.begin(), pw.end(), 0.0f);
+        } else {
+            const float* x = waveout + static_cast<size_t>(row) * row_stride + static_cast<size_t>(batch) * mi::kWaveBatch;
+            std::fill(z.begin(), z.end(), 0.0f);
+            for (int i = 0; i < mi::kWaveBatch; ++i)
+                z[2 * static_cast<size_t>(i)] = x[i] * w[static_cast<size_t>(i)];
+            mi::aspec_fft(tw.data(), z.data());
+            for (size_t j = 0; j < MI_ASPEC_BINS; ++j) {
+                const float rr = z[2 * j] * z[2 * j], ii = z[2 * j + 1] * z[2 * j + 1];
+                pw[j] = rr + ii;
+            }
+            mi::aspec_reduce(pw.data(), band, &rec);
+        }
+        records[k] = rec;
+        if (power)
+            std::memcpy(power + k * MI_ASPEC_BINS, pw.data(), MI_ASPEC_BINS * sizeof(float));
+    }
+    if (row_mean) {
+        const uint64_t stored = nblocks;
+        for (int r = 0; r < rows; ++r) {
+            const uint64_t first = std::min<uint64_t>(row_first[r], stored), last = std::min<uint64_t>(row_first[r + 1], stored);
+            const uint64_t n = last > first ? last - first : 0;
+            row_blocks[r] = static_cast<uint32_t>(n);
+            for (size_t j = 0; j < MI_ASPEC_BINS; ++j) {
+                double s = 0.0;
+                for (uint64_t k = first; k < first + n; ++k)
+                    s += static_cast<double>(power[k * MI_ASPEC_BINS + j]);
+                row_mean[static_cast<size_t>(r) * MI_ASPEC_BINS + j] = n ? static_cast<float>(s / static_cast<double>(n)) : 0.0f;
+            }
+        }
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_aspec_notch_host(const float* row_mean, uint32_t row_blocks, const mi_aspec_record* records, size_t n, const mi_aspec_cfg* cfg,
+                                   const mi_aspec_rule* rule, mi_aspec_notch* out) {
+    if (!row_mean || !out || (n && !records))
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::AspecBand band;
+    if (const int rc = mi::aspec_band(cfg, &band))
+        return rc;
+    const uint32_t min_blocks = rule && rule->min_blocks ? rule->min_blocks : 8u;
+    const float ratio = rule && rule->ratio != 0.0f ? rule->ratio : 16.0f;
+    if (!(ratio >= 0.0f) || !std::isfinite(ratio))
+        return fail(MI_ERR_INVALID, "audio spectrum stage: the ratio must be finite and not negative (0 = 16)");
+    uint32_t p = band.lo;
+    for (uint32_t j = band.lo + 1; j <= band.hi; ++j)
+        if (row_mean[j] > row_mean[p])
+            p = j;
+    std::vector<float> around;
+    for (uint32_t j = band.lo; j <= band.hi; ++j) {
+        const uint32_t d = j > p ? j - p : p - j;
+        if (d >= 3 && d <= 34)
+            around.push_back(row_mean[j]);
+    }
+    std::sort(around.begin(), around.end());
+    const float floor = around.empty() ? 0.0f : around[(around.size() - 1) / 2];
+    const float threshold = ratio * floor;
+    double num = 0.0, den = 0.0;
+    for (uint32_t j = p - band.lo < 1 ? band.lo : p - 1; j <= (band.hi - p < 1 ? band.hi : p + 1); ++j) {
+        num += static_cast<double>(j) * static_cast<double>(row_mean[j]);
+        den += static_cast<double>(row_mean[j]);
+    }
+    uint32_t votes = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t d = static_cast<int64_t>(records[i].peak_bin) - static_cast<int64_t>(p);
+        votes += d >= -1 && d <= 1 ? 1u : 0u;
+    }
+    const double hz_per_bin = static_cast<double>(mi::kWaveRate) / MI_ASPEC_FFT;
+    out->found = row_blocks >= min_blocks && row_mean[p] > 0.0f && row_mean[p] > threshold ? 1u : 0u;
+    out->bin = p;
+    out->freq_hz = hz_per_bin * (den > 0.0 ? num / den : static_cast<double>(p));
+    out->peak = static_cast<double>(row_mean[p]);
+    out->floor = static_cast<double>(floor);
+    out->votes = votes;
+    out->blocks = row_blocks;
     return MI_OK;
 }

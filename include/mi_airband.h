@@ -935,6 +935,109 @@ int mi_pcm_plan_host(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows
  * *len = the header's length; MI_ERR_INVALID if cap is below it or the file would pass 2^32 - 1 bytes. */
 int mi_pcm_wav_header(const mi_pcm_cfg* cfg, uint64_t nblocks, void* buf, size_t cap, size_t* len);
 
+/* ---------------- audio spectrum stage: a power spectrum per travelling block, a long-term spectrum per row ----------------
+ * Every channel of the reference has a `notch` key (config.cpp:388-392, 519-567; filters.cpp:30-64) and stage 2 honours
+ * mi_channel_cfg.notch_freq / notch_q; this stage is what tells a caller what to put there.  What a notch removes -- the whistle of
+ * offset-carrier (CLIMAX) AM operation, a sub-audible tone that leaks through, mains hum -- is a steady narrow line in the open
+ * audio, which the 51-tone bank of mi_tones_* cannot see.  A post-stage like the PCM stage: it reads the audio
+ * mi_demod_process_device wrote and the index, row starts and counts mi_outgate_process_device left in device memory, and writes one
+ * record (and optionally one power row) per travelling block and one mean spectrum per row.  It is stateless: nothing is carried
+ * between calls, there is no row mask and no state blob.
+ *
+ * Frame.  Block k of the index, (row, batch), is the 2000 samples x[0 .. 1999] of d_waveout at row * row_stride + batch * 2000.
+ * Window.  w[i] = (float)(0.5 - 0.5 cos(2 pi i / 1999)), i = 0 .. 1999 (Hann), evaluated in float64 for i <= 999 and mirrored,
+ *   w[1999 - i] = w[i], so that it is symmetric bit for bit: mi_aspec_window.  The device gets that table from the host.
+ * Input.  u[i] = x[i] * w[i], one float32 multiply; u[2000 .. 2047] = 0.0f; the FFT input is the complex sequence (u[i], 0.0f).
+ * Spectrum.  X = the documented FFT at N = MI_ASPEC_FFT = 2048 with the twiddles mi_plan_twiddles gives at
+ *   fft_size_log 11 (the table depends on N only).  P[j] = X[j].re * X[j].re + X[j].im * X[j].im for j = 0 .. MI_ASPEC_BINS - 1, both
+ *   products and the sum rounded on their own in float32; no square root.  Bin j is j * MI_WAVE_RATE / 2048 = j * 7.8125 Hz.  The
+ *   real-input halving trick is not used and nothing is pruned for the zero imaginary parts: the full graph is the definition.
+ * Band.  mi_aspec_cfg { lo_hz, hi_hz }, 0 = the default 60 / 3800.  lo_bin = (lo_hz * 2048 + 15999) / 16000 and hi_bin = hi_hz * 2048
+ *   / 16000 in integers; a configuration is refused unless 1 <= lo_bin <= hi_bin <= 1023.  mi_aspec_band returns the two bins; the
+ *   defaults give 8 and 486.
+ * Record of block k (mi_aspec_record, 32 bytes):
+ *   peak_bin    the bin in [lo_bin, hi_bin] with the largest P, the lowest bin on ties;  peak_power = its P
+ *   band_power  a float64 sum of P over the band in this order: thread t of 256 adds, bins ascending, those of the bins t, t + 256,
+ *               t + 512, t + 768 that lie in the band (starting from 0.0); then acc[t] += acc[t + d] for t < d, d = 128, 64, .., 1;
+ *               band_power = acc[0]
+ *   line_power  the float64 sum of P[peak_bin - MI_ASPEC_LINE_HALF .. peak_bin + MI_ASPEC_LINE_HALF], clipped to the band, bins ascending
+ *   An index entry with row >= rows or batch >= nbatches gives the record {row, batch, 0xFFFFFFFF, 0, 0, 0} and a power row of
+ *   zeros; nothing is read out of range.  NaN and Inf in the audio are unspecified, as everywhere behind the demodulator.
+ * Power rows.  d_power [max_blocks][1024], optional: row k holds P[0 .. 1023] of block k.
+ * Row mean.  d_row_mean [rows][1024] and d_row_blocks [rows], optional (both or neither).  With stored = min(d_count[1], max_blocks),
+ *   row r's blocks are the k in [d_row_first[r], d_row_first[r + 1]) that lie in [0, stored), n of them: row_blocks[r] = n and
+ *   row_mean[r][j] = (float)(S / n) with S the float64 sum of d_power[k][j] over those k ascending; n = 0 gives zeros.  A non-NULL
+ *   d_row_mean needs d_power, d_row_first and d_row_blocks, else the call is refused: the handle allocates no per-block scratch.
+ * Nothing is written at or beyond `stored` in d_records or d_power.
+ * Execution: asynchronous on `hip_stream`, no host synchronisation; one kernel (one workgroup per block), and a second one (one
+ *   thread per row and bin) only when a row mean is wanted.  No atomics: every byte is the same on every run and equals
+ *   mi_aspec_plan_host's.  mi_aspec_download is the one place that synchronises.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, a refused band, misaligned buffers, nbatches
+ * outside 1 .. max_batches, or a row mean without what it needs. */
+enum { MI_ASPEC_FFT_LOG = 11, MI_ASPEC_FFT = 2048, MI_ASPEC_BINS = 1024, MI_ASPEC_LINE_HALF = 2 };
+typedef struct { uint32_t lo_hz, hi_hz; } mi_aspec_cfg; /* 0 = 60 / 3800 */
+typedef struct {
+    uint32_t row, batch;
+    uint32_t peak_bin;  /* 0xFFFFFFFF: not an entry of this call */
+    float peak_power;
+    double band_power, line_power;
+} mi_aspec_record; /* 32 bytes */
+typedef struct mi_aspec mi_aspec;
+
+/* cfg NULL = the defaults.  rows and max_batches within the gate's limits (1 <= rows < 2^20, rows * max_batches < 2^24);
+ * max_blocks: capacity of the caller's d_records (and d_power) in blocks, 0 = rows * max_batches. */
+int mi_aspec_create(const mi_aspec_cfg* cfg, int rows, int max_batches, size_t max_blocks, int gpu, mi_aspec** out);
+void mi_aspec_destroy(mi_aspec* a);
+/* One call over nbatches (1 .. max_batches) batches: d_waveout [rows][row_stride] with alignment and strides as for
+ * mi_outgate_process_device; d_index (8-byte aligned), d_row_first [rows + 1] (may be NULL without a row mean) and d_count [2] in
+ * device memory exactly as mi_outgate_process_device left them; d_records [max_blocks] (8-byte aligned); d_power [max_blocks][1024]
+ * or NULL and d_row_mean [rows][1024] or NULL (16-byte aligned); d_row_blocks [rows], non-NULL exactly when d_row_mean is. */
+int mi_aspec_process_device(mi_aspec* a, const float* d_waveout, size_t row_stride, int nbatches, const mi_gate_block* d_index,
+                            const uint32_t* d_row_first, const uint32_t* d_count, mi_aspec_record* d_records, float* d_power, float* d_row_mean,
+                            uint32_t* d_row_blocks, void* hip_stream);
+/* Results of the last mi_aspec_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the two counts it
+ * was given and copies exactly min(count[1], max_blocks) records and power rows, rows * 1024 means and rows block counts; on return
+ * count[0] is the gate's count[0] and count[1] the number of records copied.  Each destination may be NULL; one the call did not
+ * write (power, row_mean, row_blocks) is refused.  The one place that synchronises. */
+int mi_aspec_download(mi_aspec* a, void* hip_stream, mi_aspec_record* records, float* power, float* row_mean, uint32_t* row_blocks,
+                      uint32_t* count /* [2] */);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {blocks, rows}; rows is 0 for a call without a row mean.  tools/aspec_rate.py. */
+int mi_aspec_set_timing(mi_aspec* a, int on);
+int mi_aspec_last_launch_ms(mi_aspec* a, float* ms /* [2] */);
+/* The 2000 window coefficients.  Host only. */
+int mi_aspec_window(float* out /* [MI_WAVE_BATCH] */);
+/* lo_bin and hi_bin under cfg (NULL = the defaults), or the refusal.  Host only. */
+int mi_aspec_band(const mi_aspec_cfg* cfg, uint32_t* lo_bin, uint32_t* hi_bin);
+/* The host twin: no GPU and no HIP call; the same bytes.  waveout [rows][row_stride]; index [nblocks] from the host (any order,
+ * repeats allowed), stored = nblocks; records holds nblocks entries and power, if not NULL, nblocks * 1024 floats, all of which are
+ * written; row_first [rows + 1], row_mean [rows][1024] and row_blocks [rows] follow the rule above (row_mean needs power, row_first
+ * and row_blocks).  The rows are cut by row_first alone, whatever rows the entries name. */
+int mi_aspec_plan_host(const mi_aspec_cfg* cfg, int rows, int nbatches, const float* waveout, size_t row_stride, const mi_gate_block* index,
+                       size_t nblocks, const uint32_t* row_first, mi_aspec_record* records, float* power, float* row_mean, uint32_t* row_blocks);
+
+/* From a row's mean spectrum to a notch_freq: no GPU and no HIP call, float64 except where stated.  With [lo_bin, hi_bin] of cfg:
+ *   p        the band bin with the largest mean, the lowest bin on ties
+ *   floor    the median of the means of the band bins j with 3 <= |j - p| <= 34 (a line under the Hann window covers p - 2 .. p + 2;
+ *            34 bins are 266 Hz): the element at index (m - 1) / 2 of those m values sorted ascending; 0 when m = 0
+ *   found    iff row_blocks >= min_blocks and mean[p] > 0 and mean[p] > ratio * floor, the product one float32 multiply
+ *   freq_hz  7.8125 * (sum of j * mean[j]) / (sum of mean[j]) over j = p - 1 .. p + 1 clipped to the band, j ascending; 7.8125 * p
+ *            where the second sum is 0
+ *   votes    the number of the given records (the row's: records[row_first[r] .. row_first[r + 1])) with |peak_bin - p| <= 1; it is
+ *            reported, it is not a condition
+ *   peak = mean[p], blocks = row_blocks.
+ * rule NULL or a field that is 0 takes its default: min_blocks 8 (one second of open audio), ratio 16.0f.  The defaults are a
+ * caller's settings like the finder's ratio, not tolerances; they have been tried on synthetic signals only (DESIGN.md 5j has the
+ * table).  The function suggests no Q: the reference's default notch_q of 10 stays the caller's choice.  records may be NULL with
+ * n = 0.  MI_ERR_INVALID: NULL arguments, a refused band, a ratio that is negative or not finite. */
+typedef struct { uint32_t min_blocks; float ratio; } mi_aspec_rule; /* 0 = 8 / 16.0f */
+typedef struct {
+    uint32_t found, bin;
+    double freq_hz, peak, floor;
+    uint32_t votes, blocks;
+} mi_aspec_notch; /* 40 bytes */
+int mi_aspec_notch_host(const float* row_mean /* [1024] */, uint32_t row_blocks, const mi_aspec_record* records, size_t n,
+                        const mi_aspec_cfg* cfg /* NULL = defaults */, const mi_aspec_rule* rule /* NULL = defaults */, mi_aspec_notch* out);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
