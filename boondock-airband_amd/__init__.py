@@ -153,6 +153,15 @@ PCM_TAPS, PCM_HISTORY = 63, 62  # MI_PCM_TAPS, MI_PCM_HISTORY
 PCM_STATE_DTYPE = np.dtype([("x", "<f4", (PCM_HISTORY,))])  # one row of the PCM stage's state blob, MI_PCM_STATE_ROW_BYTES = 248
 
 
+class VbandRow(C.Structure):  # mi_vband_row: 0 = no edge on that side
+    _fields_ = [("hp_hz", C.c_uint32), ("lp_hz", C.c_uint32)]
+
+
+VBAND_TAPS, VBAND_HISTORY = 511, 510  # MI_VBAND_TAPS, MI_VBAND_HISTORY
+VBAND_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in VbandRow._fields_])  # the same 8 bytes as a numpy record
+VBAND_STATE_DTYPE = np.dtype([("x", "<f4", (VBAND_HISTORY,))])  # one row of the voice band stage's state blob, MI_VBAND_STATE_ROW_BYTES = 2040
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -232,6 +241,8 @@ ABI_SYMBOLS = [
     "mi_pcm_set_state", "mi_pcm_set_timing", "mi_pcm_last_launch_ms", "mi_pcm_block_bytes", "mi_pcm_taps", "mi_pcm_plan_host", "mi_pcm_wav_header",
     "mi_aspec_create", "mi_aspec_destroy", "mi_aspec_process_device", "mi_aspec_download", "mi_aspec_set_timing", "mi_aspec_last_launch_ms",
     "mi_aspec_window", "mi_aspec_band", "mi_aspec_plan_host", "mi_aspec_notch_host",
+    "mi_vband_default_row", "mi_vband_create", "mi_vband_destroy", "mi_vband_set_rows", "mi_vband_process_device", "mi_vband_state_size",
+    "mi_vband_get_state", "mi_vband_set_state", "mi_vband_set_timing", "mi_vband_last_launch_ms", "mi_vband_taps", "mi_vband_plan_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -358,6 +369,21 @@ def lib():
         L.mi_pcm_taps.argtypes = [vp]
         L.mi_pcm_plan_host.argtypes = [C.POINTER(PcmCfg), vp, C.c_int, C.c_int, vp, sz, vp, sz, vp, vp]
         L.mi_pcm_wav_header.argtypes = [C.POINTER(PcmCfg), C.c_uint64, vp, sz, C.POINTER(sz)]
+        L.mi_vband_default_row.argtypes = []
+        L.mi_vband_default_row.restype = VbandRow
+        L.mi_vband_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mi_vband_destroy.argtypes = [vp]
+        L.mi_vband_destroy.restype = None
+        L.mi_vband_set_rows.argtypes = [vp, vp, vp]
+        L.mi_vband_process_device.argtypes = [vp, vp, sz, C.c_int, vp, sz, vp]
+        L.mi_vband_state_size.argtypes = [vp]
+        L.mi_vband_state_size.restype = sz
+        L.mi_vband_get_state.argtypes = [vp, vp, sz]
+        L.mi_vband_set_state.argtypes = [vp, vp, sz]
+        L.mi_vband_set_timing.argtypes = [vp, C.c_int]
+        L.mi_vband_last_launch_ms.argtypes = [vp, vp]
+        L.mi_vband_taps.argtypes = [C.c_uint32, C.c_uint32, vp]
+        L.mi_vband_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
         L.mi_aspec_create.argtypes = [C.POINTER(AspecCfg), C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
         L.mi_aspec_destroy.argtypes = [vp]
         L.mi_aspec_destroy.restype = None
@@ -478,7 +504,7 @@ class _PostStage(_Handle):
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
-        .view(PCM_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -489,7 +515,7 @@ class _PostStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means"""
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
         return tuple(ms)
@@ -1155,6 +1181,83 @@ def pcm_wav_header(nblocks, rate=0, fmt=0):
     n = C.c_size_t(0)
     _check(lib().mi_pcm_wav_header(C.byref(_pcm_cfg(rate, fmt)), int(nblocks), _ptr(buf), buf.size, C.byref(n)))
     return buf[:n.value].tobytes()
+
+
+def vband_default_row():
+    """mi_vband_default_row: (100, 2500), the reference's highpass / lowpass defaults"""
+    r = lib().mi_vband_default_row()
+    return r.hp_hz, r.lp_hz
+
+
+def _vband_rows(rows_cfg, rows):
+    """None (the default row everywhere), one (hp_hz, lp_hz) pair for every row, or a pair per row -> [rows] of VBAND_ROW_DTYPE"""
+    if rows_cfg is None:
+        rows_cfg = vband_default_row()
+    a = np.asarray(rows_cfg)
+    if a.dtype != VBAND_ROW_DTYPE:
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(rows_cfg, np.uint32).reshape(-1, 2), (rows, 2))).view(VBAND_ROW_DTYPE).reshape(-1)
+    a = np.ascontiguousarray(a)
+    assert a.shape == (rows,)
+    return a
+
+
+class Vband(_PostStage):
+    """mi_vband: the voice band stage -- the reference's `highpass` / `lowpass` keys as a 511-tap linear-phase FIR per row over the
+    demodulator's audio, written as a plane of the same layout (delayed by 255 samples, clamped to [-1, 1]) that the gate, the
+    splitter, the PCM stage and the mixer take in its place.  row_enabled: truth value per row (a disabled row's output is not
+    written and its carried samples stay); rows_cfg: (hp_hz, lp_hz) for every row or one pair per row, 0 = no edge on that side,
+    None = the defaults 100 / 2500.  state() gives rows * 2040 bytes, .view(VBAND_STATE_DTYPE): the 510 input samples a row carries
+    into its next call."""
+    _destroy, _prefix, _launches = "mi_vband_destroy", "mi_vband", 2
+
+    def __init__(self, row_enabled, rows_cfg=None, max_batches=1, gpu=0):
+        en = _flags(row_enabled)
+        self.rows, self.max_batches = en.size, max_batches
+        cfg = _vband_rows(rows_cfg, self.rows)
+        self._h = C.c_void_p()
+        _check(lib().mi_vband_create(_ptr(cfg), _ptr(en), self.rows, max_batches, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled=None, rows_cfg=None):
+        """other rows and / or other settings from the next call on (None = keep); the carried samples stay"""
+        en = None if row_enabled is None else _flags(row_enabled)
+        cfg = None if rows_cfg is None else _vband_rows(rows_cfg, self.rows)
+        assert en is None or en.size == self.rows
+        _check(lib().mi_vband_set_rows(self._h, None if cfg is None else _ptr(cfg), None if en is None else _ptr(en)))
+
+    def process_device(self, d_waveout, row_stride, nbatches, d_out, out_stride, hip_stream=None):
+        """Raw device pointers (ints), the strides in floats; d_out [rows][out_stride] must not overlap d_waveout; asynchronous on
+        hip_stream."""
+        _check(lib().mi_vband_process_device(self._h, d_waveout, row_stride, nbatches, d_out, out_stride, hip_stream))
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        self._call("set_state", _ptr(buf), buf.size)
+
+
+def vband_plan_host(row_enabled, waveout, rows_cfg=None, state=None, nbatches=None, out=None):
+    """mi_vband_plan_host: the voice band stage's plane from audio on the host, no GPU.  waveout: float32 [rows][row_stride];
+    rows_cfg as for Vband; state: the blob (rows * 2040 bytes) or None (a fresh one); nbatches: batches of the call, default
+    row_stride // WAVE_BATCH; out: float32 [rows][out_stride] to write into (a disabled row's floats stay), default zeros
+    [rows][nbatches * WAVE_BATCH].  Returns (out, state after the call)."""
+    en = _flags(row_enabled)
+    waveout = np.ascontiguousarray(waveout, dtype=np.float32)
+    assert waveout.ndim == 2 and waveout.shape[0] == en.size
+    rows, row_stride = waveout.shape
+    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
+    cfg = _vband_rows(rows_cfg, rows)
+    state = np.zeros(rows * VBAND_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * VBAND_STATE_DTYPE.itemsize
+    out = np.zeros((rows, nb * WAVE_BATCH), np.float32) if out is None else out
+    assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == rows and out.flags.c_contiguous
+    _check(lib().mi_vband_plan_host(_ptr(cfg), _ptr(en), rows, nb, _ptr(waveout), row_stride, _ptr(state), _ptr(out), out.shape[1]))
+    return out, state
+
+
+def vband_taps(hp_hz, lp_hz):
+    """mi_vband_taps: the 511 float32 taps of a row with these settings (0 = no edge on that side)"""
+    h = np.zeros(VBAND_TAPS, np.float32)
+    _check(lib().mi_vband_taps(int(hp_hz), int(lp_hz), _ptr(h)))
+    return h
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

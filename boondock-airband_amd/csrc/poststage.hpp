@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -169,6 +169,25 @@ struct AspecBand {
 int aspec_band(const mi_aspec_cfg* cfg, AspecBand* out);
 void aspec_window(float* w);
 int aspec_twiddles(std::vector<float>& tw);
+
+// The voice band stage (include/mi_airband.h "voice band stage").  One row of its state: the checkpoint blob is an array of these,
+// and vband.hip keeps the same array in device memory.
+struct VbandRowState {
+    float x[MI_VBAND_HISTORY];  // the last 510 input samples of the row's last batch, oldest first
+};
+static_assert(sizeof(VbandRowState) == MI_VBAND_STATE_ROW_BYTES && MI_VBAND_HISTORY == MI_VBAND_TAPS - 1 && MI_VBAND_TAPS % 2 == 1 &&
+                  sizeof(mi_vband_row) == 8 && MI_VBAND_STATE_ROW_BYTES % 8 == 0 && MI_VBAND_HISTORY <= kWaveBatch,
+              "the voice band stage's blob and settings layouts are ABI");
+constexpr int kVbandTapRow = 512;  // floats of one class of the device's tap table: the 511 taps and a zero that is never read
+
+// What both halves of the voice band stage share (poststage_host.cpp).  vband_row_ok: MI_OK, or the settings' refusal with its
+// message set.  vband_taps: h[511] of valid settings.  vband_classes: the rows' settings (NULL = the default row everywhere)
+// checked and deduplicated in order of first appearance -- class_of[rows] and the distinct settings --, or the first refusal.
+// vband_overlap: whether the planes [rows][stride] share a byte over a call of nbatches batches.
+int vband_row_ok(const mi_vband_row& r);
+void vband_taps(const mi_vband_row& r, float* h);
+int vband_classes(const mi_vband_row* row_cfg, size_t rows, std::vector<uint32_t>& class_of, std::vector<mi_vband_row>& classes);
+bool vband_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

@@ -3,8 +3,8 @@
 // device walk and with the Python model, which are the other two statements of the same rule.  The band survey's host half lives here
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
 // (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; the PCM
-// stage's twin mi_pcm_plan_host with its taps and WAV headers; and the audio spectrum stage's twin mi_aspec_plan_host with its window,
-// band and the notch vote.
+// stage's twin mi_pcm_plan_host with its taps and WAV headers; the audio spectrum stage's twin mi_aspec_plan_host with its window,
+// band and the notch vote; and the voice band stage's twin mi_vband_plan_host with its settings, taps and classes.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1025,5 +1025,120 @@ extern "C" int mi_aspec_notch_host(const float* row_mean, uint32_t row_blocks, c
     out->floor = static_cast<double>(floor);
     out->votes = votes;
     out->blocks = row_blocks;
+    return MI_OK;
+}
+
+// ---- voice band stage, host side (include/mi_airband.h "voice band stage"): the settings' check, the taps and the classes both
+// halves share, and the twin of vband.hip -- one block at a time, tap by tap over all of its outputs, all 511 taps in the sum.
+namespace mi {
+
+int vband_row_ok(const mi_vband_row& r) {
+    if (r.hp_hz != 0 && (r.hp_hz < 50 || r.hp_hz > 4000))
+        return fail(MI_ERR_INVALID, "voice band stage: hp_hz must be 0 or 50 .. 4000");
+    if (r.lp_hz != 0 && (r.lp_hz < 500 || r.lp_hz > 7800))
+        return fail(MI_ERR_INVALID, "voice band stage: lp_hz must be 0 or 500 .. 7800");
+    if (r.lp_hz != 0 && r.lp_hz < r.hp_hz + 200)
+        return fail(MI_ERR_INVALID, "voice band stage: lp_hz must be 0 or at least hp_hz + 200");
+    return MI_OK;
+}
+
+// The design in float64.  The lower half and the centre come from the formula; the upper half is its mirror image, so that the
+// symmetry holds bit for bit whatever cos() does with the two arguments.
+void vband_taps(const mi_vband_row& r, float* h) {
+    const double pi = 3.14159265358979323846;
+    const int centre = MI_VBAND_HISTORY / 2;
+    const double fl = r.hp_hz / static_cast<double>(kWaveRate), fh = r.lp_hz / static_cast<double>(kWaveRate);
+    const auto sinc = [pi](double t) { return t == 0.0 ? 1.0 : std::sin(pi * t) / (pi * t); };
+    for (int k = 0; k <= centre; ++k) {
+        const int c = k - centre;
+        const double upper = r.lp_hz ? 2.0 * fh * sinc(2.0 * fh * c) : (c == 0 ? 1.0 : 0.0);
+        const double g = (upper - 2.0 * fl * sinc(2.0 * fl * c)) *
+                         (0.42 - 0.5 * std::cos(2.0 * pi * k / MI_VBAND_HISTORY) + 0.08 * std::cos(4.0 * pi * k / MI_VBAND_HISTORY));
+        h[k] = h[MI_VBAND_HISTORY - k] = static_cast<float>(g);
+    }
+}
+
+int vband_classes(const mi_vband_row* row_cfg, size_t rows, std::vector<uint32_t>& class_of, std::vector<mi_vband_row>& classes) {
+    class_of.assign(rows, 0);
+    classes.clear();
+    for (size_t r = 0; r < rows; ++r) {
+        const mi_vband_row s = row_cfg ? row_cfg[r] : mi_vband_default_row();
+        if (const int rc = vband_row_ok(s))
+            return rc;
+        size_t c = 0;
+        while (c < classes.size() && (classes[c].hp_hz != s.hp_hz || classes[c].lp_hz != s.lp_hz))
+            ++c;
+        if (c == classes.size())
+            classes.push_back(s);
+        class_of[r] = static_cast<uint32_t>(c);
+    }
+    return MI_OK;
+}
+
+bool vband_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches) {
+    const size_t call = nbatches * static_cast<size_t>(kWaveBatch);
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t a_end = a + ((rows - 1) * in_stride + call) * sizeof(float), b_end = b + ((rows - 1) * out_stride + call) * sizeof(float);
+    return a < b_end && b < a_end;
+}
+
+}  // namespace mi
+
+extern "C" mi_vband_row mi_vband_default_row(void) {
+    return mi_vband_row{100, 2500};
+}
+
+extern "C" int mi_vband_taps(uint32_t hp_hz, uint32_t lp_hz, float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    const mi_vband_row r{hp_hz, lp_hz};
+    if (const int rc = mi::vband_row_ok(r))
+        return rc;
+    mi::vband_taps(r, out);
+    return MI_OK;
+}
+
+extern "C" int mi_vband_plan_host(const mi_vband_row* row_cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* waveout,
+                                  size_t row_stride, void* state_inout, float* out, size_t out_stride) {
+    if (!row_enabled || !waveout || !state_inout || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1)
+        return fail(MI_ERR_INVALID, "vband plan needs rows >= 1 and nbatches >= 1");
+    std::vector<uint32_t> class_of;
+    std::vector<mi_vband_row> classes;
+    if (const int rc = mi::vband_classes(row_cfg, static_cast<size_t>(rows), class_of, classes))
+        return rc;
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch || out_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    if (mi::vband_overlap(waveout, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
+        return fail(MI_ERR_INVALID, "the output overlaps the audio buffer");
+    mi::VbandRowState* state = static_cast<mi::VbandRowState*>(state_inout);
+    std::vector<float> taps(classes.size() * MI_VBAND_TAPS);
+    for (size_t c = 0; c < classes.size(); ++c)
+        mi::vband_taps(classes[c], taps.data() + c * MI_VBAND_TAPS);
+    std::vector<float> x(MI_VBAND_HISTORY + mi::kWaveBatch), acc(mi::kWaveBatch);
+    for (int r = 0; r < rows; ++r) {
+        if (!row_enabled[r])
+            continue;
+        const float* const h = taps.data() + class_of[r] * MI_VBAND_TAPS;
+        const float* const row = waveout + static_cast<size_t>(r) * row_stride;
+        for (int b = 0; b < nbatches; ++b) {
+            // x[510 + n] = sample n of the block, x[0 .. 509] = the 510 before it
+            const float* const blk = row + static_cast<size_t>(b) * mi::kWaveBatch;
+            std::memcpy(x.data(), b ? blk - MI_VBAND_HISTORY : state[r].x, MI_VBAND_HISTORY * sizeof(float));
+            std::memcpy(x.data() + MI_VBAND_HISTORY, blk, mi::kWaveBatch * sizeof(float));
+            std::fill(acc.begin(), acc.end(), 0.0f);
+            for (int k = 0; k < MI_VBAND_TAPS; ++k) {  // (every output takes its taps in ascending order)
+                const float hk = h[k];
+                const float* const xk = x.data() + MI_VBAND_HISTORY - k;
+                for (int n = 0; n < mi::kWaveBatch; ++n)
+                    acc[n] = acc[n] + hk * xk[n];
+            }
+            float* const dst = out + static_cast<size_t>(r) * out_stride + static_cast<size_t>(b) * mi::kWaveBatch;
+            for (int n = 0; n < mi::kWaveBatch; ++n)
+                dst[n] = std::fmin(std::fmax(acc[n], -1.0f), 1.0f);
+        }
+        std::memcpy(state[r].x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_VBAND_HISTORY, MI_VBAND_HISTORY * sizeof(float));
+    }
     return MI_OK;
 }

@@ -1038,6 +1038,79 @@ typedef struct {
 int mi_aspec_notch_host(const float* row_mean /* [1024] */, uint32_t row_blocks, const mi_aspec_record* records, size_t n,
                         const mi_aspec_cfg* cfg /* NULL = defaults */, const mi_aspec_rule* rule /* NULL = defaults */, mi_aspec_notch* out);
 
+/* ---------------- voice band stage: per-row highpass / lowpass FIR over the demodulator's audio, on the device ----------------
+ * Every channel and every mixer of the reference has a `highpass` and a `lowpass` key (config.cpp:327-328, defaults 100 and 2500 Hz,
+ * checked at :336-338) whose only effect is in airlame_init (output.cpp:147-171: lame_set_highpassfreq / lame_set_lowpassfreq): the
+ * reference shapes the audio band inside the MP3 encoder.  The device chain has no encoder; this stage is where the two keys act.  A
+ * post-stage like the PCM stage: it reads the audio mi_demod_process_device wrote and writes a filtered plane in the same layout,
+ * d_out [rows][out_stride], so the gate, the splitter, the PCM stage, the spectrum stage and the mixer run on it unchanged.  The
+ * stage filters every batch of every enabled row, whether it travels or not: there is no index and no download entry, and the PCM
+ * stage's 62-sample reach into a batch that does not travel reads defined values.  mi_tones_* and mi_aspec_* are meant to keep
+ * reading the unfiltered plane: what they look for is what this stage removes.
+ *
+ * Stream model.  As for the PCM stage: a row's audio is one running sequence x over all batches of all calls the row was enabled in;
+ * samples before the handle's first call are 0.
+ * Row settings.  mi_vband_row { hp_hz, lp_hz } per row: hp_hz = 0 means no lower edge, lp_hz = 0 no upper edge, both 0 a pure delay,
+ * which keeps rows aligned for the mixer.  Settings are refused unless hp_hz == 0 || 50 <= hp_hz <= 4000, lp_hz == 0 || 500 <= lp_hz
+ * <= 7800, and lp_hz == 0 || lp_hz >= hp_hz + 200 -- those of a disabled row too.  mi_vband_default_row gives 100 / 2500, the
+ * reference's defaults.
+ * Taps h (mi_vband_taps), MI_VBAND_TAPS = 511 with the centre at 255, designed in float64 and cast to float32 once.  With c = k - 255,
+ * fl = hp_hz / 16000.0 and fh = lp_hz / 16000.0:
+ *   g[k] = (U(c) - 2 fl sinc(2 fl c)) * (0.42 - 0.5 cos(2 pi k / 510) + 0.08 cos(4 pi k / 510))
+ *   U(c) = 2 fh sinc(2 fh c) where lp_hz != 0; where lp_hz == 0 (fh = 0.5: the whole band) U(0) = 1 and U(c) = 0 otherwise, exactly
+ * with sinc(t) = sin(pi t) / (pi t) and sinc(0) = 1, evaluated for k <= 255; h[k] = (float)g[k] and h[510 - k] = h[k], so that h is
+ * symmetric bit for bit.  There is no normalisation.  Both settings 0 give exactly a unit impulse at tap 255.  A windowed-sinc band
+ * filter under a Blackman window: within +-0.01 dB from 100 Hz inside each edge, below -70 dB from 100 Hz outside it (DESIGN.md has
+ * the measured table).
+ * Output.  Sample n of the row's sequence:  y[n] = sum over k = 0 .. 510 of h[k] * x[n - k]  in float32, every product and every sum
+ * rounded on its own, k ascending, starting from 0.0f; no fused multiply-add and no folding of the symmetric taps.  Then
+ * out = fminf(fmaxf(y, -1.0f), 1.0f): sum |h| is 2.5 to 3.0 for usual settings and everything behind the demodulator relies on
+ * |x| <= 1 (the reference clamps at the same place in its own gate, rtl_airband.cpp:612-641).  Indices below the call's first sample
+ * reach into the 510 samples the handle carries for the row.  NaN and Inf are unspecified, as everywhere behind the demodulator.
+ *   Where all 2510 samples a block's outputs depend on compare equal to zero, the definition gives +0.0f throughout (products of +-0
+ *   added to +0.0f stay +0.0f); the device writes that without summing.  No byte depends on it.
+ * Delay.  The filter is causal and delays the audio by 255 samples (15.9 ms) against the demodulator's flags: the last samples of a
+ * transmission can land in the batch after the one whose flag closes.  A caller keeps them with the gate's open trail
+ * (MI_GATE_OPEN_TRAIL), which lets that batch travel.
+ * State: per row the last 510 input samples of the last batch of the last call the row was enabled in, zeros at first; the blob is
+ * rows * MI_VBAND_STATE_ROW_BYTES bytes of little-endian float32, oldest sample first.  A disabled row's output row is not written
+ * and its carried samples keep their bytes.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned or overlapping
+ * buffers, nbatches outside 1 .. max_batches. */
+enum { MI_VBAND_TAPS = 511, MI_VBAND_HISTORY = 510, MI_VBAND_STATE_ROW_BYTES = 2040 };
+typedef struct { uint32_t hp_hz, lp_hz; } mi_vband_row; /* 0 = no edge on that side */
+typedef struct mi_vband mi_vband;
+
+/* { 100, 2500 }: the reference's defaults (config.cpp:327-328). */
+mi_vband_row mi_vband_default_row(void);
+/* row_cfg [rows] (NULL = the default row everywhere); row_enabled [rows] as for mi_pcm_create; rows and max_batches within the
+ * gate's limits (1 <= rows < 2^20, rows * max_batches < 2^24).  Rows with equal settings share one tap table on the device. */
+int mi_vband_create(const mi_vband_row* row_cfg /* [rows] */, const uint8_t* row_enabled, int rows, int max_batches, int gpu, mi_vband** out);
+void mi_vband_destroy(mi_vband* v);
+/* Other settings (row_cfg [rows], NULL = keep) and / or other rows (row_enabled [rows], NULL = keep) from the next call on; at least
+ * one of the two.  All state stays.  Completes the work queued on the device first. */
+int mi_vband_set_rows(mi_vband* v, const mi_vband_row* row_cfg, const uint8_t* row_enabled);
+/* One call over nbatches (1 .. max_batches) batches: d_waveout [rows][row_stride] and d_out [rows][out_stride], both 16-byte
+ * aligned with strides that are multiples of 4 floats and at least nbatches * 2000; the two planes must not overlap (the call is
+ * refused when they do).  Asynchronous on `hip_stream`, no host synchronisation; two kernels without atomics -- the filter, then the
+ * copy of the enabled rows' last 510 input samples into the carried state -- so every byte is the same on every run and equals
+ * mi_vband_plan_host's. */
+int mi_vband_process_device(mi_vband* v, const float* d_waveout, size_t row_stride, int nbatches, float* d_out, size_t out_stride, void* hip_stream);
+/* Checkpoint / resume, rows * MI_VBAND_STATE_ROW_BYTES bytes in the layout above (mi_vband_plan_host reads and writes the same
+ * bytes).  Both complete queued work first. */
+size_t mi_vband_state_size(const mi_vband* v);
+int mi_vband_get_state(mi_vband* v, void* buf, size_t len);
+int mi_vband_set_state(mi_vband* v, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {filter, tails}.  tools/vband_rate.py. */
+int mi_vband_set_timing(mi_vband* v, int on);
+int mi_vband_last_launch_ms(mi_vband* v, float* ms /* [2] */);
+/* The 511 taps h[0 .. 510] of a row with these settings, or the settings' refusal.  Host only. */
+int mi_vband_taps(uint32_t hp_hz, uint32_t lp_hz, float* out /* [MI_VBAND_TAPS] */);
+/* The host twin: no GPU and no HIP call; the same bytes and the same state blob.  waveout [rows][row_stride], out [rows][out_stride]
+ * (no alignment asked, no overlap allowed); state_inout rows * MI_VBAND_STATE_ROW_BYTES bytes, read and updated. */
+int mi_vband_plan_host(const mi_vband_row* row_cfg /* [rows], NULL = defaults */, const uint8_t* row_enabled, int rows, int nbatches,
+                       const float* waveout, size_t row_stride, void* state_inout, float* out, size_t out_stride);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
