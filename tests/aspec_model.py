@@ -167,6 +167,32 @@ def full_index(rows, nb):
     return idx, (np.arange(rows + 1) * nb).astype(np.uint32)
 
 
+def foreign_audio(group, rows, nbatches, max_batches):
+    """the audio of the foreign-index cases (pcm_model.foreign_index): row r takes builder (rows * group + r) mod 13, so groups 0 .. 4
+    of three rows go through all thirteen; laid out for max_batches with pcm_model.FOREIGN_FILL behind the call"""
+    from pcm_model import foreign_wave
+    names = list(BUILDERS)
+    wave = np.stack([audio(names[(rows * group + r) % len(names)], 1, nbatches, group)[0] for r in range(rows)])
+    return foreign_wave(wave, nbatches, max_batches)
+
+
+FOREIGN_GROUPS = 5
+
+
+@functools.lru_cache(maxsize=None)
+def foreign_reference(case, group, lo_hz=0, hi_hz=0):
+    """(wave, index, count, row_first, max_blocks, stored, the model's (records, power, mean, row counts)) of one foreign-index case,
+    computed once for the tests that compare the twin and the device with it"""
+    import pcm_model as pm
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    index, count, row_first, cap, stored = pm.foreign_case(case, rows, nb, mb)
+    wave = foreign_audio(group, rows, nb, mb)
+    want = aspec_model(wave, index, row_first, lo_hz, hi_hz, nbatches=nb, stored=stored)
+    for a in (wave, index, count, row_first) + want:
+        a.setflags(write=False)
+    return wave, index, count, row_first, cap, stored, want
+
+
 # ---------------- audio ----------------
 
 def _time(nb):

@@ -204,6 +204,130 @@ def drawn_index(rows, nb, seed, keep=0.7):
     return idx[take]
 
 
+FOREIGN = 0xFFFFFFFF
+FOREIGN_SHAPE = (3, 2, 8)  # rows, nbatches of the call, max_batches of the handle: a grid of 6 under a capacity of 24
+FOREIGN_FILL = np.float32(0.5)  # what the input holds behind the call's batches
+
+
+def foreign_index(rows=3, nbatches=2, max_batches=8, entries=20):
+    """An index no gate writes, for a call of `nbatches` on a handle of `max_batches`: (index [entries][2], count [2] = (entries,
+    entries), row_first [rows + 1]).  The stages launch min(rows * nbatches, max_blocks) workgroups, and workgroup g takes the
+    entries g, g + grid, g + 2 grid, ...; at rows 3, nbatches 2 (a grid of 6) the columns below are one workgroup's trips.  V is an
+    entry of the call, the others are not: A has row == rows, B batch == nbatches, C 0xFFFFFFFF in both fields, D a batch in
+    nbatches + 1 .. max_batches - 1, which the input is laid out for (foreign_wave) and the call is not.
+
+        g      0        1        2        3        4        5
+        k=g    V(2,1)   C        V(0,1)   V(1,0)   B(2,.)   V(2,0)
+        +6     A(.,0)   B(0,.)   V(2,0)   D(0,+1)  V(2,1)   C
+        +12    V(0,0)   V(1,0)   D(2,+5)  A(.,1)   V(1,1)   V(0,1)
+        +18    D(1,+3)  V(1,1)   V(2,1)   B(1,.)   D(0,+2)  V(1,0)     (entries 20 .. 23 only where asked for)
+
+    The first 13 entries alone (a capacity of 13) still hold every kind and every order of neighbours.  row_first is not a gate's:
+    row 0 has its start behind its end, row 1's slice runs past what is stored, row 2's begins behind that.  It is laid out for
+    `entries` stored blocks; foreign_row_first gives it for another number."""
+    r, n, m = rows, nbatches, max_batches
+    assert r >= 3 and n >= 2 and m >= n + 6 and 13 <= entries <= 24
+    f = FOREIGN
+    index = np.array([[2, 1], [f, f], [0, 1], [1, 0], [2, n], [2, 0],
+                      [r, 0], [0, n], [2, 0], [0, n + 1], [2, 1], [f, f],
+                      [0, 0], [1, 0], [2, n + 5], [r, 1], [1, 1], [0, 1],
+                      [1, n + 3], [1, 1], [2, 1], [1, n], [0, n + 2], [1, 0]], np.uint32)[:entries]
+    return index, np.array([entries, entries], np.uint32), foreign_row_first(rows, entries)
+
+
+def foreign_row_first(rows, stored):
+    """row 0: first > last, no block.  Row 1: 2 .. stored + 1, cut by `stored`.  Row 2: begins at stored + 1, behind it.  (The largest
+    value is stored + 2: a walk that did not clip would still stay within two guard blocks behind the capacity.)"""
+    return np.array([5, 2] + [stored + 1] * (rows - 2) + [stored + 2], np.uint32)
+
+
+def foreign_kinds(index, rows, nbatches, max_batches):
+    """per entry one of V (of the call), A (row == rows), B (batch == nbatches), C (0xFFFFFFFF twice), D (a batch of the handle behind
+    the call); anything else is a mistake in the builder"""
+    kinds = []
+    for row, batch in np.asarray(index, np.int64).reshape(-1, 2):
+        if row < rows and batch < nbatches:
+            kinds.append("V")
+        elif row == rows and batch < nbatches:
+            kinds.append("A")
+        elif row < rows and batch == nbatches:
+            kinds.append("B")
+        elif row == FOREIGN and batch == FOREIGN:
+            kinds.append("C")
+        else:
+            assert row < rows and nbatches < batch < max_batches, (row, batch)
+            kinds.append("D")
+    return "".join(kinds)
+
+
+def assert_foreign_properties(index, row_first, rows, nbatches, max_batches, stored, grid=None):
+    """What foreign_index is built for, stated on the index alone: over the first `stored` entries, walked as a grid of `grid`
+    workgroups walks them."""
+    grid = min(rows * nbatches, stored) if grid is None else grid
+    index = np.asarray(index, np.int64).reshape(-1, 2)[:stored]
+    kinds = foreign_kinds(index, rows, nbatches, max_batches)
+    trips = [kinds[g::grid] for g in range(grid)]  # entries k, k + grid, k + 2 grid, ... go to one workgroup
+    assert stored > grid and all(len(t) >= 2 for t in trips), "every workgroup makes a second trip"
+    assert max(len(t) for t in trips) >= 3
+    zero = lambda t: "Z" if t != "V" else "V"
+    pairs = {zero(a) + zero(b) for t in trips for a, b in zip(t, t[1:])}
+    assert pairs == {"VV", "VZ", "ZV", "ZZ"}, f"orders of neighbouring trips: {sorted(pairs)}"
+    assert any(t[0] != "V" for t in trips) and any(t[-1] != "V" for t in trips), "a zero entry as a first and as a last trip"
+    assert set(kinds) == set("VABCD"), f"kinds {sorted(set(kinds))}"
+    valid = [k for k in range(stored) if kinds[k] == "V"]
+    seen = {}
+    for k in valid:
+        seen.setdefault(tuple(index[k]), []).append(k)
+    assert any(len({k % grid for k in ks}) >= 2 for ks in seen.values()), "one valid entry twice, in different workgroups"
+    order = [tuple(index[k]) for k in valid]
+    assert order != sorted(order), "valid entries are unsorted"
+    assert any(k >= grid and index[k][1] == 0 for k in valid) and any(k >= grid and index[k][1] == 1 for k in valid), \
+        "batch 0 (the carried state) and batch 1 (the previous batch) in a later trip"
+    first = np.asarray(row_first, np.int64)
+    assert len(first) == rows + 1
+    assert first[0] > first[1], "a row with first > last"
+    assert any(first[r] < stored < first[r + 1] for r in range(rows)), "a row slice cut by `stored`"
+    assert any(stored < first[r] < first[r + 1] for r in range(rows)), "a row slice that begins behind `stored`"
+    return kinds
+
+
+def foreign_wave(wave, nbatches, max_batches):
+    """the call's audio in a buffer laid out for all of the handle's batches, FOREIGN_FILL behind the call: a stage that read a batch
+    behind the call would encode something, not fault"""
+    wave = np.asarray(wave, np.float32)
+    out = np.full((wave.shape[0], max_batches * WAVE_BATCH), FOREIGN_FILL)
+    out[:, :nbatches * WAVE_BATCH] = wave[:, :nbatches * WAVE_BATCH]
+    return out
+
+
+def stored_blocks(count, max_blocks):
+    """what the stages make of a count and a capacity: min(count[1], max_blocks)"""
+    return min(int(count[1]), int(max_blocks))
+
+
+FOREIGN_CASES = ("20 entries", "capacity 13", "count 40")
+
+
+def foreign_case(name, rows=3, nbatches=2, max_batches=8):
+    """(index, count, row_first, max_blocks, stored) of the three shapes the foreign index is run at.  "20 entries": 20 entries under
+    the handle's full capacity of rows * max_batches.  "capacity 13": the same 20 under max_blocks 13, three trips for workgroup 0 and
+    two for the others.  "count 40": a count written by hand above the capacity, over an index buffer of exactly rows * max_batches
+    entries; min(count[1], max_blocks) of them are stored.  The properties hold over what is stored."""
+    full = rows * max_batches
+    if name == "20 entries":
+        (index, count, _), cap = foreign_index(rows, nbatches, max_batches, 20), full
+    elif name == "capacity 13":
+        (index, count, _), cap = foreign_index(rows, nbatches, max_batches, 20), 13
+    else:
+        assert name == "count 40" and full == 24
+        (index, _, _), count, cap = foreign_index(rows, nbatches, max_batches, full), np.array([40, 40], np.uint32), full
+    stored = stored_blocks(count, cap)
+    assert stored <= len(index)
+    row_first = foreign_row_first(rows, stored)
+    assert_foreign_properties(index, row_first, rows, nbatches, max_batches, stored)
+    return index, count, row_first, cap, stored
+
+
 # ---------------- audio ----------------
 
 def voice_tones(rows, nb, seed=0):

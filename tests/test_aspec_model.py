@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import aspec_model as am
+import pcm_model as pm
 from aspec_model import BINS, HZ_PER_BIN, NONE, WAVE_BATCH, aspec_model, audio, notch_model
 
 SENT = np.float32(-7.25)
@@ -109,6 +110,43 @@ def test_unsorted_repeated_and_out_of_range_entries_into_sentinel_filled_outputs
     # without the power rows and the row mean the records are the same
     rec2, none, mean2, blocks2 = pkg.aspec_plan_host(rows, wave, idx, None, want_power=False)
     assert rec2.tobytes() == want[0].tobytes() and none is None and mean2 is None and blocks2 is None
+
+
+@pytest.mark.parametrize("lo_hz,hi_hz", [(0, 0), (300, 3000)])
+@pytest.mark.parametrize("case", pm.FOREIGN_CASES)
+def test_twin_equals_model_on_the_foreign_index(pkg, case, lo_hz, hi_hz):
+    """pcm_model.foreign_index -- 20 or 24 entries for a call whose grid is 6, zero entries of every kind before, between and behind
+    valid ones, a row_first that is not a gate's -- over the thirteen builders, three rows at a time, the input laid out for the
+    handle's 8 batches: the twin through the C entry point into sentinel-filled outputs with a guard behind the capacity writes
+    exactly min(count[1], max_blocks) records and power rows, and the row means over the slices as `stored` cuts them."""
+    import ctypes as C
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    cfg = pkg.AspecCfg(lo_hz, hi_hz)
+    guard = 2
+    for group in range(am.FOREIGN_GROUPS):
+        wave, index, count, row_first, cap, stored, want = am.foreign_reference(case, group, lo_hz, hi_hz)
+        kinds = pm.foreign_kinds(index[:stored], rows, nb, mb)
+        what = f"{case}, group {group}, band {lo_hz} .. {hi_hz}"
+        # what the model says about the index, before anything is compared with it
+        assert [int(b) == NONE for b in want[0]["peak_bin"]] == [k != "V" for k in kinds], what
+        assert not want[1][[k != "V" for k in kinds]].any() and want[3].tolist() == [0, stored - 2, 0], what
+        assert want[0]["row"].tolist() == index[:stored, 0].tolist() and want[0]["batch"].tolist() == index[:stored, 1].tolist()
+        twice = [k for k in range(stored) if tuple(index[k]) == (2, 1)]
+        assert len(twice) >= 2 and all(want[0][k] == want[0][twice[0]] and want[1][k].tobytes() == want[1][twice[0]].tobytes() for k in twice)
+        as_handle = aspec_model(wave, index[[k for k in range(stored) if kinds[k] in "BD"]], None, lo_hz, hi_hz, nbatches=mb)
+        assert (as_handle[0]["peak_bin"] != NONE).all() and as_handle[1].any(axis=1).all(), "a batch behind the call holds audio: reading it would show"
+        rec = np.full(cap + guard, SENT, np.float32).repeat(8).view(pkg.ASPEC_RECORD_DTYPE)
+        power, mean, blocks = np.full((cap + guard, BINS), SENT), np.full((rows + 1, BINS), SENT), np.full(rows + 1, 0xA5A5A5A5, np.uint32)
+        sent_rec = rec[stored:].tobytes()
+        n = pm.stored_blocks(count, cap)
+        assert pkg.lib().mi_aspec_plan_host(C.byref(cfg), rows, nb, ptr(wave), wave.shape[1], ptr(index), n, ptr(row_first), ptr(rec), ptr(power), ptr(mean),
+                                            ptr(blocks)) == 0
+        same((rec[:stored], power[:stored], mean[:rows], blocks[:rows]), want, what)
+        assert rec[stored:].tobytes() == sent_rec and (power[stored:] == SENT).all() and (mean[rows] == SENT).all() and blocks[rows] == 0xA5A5A5A5, what
+        # without the power rows the records are the same; a row mean needs them
+        rec2, none, _, _ = pkg.aspec_plan_host(rows, wave, index[:stored], None, lo_hz, hi_hz, nbatches=nb, want_power=False)
+        assert rec2.tobytes() == want[0].tobytes() and none is None
 
 
 # The largest |P - P64| / max P64 of a block over every builder at 3 rows x 2 batches, P64 from numpy.fft in float64 over the same

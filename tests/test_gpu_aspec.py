@@ -3,12 +3,15 @@ host twin mi_aspec_plan_host.
 
 Every comparison is bit for bit: records, power rows, row means and row counts travel and are compared as bytes -- the FFT's graph
 and the order of every sum are part of the definition.  The index, the row starts and the counts the stage reads are the ones an
-output gate wrote on the same stream just before, with no host step between.  The destinations are filled with a sentinel before a
+output gate wrote on the same stream just before, with no host step between -- or, in run_by_hand, ones uploaded by hand that no
+gate writes: more entries than the call's grid has workgroups, entries that are not of the call, row starts that what is stored
+cuts.  The destinations are filled with a sentinel before a
 call and are longer than the capacity the stage is told; what it must not write must still hold the sentinel afterwards."""
 import numpy as np
 import pytest
 
 import aspec_model as am
+import pcm_model as pm
 from aspec_model import BINS, RECORD, WAVE_BATCH, aspec_model, audio
 from common import AGC_EXTRA, bytes_for_batches
 from gate_model import draw_flags, gate_model
@@ -194,6 +197,80 @@ def test_two_calls_on_one_handle(pkg):
     again = run_call(pkg, spec, audio("voice_whistle", rows, nb), axc, "the first call again")
     for x, y in zip(first, again):
         assert x.tobytes() == y.tobytes()
+    spec.close()
+
+
+def run_by_hand(pkg, spec, wave, index, count, row_first, stored, want, what, band=(0, 0), power=True, mean=True):
+    """One call of FOREIGN_SHAPE's nbatches with an index, row starts and counts uploaded by hand (no gate) over an input laid out
+    for the handle's max_batches, the destinations sentinel-filled with guard blocks behind the capacity: records, power rows, row
+    means and row counts on the device and as downloaded against the model `want` and the twin over the first `stored` entries."""
+    import torch
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    room = spec.max_blocks
+    assert stored == pm.stored_blocks(count, room) <= len(index) and spec.rows == rows and spec.max_batches == mb
+    twin = pkg.aspec_plan_host(rows, wave, index[:stored], row_first, *band, nbatches=nb)
+    for name, x, y in zip(("records", "power", "mean", "row counts"), want, twin):
+        assert x is None or x.tobytes() == y.tobytes(), f"{what}: the twin's {name}"
+    s = torch.cuda.current_stream().cuda_stream
+    d = Dest(rows, mb, room, power, mean)
+    d.index[:len(index)] = to_dev(index.view(np.int32))  # (what lies behind the entries holds the sentinel: of no call either)
+    d_w, d_first, d_count = to_dev(wave), to_dev(row_first.view(np.int32)), to_dev(count.view(np.int32))
+    spec.process_device(d_w.data_ptr(), mb * WAVE_BATCH, nb, d.index.data_ptr(), d_first.data_ptr() if mean else None, d_count.data_ptr(),
+                        d.records.data_ptr(), d.power.data_ptr() if power else None, d.mean.data_ptr() if mean else None,
+                        d.row_blocks.data_ptr() if mean else None, hip_stream=s)
+    records, pw, mn, blocks, cnt = spec.download(s)
+    assert (int(cnt[0]), int(cnt[1])) == (int(count[0]), stored), f"{what}: counts {cnt}"
+    raw = d.records.cpu().numpy()
+    got = raw[:stored * 32].view(RECORD)
+    assert got.tobytes() == want[0].tobytes(), f"{what}: records on the device differ at {np.flatnonzero(got != want[0])}"
+    assert (raw[stored * 32:] == SENT_BYTE).all(), f"{what}: something was written behind record {stored}"
+    assert records.tobytes() == got.tobytes(), f"{what}: the records download returns"
+    if power:
+        raw = d.power.cpu().numpy()
+        assert raw[:stored * BINS * 4].tobytes() == want[1].tobytes(), f"{what}: power rows on the device"
+        assert (raw[stored * BINS * 4:] == SENT_BYTE).all(), f"{what}: something was written behind power row {stored}"
+        assert pw.tobytes() == raw[:stored * BINS * 4].tobytes(), f"{what}: the power rows download returns"
+    else:
+        assert pw is None
+    if mean:
+        assert d.mean.cpu().numpy().tobytes() == want[2].tobytes(), f"{what}: row means on the device"
+        assert d.row_blocks.cpu().numpy().tobytes() == want[3].tobytes(), f"{what}: row counts on the device"
+        assert mn.tobytes() == want[2].tobytes() and blocks.tobytes() == want[3].tobytes(), f"{what}: the row means download returns"
+    else:
+        assert mn is None and blocks is None
+
+
+@gpu
+@pytest.mark.parametrize("lo_hz,hi_hz", [(0, 0), (300, 3000)])
+@pytest.mark.parametrize("case", pm.FOREIGN_CASES)
+def test_foreign_index_on_a_grid_shorter_than_the_count(pkg, case, lo_hz, hi_hz):
+    """pcm_model.foreign_index, uploaded by hand: 3 rows on a handle of 8 batches, a call of 2, so 6 workgroups walk 20 entries (13
+    under max_blocks 13; 24 under a count of 40), each making two to four trips over the same LDS with the window, the twiddles and
+    the sample places it loaded once, and zero entries of every kind as first, middle and last trips; a row_first that is not a
+    gate's, its slices cut by what is stored.  Every builder, three rows at a time; with a row mean, with the power rows alone and
+    with records alone."""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    cap = pm.foreign_case(case)[3]
+    spec = pkg.Aspec(rows, max_batches=mb, lo_hz=lo_hz, hi_hz=hi_hz, max_blocks=0 if cap == rows * mb else cap)
+    assert spec.max_blocks == cap
+    for group in range(am.FOREIGN_GROUPS):
+        wave, index, count, row_first, _, stored, want = am.foreign_reference(case, group, lo_hz, hi_hz)
+        assert min(rows * nb, cap) == 6 < stored and (want[0]["peak_bin"] == am.NONE).sum() == sum(k != "V" for k in pm.foreign_kinds(index[:stored], rows, nb, mb))
+        for power, mean in ((True, True), (True, False), (False, False)) if group == 0 else ((True, True),):
+            run_by_hand(pkg, spec, wave, index, count, row_first, stored, want if mean else want[:2] + (None, None),
+                        f"{case}, group {group}, power {power}, mean {mean}", (lo_hz, hi_hz), power, mean)
+    spec.close()
+
+
+@gpu
+def test_a_call_shorter_than_the_handle(pkg):
+    """the ordinary short last call: 2 batches on a handle of 8 with the full valid index of 6, grid and count the same"""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    spec = pkg.Aspec(rows, max_batches=mb)
+    index, row_first = am.full_index(rows, nb)
+    wave = am.foreign_audio(3, rows, nb, mb)
+    want = aspec_model(wave, index, row_first, nbatches=nb)
+    run_by_hand(pkg, spec, wave, index, np.array([len(index)] * 2, np.uint32), row_first, len(index), want, "short call")
     spec.close()
 
 

@@ -3,7 +3,8 @@ mi_pcm_plan_host.
 
 Every comparison is bit for bit: blocks and the state blob travel and are compared as bytes -- the order of the filter's sum, the
 rounding of the quantiser and the encoder's recurrence are part of the definition.  The index and the counts the stage reads are the
-ones an output gate wrote on the same stream just before, with no host step between.  The destination is filled with a sentinel
+ones an output gate wrote on the same stream just before, with no host step between -- or, in run_by_hand, ones uploaded by hand
+that no gate writes: more entries than the call's grid has workgroups, and entries that are not of the call.  The destination is filled with a sentinel
 before a call and is longer than the capacity the stage is told; what it must not write must still hold the sentinel afterwards."""
 import numpy as np
 import pytest
@@ -172,6 +173,69 @@ def test_padded_strides_on_a_side_stream(pkg, rate, fmt):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     run_calls(pkg, audio("voice", 5, 5), flags_for(5, 5, seed=11), (3, 2), rate, fmt, "padded, side stream", pad=3, stream=side)
+
+
+def run_by_hand(pkg, pcm, long, index, count, stored, rate, fmt, what, calls=2):
+    """`calls` consecutive calls of FOREIGN_SHAPE's nbatches on one handle over `long`, with an index and counts uploaded by hand
+    (no gate), the input laid out for the handle's max_batches with FOREIGN_FILL behind the call, the destination sentinel-filled
+    with guard blocks behind the capacity: blocks on the device and as downloaded against the model and the twin over the first
+    `stored` entries, the state blob before and after every call."""
+    import torch
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    bb, room = pm.block_bytes(rate, fmt), pcm.max_blocks
+    assert stored == pm.stored_blocks(count, room) <= len(index) and pcm.rows == rows and pcm.max_batches == mb
+    s = torch.cuda.current_stream().cuda_stream
+    d_index = torch.full((rows * mb + GUARD, 2), SENT32, dtype=torch.int32, device="cuda")  # (what lies behind the entries is of no call either)
+    d_index[:len(index)] = to_dev(index.view(np.int32))
+    d_count = to_dev(count.view(np.int32))
+    state = pcm.state().view(pm.STATE).reshape(rows)
+    for call in range(calls):
+        w = pm.foreign_wave(long[:, call * nb * WAVE_BATCH:], nb, mb)
+        want, after = pcm_model(w, index[:stored], state, rate=rate, fmt=fmt, nbatches=nb)
+        twin_blocks, twin_state = pkg.pcm_plan_host(np.ones(rows), w, index[:stored], state, rate, fmt, nbatches=nb)
+        assert twin_blocks.tobytes() == want.tobytes() and twin_state.tobytes() == after.tobytes(), f"{what}, call {call}: the twin"
+        d_w = to_dev(w)
+        d_out = torch.full(((room + GUARD) * bb,), SENT_BYTE, dtype=torch.uint8, device="cuda")
+        pcm.process_device(d_w.data_ptr(), mb * WAVE_BATCH, nb, d_index.data_ptr(), d_count.data_ptr(), d_out.data_ptr(), hip_stream=s)
+        got, cnt = pcm.download(s)
+        raw = d_out.cpu().numpy()
+        assert (int(cnt[0]), int(cnt[1])) == (int(count[0]), stored), f"{what}, call {call}: counts {cnt}"
+        assert raw[:stored * bb].tobytes() == want.tobytes(), f"{what}, call {call}: blocks on the device differ in " \
+            f"{sorted(set(np.flatnonzero(raw[:stored * bb] != want.reshape(-1)) // bb))}"
+        assert (raw[stored * bb:] == SENT_BYTE).all(), f"{what}, call {call}: something was written behind block {stored}"
+        assert got.shape == (stored, bb) and got.tobytes() == raw[:stored * bb].tobytes(), f"{what}, call {call}: what download returns"
+        assert pcm.state().tobytes() == after.tobytes(), f"{what}, call {call}: state blob after"
+        state = after
+    return state
+
+
+@gpu
+@pytest.mark.parametrize("rate,fmt", CONFIGS)
+@pytest.mark.parametrize("case", pm.FOREIGN_CASES)
+def test_foreign_index_on_a_grid_shorter_than_the_count(pkg, case, rate, fmt):
+    """pcm_model.foreign_index, uploaded by hand: 3 rows on a handle of 8 batches, a call of 2, so 6 workgroups walk 20 entries (13
+    under max_blocks 13; 24 under a count of 40), each making two to four trips over the same LDS, with zero entries of every kind
+    as first, middle and last trips.  Twice in a row on one handle: the second call's batch 0 entries, later trips among them, read
+    the first call's tails."""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    index, count, _, cap, stored = pm.foreign_case(case)
+    pcm = pkg.Pcm(np.ones(rows), max_batches=mb, rate=rate, fmt=fmt, max_blocks=0 if cap == rows * mb else cap)
+    assert pcm.max_blocks == cap and min(rows * nb, cap) == 6 < stored
+    long = audio("noise" if fmt == IMA4 else "voice", rows, 2 * nb)
+    state = run_by_hand(pkg, pcm, long, index, count, stored, rate, fmt, f"{case}, {rate} / {fmt}")
+    assert state["x"].tobytes() == long[:, -HISTORY:].tobytes()
+    pcm.close()
+
+
+@gpu
+@pytest.mark.parametrize("rate,fmt", CONFIGS)
+def test_a_call_shorter_than_the_handle(pkg, rate, fmt):
+    """the ordinary short last call: 2 batches on a handle of 8 with the full valid index of 6, grid and count the same"""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    pcm = pkg.Pcm(np.ones(rows), max_batches=mb, rate=rate, fmt=fmt)
+    index = pm.full_index(rows, nb)
+    run_by_hand(pkg, pcm, audio("voice", rows, 2 * nb), index, np.array([len(index)] * 2, np.uint32), len(index), rate, fmt, "short call")
+    pcm.close()
 
 
 @gpu

@@ -199,6 +199,151 @@ def test_timing_and_argument_errors(pkg):
     vb.close()
 
 
+CHAIN_BAND, CHAIN_WINDOW, CHAIN_TONE = (300, 3400), 3200, 12  # tone 12 of the table is 100.0 Hz; at 3200 samples it has a k of its own (20)
+CHAIN_MIX = [(0, 1.0, -0.5), (1, 0.5, 0.5)]
+# The 100.0 Hz Goertzel power of the filtered plane's windows relative to the unfiltered plane's, row 0, from the host twins
+# (mi_vband_plan_host into mi_tones_plan_host, window 3200) on the CPU oracle's audio of the capture, which opens batches 12 .. 23
+# and so completes seven windows: -43.4 dB in the window that begins with the squelch's opening -- the filter's 510 samples of history
+# reach back into the closed batch, and the step at the opening rings through the highpass -- and -84.6 to -87.6 dB in the six whose
+# history lies in open batches too.  test_chain_tone_figures_on_the_oracle holds these to 0.1 dB; the device test asserts 10 dB more.
+CHAIN_WORST_DB, CHAIN_SETTLED_DB = -43.4, (-87.6, -84.6)
+
+
+def chain_tone_ratios(calls, flags, filtered, unfiltered):
+    """[(first sample, dB, settled)] of row 0's windows that lie wholly in open batches: 10 log10 of the filtered records' power of
+    CHAIN_TONE over the unfiltered records' of the same window.  calls: batches per call; flags [rows][all batches]; filtered and
+    unfiltered: per call (records, powers, row_first_record).  settled: the 510 samples the filter carries in front of the window
+    lie in open batches as well."""
+    out, done = [], 0
+    is_open = flags[0] != ord(" ")
+    for n, (rf, pf, ff), (ru, pu, fu) in zip(calls, filtered, unfiltered):
+        assert ff[0] == fu[0] == 0 and ff[1] == fu[1] and rf["seq"].tolist() == ru["seq"].tolist() and rf["end_sample"].tolist() == ru["end_sample"].tolist()
+        for k in range(ff[1]):
+            end = (done + int(rf[k]["end_batch"])) * WAVE_BATCH + int(rf[k]["end_sample"])
+            first = end - CHAIN_WINDOW + 1
+            if first < 0 or not is_open[first // WAVE_BATCH:end // WAVE_BATCH + 1].all():
+                continue
+            settled = first >= vm.HISTORY and bool(is_open[(first - vm.HISTORY) // WAVE_BATCH])
+            assert pu[k, CHAIN_TONE] > 0
+            out.append((first, float(10 * np.log10(max(float(pf[k, CHAIN_TONE]), 1e-300) / float(pu[k, CHAIN_TONE]))), settled))
+        done += n
+    return out
+
+
+def test_chain_tone_figures_on_the_oracle(pkg):
+    """(no GPU) where CHAIN_WORST_DB and CHAIN_SETTLED_DB come from: the capture through the CPU oracle, then the two host twins"""
+    from common import oracle_run
+    from test_tones_model import E2E_BATCHES, e2e_setup
+    dev, chans, cfg, nbytes = e2e_setup(pkg)
+    n, wo, axc, _ = oracle_run(dev, chans, pkg.iqgen_host(cfg, 0, 0, nbytes // 2), E2E_BATCHES)
+    assert n == E2E_BATCHES
+    filt, _ = pkg.vband_plan_host(np.ones(len(chans)), wo, CHAIN_BAND)
+    f, u = (pkg.tones_plan_host(np.ones(len(chans)), axc, plane, None, CHAIN_WINDOW) for plane in (filt, wo))
+    ratios = chain_tone_ratios((n,), axc, [(f[0], f[1], f[2])], [(u[0], u[1], u[2])])
+    print("flags:", bytes(axc[0]).decode(), " windows (first sample, dB, settled):", [(a, round(b, 2), c) for a, b, c in ratios])
+    settled = [db for _, db, s in ratios if s]
+    assert len(ratios) == 7 and len(settled) == 6
+    assert abs(max(db for _, db, _ in ratios) - CHAIN_WORST_DB) < 0.1
+    assert abs(min(settled) - CHAIN_SETTLED_DB[0]) < 0.1 and abs(max(settled) - CHAIN_SETTLED_DB[1]) < 0.1
+
+
+@gpu
+def test_filtered_plane_into_the_splitter_the_tone_finder_and_the_mixer(pkg):
+    """The generated NFM + 100 Hz CTCSS capture in three calls of 8 batches, with no host synchronisation inside a call: demodulator ->
+    voice band stage (300, 3400) -> splitter, tone finder (window 3200) and mixer, all three on the filtered plane; a second tone
+    finder reads the unfiltered plane over the same flags.  The filtered plane is laid out two batches and four floats longer than
+    the call and the consumers are handed that out_stride as their row_stride; the padding holds a sentinel that must survive.
+    Expected values come from the host side alone, on the audio and flags the demodulator returned: mi_vband_plan_host chained into
+    mi_tx_plan_host and mi_tones_plan_host, and the oracle's ao_mixer_run with mixer_model.numpy_mixer; records, powers, left /
+    right / flags and the three state blobs are compared as bytes.
+
+    One physical assertion, on the row with the tone: the 100.0 Hz Goertzel power of the filtered plane's windows relative to the
+    unfiltered plane's.  The host twins on the CPU oracle's audio of this capture (test_chain_tone_figures_on_the_oracle) give -43.4
+    dB for the window that begins with the squelch's opening and -84.6 to -87.6 dB for the six windows whose filter history lies in
+    open batches too; asserted here are those worst values plus 10 dB -- the Goertzel window leaks voice-band energy into the bin,
+    and the device's audio is not the oracle's to the bit -- over at least 4 windows.  The vote on the filtered plane is printed, not
+    asserted: it is relative among the 51 tones, and a highpass that lowers them alike may leave it unchanged."""
+    import torch
+    import libs
+    from mixer_model import numpy_mixer
+    from test_gpu_mixer import Dest as MixDest
+    from test_gpu_tones import Dest as TonesDest, check as tones_check, tones_call
+    from test_gpu_txsplit import Dest as TxDest, check as tx_check, tx_call
+    from test_tones_model import e2e_setup
+    calls = (8, 8, 8)
+    dev, chans, cfg, nbytes = e2e_setup(pkg)
+    rows = len(chans)
+    ones = np.ones(rows, np.uint8)
+    s = torch.cuda.current_stream().cuda_stream
+    d_iq = torch.zeros((1, nbytes), dtype=torch.uint8, device="cuda")
+    pkg.iqgen_device(cfg, 0, 1, nbytes, 0, nbytes // 2, d_iq.data_ptr(), s)
+    d = pkg.Demod(dev, chans, nstreams=1, max_batches=max(calls))
+    vb = pkg.Vband(ones, CHAIN_BAND, max_batches=max(calls))
+    tx = pkg.TxSplit(ones, max_batches=max(calls))
+    tn = [pkg.Tones(ones, max_batches=max(calls), window=CHAIN_WINDOW) for _ in range(2)]  # the filtered plane, the unfiltered plane
+    mixer = pkg.Mixer(CHAIN_MIX)
+    assert mixer.stereo
+    outs, done = [], 0
+    for n in calls:
+        stride, out_stride = n * WAVE_BATCH, (n + 2) * WAVE_BATCH + 4
+        wo = torch.zeros((rows, stride), dtype=torch.float32, device="cuda")
+        ax = torch.zeros((rows, n), dtype=torch.uint8, device="cuda")
+        filt = torch.full((rows, out_stride), float(SENT), dtype=torch.float32, device="cuda")
+        tx_dest = TxDest(rows, rows * (n + 1))
+        tn_dest = [TonesDest(rows, rows * pkg.tones_max_windows(CHAIN_WINDOW, n)) for _ in tn]
+        mix_dest = MixDest(n)
+        pos = 0 if done == 0 else (done * WAVE_BATCH + AGC_EXTRA) * d.hop_bytes
+        d.process_device(d_iq.data_ptr() + pos, nbytes, n, wo.data_ptr(), ax.data_ptr(), hip_stream=s)
+        vb.process_device(wo.data_ptr(), stride, n, filt.data_ptr(), out_stride, hip_stream=s)
+        tx.process_device(filt.data_ptr(), out_stride, ax.data_ptr(), n, n, tx_dest.records.data_ptr(), tx_dest.row_first.data_ptr(), tx_dest.count.data_ptr(),
+                          hip_stream=s)
+        for t, plane, row_stride, dest in zip(tn, (filt, wo), (out_stride, stride), tn_dest):
+            t.process_device(plane.data_ptr(), row_stride, ax.data_ptr(), n, n, dest.records.data_ptr(), dest.row_first.data_ptr(), dest.count.data_ptr(),
+                             d_powers=dest.powers.data_ptr(), hip_stream=s)
+        mixer.process_device(filt.data_ptr(), out_stride, ax.data_ptr(), n, n, mix_dest.left.data_ptr(), mix_dest.right.data_ptr(), mix_dest.out.data_ptr(),
+                             hip_stream=s)
+        got_tx = tx.download(s)  # (the first wait of the call)
+        got_tn = [t.download(s) for t in tn]
+        outs.append((n, wo.cpu().numpy(), ax.cpu().numpy(), filt.cpu().numpy(), got_tx, tx_dest, got_tn, tn_dest, mix_dest))
+        done += n
+    states = vb.state(), tx.state(), tn[0].state(), tn[1].state()
+    for h in [d, vb, tx, mixer] + tn:
+        h.close()
+    flags = np.concatenate([o[2] for o in outs], axis=1)
+    print("flags per row:", [bytes(f).decode() for f in flags])
+    vb_state = tx_state = None
+    tn_state = [None, None]
+    for i, (n, wo, ax, filt, got_tx, tx_dest, got_tn, tn_dest, mix_dest) in enumerate(outs):
+        blank = np.full(filt.shape, SENT)
+        want, vb_state = pkg.vband_plan_host(ones, wo, CHAIN_BAND, vb_state, nbatches=n, out=blank)
+        assert (want[:, n * WAVE_BATCH:] == SENT).all()
+        assert filt.tobytes() == want.tobytes(), f"call {i}: the filtered plane, or the sentinel behind it"
+        want_rec, want_first, _, tx_state = pkg.tx_plan_host(ones, ax, tx_state, want, nbatches=n)
+        tx_check(f"call {i}: the splitter", got_tx, tx_dest, rows, want_rec, want_first)
+        assert (want_rec["energy"][want_rec["nblocks"] > 0] > 0).all()
+        for j, (plane, what) in enumerate(((want, "filtered"), (wo, "unfiltered"))):
+            rec, pw, first, _, tn_state[j] = pkg.tones_plan_host(ones, ax, plane, tn_state[j], CHAIN_WINDOW, nbatches=n)
+            tones_check(f"call {i}: the tone finder on the {what} plane", got_tn[j], tn_dest[j], rows, rec, pw, first)
+        left, right, out = libs.oracle_mixer(CHAIN_MIX, want, ax, n)
+        model = numpy_mixer(CHAIN_MIX, want, ax, n)
+        assert left.tobytes() == model[0].tobytes() and right.tobytes() == model[1].tobytes() and out.tobytes() == model[2].tobytes()
+        torch.cuda.synchronize()
+        mix_dest.check(f"call {i}: the mixer", left.tobytes(), right.tobytes(), out.tobytes())
+        if (ax != ord(" ")).any():
+            assert np.abs(left).max() > 0
+    assert states[0].tobytes() == vb_state.tobytes() and states[1].tobytes() == tx_state.tobytes()
+    assert states[2].tobytes() == tn_state[0].tobytes() and states[3].tobytes() == tn_state[1].tobytes()
+    ratios = chain_tone_ratios(calls, flags, *[[(o[6][j][0], o[6][j][1], o[6][j][2]) for o in outs] for j in range(2)])
+    print("row 0, 100.0 Hz, filtered over unfiltered (first sample, dB, settled):", [(a, round(b, 2), c) for a, b, c in ratios])
+    settled = [db for _, db, ok in ratios if ok]
+    assert len(ratios) >= 4 and len(settled) >= 4, "the capture should open the row with the tone for half of its batches"
+    assert max(db for _, db, _ in ratios) <= CHAIN_WORST_DB + 10.0
+    assert max(settled) <= CHAIN_SETTLED_DB[1] + 10.0
+    for j, what in enumerate(("filtered", "unfiltered")):
+        v = pkg.tones_vote_host(np.concatenate([o[6][j][0][o[6][j][2][0]:o[6][j][2][1]] for o in outs]))
+        print(f"vote on the {what} plane, row 0: found {v.found} tone {v.tone} ({v.freq_hz} Hz), {v.votes} of {v.windows} windows")
+
+
 @gpu
 def test_chain_behind_the_demodulator(pkg):
     """The generated NFM + 100 Hz CTCSS capture of the tone finder's tests in three calls of 8 batches, with no host synchronisation

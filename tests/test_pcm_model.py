@@ -178,6 +178,75 @@ def test_capped_nblocks_leaves_the_rest_alone(pkg, rate, fmt):
     assert none.shape == (0, bb) and model_state.tobytes() == after.tobytes()
 
 
+# ---------------- a foreign index: entries no gate writes, more of them than the call's grid ----------------
+
+GUARD = 2  # blocks behind the capacity that must keep the sentinel
+
+
+def test_foreign_index_is_what_it_is_built_for():
+    """the properties on the index alone, at the shape the builder is drawn for and at each of the three cases; the three row
+    slices; and that the zero entries of kinds B and D point at audio: with the input laid out for the handle's batches, a stage
+    that took them for entries of the call would encode FOREIGN_FILL, not fault and not write zeros"""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    index, count, row_first = pm.foreign_index(rows, nb, mb)
+    assert index.shape == (20, 2) and index.dtype == np.uint32 and count.tolist() == [20, 20] and row_first.tolist() == [5, 2, 21, 22]
+    kinds = pm.assert_foreign_properties(index, row_first, rows, nb, mb, 20, grid=rows * nb)
+    assert kinds == "VCVVBV" "ABVDVC" "VVDAVV" "DV"
+    for name in pm.FOREIGN_CASES:
+        index, count, row_first, cap, stored = pm.foreign_case(name)
+        assert (len(index), count.tolist(), cap, stored) == {"20 entries": (20, [20, 20], 24, 20), "capacity 13": (20, [20, 20], 13, 13),
+                                                            "count 40": (24, [40, 40], 24, 24)}[name]
+        # entries k, k + 6, k + 12, k + 18 of a grid of 6 go to one workgroup: workgroup 0 makes the most trips
+        assert [len(range(g, stored, 6)) for g in range(6)] == {20: [4, 4, 3, 3, 3, 3], 13: [3, 2, 2, 2, 2, 2], 24: [4] * 6}[stored]
+    wave = pm.foreign_wave(audio("noise", rows, nb), nb, mb)
+    assert wave.shape == (rows, mb * WAVE_BATCH) and (wave[:, nb * WAVE_BATCH:] == pm.FOREIGN_FILL).all()
+    index = pm.foreign_index(rows, nb, mb, 24)[0]
+    kinds = pm.foreign_kinds(index, rows, nb, mb)
+    for rate, fmt in CONFIGS:
+        as_call, _ = pcm_model(wave, index, rate=rate, fmt=fmt, nbatches=nb)
+        as_handle, _ = pcm_model(wave, index, rate=rate, fmt=fmt, nbatches=mb)
+        for k, kind in enumerate(kinds):
+            assert as_call[k].any() == (kind == "V"), (k, kind)
+            assert as_handle[k].any() == (kind in "VBD"), (k, kind)
+
+
+@pytest.mark.parametrize("rate,fmt", CONFIGS)
+@pytest.mark.parametrize("case", pm.FOREIGN_CASES)
+def test_twin_equals_model_on_the_foreign_index(pkg, case, rate, fmt):
+    """Two calls of 2 batches over buffers laid out for 8, fresh and then from the first call's tails, through the C entry point into
+    a sentinel-filled destination with a guard behind the capacity: exactly min(count[1], max_blocks) blocks are written, the zero
+    entries are zero blocks, the entry that occurs twice has the same bytes twice, and batch 0 entries read the carried samples."""
+    rows, nb, mb = pm.FOREIGN_SHAPE
+    index, count, _, cap, stored = pm.foreign_case(case)
+    kinds = pm.foreign_kinds(index[:stored], rows, nb, mb)
+    bb = pm.block_bytes(rate, fmt)
+    en, cfg = np.ones(rows, np.uint8), pkg.PcmCfg(rate, fmt)
+    for name in ("voice", "noise"):
+        long = audio(name, rows, 2 * nb)
+        state = pm.fresh_state(rows)
+        for call in range(2):
+            wave = pm.foreign_wave(long[:, call * nb * WAVE_BATCH:], nb, mb)
+            want, after = pcm_model(wave, index[:stored], state, rate=rate, fmt=fmt, nbatches=nb)
+            out = np.full((cap + GUARD) * bb, SENT, np.uint8)
+            blob = np.concatenate([state.view(np.uint8).reshape(-1), np.full(16, SENT, np.uint8)])
+            n = pm.stored_blocks(count, cap)
+            assert pkg.lib().mi_pcm_plan_host(C.byref(cfg), ptr(en), rows, nb, ptr(wave), wave.shape[1], ptr(index), n, ptr(blob), ptr(out)) == 0
+            what = f"{case}, {name}, call {call}"
+            assert out[:stored * bb].tobytes() == want.tobytes(), f"{what}: blocks"
+            assert (out[stored * bb:] == SENT).all(), f"{what}: something was written behind block {stored}"
+            assert blob[:rows * 248].tobytes() == after.tobytes() and (blob[rows * 248:] == SENT).all(), f"{what}: state"
+            got = out[:stored * bb].reshape(stored, bb)
+            assert [bool(b.any()) for b in got] == [k == "V" for k in kinds], what
+            twice = [k for k in range(stored) if tuple(index[k]) == (2, 1)]
+            assert len(twice) >= 2 and all(got[k].tobytes() == got[twice[0]].tobytes() for k in twice)
+            if call and rate == 8000:  # the carried samples are in the bytes: the same entries from a fresh state differ at batch 0 alone
+                fresh, _ = pcm_model(wave, index[:stored], None, rate=rate, fmt=fmt, nbatches=nb)
+                differ = [k for k in range(stored) if fresh[k].tobytes() != want[k].tobytes()]
+                assert differ == [k for k in range(stored) if kinds[k] == "V" and index[k][1] == 0] and any(k >= rows * nb for k in differ)
+            state = after
+        assert state["x"].tobytes() == long[:, -HISTORY:].tobytes()
+
+
 # ---------------- the IMA encoder ----------------
 
 def ima_blocks(pkg, name, rate, rows=2, nb=2):
