@@ -162,6 +162,15 @@ VBAND_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in VbandRow._fields_])  # 
 VBAND_STATE_DTYPE = np.dtype([("x", "<f4", (VBAND_HISTORY,))])  # one row of the voice band stage's state blob, MI_VBAND_STATE_ROW_BYTES = 2040
 
 
+class LimitRow(C.Structure):  # mi_limit_row
+    _fields_ = [("pregain", C.c_float), ("ceiling", C.c_float)]
+
+
+LIMIT_LOOKAHEAD, LIMIT_WINDOW, LIMIT_HISTORY = 63, 1024, 1086  # MI_LIMIT_*
+LIMIT_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in LimitRow._fields_])  # the same 8 bytes as a numpy record
+LIMIT_STATE_DTYPE = np.dtype([("x", "<f4", (LIMIT_HISTORY,))])  # one row of the limiter stage's state blob, MI_LIMIT_STATE_ROW_BYTES = 4344
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -243,6 +252,8 @@ ABI_SYMBOLS = [
     "mi_aspec_window", "mi_aspec_band", "mi_aspec_plan_host", "mi_aspec_notch_host",
     "mi_vband_default_row", "mi_vband_create", "mi_vband_destroy", "mi_vband_set_rows", "mi_vband_process_device", "mi_vband_state_size",
     "mi_vband_get_state", "mi_vband_set_state", "mi_vband_set_timing", "mi_vband_last_launch_ms", "mi_vband_taps", "mi_vband_plan_host",
+    "mi_limit_default_row", "mi_limit_create", "mi_limit_destroy", "mi_limit_set_rows", "mi_limit_process_device", "mi_limit_state_size",
+    "mi_limit_get_state", "mi_limit_set_state", "mi_limit_set_timing", "mi_limit_last_launch_ms", "mi_limit_plan_host", "mi_limit_pregain_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -384,6 +395,21 @@ def lib():
         L.mi_vband_last_launch_ms.argtypes = [vp, vp]
         L.mi_vband_taps.argtypes = [C.c_uint32, C.c_uint32, vp]
         L.mi_vband_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
+        L.mi_limit_default_row.argtypes = []
+        L.mi_limit_default_row.restype = LimitRow
+        L.mi_limit_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mi_limit_destroy.argtypes = [vp]
+        L.mi_limit_destroy.restype = None
+        L.mi_limit_set_rows.argtypes = [vp, vp, vp]
+        L.mi_limit_process_device.argtypes = [vp, vp, sz, C.c_int, vp, sz, vp]
+        L.mi_limit_state_size.argtypes = [vp]
+        L.mi_limit_state_size.restype = sz
+        L.mi_limit_get_state.argtypes = [vp, vp, sz]
+        L.mi_limit_set_state.argtypes = [vp, vp, sz]
+        L.mi_limit_set_timing.argtypes = [vp, C.c_int]
+        L.mi_limit_last_launch_ms.argtypes = [vp, vp]
+        L.mi_limit_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
+        L.mi_limit_pregain_host.argtypes = [vp, sz, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
         L.mi_aspec_create.argtypes = [C.POINTER(AspecCfg), C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
         L.mi_aspec_destroy.argtypes = [vp]
         L.mi_aspec_destroy.restype = None
@@ -504,7 +530,7 @@ class _PostStage(_Handle):
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
-        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -515,7 +541,7 @@ class _PostStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy"""
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
         return tuple(ms)
@@ -1258,6 +1284,89 @@ def vband_taps(hp_hz, lp_hz):
     h = np.zeros(VBAND_TAPS, np.float32)
     _check(lib().mi_vband_taps(int(hp_hz), int(lp_hz), _ptr(h)))
     return h
+
+
+def limit_default_row():
+    """mi_limit_default_row: (1.0, 0.89125094): no gain in front, a ceiling of -1 dBFS"""
+    r = lib().mi_limit_default_row()
+    return r.pregain, r.ceiling
+
+
+def _limit_rows(rows_cfg, rows):
+    """None (the default row everywhere), one (pregain, ceiling) pair for every row, or a pair per row -> [rows] of LIMIT_ROW_DTYPE"""
+    if rows_cfg is None:
+        rows_cfg = limit_default_row()
+    a = np.asarray(rows_cfg)
+    if a.dtype != LIMIT_ROW_DTYPE:
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(rows_cfg, np.float32).reshape(-1, 2), (rows, 2))).view(LIMIT_ROW_DTYPE).reshape(-1)
+    a = np.ascontiguousarray(a)
+    assert a.shape == (rows,)
+    return a
+
+
+class Limit(_PostStage):
+    """mi_limit: the peak limiter stage -- a look-ahead gain per row that keeps a plane of audio (the demodulator's, the voice band
+    stage's, a mixer's sum) inside a ceiling without clipping it, written as a plane of the same layout (delayed by 63 samples) that
+    the gate, the splitter, the PCM stage and the mixer take in its place.  row_enabled: truth value per row (a disabled row's output
+    is not written and its carried samples stay); rows_cfg: (pregain, ceiling) for every row or one pair per row, None = the defaults
+    1.0 / 0.89125094.  Rows are independent: no stereo link.  state() gives rows * 4344 bytes, .view(LIMIT_STATE_DTYPE): the 1086
+    input samples a row carries into its next call."""
+    _destroy, _prefix, _launches = "mi_limit_destroy", "mi_limit", 2
+
+    def __init__(self, row_enabled, rows_cfg=None, max_batches=1, gpu=0):
+        en = _flags(row_enabled)
+        self.rows, self.max_batches = en.size, max_batches
+        cfg = _limit_rows(rows_cfg, self.rows)
+        self._h = C.c_void_p()
+        _check(lib().mi_limit_create(_ptr(cfg), _ptr(en), self.rows, max_batches, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled=None, rows_cfg=None):
+        """other rows and / or other settings from the next call on (None = keep); the carried samples stay, and count under the new
+        pregain"""
+        en = None if row_enabled is None else _flags(row_enabled)
+        cfg = None if rows_cfg is None else _limit_rows(rows_cfg, self.rows)
+        assert en is None or en.size == self.rows
+        _check(lib().mi_limit_set_rows(self._h, None if cfg is None else _ptr(cfg), None if en is None else _ptr(en)))
+
+    def process_device(self, d_in, row_stride, nbatches, d_out, out_stride, hip_stream=None):
+        """Raw device pointers (ints), the strides in floats; d_out [rows][out_stride] must not overlap d_in; asynchronous on
+        hip_stream."""
+        _check(lib().mi_limit_process_device(self._h, d_in, row_stride, nbatches, d_out, out_stride, hip_stream))
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        self._call("set_state", _ptr(buf), buf.size)
+
+
+def limit_plan_host(row_enabled, plane, rows_cfg=None, state=None, nbatches=None, out=None):
+    """mi_limit_plan_host: the limiter stage's plane from audio on the host, no GPU.  plane: float32 [rows][row_stride]; rows_cfg as
+    for Limit; state: the blob (rows * 4344 bytes) or None (a fresh one); nbatches: batches of the call, default row_stride //
+    WAVE_BATCH; out: float32 [rows][out_stride] to write into (a disabled row's floats stay), default zeros [rows][nbatches *
+    WAVE_BATCH].  Returns (out, state after the call)."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows, row_stride = plane.shape
+    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
+    cfg = _limit_rows(rows_cfg, rows)
+    state = np.zeros(rows * LIMIT_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * LIMIT_STATE_DTYPE.itemsize
+    out = np.zeros((rows, nb * WAVE_BATCH), np.float32) if out is None else out
+    assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == rows and out.flags.c_contiguous
+    _check(lib().mi_limit_plan_host(_ptr(cfg), _ptr(en), rows, nb, _ptr(plane), row_stride, _ptr(state), _ptr(out), out.shape[1]))
+    return out, state
+
+
+def limit_pregain_host(records, row, ceiling=None, percentile=0):
+    """mi_limit_pregain_host: a pregain for `row` from the splitter's records (TX_RECORD_DTYPE): the ceiling (None = the default row's)
+    over the peak at `percentile` (1 .. 100, 0 = 90) of the row's records with blocks, clamped into [2^-10, 2^10]; 1.0 without such
+    records.  Returns (pregain, used).  Tried on synthetic signals only."""
+    records = np.ascontiguousarray(records, dtype=TX_RECORD_DTYPE).reshape(-1)
+    ceiling = limit_default_row()[1] if ceiling is None else ceiling
+    pregain, used = C.c_float(0.0), C.c_uint32(0)
+    _check(lib().mi_limit_pregain_host(_ptr(records) if records.size else None, records.size, int(row), float(ceiling), int(percentile), C.byref(pregain),
+                                       C.byref(used)))
+    return np.float32(pregain.value), used.value
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -188,6 +188,20 @@ int vband_row_ok(const mi_vband_row& r);
 void vband_taps(const mi_vband_row& r, float* h);
 int vband_classes(const mi_vband_row* row_cfg, size_t rows, std::vector<uint32_t>& class_of, std::vector<mi_vband_row>& classes);
 bool vband_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches);
+
+// The peak limiter stage (include/mi_airband.h "peak limiter stage").  One row of its state: the checkpoint blob is an array of
+// these, and limit.hip keeps the same array in device memory.
+struct LimitRowState {
+    float x[MI_LIMIT_HISTORY];  // the last 1086 input samples of the row's last batch, oldest first
+};
+static_assert(sizeof(LimitRowState) == MI_LIMIT_STATE_ROW_BYTES && MI_LIMIT_HISTORY == MI_LIMIT_LOOKAHEAD + MI_LIMIT_WINDOW - 1 &&
+                  (MI_LIMIT_WINDOW & (MI_LIMIT_WINDOW - 1)) == 0 && MI_LIMIT_LOOKAHEAD + 1 == 64 && sizeof(mi_limit_row) == 8 &&
+                  MI_LIMIT_STATE_ROW_BYTES % 8 == 0 && MI_LIMIT_HISTORY <= kWaveBatch,
+              "the limiter stage's blob and settings layouts are ABI");
+// limit_row_ok: MI_OK, or the settings' refusal with its message set.  limit_rows: the rows' settings (NULL = the default row
+// everywhere) checked, or the first refusal.  (poststage_host.cpp)
+int limit_row_ok(const mi_limit_row& r);
+int limit_rows(const mi_limit_row* row_cfg, size_t rows, std::vector<mi_limit_row>& out);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

@@ -4,7 +4,8 @@
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
 // (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; the PCM
 // stage's twin mi_pcm_plan_host with its taps and WAV headers; the audio spectrum stage's twin mi_aspec_plan_host with its window,
-// band and the notch vote; and the voice band stage's twin mi_vband_plan_host with its settings, taps and classes.
+// band and the notch vote; the voice band stage's twin mi_vband_plan_host with its settings, taps and classes; and the peak limiter
+// stage's twin mi_limit_plan_host with its settings and the pregain helper.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1140,5 +1141,112 @@ extern "C" int mi_vband_plan_host(const mi_vband_row* row_cfg, const uint8_t* ro
         }
         std::memcpy(state[r].x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_VBAND_HISTORY, MI_VBAND_HISTORY * sizeof(float));
     }
+    return MI_OK;
+}
+
+// ---- peak limiter stage, host side (include/mi_airband.h "peak limiter stage"): the settings' check, the twin of limit.hip -- a row's
+// whole call at once, the window maximum by ten doublings, the 64 gains of an output added one array at a time -- and the pregain
+// helper.
+namespace mi {
+
+int limit_row_ok(const mi_limit_row& r) {
+    if (!std::isfinite(r.pregain) || r.pregain < 0.0009765625f || r.pregain > 1024.0f)
+        return fail(MI_ERR_INVALID, "limiter stage: pregain must be finite and within 2^-10 .. 2^10");
+    if (!std::isfinite(r.ceiling) || r.ceiling < 0.0625f || r.ceiling > 1.0f)
+        return fail(MI_ERR_INVALID, "limiter stage: ceiling must be finite and within 0.0625 .. 1");
+    return MI_OK;
+}
+
+int limit_rows(const mi_limit_row* row_cfg, size_t rows, std::vector<mi_limit_row>& out) {
+    out.assign(rows, mi_limit_default_row());
+    for (size_t r = 0; r < rows; ++r) {
+        if (row_cfg)
+            out[r] = row_cfg[r];
+        if (const int rc = limit_row_ok(out[r]))
+            return rc;
+    }
+    return MI_OK;
+}
+
+}  // namespace mi
+
+extern "C" mi_limit_row mi_limit_default_row(void) {
+    return mi_limit_row{1.0f, 0.89125094f};
+}
+
+extern "C" int mi_limit_plan_host(const mi_limit_row* row_cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* in, size_t row_stride,
+                                  void* state_inout, float* out, size_t out_stride) {
+    if (!row_enabled || !in || !state_inout || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1)
+        return fail(MI_ERR_INVALID, "limit plan needs rows >= 1 and nbatches >= 1");
+    std::vector<mi_limit_row> cfg;
+    if (const int rc = mi::limit_rows(row_cfg, static_cast<size_t>(rows), cfg))
+        return rc;
+    const size_t n = static_cast<size_t>(nbatches) * mi::kWaveBatch;
+    if (row_stride < n || out_stride < n)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    if (mi::vband_overlap(in, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
+        return fail(MI_ERR_INVALID, "the output overlaps the input plane");
+    mi::LimitRowState* state = static_cast<mi::LimitRowState*>(state_inout);
+    const size_t hist = MI_LIMIT_HISTORY, look = MI_LIMIT_LOOKAHEAD;
+    std::vector<float> u(hist + n), p(hist + n), s(n);
+    for (int r = 0; r < rows; ++r) {
+        if (!row_enabled[r])
+            continue;
+        const float pregain = cfg[r].pregain, ceiling = cfg[r].ceiling;
+        const float* const row = in + static_cast<size_t>(r) * row_stride;
+        // u[1086 + i] = sample i of the call times the pregain, u[0 .. 1085] = the carried samples times it
+        for (size_t i = 0; i < hist; ++i)
+            u[i] = state[r].x[i] * pregain;
+        for (size_t i = 0; i < n; ++i)
+            u[hist + i] = row[i] * pregain;
+        // p[i] = max of |u| over the w values that end at i, w = 1, 2, 4, .. 1024 (fewer where the array begins: no output reads those)
+        for (size_t i = 0; i < hist + n; ++i)
+            p[i] = std::fabs(u[i]);
+        for (size_t w = 1; w < MI_LIMIT_WINDOW; w *= 2)
+            for (size_t i = hist + n - 1; i >= w; --i)  // (downwards: p[i - w] is still the narrower window's)
+                p[i] = std::max(p[i], p[i - w]);
+        // the gain of window maximum p[i], in p's place
+        for (size_t i = 0; i < hist + n; ++i)
+            p[i] = p[i] > ceiling ? ceiling / p[i] : 1.0f;
+        // output i adds the gains of samples i - 63 .. i, which are p[1023 + i] .. p[1086 + i], in that order
+        std::fill(s.begin(), s.end(), 0.0f);
+        for (size_t k = 0; k <= look; ++k) {
+            const float* const rk = p.data() + (hist - look) + k;
+            for (size_t i = 0; i < n; ++i)
+                s[i] = s[i] + rk[i];
+        }
+        float* const dst = out + static_cast<size_t>(r) * out_stride;
+        for (size_t i = 0; i < n; ++i) {
+            const float g = s[i] * 0.015625f;
+            const float y = u[hist - look + i] * g;
+            dst[i] = std::fmin(std::fmax(y, -ceiling), ceiling);
+        }
+        std::memcpy(state[r].x, row + n - hist, hist * sizeof(float));
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_limit_pregain_host(const mi_tx_record* records, size_t n, uint32_t row, float ceiling, uint32_t percentile, float* pregain, uint32_t* used) {
+    if (!pregain || !used || (!records && n))
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!std::isfinite(ceiling) || ceiling < 0.0625f || ceiling > 1.0f)
+        return fail(MI_ERR_INVALID, "limiter pregain: ceiling must be finite and within 0.0625 .. 1");
+    if (percentile > 100)
+        return fail(MI_ERR_INVALID, "limiter pregain: percentile must be 1 .. 100, or 0 for 90");
+    if (percentile == 0)
+        percentile = 90;
+    std::vector<float> peaks;
+    for (size_t i = 0; i < n; ++i)
+        if (records[i].row == row && records[i].nblocks > 0 && records[i].peak > 0.0f)
+            peaks.push_back(records[i].peak);
+    *used = static_cast<uint32_t>(peaks.size());
+    *pregain = 1.0f;
+    if (peaks.empty())
+        return MI_OK;
+    std::sort(peaks.begin(), peaks.end());
+    const float peak = peaks[static_cast<size_t>((static_cast<uint64_t>(peaks.size()) - 1) * percentile / 100)];
+    *pregain = std::fmin(std::fmax(ceiling / peak, 0.0009765625f), 1024.0f);
     return MI_OK;
 }

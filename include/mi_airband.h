@@ -1111,6 +1111,96 @@ int mi_vband_taps(uint32_t hp_hz, uint32_t lp_hz, float* out /* [MI_VBAND_TAPS] 
 int mi_vband_plan_host(const mi_vband_row* row_cfg /* [rows], NULL = defaults */, const uint8_t* row_enabled, int rows, int nbatches,
                        const float* waveout, size_t row_stride, void* state_inout, float* out, size_t out_stride);
 
+/* ---------------- peak limiter stage: look-ahead gain per row, on the device ----------------
+ * Nothing else behind the demodulator bounds the level of the audio without clipping it: mi_mixer_process_device adds its open inputs
+ * and does not clamp (the reference leaves that to LAME), a channel's ampfactor (config.cpp:623) is multiplied in just before the
+ * demodulator's hard clamp, mi_vband_* ends in a clamp, and the PCM stage's int16 quantiser saturates.  This stage keeps peaks inside
+ * a ceiling by turning the gain down ahead of them.  A post-stage like the voice band stage: it reads a plane [rows][row_stride] of
+ * float32 audio -- what mi_demod_process_device, mi_vband_process_device or mi_mixer_process_device wrote; a mixer's d_left is a plane
+ * of one row -- and writes a plane d_out [rows][out_stride] of the same layout, which the gate, the splitter, the PCM stage and the
+ * mixer take in its place.  Every batch of every enabled row is handled: there is no index and no download entry.
+ *
+ * Stream model.  As for the voice band stage: a row's audio is one running sequence x over all batches of all calls the row was
+ * enabled in; samples before the handle's first call are 0.
+ * Constants.  The look-ahead and delay D = MI_LIMIT_LOOKAHEAD = 63 samples (3.9 ms).  The peak window W = MI_LIMIT_WINDOW = 1024
+ * samples: 63 ahead of the sample being scaled, that sample, and 960 behind it (a hold of 60 ms).  The gain is the mean of D + 1 = 64
+ * values, a power of two, so the division is exact.  The history is D + W - 1 = MI_LIMIT_HISTORY = 1086 samples.
+ * Row settings.  mi_limit_row { pregain, ceiling } per row.  Settings are refused unless both are finite, 2^-10 <= pregain <= 2^10
+ * and 0.0625f <= ceiling <= 1.0f -- those of a disabled row too.  mi_limit_default_row gives { 1.0f, 0.89125094f } (-1 dBFS).
+ * Output.  Sample n of the row's sequence, everything float32, every operation rounded on its own, no fused multiply-add:
+ *   u[n] = x[n] * pregain
+ *   a[n] = fabsf(u[n])
+ *   p[n] = max over k = 0 .. 1023 of a[n - k]                      (order-free)
+ *   r[n] = p[n] > ceiling ? ceiling / p[n] : 1.0f                  (the correctly rounded IEEE division)
+ *   s[n] = ((0.0f + r[n - 63]) + r[n - 62]) + ... + r[n]           (m ascending)
+ *   g[n] = s[n] * 0.015625f                                        (exact)
+ *   y[n] = u[n - 63] * g[n]
+ *   out[n] = fminf(fmaxf(y[n], -ceiling), ceiling)
+ * Indices below the call's first sample reach into the 1086 input samples x the handle carries for the row -- x, not u: after
+ * mi_limit_set_rows the carried samples count under the new pregain.  NaN and Inf are unspecified, as everywhere behind the
+ * demodulator.  Inputs beyond +-1, such as a mixer's sum, are what the stage is for and are fully specified.
+ * What follows from the definition:
+ *   1. Ceiling.  Each r[m] with m in [n - 63, n] has u[n - 63] inside its window, so in exact arithmetic g[n] * |u[n - 63]| <= ceiling.
+ *      The float32 chain adds at most about 70 relative roundings of 2^-24 (one division, 63 additions, one product): |y| exceeds the
+ *      ceiling by a few parts in 10^6 at most, and the final clamp moves such a value by a few float32 steps.  |out| <= ceiling holds
+ *      exactly.
+ *   2. Transparency.  Where no a[] within a sample's reach exceeds the ceiling, every r is 1.0f, s exactly 64.0f and g exactly 1.0f:
+ *      out[n] is u[n - 63] bit for bit, signed zeros and subnormal values included.  The device writes a block whose 3086 staged
+ *      values a[] have a maximum that is not over the ceiling without the sliding maximum, the division and the sum.  No byte depends
+ *      on which path ran.
+ *   3. A lone peak at index q of a row that is otherwise under the ceiling.  The gain leaves 1.0f first for the output that carries
+ *      input sample q - 63; it is lowest, <= ceiling / a[q] apart from the rounding of item 1, for input samples q .. q + 960; it is
+ *      exactly 1.0f again from input sample q + 1024 on.
+ *   4. Steady signal.  A steady tone or square wave over the ceiling gives a constant p from sample 1023 of its steady part, hence
+ *      constant r and g: the output is the input times one number, without distortion.
+ * Delay.  Output sample n carries input sample n - 63.  Behind mi_vband_* the two delays add to 318 samples; a caller keeps a
+ * transmission's tail with the gate's open trail (MI_GATE_OPEN_TRAIL), as for the voice band stage.
+ * Rows are independent: there is no stereo link between a mixer's left and right row, so a peak on one side leaves the other side's
+ * gain alone and the image may shift for the length of the hold.  A linked mode is not part of this stage.
+ * State: per row the last 1086 input samples of the last batch of the last call the row was enabled in, zeros at first; the blob is
+ * rows * MI_LIMIT_STATE_ROW_BYTES bytes of little-endian float32, oldest sample first.  A disabled row's output row is not written
+ * and its carried samples keep their bytes.
+ * The defaults (ceiling, look-ahead, window) and mi_limit_pregain_host were tried on synthetic signals only.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned or overlapping
+ * buffers, nbatches outside 1 .. max_batches. */
+enum { MI_LIMIT_LOOKAHEAD = 63, MI_LIMIT_WINDOW = 1024, MI_LIMIT_HISTORY = 1086, MI_LIMIT_STATE_ROW_BYTES = 4344 };
+typedef struct { float pregain; float ceiling; } mi_limit_row;
+typedef struct mi_limit mi_limit;
+
+/* { 1.0f, 0.89125094f }: no gain in front, a ceiling of -1 dBFS. */
+mi_limit_row mi_limit_default_row(void);
+/* row_cfg [rows] (NULL = the default row everywhere); row_enabled [rows] as for mi_vband_create; rows and max_batches within the
+ * gate's limits (1 <= rows < 2^20, rows * max_batches < 2^24). */
+int mi_limit_create(const mi_limit_row* row_cfg /* [rows] */, const uint8_t* row_enabled, int rows, int max_batches, int gpu, mi_limit** out);
+void mi_limit_destroy(mi_limit* l);
+/* Other settings (row_cfg [rows], NULL = keep) and / or other rows (row_enabled [rows], NULL = keep) from the next call on; at least
+ * one of the two.  All state stays.  Completes the work queued on the device first. */
+int mi_limit_set_rows(mi_limit* l, const mi_limit_row* row_cfg, const uint8_t* row_enabled);
+/* One call over nbatches (1 .. max_batches) batches: d_in [rows][row_stride] and d_out [rows][out_stride], both 16-byte aligned with
+ * strides that are multiples of 4 floats and at least nbatches * 2000; the two planes must not overlap (the call is refused when
+ * they do).  Asynchronous on `hip_stream`, no host synchronisation; two kernels without atomics -- the limiter, then the copy of the
+ * enabled rows' last 1086 input samples into the carried state -- so every byte is the same on every run and equals
+ * mi_limit_plan_host's. */
+int mi_limit_process_device(mi_limit* l, const float* d_in, size_t row_stride, int nbatches, float* d_out, size_t out_stride, void* hip_stream);
+/* Checkpoint / resume, rows * MI_LIMIT_STATE_ROW_BYTES bytes in the layout above (mi_limit_plan_host reads and writes the same
+ * bytes).  Both complete queued work first. */
+size_t mi_limit_state_size(const mi_limit* l);
+int mi_limit_get_state(mi_limit* l, void* buf, size_t len);
+int mi_limit_set_state(mi_limit* l, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[2] = {limit, tails}.  tools/limit_rate.py. */
+int mi_limit_set_timing(mi_limit* l, int on);
+int mi_limit_last_launch_ms(mi_limit* l, float* ms /* [2] */);
+/* The host twin: no GPU and no HIP call; the same bytes and the same state blob.  in [rows][row_stride], out [rows][out_stride] (no
+ * alignment asked, no overlap allowed); state_inout rows * MI_LIMIT_STATE_ROW_BYTES bytes, read and updated. */
+int mi_limit_plan_host(const mi_limit_row* row_cfg /* [rows], NULL = defaults */, const uint8_t* row_enabled, int rows, int nbatches,
+                       const float* in, size_t row_stride, void* state_inout, float* out, size_t out_stride);
+/* A pregain for one row from what the splitter recorded of it, host only.  Of records[0 .. n) those with this row, nblocks > 0 and
+ * peak > 0 count, *used of them; their peaks are sorted ascending and the one at index (used - 1) * percentile / 100 (in integers;
+ * percentile 1 .. 100, 0 = 90) is taken: *pregain = ceiling / that peak as a float32 division, clamped into [2^-10, 2^10], or 1.0f
+ * where used == 0.  records may be NULL with n = 0.  MI_ERR_INVALID: NULL arguments, a ceiling mi_limit_create would refuse, a
+ * percentile over 100.  Tried on synthetic signals only. */
+int mi_limit_pregain_host(const mi_tx_record* records, size_t n, uint32_t row, float ceiling, uint32_t percentile, float* pregain, uint32_t* used);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
