@@ -536,6 +536,11 @@ class _PostStage(_Handle):
         self._call("get_state", _ptr(buf), n)
         return buf
 
+    def set_state(self, buf):
+        """The state blob back in (*_set_state): bytes as state() gave them, or an array of the stage's *_STATE_DTYPE."""
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        self._call("set_state", _ptr(buf), buf.size)
+
     def set_timing(self, on=True):
         self._call("set_timing", 1 if on else 0)
 
@@ -950,7 +955,7 @@ class OutputGate(_PostStage):
         k = int(count[1])
         return blocks[:k], None if iq is None else iq[:k], index[:k], row_first, count
 
-    def set_state(self, buf):
+    def set_state(self, buf):  # (its own: truth values, converted to bytes and not viewed as them)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         self._call("set_state", _ptr(buf), buf.size)
 
@@ -1012,10 +1017,6 @@ class TxSplit(_PostStage):
         _check(lib().mi_txsplit_download(self._h, hip_stream, _ptr(records), _ptr(row_first),
                                          _ptr(count)))
         return records[:int(count[1])], row_first, count
-
-    def set_state(self, buf):
-        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        self._call("set_state", _ptr(buf), buf.size)
 
 
 def tx_plan_host(row_enabled, axc, state=None, waveout=None, cfg=None, max_records=0, nbatches=None):
@@ -1094,10 +1095,6 @@ class Tones(_PostStage):
         k = int(count[1])
         return records[:k], None if powers is None else powers[:k], row_first, count
 
-    def set_state(self, buf):
-        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        self._call("set_state", _ptr(buf), buf.size)
-
 
 def tones_plan_host(row_enabled, axc, waveout, state=None, window=0, max_records=0, nbatches=None, want_powers=True):
     """mi_tones_plan_host: the tone finder's records (and powers) from flags and audio on the host, no GPU.  axc: uint8 [rows][axc_stride];
@@ -1170,10 +1167,6 @@ class Pcm(_PostStage):
         _check(lib().mi_pcm_download(self._h, hip_stream, _ptr(blocks), _ptr(count)))
         return blocks[:int(count[1])], count
 
-    def set_state(self, buf):
-        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        self._call("set_state", _ptr(buf), buf.size)
-
 
 def pcm_plan_host(row_enabled, waveout, index, state=None, rate=0, fmt=0, nbatches=None):
     """mi_pcm_plan_host: the PCM stage's blocks from audio and an index on the host, no GPU.  waveout: float32 [rows][row_stride];
@@ -1209,6 +1202,56 @@ def pcm_wav_header(nblocks, rate=0, fmt=0):
     return buf[:n.value].tobytes()
 
 
+def _row_settings(rows_cfg, rows, dtype, scalar, default):
+    """None (default() everywhere), one pair of `scalar`s for every row, or a pair per row -> [rows] of `dtype`"""
+    if rows_cfg is None:
+        rows_cfg = default()
+    a = np.asarray(rows_cfg)
+    if a.dtype != dtype:
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(rows_cfg, scalar).reshape(-1, 2), (rows, 2))).view(dtype).reshape(-1)
+    a = np.ascontiguousarray(a)
+    assert a.shape == (rows,)
+    return a
+
+
+class _PlaneStage(_PostStage):
+    """A post-stage that reads a plane [rows][row_stride] and writes one of the same layout under per-row settings (Vband, Limit):
+    `_rows_of`(rows_cfg, rows) gives the settings as the library takes them.  A subclass adds process_device under its own argument names."""
+    _launches = 2
+    _rows_of = None
+
+    def __init__(self, row_enabled, rows_cfg=None, max_batches=1, gpu=0):
+        en = _flags(row_enabled)
+        self.rows, self.max_batches = en.size, max_batches
+        cfg = type(self)._rows_of(rows_cfg, self.rows)
+        self._h = C.c_void_p()
+        _check(getattr(lib(), f"{self._prefix}_create")(_ptr(cfg), _ptr(en), self.rows, max_batches, gpu, C.byref(self._h)))
+
+    def set_rows(self, row_enabled=None, rows_cfg=None):
+        """other rows and / or other settings from the next call on (None = keep); the carried samples stay (and, in the limiter,
+        count under the new pregain)"""
+        en = None if row_enabled is None else _flags(row_enabled)
+        cfg = None if rows_cfg is None else type(self)._rows_of(rows_cfg, self.rows)
+        assert en is None or en.size == self.rows
+        self._call("set_rows", None if cfg is None else _ptr(cfg), None if en is None else _ptr(en))
+
+
+def _plane_plan_host(fn, rows_of, state_dtype, row_enabled, plane, rows_cfg, state, nbatches, out):
+    """the host twin `fn` of a _PlaneStage: (out, state after the call)"""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows, row_stride = plane.shape
+    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
+    cfg = rows_of(rows_cfg, rows)
+    state = np.zeros(rows * state_dtype.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * state_dtype.itemsize
+    out = np.zeros((rows, nb * WAVE_BATCH), np.float32) if out is None else out
+    assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == rows and out.flags.c_contiguous
+    _check(fn(_ptr(cfg), _ptr(en), rows, nb, _ptr(plane), row_stride, _ptr(state), _ptr(out), out.shape[1]))
+    return out, state
+
+
 def vband_default_row():
     """mi_vband_default_row: (100, 2500), the reference's highpass / lowpass defaults"""
     r = lib().mi_vband_default_row()
@@ -1217,47 +1260,22 @@ def vband_default_row():
 
 def _vband_rows(rows_cfg, rows):
     """None (the default row everywhere), one (hp_hz, lp_hz) pair for every row, or a pair per row -> [rows] of VBAND_ROW_DTYPE"""
-    if rows_cfg is None:
-        rows_cfg = vband_default_row()
-    a = np.asarray(rows_cfg)
-    if a.dtype != VBAND_ROW_DTYPE:
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(rows_cfg, np.uint32).reshape(-1, 2), (rows, 2))).view(VBAND_ROW_DTYPE).reshape(-1)
-    a = np.ascontiguousarray(a)
-    assert a.shape == (rows,)
-    return a
+    return _row_settings(rows_cfg, rows, VBAND_ROW_DTYPE, np.uint32, vband_default_row)
 
 
-class Vband(_PostStage):
+class Vband(_PlaneStage):
     """mi_vband: the voice band stage -- the reference's `highpass` / `lowpass` keys as a 511-tap linear-phase FIR per row over the
     demodulator's audio, written as a plane of the same layout (delayed by 255 samples, clamped to [-1, 1]) that the gate, the
     splitter, the PCM stage and the mixer take in its place.  row_enabled: truth value per row (a disabled row's output is not
     written and its carried samples stay); rows_cfg: (hp_hz, lp_hz) for every row or one pair per row, 0 = no edge on that side,
     None = the defaults 100 / 2500.  state() gives rows * 2040 bytes, .view(VBAND_STATE_DTYPE): the 510 input samples a row carries
     into its next call."""
-    _destroy, _prefix, _launches = "mi_vband_destroy", "mi_vband", 2
-
-    def __init__(self, row_enabled, rows_cfg=None, max_batches=1, gpu=0):
-        en = _flags(row_enabled)
-        self.rows, self.max_batches = en.size, max_batches
-        cfg = _vband_rows(rows_cfg, self.rows)
-        self._h = C.c_void_p()
-        _check(lib().mi_vband_create(_ptr(cfg), _ptr(en), self.rows, max_batches, gpu, C.byref(self._h)))
-
-    def set_rows(self, row_enabled=None, rows_cfg=None):
-        """other rows and / or other settings from the next call on (None = keep); the carried samples stay"""
-        en = None if row_enabled is None else _flags(row_enabled)
-        cfg = None if rows_cfg is None else _vband_rows(rows_cfg, self.rows)
-        assert en is None or en.size == self.rows
-        _check(lib().mi_vband_set_rows(self._h, None if cfg is None else _ptr(cfg), None if en is None else _ptr(en)))
+    _destroy, _prefix, _rows_of = "mi_vband_destroy", "mi_vband", _vband_rows
 
     def process_device(self, d_waveout, row_stride, nbatches, d_out, out_stride, hip_stream=None):
         """Raw device pointers (ints), the strides in floats; d_out [rows][out_stride] must not overlap d_waveout; asynchronous on
         hip_stream."""
-        _check(lib().mi_vband_process_device(self._h, d_waveout, row_stride, nbatches, d_out, out_stride, hip_stream))
-
-    def set_state(self, buf):
-        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        self._call("set_state", _ptr(buf), buf.size)
+        self._call("process_device", d_waveout, row_stride, nbatches, d_out, out_stride, hip_stream)
 
 
 def vband_plan_host(row_enabled, waveout, rows_cfg=None, state=None, nbatches=None, out=None):
@@ -1265,18 +1283,7 @@ def vband_plan_host(row_enabled, waveout, rows_cfg=None, state=None, nbatches=No
     rows_cfg as for Vband; state: the blob (rows * 2040 bytes) or None (a fresh one); nbatches: batches of the call, default
     row_stride // WAVE_BATCH; out: float32 [rows][out_stride] to write into (a disabled row's floats stay), default zeros
     [rows][nbatches * WAVE_BATCH].  Returns (out, state after the call)."""
-    en = _flags(row_enabled)
-    waveout = np.ascontiguousarray(waveout, dtype=np.float32)
-    assert waveout.ndim == 2 and waveout.shape[0] == en.size
-    rows, row_stride = waveout.shape
-    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
-    cfg = _vband_rows(rows_cfg, rows)
-    state = np.zeros(rows * VBAND_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
-    assert state.size == rows * VBAND_STATE_DTYPE.itemsize
-    out = np.zeros((rows, nb * WAVE_BATCH), np.float32) if out is None else out
-    assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == rows and out.flags.c_contiguous
-    _check(lib().mi_vband_plan_host(_ptr(cfg), _ptr(en), rows, nb, _ptr(waveout), row_stride, _ptr(state), _ptr(out), out.shape[1]))
-    return out, state
+    return _plane_plan_host(lib().mi_vband_plan_host, _vband_rows, VBAND_STATE_DTYPE, row_enabled, waveout, rows_cfg, state, nbatches, out)
 
 
 def vband_taps(hp_hz, lp_hz):
@@ -1294,48 +1301,22 @@ def limit_default_row():
 
 def _limit_rows(rows_cfg, rows):
     """None (the default row everywhere), one (pregain, ceiling) pair for every row, or a pair per row -> [rows] of LIMIT_ROW_DTYPE"""
-    if rows_cfg is None:
-        rows_cfg = limit_default_row()
-    a = np.asarray(rows_cfg)
-    if a.dtype != LIMIT_ROW_DTYPE:
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(rows_cfg, np.float32).reshape(-1, 2), (rows, 2))).view(LIMIT_ROW_DTYPE).reshape(-1)
-    a = np.ascontiguousarray(a)
-    assert a.shape == (rows,)
-    return a
+    return _row_settings(rows_cfg, rows, LIMIT_ROW_DTYPE, np.float32, limit_default_row)
 
 
-class Limit(_PostStage):
+class Limit(_PlaneStage):
     """mi_limit: the peak limiter stage -- a look-ahead gain per row that keeps a plane of audio (the demodulator's, the voice band
     stage's, a mixer's sum) inside a ceiling without clipping it, written as a plane of the same layout (delayed by 63 samples) that
     the gate, the splitter, the PCM stage and the mixer take in its place.  row_enabled: truth value per row (a disabled row's output
     is not written and its carried samples stay); rows_cfg: (pregain, ceiling) for every row or one pair per row, None = the defaults
     1.0 / 0.89125094.  Rows are independent: no stereo link.  state() gives rows * 4344 bytes, .view(LIMIT_STATE_DTYPE): the 1086
     input samples a row carries into its next call."""
-    _destroy, _prefix, _launches = "mi_limit_destroy", "mi_limit", 2
-
-    def __init__(self, row_enabled, rows_cfg=None, max_batches=1, gpu=0):
-        en = _flags(row_enabled)
-        self.rows, self.max_batches = en.size, max_batches
-        cfg = _limit_rows(rows_cfg, self.rows)
-        self._h = C.c_void_p()
-        _check(lib().mi_limit_create(_ptr(cfg), _ptr(en), self.rows, max_batches, gpu, C.byref(self._h)))
-
-    def set_rows(self, row_enabled=None, rows_cfg=None):
-        """other rows and / or other settings from the next call on (None = keep); the carried samples stay, and count under the new
-        pregain"""
-        en = None if row_enabled is None else _flags(row_enabled)
-        cfg = None if rows_cfg is None else _limit_rows(rows_cfg, self.rows)
-        assert en is None or en.size == self.rows
-        _check(lib().mi_limit_set_rows(self._h, None if cfg is None else _ptr(cfg), None if en is None else _ptr(en)))
+    _destroy, _prefix, _rows_of = "mi_limit_destroy", "mi_limit", _limit_rows
 
     def process_device(self, d_in, row_stride, nbatches, d_out, out_stride, hip_stream=None):
         """Raw device pointers (ints), the strides in floats; d_out [rows][out_stride] must not overlap d_in; asynchronous on
         hip_stream."""
-        _check(lib().mi_limit_process_device(self._h, d_in, row_stride, nbatches, d_out, out_stride, hip_stream))
-
-    def set_state(self, buf):
-        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
-        self._call("set_state", _ptr(buf), buf.size)
+        self._call("process_device", d_in, row_stride, nbatches, d_out, out_stride, hip_stream)
 
 
 def limit_plan_host(row_enabled, plane, rows_cfg=None, state=None, nbatches=None, out=None):
@@ -1343,18 +1324,7 @@ def limit_plan_host(row_enabled, plane, rows_cfg=None, state=None, nbatches=None
     for Limit; state: the blob (rows * 4344 bytes) or None (a fresh one); nbatches: batches of the call, default row_stride //
     WAVE_BATCH; out: float32 [rows][out_stride] to write into (a disabled row's floats stay), default zeros [rows][nbatches *
     WAVE_BATCH].  Returns (out, state after the call)."""
-    en = _flags(row_enabled)
-    plane = np.ascontiguousarray(plane, dtype=np.float32)
-    assert plane.ndim == 2 and plane.shape[0] == en.size
-    rows, row_stride = plane.shape
-    nb = row_stride // WAVE_BATCH if nbatches is None else nbatches
-    cfg = _limit_rows(rows_cfg, rows)
-    state = np.zeros(rows * LIMIT_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
-    assert state.size == rows * LIMIT_STATE_DTYPE.itemsize
-    out = np.zeros((rows, nb * WAVE_BATCH), np.float32) if out is None else out
-    assert out.dtype == np.float32 and out.ndim == 2 and out.shape[0] == rows and out.flags.c_contiguous
-    _check(lib().mi_limit_plan_host(_ptr(cfg), _ptr(en), rows, nb, _ptr(plane), row_stride, _ptr(state), _ptr(out), out.shape[1]))
-    return out, state
+    return _plane_plan_host(lib().mi_limit_plan_host, _limit_rows, LIMIT_STATE_DTYPE, row_enabled, plane, rows_cfg, state, nbatches, out)
 
 
 def limit_pregain_host(records, row, ceiling=None, percentile=0):

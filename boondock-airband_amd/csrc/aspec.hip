@@ -3,7 +3,7 @@
 // should hold is read off that mean by mi_aspec_notch_host.  The window, the FFT, the band and the order of every sum are in
 // include/mi_airband.h.  A post-stage of its own like the PCM stage: one launch, or two, on the caller's stream, no atomics, no state.
 // It reads the gate's index, row starts and counts where the gate left them, in device memory.  mi_aspec_plan_host
-// (poststage_host.cpp) is the host twin.
+// (poststage_host.cpp) is the host twin.  The handle's base and the bodies of the entry points every stage repeats are in poststage.hpp.
 //
 // Compile with -ffp-contract=off (the FFT spec).
 #include <hip/hip_runtime.h>
@@ -15,16 +15,15 @@
 #include "fft_radix8.hpp"
 #include "poststage.hpp"
 
-struct mi_aspec {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "audio spectrum stage";
+
+struct mi_aspec : mi::BatchStage {
+    mi_aspec() : BatchStage(kName, 2) {}
     uint32_t max_blocks = 0;
     mi::AspecBand band{};
     mi::DevBuf<float> d_window;       // [2000]
     mi::DevBuf<float> d_tw;           // [1024] x {re, im}
     mi::PinnedBuf<uint32_t> h_count;  // [2], landing place of the counts in mi_aspec_download
-    mi::LaunchTiming timing{"audio spectrum stage", 2};  // mi_aspec_set_timing
     // what the last mi_aspec_process_device was given (what mi_aspec_download reads)
     const mi_aspec_record* last_records = nullptr;
     const float* last_power = nullptr;
@@ -205,8 +204,8 @@ int mi_aspec_create(const mi_aspec_cfg* cfg, int rows, int max_batches, size_t m
     mi::AspecBand band;
     if (const int rc = mi::aspec_band(cfg, &band))
         return rc;
-    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return fail(MI_ERR_INVALID, "audio spectrum stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    if (const int rc = mi::batch_geometry_ok(kName, rows, max_batches))
+        return rc;
     std::vector<float> tw, window(mi::kWaveBatch);
     if (const int rc = mi::aspec_twiddles(tw))
         return rc;
@@ -230,10 +229,7 @@ int mi_aspec_create(const mi_aspec_cfg* cfg, int rows, int max_batches, size_t m
 }
 
 void mi_aspec_destroy(mi_aspec* a) {
-    if (!a)
-        return;
-    (void)hipSetDevice(a->gpu);
-    delete a;
+    mi::destroy(a);
 }
 
 int mi_aspec_process_device(mi_aspec* a, const float* d_waveout, size_t row_stride, int nbatches, const mi_gate_block* d_index, const uint32_t* d_row_first,
@@ -268,6 +264,7 @@ int mi_aspec_process_device(mi_aspec* a, const float* d_waveout, size_t row_stri
     a->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "audio spectrum stage kernel launch failed");
+    a->called = true;
     a->last_records = d_records;
     a->last_power = d_power;
     a->last_row_mean = d_row_mean;
@@ -303,17 +300,11 @@ int mi_aspec_download(mi_aspec* a, void* hip_stream, mi_aspec_record* records, f
 }
 
 int mi_aspec_set_timing(mi_aspec* a, int on) {
-    if (!a)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return a->timing.enable(a->gpu, on != 0);
+    return mi::set_timing(a, on);
 }
 
 int mi_aspec_last_launch_ms(mi_aspec* a, float* ms) {
-    if (!a || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!a->timing.on || !a->last_count)
-        return fail(MI_ERR_INVALID, "no timed mi_aspec_process_device call");
-    return a->timing.elapsed(a->gpu, ms);
+    return mi::last_launch_ms(a, ms, "mi_aspec_process_device");
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // (src/config.cpp:623) is multiplied in before the demodulator's hard clamp, and the PCM stage's quantiser saturates.  The window
 // maximum, the gain, the order of its 64-term mean, the clamp and the state blob are in include/mi_airband.h.  A post-stage like the
 // voice band stage: two launches on the caller's stream, no atomics.  It writes a plane in the layout of the one it reads.
-// mi_limit_plan_host (poststage_host.cpp) is the host twin.
+// mi_limit_plan_host (poststage_host.cpp) is the host twin.  The handle's base and the bodies of the entry points every stage repeats
+// are in poststage.hpp, the tails kernel in carry.hpp (whose load of the lead k_limit restates: see there).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -11,22 +12,19 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
+#include "carry.hpp"
 #include "poststage.hpp"
 
-struct mi_limit {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
-    mi::DevBuf<uint8_t> d_enabled;           // [rows]
+constexpr char kName[] = "limiter stage";
+
+struct mi_limit : mi::RowStage {
+    mi_limit() : RowStage(kName, 2) {}
     mi::DevBuf<mi_limit_row> d_cfg;          // [rows]
     mi::DevBuf<mi::LimitRowState> d_state;   // [rows]: the checkpoint blob as it is
-    mi::LaunchTiming timing{"limiter stage", 2};  // mi_limit_set_timing
-    bool called = false;
 };
 
 namespace {
 
-using mi::aligned;
 using mi::as_flags;
 using mi::fail;
 constexpr int kThreads = 256;
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_limit(const uint8_t* __restrict__ 
         float4* const dst = reinterpret_cast<float4*>(out + static_cast<size_t>(row) * out_stride + static_cast<size_t>(batch) * kBatch);
         int over = 0;
         for (int q = t; q < kStage / 4; q += kThreads) {
-            float4 v;
+            float4 v;  // (mi::load_lead4 of carry.hpp, kept as the stage had it: with the shared one the transparent path measured 2 % off)
             if (q >= kLead / 4 || batch != 0) {
                 v = reinterpret_cast<const float4*>(blk - kLead)[q];
             } else {  // floats 4q .. 4q + 3 of the lead are carried samples 4q - 2 .. 4q + 1
@@ -164,17 +162,7 @@ __global__ __launch_bounds__(kThreads) void k_limit(const uint8_t* __restrict__ 
     }
 }
 
-// Launch 2, behind the limiter in the stream, which read the old ones: the last 1086 input samples of the call are an enabled row's
-// new carried samples.  One workgroup per row.
-__global__ __launch_bounds__(kThreads) void k_limit_tails(const uint8_t* __restrict__ enabled, const float* __restrict__ wave, const size_t row_stride,
-                                                          const uint32_t rows, const uint32_t nbatches, mi::LimitRowState* __restrict__ state) {
-    const uint32_t row = blockIdx.x;
-    if (row >= rows || !enabled[row])
-        return;
-    const float* const tail = wave + static_cast<size_t>(row) * row_stride + static_cast<size_t>(nbatches) * kBatch - MI_LIMIT_HISTORY;
-    for (int j = threadIdx.x; j < MI_LIMIT_HISTORY; j += kThreads)
-        state[row].x[j] = tail[j];
-}
+// Launch 2.  mi::k_carry_tails (carry.hpp): the last 1086 input samples of the call are an enabled row's new carried samples.
 
 }  // namespace
 
@@ -183,8 +171,8 @@ extern "C" {
 int mi_limit_create(const mi_limit_row* row_cfg, const uint8_t* row_enabled, int rows, int max_batches, int gpu, mi_limit** out) {
     if (!row_enabled || !out)
         return fail(MI_ERR_INVALID, "NULL argument");
-    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return fail(MI_ERR_INVALID, "limiter stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    if (const int rc = mi::batch_geometry_ok(kName, rows, max_batches))
+        return rc;
     const size_t n = static_cast<size_t>(rows);
     std::vector<mi_limit_row> cfg;
     if (const int rc = mi::limit_rows(row_cfg, n, cfg))
@@ -205,10 +193,7 @@ int mi_limit_create(const mi_limit_row* row_cfg, const uint8_t* row_enabled, int
 }
 
 void mi_limit_destroy(mi_limit* l) {
-    if (!l)
-        return;
-    (void)hipSetDevice(l->gpu);
-    delete l;
+    mi::destroy(l);
 }
 
 int mi_limit_set_rows(mi_limit* l, const mi_limit_row* row_cfg, const uint8_t* row_enabled) {
@@ -233,16 +218,8 @@ int mi_limit_set_rows(mi_limit* l, const mi_limit_row* row_cfg, const uint8_t* r
 }
 
 int mi_limit_process_device(mi_limit* l, const float* d_in, size_t row_stride, int nbatches, float* d_out, size_t out_stride, void* hip_stream) {
-    if (!l || !d_in || !d_out)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (nbatches < 1 || nbatches > l->max_batches)
-        return fail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
-    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch || out_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
-        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
-    if (row_stride % 4 != 0 || out_stride % 4 != 0 || !aligned(d_in, 16) || !aligned(d_out, 16))
-        return fail(MI_ERR_INVALID, "the input plane and the output must be 16-byte aligned with row strides that are multiples of 4 floats");
-    if (mi::vband_overlap(d_in, row_stride, d_out, out_stride, static_cast<size_t>(l->rows), static_cast<size_t>(nbatches)))
-        return fail(MI_ERR_INVALID, "the output overlaps the input plane");
+    if (const int rc = mi::plane_call_ok(l, d_in, row_stride, nbatches, d_out, out_stride, "input plane"))
+        return rc;
     if (hipSetDevice(l->gpu) != hipSuccess)
         return fail(MI_ERR_HIP, "hipSetDevice failed");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
@@ -251,8 +228,7 @@ int mi_limit_process_device(mi_limit* l, const float* d_in, size_t row_stride, i
     hipLaunchKernelGGL(k_limit, dim3(call < kMaxGrid ? call : kMaxGrid), dim3(kThreads), 0, q, l->d_enabled.get(), l->d_cfg.get(), d_in, row_stride, rows,
                        static_cast<uint32_t>(nbatches), l->d_state.get(), d_out, out_stride);
     l->timing.stamp(1, q);
-    hipLaunchKernelGGL(k_limit_tails, dim3(rows), dim3(kThreads), 0, q, l->d_enabled.get(), d_in, row_stride, rows, static_cast<uint32_t>(nbatches),
-                       l->d_state.get());
+    mi::launch_carry_tails<MI_LIMIT_HISTORY>(q, l->d_enabled.get(), d_in, row_stride, rows, nbatches, l->d_state.get());
     l->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "limiter stage kernel launch failed");
@@ -261,37 +237,23 @@ int mi_limit_process_device(mi_limit* l, const float* d_in, size_t row_stride, i
 }
 
 int mi_limit_set_timing(mi_limit* l, int on) {
-    if (!l)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return l->timing.enable(l->gpu, on != 0);
+    return mi::set_timing(l, on);
 }
 
 int mi_limit_last_launch_ms(mi_limit* l, float* ms) {
-    if (!l || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!l->timing.on || !l->called)
-        return fail(MI_ERR_INVALID, "no timed mi_limit_process_device call");
-    return l->timing.elapsed(l->gpu, ms);
+    return mi::last_launch_ms(l, ms, "mi_limit_process_device");
 }
 
 size_t mi_limit_state_size(const mi_limit* l) {
-    return l ? static_cast<size_t>(l->rows) * sizeof(mi::LimitRowState) : 0;
+    return mi::state_size(l, &mi_limit::d_state);
 }
 
 int mi_limit_get_state(mi_limit* l, void* buf, size_t len) {
-    if (!l || !buf || len != mi_limit_state_size(l))
-        return fail(MI_ERR_INVALID, "limiter stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(l->gpu, buf, l->d_state, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "limiter stage: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, l, &mi_limit::d_state, buf, len);
 }
 
 int mi_limit_set_state(mi_limit* l, const void* buf, size_t len) {
-    if (!l || !buf || len != mi_limit_state_size(l))
-        return fail(MI_ERR_INVALID, "limiter stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(l->gpu, l->d_state, buf, len, hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "limiter stage: writing the state failed");
-    return MI_OK;
+    return mi::set_state(kName, l, &mi_limit::d_state, buf, len);
 }
 
 }  // extern "C"

@@ -31,8 +31,8 @@
 #include "../../include/mi_airband.h"
 #include "poststage.hpp"
 
-struct mi_occupancy {
-    int gpu = 0;
+struct mi_occupancy : mi::Stage {
+    mi_occupancy() : Stage("channel finder", 4) {}
     int nstreams = 0;
     int max_cells = 0;
     int log2n = 0, fft_size = 0;
@@ -42,8 +42,6 @@ struct mi_occupancy {
     mi::DevBuf<int> d_rank;               // [nstreams][fft_size]: a run start's number within its stream, -1 elsewhere
     mi::DevBuf<uint32_t> d_stream_count;  // [nstreams]
     mi::PinnedBuf<uint32_t> h_count;      // [2], landing place of the counts in mi_occupancy_download
-    mi::LaunchTiming timing{"channel finder", 4};  // mi_occupancy_set_timing
-    bool timed = false;                   // the last call was stamped
     // destinations of the last mi_occupancy_process_device (what mi_occupancy_download reads)
     const mi_occ_bin* last_bins = nullptr;
     const mi_occ_candidate* last_cands = nullptr;
@@ -325,10 +323,7 @@ int mi_occupancy_create(const mi_device_cfg* dev, const mi_occ_cfg* cfg, int nst
 }
 
 void mi_occupancy_destroy(mi_occupancy* o) {
-    if (!o)
-        return;
-    (void)hipSetDevice(o->gpu);
-    delete o;
+    mi::destroy(o);
 }
 
 int mi_occupancy_set_streams(mi_occupancy* o, const uint8_t* stream_enabled) {
@@ -375,7 +370,7 @@ int mi_occupancy_process_device(mi_occupancy* o, const float* d_mean, const floa
     o->timing.stamp(4, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "channel finder kernel launch failed");
-    o->timed = o->timing.on;
+    o->called = o->timing.on;  // (a stamped call: last_launch_ms refuses after any other)
     o->last_bins = d_bins;
     o->last_cands = d_cands;
     o->last_stream_first = d_stream_first;
@@ -407,17 +402,11 @@ int mi_occupancy_download(mi_occupancy* o, void* hip_stream, mi_occ_bin* bins, m
 }
 
 int mi_occupancy_set_timing(mi_occupancy* o, int on) {
-    if (!o)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return o->timing.enable(o->gpu, on != 0);
+    return mi::set_timing(o, on);
 }
 
 int mi_occupancy_last_launch_ms(mi_occupancy* o, float* ms) {
-    if (!o || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!o->timing.on || !o->timed)
-        return fail(MI_ERR_INVALID, "no timed mi_occupancy_process_device call");
-    return o->timing.elapsed(o->gpu, ms);
+    return mi::last_launch_ms(o, ms, "mi_occupancy_process_device");
 }
 
 }  // extern "C"

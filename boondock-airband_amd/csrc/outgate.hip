@@ -6,6 +6,7 @@
 // A post-stage of its own like the mixer (mixer.hip): three small launches on the caller's stream, no atomics -- a block's place is
 // its row's exclusive prefix plus its rank within the row, so the packed order is rows ascending, batches ascending, on every run.
 // Everything moved is a copy: bandwidth-bound, one float4 per lane per access.  mi_gate_plan_host (poststage_host.cpp) is the host twin.
+// The handle's base and the bodies of the entry points every stage repeats are in poststage.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,17 +16,16 @@
 #include "../../include/mi_airband.h"
 #include "poststage.hpp"
 
-struct mi_outgate {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "output gate";
+
+struct mi_outgate : mi::BatchStage {
+    mi_outgate() : BatchStage(kName, 3) {}
     uint32_t max_blocks = 0;
     bool any_iq = false;
     mi::DevBuf<uint8_t> d_rule, d_has_iq, d_carried;  // [rows]
     mi::DevBuf<int> d_rank;                           // [rows][nbatches of the call]: place within the row, -1 = does not travel
     mi::DevBuf<uint32_t> d_row_count;                 // [rows]
     mi::PinnedBuf<uint32_t> h_count;                  // [2], landing place of the counts in mi_outgate_download
-    mi::LaunchTiming timing{"output gate", 3};        // mi_outgate_set_timing
     // destinations of the last mi_outgate_process_device (what mi_outgate_download reads)
     const float* last_blocks = nullptr;
     const float* last_iq_blocks = nullptr;
@@ -117,8 +117,8 @@ extern "C" {
 int mi_outgate_create(const uint8_t* row_rule, const uint8_t* row_has_iq, int rows, int max_batches, size_t max_blocks, int gpu, mi_outgate** out) {
     if (!row_rule || !out)
         return fail(MI_ERR_INVALID, "NULL argument");
-    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return fail(MI_ERR_INVALID, "output gate needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    if (const int rc = mi::batch_geometry_ok(kName, rows, max_batches))
+        return rc;
     const size_t all = static_cast<size_t>(rows) * static_cast<size_t>(max_batches);
     if (!rules_valid(row_rule, rows))
         return fail(MI_ERR_INVALID, "gate rule out of range 0..3");
@@ -146,10 +146,7 @@ int mi_outgate_create(const uint8_t* row_rule, const uint8_t* row_has_iq, int ro
 }
 
 void mi_outgate_destroy(mi_outgate* g) {
-    if (!g)
-        return;
-    (void)hipSetDevice(g->gpu);
-    delete g;
+    mi::destroy(g);
 }
 
 int mi_outgate_set_rules(mi_outgate* g, const uint8_t* row_rule) {
@@ -195,6 +192,7 @@ int mi_outgate_process_device(mi_outgate* g, const float* d_waveout, size_t row_
     g->timing.stamp(3, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "output gate kernel launch failed");
+    g->called = true;
     g->last_blocks = d_blocks;
     g->last_iq_blocks = iq ? d_iq_blocks : nullptr;
     g->last_index = d_index;
@@ -229,32 +227,22 @@ int mi_outgate_download(mi_outgate* g, void* hip_stream, float* blocks, float* i
 }
 
 int mi_outgate_set_timing(mi_outgate* g, int on) {
-    if (!g)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return g->timing.enable(g->gpu, on != 0);
+    return mi::set_timing(g, on);
 }
 
 int mi_outgate_last_launch_ms(mi_outgate* g, float* ms) {
-    if (!g || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!g->timing.on || !g->last_count)
-        return fail(MI_ERR_INVALID, "no timed mi_outgate_process_device call");
-    return g->timing.elapsed(g->gpu, ms);
+    return mi::last_launch_ms(g, ms, "mi_outgate_process_device");
 }
 
 size_t mi_outgate_state_size(const mi_outgate* g) {
-    return g ? static_cast<size_t>(g->rows) : 0;
+    return mi::state_size(g, &mi_outgate::d_carried);
 }
 
 int mi_outgate_get_state(mi_outgate* g, void* buf, size_t len) {
-    if (!g || !buf || len != static_cast<size_t>(g->rows))
-        return fail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
-    if (!mi::sync_copy(g->gpu, buf, g->d_carried, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "output gate: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, g, &mi_outgate::d_carried, buf, len);
 }
 
-int mi_outgate_set_state(mi_outgate* g, const void* buf, size_t len) {
+int mi_outgate_set_state(mi_outgate* g, const void* buf, size_t len) {  // (its own body: the blob is taken as truth values, not as it is)
     if (!g || !buf || len != static_cast<size_t>(g->rows))
         return fail(MI_ERR_INVALID, "output gate state: NULL argument or wrong length");
     if (!mi::sync_copy(g->gpu, g->d_carried, mi::as_flags(buf, len).data(), len, hipMemcpyHostToDevice))

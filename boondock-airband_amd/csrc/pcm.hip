@@ -4,7 +4,8 @@
 // MP3 stays with the host; this is the arithmetic whose every byte can be defined.  The filter, the quantiser, the encoder step and
 // the state blob are in include/mi_airband.h.  A post-stage of its own like the gate and the splitter: two launches on the caller's
 // stream, no atomics.  It reads the gate's index and counts where the gate left them, in device memory.  mi_pcm_plan_host
-// (poststage_host.cpp) is the host twin.
+// (poststage_host.cpp) is the host twin.  The handle's base and the bodies of the entry points every stage repeats are in
+// poststage.hpp, the lead's load and the tails kernel in carry.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -12,19 +13,18 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
+#include "carry.hpp"
 #include "poststage.hpp"
 
-struct mi_pcm {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "PCM stage";
+
+struct mi_pcm : mi::RowStage {
+    mi_pcm() : RowStage(kName, 2) {}
     uint32_t max_blocks = 0;
     mi::PcmGeometry geo{};
     mi::PcmLiveTaps taps{};
-    mi::DevBuf<uint8_t> d_enabled;          // [rows]
     mi::DevBuf<mi::PcmRowState> d_state;    // [rows]: the checkpoint blob as it is
     mi::PinnedBuf<uint32_t> h_count;        // [2], landing place of the counts in mi_pcm_download
-    mi::LaunchTiming timing{"PCM stage", 2};  // mi_pcm_set_timing
     // what the last mi_pcm_process_device was given (what mi_pcm_download reads)
     const void* last_out = nullptr;
     const uint32_t* last_count = nullptr;
@@ -40,7 +40,7 @@ constexpr int kBatch = mi::kWaveBatch;        // 2000 floats = 500 float4
 constexpr int kLead = 64;                     // floats loaded in front of the block: the 62 of the history behind two that are not used
 constexpr int kHalf = (kLead + kBatch) / 2;   // 1032 even and as many odd samples
 constexpr int kImaS = MI_PCM_IMA_SAMPLES, kImaB = MI_PCM_IMA_BYTES;
-static_assert(kLead >= MI_PCM_HISTORY && kLead % 4 == 0 && kBatch % 4 == 0 && MI_PCM_HISTORY % 2 == 0, "the lead is whole float4s, the history whole float2s");
+static_assert((kLead + kBatch) % 4 == 0, "what is loaded is whole float4s");
 static_assert(kBatch / kImaS <= kThreads && kImaB == 16 && (kImaS - 1) % 8 == 0, "one lane per sub-block, one uint4 each");
 
 __constant__ int kStepTable[mi::kImaSteps] = {
@@ -132,15 +132,7 @@ __global__ __launch_bounds__(kThreads) void k_pcm_encode(const float* __restrict
         const float* const blk = wave + static_cast<size_t>(row) * row_stride + static_cast<size_t>(batch) * kBatch;
         if (kDecimate) {
             for (int q = t; q < (kLead + kBatch) / 4; q += kThreads) {
-                float4 v;
-                if (q >= kLead / 4 || batch != 0) {
-                    v = reinterpret_cast<const float4*>(blk - kLead)[q];
-                } else {  // floats 4q .. 4q + 3 of the lead are carried samples 4q - 2 .. 4q + 1
-                    const float* const h = state[row].x + 4 * q;
-                    const float2 a = q ? *reinterpret_cast<const float2*>(h - 2) : make_float2(0.0f, 0.0f);
-                    const float2 b = *reinterpret_cast<const float2*>(h);
-                    v = make_float4(a.x, a.y, b.x, b.y);
-                }
+                const float4 v = mi::load_lead4<kLead>(blk, state[row], q, batch == 0);
                 *reinterpret_cast<float2*>(ev + 2 * q) = make_float2(v.x, v.z);
                 *reinterpret_cast<float2*>(od + 2 * q) = make_float2(v.y, v.w);
             }
@@ -171,15 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_pcm_encode(const float* __restrict
     }
 }
 
-// Launch 2, behind the encoder in the stream, which read the old ones: the last 62 samples of the call are an enabled row's new
-// carried samples.  One wave per row.
-__global__ __launch_bounds__(kThreads) void k_pcm_tails(const uint8_t* __restrict__ enabled, const float* __restrict__ wave, const size_t row_stride,
-                                                        const uint32_t rows, const uint32_t nbatches, mi::PcmRowState* __restrict__ state) {
-    const uint32_t row = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), j = threadIdx.x & 63;
-    if (row >= rows || j >= MI_PCM_HISTORY || !enabled[row])
-        return;
-    state[row].x[j] = wave[static_cast<size_t>(row) * row_stride + static_cast<size_t>(nbatches) * kBatch - MI_PCM_HISTORY + j];
-}
+// Launch 2.  mi::k_carry_tails (carry.hpp): the last 62 samples of the call are an enabled row's new carried samples.
 
 template <bool kDecimate, bool kIma>
 void launch_encode(const mi_pcm* p, hipStream_t q, unsigned grid, const float* d_waveout, size_t row_stride, int nbatches, const mi_gate_block* d_index,
@@ -198,8 +182,8 @@ int mi_pcm_create(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows, i
     mi::PcmGeometry geo;
     if (const int rc = mi::pcm_geometry(cfg, &geo))
         return rc;
-    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return fail(MI_ERR_INVALID, "PCM stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    if (const int rc = mi::batch_geometry_ok(kName, rows, max_batches))
+        return rc;
     if (const int rc = mi::check_gpu(gpu, "no HIP device: the PCM stage runs on the GPU only"))
         return rc;
     mi_pcm* p = new mi_pcm();
@@ -220,20 +204,11 @@ int mi_pcm_create(const mi_pcm_cfg* cfg, const uint8_t* row_enabled, int rows, i
 }
 
 void mi_pcm_destroy(mi_pcm* p) {
-    if (!p)
-        return;
-    (void)hipSetDevice(p->gpu);
-    delete p;
+    mi::destroy(p);
 }
 
 int mi_pcm_set_rows(mi_pcm* p, const uint8_t* row_enabled) {
-    if (!p || !row_enabled)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    const std::vector<uint8_t> flags = as_flags(row_enabled, static_cast<size_t>(p->rows));
-    // (a call still queued reads the rows it was made with)
-    if (!mi::sync_copy(p->gpu, p->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "PCM stage: uploading the rows failed");
-    return MI_OK;
+    return mi::set_enabled(kName, p, row_enabled);
 }
 
 int mi_pcm_process_device(mi_pcm* p, const float* d_waveout, size_t row_stride, int nbatches, const mi_gate_block* d_index, const uint32_t* d_count,
@@ -264,11 +239,11 @@ int mi_pcm_process_device(mi_pcm* p, const float* d_waveout, size_t row_stride, 
     else
         launch_encode<false, false>(p, q, grid, d_waveout, row_stride, nbatches, d_index, d_count, d_out);
     p->timing.stamp(1, q);
-    hipLaunchKernelGGL(k_pcm_tails, dim3((rows + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, q, p->d_enabled.get(), d_waveout, row_stride, rows,
-                       static_cast<uint32_t>(nbatches), p->d_state.get());
+    mi::launch_carry_tails<MI_PCM_HISTORY>(q, p->d_enabled.get(), d_waveout, row_stride, rows, nbatches, p->d_state.get());
     p->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "PCM stage kernel launch failed");
+    p->called = true;
     p->last_out = d_out;
     p->last_count = d_count;
     return MI_OK;
@@ -291,37 +266,23 @@ int mi_pcm_download(mi_pcm* p, void* hip_stream, void* out, uint32_t* count) {
 }
 
 int mi_pcm_set_timing(mi_pcm* p, int on) {
-    if (!p)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return p->timing.enable(p->gpu, on != 0);
+    return mi::set_timing(p, on);
 }
 
 int mi_pcm_last_launch_ms(mi_pcm* p, float* ms) {
-    if (!p || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!p->timing.on || !p->last_count)
-        return fail(MI_ERR_INVALID, "no timed mi_pcm_process_device call");
-    return p->timing.elapsed(p->gpu, ms);
+    return mi::last_launch_ms(p, ms, "mi_pcm_process_device");
 }
 
 size_t mi_pcm_state_size(const mi_pcm* p) {
-    return p ? static_cast<size_t>(p->rows) * sizeof(mi::PcmRowState) : 0;
+    return mi::state_size(p, &mi_pcm::d_state);
 }
 
 int mi_pcm_get_state(mi_pcm* p, void* buf, size_t len) {
-    if (!p || !buf || len != mi_pcm_state_size(p))
-        return fail(MI_ERR_INVALID, "PCM stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(p->gpu, buf, p->d_state, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "PCM stage: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, p, &mi_pcm::d_state, buf, len);
 }
 
 int mi_pcm_set_state(mi_pcm* p, const void* buf, size_t len) {
-    if (!p || !buf || len != mi_pcm_state_size(p))
-        return fail(MI_ERR_INVALID, "PCM stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(p->gpu, p->d_state, buf, len, hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "PCM stage: writing the state failed");
-    return MI_OK;
+    return mi::set_state(kName, p, &mi_pcm::d_state, buf, len);
 }
 
 }  // extern "C"

@@ -1,9 +1,14 @@
 // poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
-// share on the host side: the error helper, argument checks, launch timing, the row scan's launcher and the splitter's blob layout.
+// share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage) with the
+// bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in and out,
+// the checks of a plane-in / plane-out call), the row scan's launcher and the blob layouts.  The device side of a stage that carries
+// samples from call to call -- the lead's load and the tails kernel -- is in carry.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "hip_own.hpp"
@@ -85,6 +90,120 @@ inline bool land_counts(int gpu, hipStream_t q, uint32_t* h_count, const uint32_
 // State and settings in or out between calls: whatever is queued on the device finishes first.
 inline bool sync_copy(int gpu, void* dst, const void* src, size_t len, hipMemcpyKind kind) {
     return hipSetDevice(gpu) == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(dst, src, len, kind) == hipSuccess;
+}
+
+// What every post-stage handle holds.  `called`: a process_device call has been made (the survey, the finder and the probe: a
+// stamped one), the precondition of last_launch_ms.
+struct Stage {
+    int gpu = 0;
+    LaunchTiming timing;
+    bool called = false;
+    Stage(const char* stage, int launches) : timing(stage, launches) {}
+};
+// ... a stage over [rows][max_batches] blocks of audio
+struct BatchStage : Stage {
+    using Stage::Stage;
+    int rows = 0;
+    int max_batches = 0;
+};
+// ... whose rows the caller switches on and off
+struct RowStage : BatchStage {
+    using BatchStage::BatchStage;
+    DevBuf<uint8_t> d_enabled;  // [rows]
+};
+
+// The bodies of the extern "C" entry points that differ between stages in nothing but the handle's type and the stage's name:
+// `stage` is the string the handle gives its LaunchTiming (a NULL handle has none to ask).  Each returns MI_OK or the refusal with
+// its message set.
+inline int batch_geometry_ok(const char* stage, int rows, int max_batches) {
+    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
+        return fail(MI_ERR_INVALID, std::string(stage) + " needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    return MI_OK;
+}
+
+inline int set_enabled(const char* stage, RowStage* s, const uint8_t* row_enabled) {
+    if (!s || !row_enabled)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    const std::vector<uint8_t> flags = as_flags(row_enabled, static_cast<size_t>(s->rows));
+    // (a call still queued reads the rows it was made with)
+    if (!sync_copy(s->gpu, s->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, std::string(stage) + ": uploading the rows failed");
+    return MI_OK;
+}
+
+inline int set_timing(Stage* s, int on) {
+    if (!s)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    return s->timing.enable(s->gpu, on != 0);
+}
+
+// `process_device`: the entry point's own name, e.g. "mi_pcm_process_device"
+inline int last_launch_ms(Stage* s, float* ms, const char* process_device) {
+    if (!s || !ms)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (!s->timing.on || !s->called)
+        return fail(MI_ERR_INVALID, std::string("no timed ") + process_device + " call");
+    return s->timing.elapsed(s->gpu, ms);
+}
+
+template <class H>
+void destroy(H* h) {
+    if (!h)
+        return;
+    (void)hipSetDevice(h->gpu);
+    delete h;
+}
+
+// The checkpoint blob, rows x RowState, as the device array `state` of the handle holds it.
+template <class H, class RowState>
+size_t state_size(const H* h, DevBuf<RowState> H::*) {
+    return h ? static_cast<size_t>(h->rows) * sizeof(RowState) : 0;
+}
+
+template <class H, class RowState>
+int get_state(const char* stage, H* h, DevBuf<RowState> H::*state, void* buf, size_t len) {
+    if (!h || !buf || len != state_size(h, state))
+        return fail(MI_ERR_INVALID, std::string(stage) + " state: NULL argument or wrong length");
+    if (!sync_copy(h->gpu, buf, h->*state, len, hipMemcpyDeviceToHost))
+        return fail(MI_ERR_HIP, std::string(stage) + ": reading the state failed");
+    return MI_OK;
+}
+
+// `malformed(rows, n)`: for a stage that checks a blob before it takes it -- NULL, or what is wrong with it in the stage's words
+template <class H, class RowState, class Check = std::nullptr_t>
+int set_state(const char* stage, H* h, DevBuf<RowState> H::*state, const void* buf, size_t len, Check malformed = nullptr) {
+    if (!h || !buf || len != state_size(h, state))
+        return fail(MI_ERR_INVALID, std::string(stage) + " state: NULL argument or wrong length");
+    std::vector<RowState> rows;  // (a checked blob is looked at, and uploaded, as an aligned copy)
+    if constexpr (!std::is_same<Check, std::nullptr_t>::value) {
+        rows.resize(static_cast<size_t>(h->rows));
+        std::memcpy(rows.data(), buf, len);
+        if (const char* const why = malformed(rows.data(), rows.size()))
+            return fail(MI_ERR_INVALID, std::string(stage) + " state: " + why);
+        buf = rows.data();
+    }
+    if (!sync_copy(h->gpu, h->*state, buf, len, hipMemcpyHostToDevice))
+        return fail(MI_ERR_HIP, std::string(stage) + ": writing the state failed");
+    return MI_OK;
+}
+
+// whether the planes [rows][stride] share a byte over a call of nbatches batches (poststage_host.cpp)
+bool planes_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches);
+
+// The checks of a call that reads a plane [rows][in_stride] and writes one [rows][out_stride] (voice band, limiter).  `in_noun`:
+// what the stage's texts call the plane it reads.
+inline int plane_call_ok(const BatchStage* s, const float* in, size_t in_stride, int nbatches, const float* out, size_t out_stride, const char* in_noun) {
+    if (!s || !in || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (nbatches < 1 || nbatches > s->max_batches)
+        return fail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
+    if (in_stride < static_cast<size_t>(nbatches) * kWaveBatch || out_stride < static_cast<size_t>(nbatches) * kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    if (in_stride % 4 != 0 || out_stride % 4 != 0 || !aligned(in, 16) || !aligned(out, 16))
+        return fail(MI_ERR_INVALID, std::string("the ") + in_noun + " and the output must be 16-byte aligned with row strides that are multiples of 4 floats");
+    if (planes_overlap(in, in_stride, out, out_stride, static_cast<size_t>(s->rows), static_cast<size_t>(nbatches)))
+        return fail(MI_ERR_INVALID, std::string("the output overlaps the ") + in_noun);
+    return MI_OK;
 }
 
 constexpr int kRowsPerGroup = 4;  // one wave per row, four rows per 256-thread workgroup
@@ -183,11 +302,9 @@ constexpr int kVbandTapRow = 512;  // floats of one class of the device's tap ta
 // What both halves of the voice band stage share (poststage_host.cpp).  vband_row_ok: MI_OK, or the settings' refusal with its
 // message set.  vband_taps: h[511] of valid settings.  vband_classes: the rows' settings (NULL = the default row everywhere)
 // checked and deduplicated in order of first appearance -- class_of[rows] and the distinct settings --, or the first refusal.
-// vband_overlap: whether the planes [rows][stride] share a byte over a call of nbatches batches.
 int vband_row_ok(const mi_vband_row& r);
 void vband_taps(const mi_vband_row& r, float* h);
 int vband_classes(const mi_vband_row* row_cfg, size_t rows, std::vector<uint32_t>& class_of, std::vector<mi_vband_row>& classes);
-bool vband_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches);
 
 // The peak limiter stage (include/mi_airband.h "peak limiter stage").  One row of its state: the checkpoint blob is an array of
 // these, and limit.hip keeps the same array in device memory.

@@ -1076,7 +1076,7 @@ int vband_classes(const mi_vband_row* row_cfg, size_t rows, std::vector<uint32_t
     return MI_OK;
 }
 
-bool vband_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches) {
+bool planes_overlap(const float* in, size_t in_stride, const float* out, size_t out_stride, size_t rows, size_t nbatches) {
     const size_t call = nbatches * static_cast<size_t>(kWaveBatch);
     const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
     const uintptr_t a_end = a + ((rows - 1) * in_stride + call) * sizeof(float), b_end = b + ((rows - 1) * out_stride + call) * sizeof(float);
@@ -1111,7 +1111,7 @@ extern "C" int mi_vband_plan_host(const mi_vband_row* row_cfg, const uint8_t* ro
         return rc;
     if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch || out_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
         return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
-    if (mi::vband_overlap(waveout, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
+    if (mi::planes_overlap(waveout, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
         return fail(MI_ERR_INVALID, "the output overlaps the audio buffer");
     mi::VbandRowState* state = static_cast<mi::VbandRowState*>(state_inout);
     std::vector<float> taps(classes.size() * MI_VBAND_TAPS);
@@ -1186,7 +1186,7 @@ extern "C" int mi_limit_plan_host(const mi_limit_row* row_cfg, const uint8_t* ro
     const size_t n = static_cast<size_t>(nbatches) * mi::kWaveBatch;
     if (row_stride < n || out_stride < n)
         return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
-    if (mi::vband_overlap(in, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
+    if (mi::planes_overlap(in, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
         return fail(MI_ERR_INVALID, "the output overlaps the input plane");
     mi::LimitRowState* state = static_cast<mi::LimitRowState*>(state_inout);
     const size_t hist = MI_LIMIT_HISTORY, look = MI_LIMIT_LOOKAHEAD;

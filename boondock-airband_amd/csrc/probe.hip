@@ -39,8 +39,8 @@ struct ProbeStream {
 }  // namespace
 }  // namespace mi
 
-struct mi_probe {
-    int gpu = 0;
+struct mi_probe : mi::Stage {
+    mi_probe() : Stage("channel probe", 2) {}
     int nstreams = 0;
     int max_cells = 0;
     int max_targets = 0;
@@ -55,8 +55,6 @@ struct mi_probe {
     mi::DevBuf<mi_probe_target> d_targets;  // [max_targets], the first ntargets
     mi::DevBuf<mi::ProbeStream> d_active;   // [nstreams], the first nactive
     mi::DevBuf<float2> d_z;                 // [max_targets][max_cells * wpc], the scratch plane
-    mi::LaunchTiming timing{"channel probe", 2};  // mi_probe_set_timing
-    bool timed = false;  // the last call was stamped
     // the last mi_probe_process_device (what mi_probe_download reads)
     const mi_probe_cell* last_cells = nullptr;
     size_t last_records = 0;
@@ -364,10 +362,7 @@ int mi_probe_create(const mi_device_cfg* dev, int nstreams, int max_cells, int w
 }
 
 void mi_probe_destroy(mi_probe* p) {
-    if (!p)
-        return;
-    (void)hipSetDevice(p->gpu);
-    delete p;
+    mi::destroy(p);
 }
 
 int mi_probe_set_targets(mi_probe* p, const mi_probe_target* targets, int ntargets) {
@@ -441,7 +436,7 @@ int mi_probe_process_device(mi_probe* p, const void* d_iq, size_t stream_stride_
     p->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "channel probe kernel launch failed");
-    p->timed = p->timing.on;
+    p->called = p->timing.on;  // (a stamped call: last_launch_ms refuses after any other)
     p->last_cells = d_cells;
     p->last_records = records;
     return MI_OK;
@@ -461,17 +456,11 @@ int mi_probe_download(mi_probe* p, void* hip_stream, mi_probe_cell* cells) {
 }
 
 int mi_probe_set_timing(mi_probe* p, int on) {
-    if (!p)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return p->timing.enable(p->gpu, on != 0);
+    return mi::set_timing(p, on);
 }
 
 int mi_probe_last_launch_ms(mi_probe* p, float* ms) {
-    if (!p || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!p->timing.on || !p->timed)
-        return fail(MI_ERR_INVALID, "no timed mi_probe_process_device call");
-    return p->timing.elapsed(p->gpu, ms);
+    return mi::last_launch_ms(p, ms, "mi_probe_process_device");
 }
 
 }  // extern "C"

@@ -27,8 +27,8 @@
 #include "fft_radix8.hpp"
 #include "poststage.hpp"
 
-struct mi_survey {
-    int gpu = 0;
+struct mi_survey : mi::Stage {
+    mi_survey() : Stage("band survey", 2) {}
     int nstreams = 0;
     int max_cells = 0;
     uint32_t wpc = 0;           // windows per cell
@@ -43,8 +43,6 @@ struct mi_survey {
     mi::DevBuf<int> d_streams;   // [nstreams], the first nenabled: the enabled streams, ascending
     mi::DevBuf<double> d_psum;   // [nstreams][max_cells][tiles][fft_size]
     mi::DevBuf<float> d_pmax;    // the same
-    mi::LaunchTiming timing{"band survey", 2};  // mi_survey_set_timing
-    bool timed = false;  // the last call was stamped
 };
 
 namespace mi {
@@ -378,10 +376,7 @@ int mi_survey_create(const mi_device_cfg* dev, int nstreams, int max_cells, int 
 }
 
 void mi_survey_destroy(mi_survey* s) {
-    if (!s)
-        return;
-    (void)hipSetDevice(s->gpu);
-    delete s;
+    mi::destroy(s);
 }
 
 int mi_survey_set_streams(mi_survey* s, const uint8_t* stream_enabled) {
@@ -443,22 +438,16 @@ int mi_survey_process_device(mi_survey* s, const void* d_iq, size_t stream_strid
     s->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "band survey kernel launch failed");
-    s->timed = s->timing.on;
+    s->called = s->timing.on;  // (a stamped call: last_launch_ms refuses after any other)
     return MI_OK;
 }
 
 int mi_survey_set_timing(mi_survey* s, int on) {
-    if (!s)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return s->timing.enable(s->gpu, on != 0);
+    return mi::set_timing(s, on);
 }
 
 int mi_survey_last_launch_ms(mi_survey* s, float* ms) {
-    if (!s || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!s->timing.on || !s->timed)
-        return fail(MI_ERR_INVALID, "no timed mi_survey_process_device call");
-    return s->timing.elapsed(s->gpu, ms);
+    return mi::last_launch_ms(s, ms, "mi_survey_process_device");
 }
 
 }  // extern "C"

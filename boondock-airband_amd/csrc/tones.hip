@@ -5,7 +5,8 @@
 // The rule, the record, the order of the sum and the state blob are in include/mi_airband.h.  A post-stage of its own like the gate
 // and the splitter: three launches on the caller's stream, no atomics.  A window never spans a MI_NO_SIGNAL batch, so it is one
 // contiguous range of the row's audio (a PIECE), which may begin in the carried state; what is left behind the last window of a call
-// is the row's TAIL piece, whose wave writes the state.  mi_tones_plan_host (poststage_host.cpp) is the host twin.
+// is the row's TAIL piece, whose wave writes the state.  mi_tones_plan_host (poststage_host.cpp) is the host twin.  The handle's base
+// and the bodies of the entry points every stage repeats are in poststage.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -15,20 +16,18 @@
 #include "../../include/mi_airband.h"
 #include "poststage.hpp"
 
-struct mi_tones {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "tone finder";
+
+struct mi_tones : mi::RowStage {
+    mi_tones() : RowStage(kName, 3) {}
     uint32_t window = 0;
     uint32_t max_records = 0;
-    mi::DevBuf<uint8_t> d_enabled;            // [rows]
     mi::DevBuf<mi::TonesRowState> d_state;    // [rows]: the checkpoint blob as it is
     mi::DevBuf<float> d_coeff;                // [64]: lane t's coefficient, 0 beyond the table
     mi::DevBuf<float> d_carry;                // [rows][2][64]: q1 and q2 as the call found them (the bank reads these, its tails write d_state)
     mi::DevBuf<uint4> d_piece;                // [rows][windows of the call + 1]: {first sample, samples, seq, meta}, the tail last
     mi::DevBuf<uint32_t> d_row_rec_count;     // [rows]
     mi::PinnedBuf<uint32_t> h_count;          // [2], landing place of the counts in mi_tones_download
-    mi::LaunchTiming timing{"tone finder", 3};  // mi_tones_set_timing
     // destinations of the last mi_tones_process_device (what mi_tones_download reads)
     const mi_tone_record* last_records = nullptr;
     const float* last_powers = nullptr;
@@ -249,20 +248,11 @@ int mi_tones_create(const mi_tones_cfg* cfg, const uint8_t* row_enabled, int row
 }
 
 void mi_tones_destroy(mi_tones* t) {
-    if (!t)
-        return;
-    (void)hipSetDevice(t->gpu);
-    delete t;
+    mi::destroy(t);
 }
 
 int mi_tones_set_rows(mi_tones* t, const uint8_t* row_enabled) {
-    if (!t || !row_enabled)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    const std::vector<uint8_t> flags = as_flags(row_enabled, static_cast<size_t>(t->rows));
-    // (a call still queued reads the rows it was made with)
-    if (!mi::sync_copy(t->gpu, t->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "tone finder: uploading the rows failed");
-    return MI_OK;
+    return mi::set_enabled(kName, t, row_enabled);
 }
 
 int mi_tones_process_device(mi_tones* t, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
@@ -294,6 +284,7 @@ int mi_tones_process_device(mi_tones* t, const float* d_waveout, size_t row_stri
     t->timing.stamp(3, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "tone finder kernel launch failed");
+    t->called = true;
     t->last_records = d_records;
     t->last_powers = d_powers;
     t->last_row_first = d_row_first_record;
@@ -326,41 +317,25 @@ int mi_tones_download(mi_tones* t, void* hip_stream, mi_tone_record* records, fl
 }
 
 int mi_tones_set_timing(mi_tones* t, int on) {
-    if (!t)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return t->timing.enable(t->gpu, on != 0);
+    return mi::set_timing(t, on);
 }
 
 int mi_tones_last_launch_ms(mi_tones* t, float* ms) {
-    if (!t || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!t->timing.on || !t->last_count)
-        return fail(MI_ERR_INVALID, "no timed mi_tones_process_device call");
-    return t->timing.elapsed(t->gpu, ms);
+    return mi::last_launch_ms(t, ms, "mi_tones_process_device");
 }
 
 size_t mi_tones_state_size(const mi_tones* t) {
-    return t ? static_cast<size_t>(t->rows) * sizeof(mi::TonesRowState) : 0;
+    return mi::state_size(t, &mi_tones::d_state);
 }
 
 int mi_tones_get_state(mi_tones* t, void* buf, size_t len) {
-    if (!t || !buf || len != mi_tones_state_size(t))
-        return fail(MI_ERR_INVALID, "tone finder state: NULL argument or wrong length");
-    if (!mi::sync_copy(t->gpu, buf, t->d_state, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "tone finder: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, t, &mi_tones::d_state, buf, len);
 }
 
 int mi_tones_set_state(mi_tones* t, const void* buf, size_t len) {
-    if (!t || !buf || len != mi_tones_state_size(t))
-        return fail(MI_ERR_INVALID, "tone finder state: NULL argument or wrong length");
-    std::vector<mi::TonesRowState> rows(static_cast<size_t>(t->rows));
-    std::memcpy(rows.data(), buf, len);
-    if (!mi::tones_state_ok(rows.data(), rows.size(), t->window))
-        return fail(MI_ERR_INVALID, "tone finder state: malformed blob (count >= window or a padding lane not zero)");
-    if (!mi::sync_copy(t->gpu, t->d_state, rows.data(), len, hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "tone finder: writing the state failed");
-    return MI_OK;
+    return mi::set_state(kName, t, &mi_tones::d_state, buf, len, [t](const mi::TonesRowState* rows, size_t n) {
+        return mi::tones_state_ok(rows, n, t->window) ? nullptr : "malformed blob (count >= window or a padding lane not zero)";
+    });
 }
 
 }  // extern "C"

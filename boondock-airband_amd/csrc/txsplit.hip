@@ -6,7 +6,8 @@
 // restated on the jitter-free schedule (batch b of a row at t0 + b * WAVE_BATCH / WAVE_RATE), so every time is a count of batches:
 // the rule, the thresholds, the record, the order of `energy` and the state blob are in include/mi_airband.h.  A post-stage of its
 // own like the gate (outgate.hip), whose MI_GATE_OPEN_TRAIL rule lets the same blocks travel: four small launches on the caller's
-// stream, no atomics.  mi_tx_plan_host (poststage_host.cpp) is the host twin.
+// stream, no atomics.  mi_tx_plan_host (poststage_host.cpp) is the host twin.  The handle's base and the bodies of the entry points
+// every stage repeats are in poststage.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -16,13 +17,12 @@
 #include "../../include/mi_airband.h"
 #include "poststage.hpp"
 
-struct mi_txsplit {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "transmission splitter";
+
+struct mi_txsplit : mi::RowStage {
+    mi_txsplit() : RowStage(kName, 4) {}
     uint32_t max_records = 0;
     mi_tx_cfg cfg{};
-    mi::DevBuf<uint8_t> d_enabled;         // [rows]
     mi::DevBuf<mi::TxRowState> d_state;    // [rows]: the checkpoint blob as it is
     mi::DevBuf<int> d_rank;                // [rows][nbatches of the call]: place among the row's travelling blocks, -1 = does not travel
     mi::DevBuf<mi_tx_record> d_row_rec;    // [rows][nbatches + 1]: the walk's records, peak and energy still 0
@@ -30,7 +30,6 @@ struct mi_txsplit {
     mi::DevBuf<double> d_block_sum;        // [rows][nbatches]: sum of x * x of the row's travelling block number `rank`
     mi::DevBuf<float> d_block_peak;        // the same for max |x|
     mi::PinnedBuf<uint32_t> h_count;       // [2], landing place of the counts in mi_txsplit_download
-    mi::LaunchTiming timing{"transmission splitter", 4};  // mi_txsplit_set_timing
     // destinations of the last mi_txsplit_process_device (what mi_txsplit_download reads)
     const mi_tx_record* last_records = nullptr;
     const uint32_t* last_row_first = nullptr;
@@ -280,20 +279,11 @@ int mi_txsplit_create(const mi_tx_cfg* cfg, const uint8_t* row_enabled, int rows
 }
 
 void mi_txsplit_destroy(mi_txsplit* t) {
-    if (!t)
-        return;
-    (void)hipSetDevice(t->gpu);
-    delete t;
+    mi::destroy(t);
 }
 
 int mi_txsplit_set_rows(mi_txsplit* t, const uint8_t* row_enabled) {
-    if (!t || !row_enabled)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    const std::vector<uint8_t> flags = as_flags(row_enabled, static_cast<size_t>(t->rows));
-    // (a call still queued reads the rows it was made with)
-    if (!mi::sync_copy(t->gpu, t->d_enabled, flags.data(), flags.size(), hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "transmission splitter: uploading the rows failed");
-    return MI_OK;
+    return mi::set_enabled(kName, t, row_enabled);
 }
 
 int mi_txsplit_process_device(mi_txsplit* t, const float* d_waveout, size_t row_stride, const char* d_axc, size_t axc_stride, int nbatches,
@@ -327,6 +317,7 @@ int mi_txsplit_process_device(mi_txsplit* t, const float* d_waveout, size_t row_
     t->timing.stamp(4, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "transmission splitter kernel launch failed");
+    t->called = true;
     t->last_records = d_records;
     t->last_row_first = d_row_first_record;
     t->last_count = d_count;
@@ -354,42 +345,28 @@ int mi_txsplit_download(mi_txsplit* t, void* hip_stream, mi_tx_record* records, 
 }
 
 int mi_txsplit_set_timing(mi_txsplit* t, int on) {
-    if (!t)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return t->timing.enable(t->gpu, on != 0);
+    return mi::set_timing(t, on);
 }
 
 int mi_txsplit_last_launch_ms(mi_txsplit* t, float* ms) {
-    if (!t || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!t->timing.on || !t->last_count)
-        return fail(MI_ERR_INVALID, "no timed mi_txsplit_process_device call");
-    return t->timing.elapsed(t->gpu, ms);
+    return mi::last_launch_ms(t, ms, "mi_txsplit_process_device");
 }
 
 size_t mi_txsplit_state_size(const mi_txsplit* t) {
-    return t ? static_cast<size_t>(t->rows) * sizeof(mi::TxRowState) : 0;
+    return mi::state_size(t, &mi_txsplit::d_state);
 }
 
 int mi_txsplit_get_state(mi_txsplit* t, void* buf, size_t len) {
-    if (!t || !buf || len != mi_txsplit_state_size(t))
-        return fail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
-    if (!mi::sync_copy(t->gpu, buf, t->d_state, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "transmission splitter: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, t, &mi_txsplit::d_state, buf, len);
 }
 
 int mi_txsplit_set_state(mi_txsplit* t, const void* buf, size_t len) {
-    if (!t || !buf || len != mi_txsplit_state_size(t))
-        return fail(MI_ERR_INVALID, "transmission splitter state: NULL argument or wrong length");
-    std::vector<mi::TxRowState> rows(static_cast<size_t>(t->rows));
-    std::memcpy(rows.data(), buf, len);
-    for (const mi::TxRowState& s : rows)
-        if (s.open > 1 || s.active > 1 || s.zero != 0)
-            return fail(MI_ERR_INVALID, "transmission splitter state: malformed blob");
-    if (!mi::sync_copy(t->gpu, t->d_state, rows.data(), len, hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "transmission splitter: writing the state failed");
-    return MI_OK;
+    return mi::set_state(kName, t, &mi_txsplit::d_state, buf, len, [](const mi::TxRowState* rows, size_t n) -> const char* {
+        for (size_t r = 0; r < n; ++r)
+            if (rows[r].open > 1 || rows[r].active > 1 || rows[r].zero != 0)
+                return "malformed blob";
+        return nullptr;
+    });
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // The reference shapes the band inside its MP3 encoder; the device chain has none, so the two keys act here.  The taps, the order of
 // the sum, the clamp and the state blob are in include/mi_airband.h.  A post-stage of its own like the PCM stage: two launches on
 // the caller's stream, no atomics.  It writes a plane in the layout of the one it reads.  mi_vband_plan_host (poststage_host.cpp) is
-// the host twin.
+// the host twin.  The handle's base and the bodies of the entry points every stage repeats are in poststage.hpp, the lead's load
+// and the tails kernel in carry.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -12,24 +13,21 @@
 #include <vector>
 
 #include "../../include/mi_airband.h"
+#include "carry.hpp"
 #include "poststage.hpp"
 
-struct mi_vband {
-    int gpu = 0;
-    int rows = 0;
-    int max_batches = 0;
+constexpr char kName[] = "voice band stage";
+
+struct mi_vband : mi::RowStage {
+    mi_vband() : RowStage(kName, 2) {}
     size_t classes_cap = 0;                  // classes d_taps has room for
-    mi::DevBuf<uint8_t> d_enabled;           // [rows]
     mi::DevBuf<uint32_t> d_class;            // [rows]: the row's class of settings
     mi::DevBuf<float> d_taps;                // [classes][512]: the 511 taps of a class and a zero
     mi::DevBuf<mi::VbandRowState> d_state;   // [rows]: the checkpoint blob as it is
-    mi::LaunchTiming timing{"voice band stage", 2};  // mi_vband_set_timing
-    bool called = false;
 };
 
 namespace {
 
-using mi::aligned;
 using mi::as_flags;
 using mi::fail;
 constexpr int kThreads = 256;
@@ -40,7 +38,7 @@ constexpr int kRun = 8;                  // consecutive outputs of one thread
 constexpr int kOwners = kBatch / kRun;   // 250 threads own outputs
 constexpr int kChunks = kTaps / kRun;    // 63 whole chunks of 8 taps; 7 taps behind them
 constexpr unsigned kMaxGrid = 2048;      // 8 workgroups on each of 256 CUs; a workgroup strides on from there
-static_assert(kLead >= MI_VBAND_HISTORY && kLead % 8 == 0 && kBatch % kRun == 0 && kOwners <= kThreads && kRun == 8, "a thread's run is two float4");
+static_assert(kLead % 8 == 0 && kBatch % kRun == 0 && kOwners <= kThreads && kRun == 8, "a thread's run is two float4");
 static_assert(kLead - kRun * (kChunks + 1) >= 0 && kTaps - kRun * kChunks == 7 && mi::kVbandTapRow == 512 && kChunks % 2 == 1,
               "the last chunk's window begins at the lead's first float");
 static_assert(mi::kVbandTapRow / 4 <= kThreads && MI_VBAND_HISTORY <= 2 * kThreads, "one float4 of taps per lane; the tails in two trips");
@@ -82,15 +80,7 @@ __global__ __launch_bounds__(kThreads) void k_vband_filter(const uint8_t* __rest
             reinterpret_cast<float4*>(hs)[t] = reinterpret_cast<const float4*>(taps + static_cast<size_t>(class_of[row]) * mi::kVbandTapRow)[t];
         int live = 0;
         for (int q = t; q < (kLead + kBatch) / 4; q += kThreads) {
-            float4 v;
-            if (q >= kLead / 4 || batch != 0) {
-                v = reinterpret_cast<const float4*>(blk - kLead)[q];
-            } else {  // floats 4q .. 4q + 3 of the lead are carried samples 4q - 2 .. 4q + 1
-                const float* const c = state[row].x + 4 * q;
-                const float2 a = q ? *reinterpret_cast<const float2*>(c - 2) : make_float2(0.0f, 0.0f);
-                const float2 b = *reinterpret_cast<const float2*>(c);
-                v = make_float4(a.x, a.y, b.x, b.y);
-            }
+            float4 v = mi::load_lead4<kLead>(blk, state[row], q, batch == 0);
             if (q == 0)  // (no output reaches the lead's first two floats)
                 v.x = v.y = 0.0f;
             live |= (v.x != 0.0f || v.y != 0.0f || v.z != 0.0f || v.w != 0.0f) ? 1 : 0;
@@ -127,17 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_vband_filter(const uint8_t* __rest
     }
 }
 
-// Launch 2, behind the filter in the stream, which read the old ones: the last 510 input samples of the call are an enabled row's
-// new carried samples.  One workgroup per row.
-__global__ __launch_bounds__(kThreads) void k_vband_tails(const uint8_t* __restrict__ enabled, const float* __restrict__ wave, const size_t row_stride,
-                                                          const uint32_t rows, const uint32_t nbatches, mi::VbandRowState* __restrict__ state) {
-    const uint32_t row = blockIdx.x;
-    if (row >= rows || !enabled[row])
-        return;
-    const float* const tail = wave + static_cast<size_t>(row) * row_stride + static_cast<size_t>(nbatches) * kBatch - MI_VBAND_HISTORY;
-    for (int j = threadIdx.x; j < MI_VBAND_HISTORY; j += kThreads)
-        state[row].x[j] = tail[j];
-}
+// Launch 2.  mi::k_carry_tails (carry.hpp): the last 510 input samples of the call are an enabled row's new carried samples.
 
 // the classes' taps and the rows' classes onto the device (the caller has completed queued work where a call may read them)
 int upload_settings(mi_vband* v, const std::vector<uint32_t>& class_of, const std::vector<mi_vband_row>& classes) {
@@ -163,8 +143,8 @@ extern "C" {
 int mi_vband_create(const mi_vband_row* row_cfg, const uint8_t* row_enabled, int rows, int max_batches, int gpu, mi_vband** out) {
     if (!row_enabled || !out)
         return fail(MI_ERR_INVALID, "NULL argument");
-    if (rows < 1 || rows >= (1 << 20) || max_batches < 1 || static_cast<uint64_t>(rows) * static_cast<uint64_t>(max_batches) >= (1ull << 24))
-        return fail(MI_ERR_INVALID, "voice band stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24");
+    if (const int rc = mi::batch_geometry_ok(kName, rows, max_batches))
+        return rc;
     std::vector<uint32_t> class_of;
     std::vector<mi_vband_row> classes;
     const size_t n = static_cast<size_t>(rows);
@@ -186,10 +166,7 @@ int mi_vband_create(const mi_vband_row* row_cfg, const uint8_t* row_enabled, int
 }
 
 void mi_vband_destroy(mi_vband* v) {
-    if (!v)
-        return;
-    (void)hipSetDevice(v->gpu);
-    delete v;
+    mi::destroy(v);
 }
 
 int mi_vband_set_rows(mi_vband* v, const mi_vband_row* row_cfg, const uint8_t* row_enabled) {
@@ -216,16 +193,8 @@ int mi_vband_set_rows(mi_vband* v, const mi_vband_row* row_cfg, const uint8_t* r
 }
 
 int mi_vband_process_device(mi_vband* v, const float* d_waveout, size_t row_stride, int nbatches, float* d_out, size_t out_stride, void* hip_stream) {
-    if (!v || !d_waveout || !d_out)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (nbatches < 1 || nbatches > v->max_batches)
-        return fail(MI_ERR_INVALID, "nbatches outside 1 .. max_batches");
-    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch || out_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
-        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
-    if (row_stride % 4 != 0 || out_stride % 4 != 0 || !aligned(d_waveout, 16) || !aligned(d_out, 16))
-        return fail(MI_ERR_INVALID, "the audio buffer and the output must be 16-byte aligned with row strides that are multiples of 4 floats");
-    if (mi::vband_overlap(d_waveout, row_stride, d_out, out_stride, static_cast<size_t>(v->rows), static_cast<size_t>(nbatches)))
-        return fail(MI_ERR_INVALID, "the output overlaps the audio buffer");
+    if (const int rc = mi::plane_call_ok(v, d_waveout, row_stride, nbatches, d_out, out_stride, "audio buffer"))
+        return rc;
     if (hipSetDevice(v->gpu) != hipSuccess)
         return fail(MI_ERR_HIP, "hipSetDevice failed");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
@@ -234,8 +203,7 @@ int mi_vband_process_device(mi_vband* v, const float* d_waveout, size_t row_stri
     hipLaunchKernelGGL(k_vband_filter, dim3(call < kMaxGrid ? call : kMaxGrid), dim3(kThreads), 0, q, v->d_enabled.get(), v->d_class.get(), v->d_taps.get(),
                        d_waveout, row_stride, rows, static_cast<uint32_t>(nbatches), v->d_state.get(), d_out, out_stride);
     v->timing.stamp(1, q);
-    hipLaunchKernelGGL(k_vband_tails, dim3(rows), dim3(kThreads), 0, q, v->d_enabled.get(), d_waveout, row_stride, rows, static_cast<uint32_t>(nbatches),
-                       v->d_state.get());
+    mi::launch_carry_tails<MI_VBAND_HISTORY>(q, v->d_enabled.get(), d_waveout, row_stride, rows, nbatches, v->d_state.get());
     v->timing.stamp(2, q);
     if (hipGetLastError() != hipSuccess)
         return fail(MI_ERR_HIP, "voice band stage kernel launch failed");
@@ -244,37 +212,23 @@ int mi_vband_process_device(mi_vband* v, const float* d_waveout, size_t row_stri
 }
 
 int mi_vband_set_timing(mi_vband* v, int on) {
-    if (!v)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    return v->timing.enable(v->gpu, on != 0);
+    return mi::set_timing(v, on);
 }
 
 int mi_vband_last_launch_ms(mi_vband* v, float* ms) {
-    if (!v || !ms)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    if (!v->timing.on || !v->called)
-        return fail(MI_ERR_INVALID, "no timed mi_vband_process_device call");
-    return v->timing.elapsed(v->gpu, ms);
+    return mi::last_launch_ms(v, ms, "mi_vband_process_device");
 }
 
 size_t mi_vband_state_size(const mi_vband* v) {
-    return v ? static_cast<size_t>(v->rows) * sizeof(mi::VbandRowState) : 0;
+    return mi::state_size(v, &mi_vband::d_state);
 }
 
 int mi_vband_get_state(mi_vband* v, void* buf, size_t len) {
-    if (!v || !buf || len != mi_vband_state_size(v))
-        return fail(MI_ERR_INVALID, "voice band stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(v->gpu, buf, v->d_state, len, hipMemcpyDeviceToHost))
-        return fail(MI_ERR_HIP, "voice band stage: reading the state failed");
-    return MI_OK;
+    return mi::get_state(kName, v, &mi_vband::d_state, buf, len);
 }
 
 int mi_vband_set_state(mi_vband* v, const void* buf, size_t len) {
-    if (!v || !buf || len != mi_vband_state_size(v))
-        return fail(MI_ERR_INVALID, "voice band stage state: NULL argument or wrong length");
-    if (!mi::sync_copy(v->gpu, v->d_state, buf, len, hipMemcpyHostToDevice))
-        return fail(MI_ERR_HIP, "voice band stage: writing the state failed");
-    return MI_OK;
+    return mi::set_state(kName, v, &mi_vband::d_state, buf, len);
 }
 
 }  // extern "C"

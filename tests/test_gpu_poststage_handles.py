@@ -1,5 +1,6 @@
-"""What the handle classes of the Python binding share: close() twice on every class, and the per-launch timing of the output gate and
-the transmission splitter (set_timing / last_launch_ms), at 5 rows x 3 batches."""
+"""What the handle classes of the Python binding share: close() twice on every class, and the per-launch timing of the output gate, the
+transmission splitter, the tone finder, the PCM stage, the voice band stage and the limiter stage (set_timing / last_launch_ms), at 5 rows
+x 3 batches."""
 import math
 
 import numpy as np
@@ -31,13 +32,21 @@ def test_plan_closes_twice(pkg):
     lambda pkg: pkg.Mixer([(0, 1.0, 0.0), (1, 0.5, -0.5)]),
     lambda pkg: pkg.OutputGate(np.full(ROWS, pkg.GATE_OPEN, np.uint8), max_batches=NB),
     lambda pkg: pkg.TxSplit(np.ones(ROWS), max_batches=NB),
-], ids=["Demod", "Gather", "Mixer", "OutputGate", "TxSplit"])
+    lambda pkg: pkg.Tones(np.ones(ROWS), max_batches=NB),
+    lambda pkg: pkg.Pcm(np.ones(ROWS), max_batches=NB),
+    lambda pkg: pkg.Aspec(ROWS, max_batches=NB),
+    lambda pkg: pkg.Vband(np.ones(ROWS), max_batches=NB),
+    lambda pkg: pkg.Limit(np.ones(ROWS), max_batches=NB),
+    lambda pkg: pkg.Survey(pkg.device_cfg(fft_size_log=8), nstreams=1, max_cells=1),
+    lambda pkg: pkg.Occupancy(pkg.device_cfg(fft_size_log=8), nstreams=1, max_cells=1),
+    lambda pkg: pkg.Probe(pkg.device_cfg(fft_size_log=8), nstreams=1, max_cells=1),
+], ids=["Demod", "Gather", "Mixer", "OutputGate", "TxSplit", "Tones", "Pcm", "Aspec", "Vband", "Limit", "Survey", "Occupancy", "Probe"])
 def test_handle_closes_twice(pkg, make):
     closes_twice(make(pkg))
 
 
 @gpu
-@pytest.mark.parametrize("stage,launches", [("OutputGate", 3), ("TxSplit", 4)])
+@pytest.mark.parametrize("stage,launches", [("OutputGate", 3), ("TxSplit", 4), ("Tones", 3), ("Pcm", 2), ("Vband", 2), ("Limit", 2)])
 def test_launch_timing(pkg, stage, launches):
     import torch
     rng = np.random.default_rng(launches)
@@ -55,6 +64,30 @@ def test_launch_timing(pkg, stage, launches):
             h.process_device(wave.data_ptr(), NB * WAVE_BATCH, axc.data_ptr(), NB, NB, blocks.data_ptr(), index.data_ptr(), row_first.data_ptr(),
                              count.data_ptr(), hip_stream=s)
             return h.download(s)[4]
+    elif stage == "Tones":
+        h = pkg.Tones(np.ones(ROWS), max_batches=NB)
+        records = torch.zeros(h.max_records * pkg.TONE_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+
+        def call():
+            h.process_device(wave.data_ptr(), NB * WAVE_BATCH, axc.data_ptr(), NB, NB, records.data_ptr(), row_first.data_ptr(), count.data_ptr(),
+                             hip_stream=s)
+            return h.download(s)[3]
+    elif stage == "Pcm":
+        h = pkg.Pcm(np.ones(ROWS), max_batches=NB)
+        index, _, n, _ = pkg.gate_plan_host(np.full(ROWS, pkg.GATE_OPEN, np.uint8), axc.cpu().numpy())
+        d_index = torch.from_numpy(np.ascontiguousarray(index).view(np.int32)).cuda()
+        d_n = torch.from_numpy(n.view(np.int32)).cuda()
+        blocks = torch.zeros(ROWS * NB * h.block_bytes, dtype=torch.uint8, device="cuda")
+
+        def call():
+            h.process_device(wave.data_ptr(), NB * WAVE_BATCH, NB, d_index.data_ptr(), d_n.data_ptr(), blocks.data_ptr(), hip_stream=s)
+            return h.download(s)[1]
+    elif stage in ("Vband", "Limit"):
+        h = getattr(pkg, stage)(np.ones(ROWS), max_batches=NB)
+        plane = torch.zeros_like(wave)
+
+        def call():
+            h.process_device(wave.data_ptr(), NB * WAVE_BATCH, NB, plane.data_ptr(), NB * WAVE_BATCH, hip_stream=s)
     else:
         h = pkg.TxSplit(np.ones(ROWS), max_batches=NB)
         records = torch.zeros(ROWS * (NB + 1) * pkg.TX_RECORD_DTYPE.itemsize, dtype=torch.uint8, device="cuda")

@@ -1,5 +1,5 @@
-"""What the post-stages refuse, and in which words, without a GPU: the output gate, the transmission splitter, the mixer and the two host
-twins.  Every code and text below was copied from the sources as they stood before the stages came to share one error helper and one set
+"""What the post-stages refuse, and in which words, without a GPU: the output gate, the transmission splitter, the tone finder, the PCM,
+voice band and limiter stages, the mixer and the two host twins.  Every code and text below was copied from the sources as they stood before the stages came to share one error helper and one set
 of argument checks; a call that is refused must be refused with the same code and the same bytes of mi_last_error() after it."""
 import ctypes as C
 
@@ -83,6 +83,131 @@ def test_transmission_splitter(pkg, L):
     refused(pkg, L.mi_txsplit_set_state(None, ptr(some), 32), INVALID, TX_STATE)
     assert L.mi_txsplit_state_size(None) == 0
     L.mi_txsplit_destroy(None)
+
+
+GEOMETRY_PAIRS = ((0, 1), (-1, 1), (1 << 20, 1), (4, 0), (4, -1), (1 << 12, 1 << 12), ((1 << 20) - 1, 17))  # (the gate's)
+TONES_GEOMETRY = b"tone finder needs 1 <= rows < 2^20, 1 <= max_batches <= 2^20 and rows * ((window - 1 + 2000 * max_batches) / window) < 2^24"
+TONES_WINDOW = b"tone finder: window_samples outside 800 .. 64000 (0 = the default 6400)"
+TONES_STATE = b"tone finder state: NULL argument or wrong length"
+PCM_GEOMETRY = b"PCM stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24"
+PCM_RATE = b"PCM stage: rate must be 8000 or 16000 (0 = 8000)"
+PCM_FORMAT = b"PCM stage: format must be MI_PCM_S16 or MI_PCM_IMA4 (0 = MI_PCM_S16)"
+PCM_STATE = b"PCM stage state: NULL argument or wrong length"
+VBAND_GEOMETRY = b"voice band stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24"
+VBAND_STATE = b"voice band stage state: NULL argument or wrong length"
+LIMIT_GEOMETRY = b"limiter stage needs 1 <= rows < 2^20, max_batches >= 1 and rows * max_batches < 2^24"
+LIMIT_STATE = b"limiter stage state: NULL argument or wrong length"
+
+
+def test_tone_finder(pkg, L):
+    out = C.c_void_p()
+    en, some = np.ones(4, np.uint8), np.zeros(64, np.uint8)
+    cfg = pkg.TonesCfg(0)
+    create = L.mi_tones_create
+    refused(pkg, create(C.byref(cfg), None, 4, 1, 0, 0, C.byref(out)), INVALID, NULL)
+    refused(pkg, create(C.byref(cfg), ptr(en), 4, 1, 0, 0, None), INVALID, NULL)
+    # the gate's pairs as far as the finder's own rule refuses them (its product counts windows, 2000 * max_batches / 6400 of them, so
+    # the gate's last two pass it), then that rule's own edges: max_batches over 2^20 and the product on both of its sides
+    for rows, max_batches in GEOMETRY_PAIRS[:5] + ((4, (1 << 20) + 1), (1 << 12, 1 << 14), ((1 << 20) - 1, 52)):
+        refused(pkg, create(None, ptr(en), rows, max_batches, 0, 0, C.byref(out)), INVALID, TONES_GEOMETRY)
+    for window in (1, 799, 64001, 0xFFFFFFFF):
+        refused(pkg, create(C.byref(pkg.TonesCfg(window)), ptr(en), 4, 1, 0, 0, C.byref(out)), INVALID, TONES_WINDOW)
+    refused(pkg, create(C.byref(pkg.TonesCfg(799)), None, 0, 1, 0, 0, C.byref(out)), INVALID, NULL)  # the order: NULL, the window, the geometry
+    refused(pkg, create(C.byref(pkg.TonesCfg(799)), ptr(en), 0, 1, 0, 0, C.byref(out)), INVALID, TONES_WINDOW)
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, create(None, ptr(en), 4, 1, 0, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the tone finder runs on the GPU only")
+        refused(pkg, create(C.byref(pkg.TonesCfg(800)), ptr(en), 4, 2, 3, -1, C.byref(out)), NO_DEVICE,
+                b"no HIP device: the tone finder runs on the GPU only")
+        assert not out.value
+    refused(pkg, L.mi_tones_set_rows(None, ptr(en)), INVALID, NULL)
+    refused(pkg, L.mi_tones_process_device(None, ptr(some), 0, ptr(some), 0, 1, ptr(some), None, ptr(some), ptr(some), None), INVALID, NULL)
+    refused(pkg, L.mi_tones_download(None, None, None, None, None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_tones_set_timing(None, 1), INVALID, NULL)
+    refused(pkg, L.mi_tones_last_launch_ms(None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_tones_get_state(None, ptr(some), 520), INVALID, TONES_STATE)
+    refused(pkg, L.mi_tones_set_state(None, ptr(some), 520), INVALID, TONES_STATE)
+    assert L.mi_tones_state_size(None) == 0
+    L.mi_tones_destroy(None)
+
+
+def test_pcm_stage(pkg, L):
+    out = C.c_void_p()
+    en, some = np.ones(4, np.uint8), np.zeros(64, np.uint8)
+    cfg = pkg.PcmCfg(0, 0)
+    create = L.mi_pcm_create
+    refused(pkg, create(C.byref(cfg), None, 4, 1, 0, 0, C.byref(out)), INVALID, NULL)
+    refused(pkg, create(C.byref(cfg), ptr(en), 4, 1, 0, 0, None), INVALID, NULL)
+    for rows, max_batches in GEOMETRY_PAIRS:
+        refused(pkg, create(None, ptr(en), rows, max_batches, 0, 0, C.byref(out)), INVALID, PCM_GEOMETRY)
+    for rate in (1, 7999, 44100, 0xFFFFFFFF):
+        refused(pkg, create(C.byref(pkg.PcmCfg(rate, 0)), ptr(en), 4, 1, 0, 0, C.byref(out)), INVALID, PCM_RATE)
+    for fmt in (3, 0xFFFFFFFF):
+        refused(pkg, create(C.byref(pkg.PcmCfg(16000, fmt)), ptr(en), 4, 1, 0, 0, C.byref(out)), INVALID, PCM_FORMAT)
+    refused(pkg, create(C.byref(pkg.PcmCfg(1, 3)), None, 0, 1, 0, 0, C.byref(out)), INVALID, NULL)  # the order: NULL, rate, format, the geometry
+    refused(pkg, create(C.byref(pkg.PcmCfg(1, 3)), ptr(en), 0, 1, 0, 0, C.byref(out)), INVALID, PCM_RATE)
+    refused(pkg, create(C.byref(pkg.PcmCfg(8000, 3)), ptr(en), 0, 1, 0, 0, C.byref(out)), INVALID, PCM_FORMAT)
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, create(None, ptr(en), 4, 1, 0, 0, C.byref(out)), NO_DEVICE, b"no HIP device: the PCM stage runs on the GPU only")
+        refused(pkg, create(C.byref(pkg.PcmCfg(16000, pkg.PCM_IMA4)), ptr(en), 4, 2, 3, -1, C.byref(out)), NO_DEVICE,
+                b"no HIP device: the PCM stage runs on the GPU only")
+        assert not out.value
+    refused(pkg, L.mi_pcm_set_rows(None, ptr(en)), INVALID, NULL)
+    refused(pkg, L.mi_pcm_process_device(None, ptr(some), 0, 1, ptr(some), ptr(some), ptr(some), None), INVALID, NULL)
+    refused(pkg, L.mi_pcm_download(None, None, None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_pcm_set_timing(None, 1), INVALID, NULL)
+    refused(pkg, L.mi_pcm_last_launch_ms(None, ptr(some)), INVALID, NULL)
+    refused(pkg, L.mi_pcm_get_state(None, ptr(some), 248), INVALID, PCM_STATE)
+    refused(pkg, L.mi_pcm_set_state(None, ptr(some), 248), INVALID, PCM_STATE)
+    assert L.mi_pcm_state_size(None) == 0
+    L.mi_pcm_destroy(None)
+
+
+def plane_stage(pkg, L, prefix, row_dtype, good, bad_rows, geometry, state_text, state_row_bytes, no_device):
+    """mi_vband_* and mi_limit_* have one shape: (row_cfg, row_enabled, rows, max_batches, gpu, out), settings looked at behind the geometry"""
+    out = C.c_void_p()
+    en, some = np.ones(4, np.uint8), np.zeros(64, np.uint8)
+    cfg = np.array([good] * 4, row_dtype)
+    create = getattr(L, prefix + "_create")
+    refused(pkg, create(ptr(cfg), None, 4, 1, 0, C.byref(out)), INVALID, NULL)
+    refused(pkg, create(ptr(cfg), ptr(en), 4, 1, 0, None), INVALID, NULL)
+    for rows, max_batches in GEOMETRY_PAIRS:
+        refused(pkg, create(None, ptr(en), rows, max_batches, 0, C.byref(out)), INVALID, geometry)
+    for bad, text in bad_rows:
+        worse = np.array([good, good, bad, good], row_dtype)  # (one row is enough, wherever it stands)
+        refused(pkg, create(ptr(worse), ptr(en), 4, 1, 0, C.byref(out)), INVALID, text)
+        refused(pkg, create(ptr(worse), None, 0, 1, 0, C.byref(out)), INVALID, NULL)  # the order: NULL, the geometry, the settings
+        refused(pkg, create(ptr(worse), ptr(en), 4, 0, 0, C.byref(out)), INVALID, geometry)
+    assert not out.value
+    if pkg.device_count() < 1:
+        refused(pkg, create(None, ptr(en), 4, 1, 0, C.byref(out)), NO_DEVICE, no_device)
+        refused(pkg, create(ptr(cfg), ptr(en), 4, 2, -1, C.byref(out)), NO_DEVICE, no_device)
+        assert not out.value
+    refused(pkg, getattr(L, prefix + "_set_rows")(None, ptr(cfg), ptr(en)), INVALID, NULL)
+    refused(pkg, getattr(L, prefix + "_process_device")(None, ptr(some), 0, 1, ptr(some), 0, None), INVALID, NULL)
+    refused(pkg, getattr(L, prefix + "_set_timing")(None, 1), INVALID, NULL)
+    refused(pkg, getattr(L, prefix + "_last_launch_ms")(None, ptr(some)), INVALID, NULL)
+    refused(pkg, getattr(L, prefix + "_get_state")(None, ptr(some), state_row_bytes), INVALID, state_text)
+    refused(pkg, getattr(L, prefix + "_set_state")(None, ptr(some), state_row_bytes), INVALID, state_text)
+    assert getattr(L, prefix + "_state_size")(None) == 0
+    getattr(L, prefix + "_destroy")(None)
+
+
+def test_voice_band_stage(pkg, L):
+    hp, lp, gap = (b"voice band stage: hp_hz must be 0 or 50 .. 4000", b"voice band stage: lp_hz must be 0 or 500 .. 7800",
+                   b"voice band stage: lp_hz must be 0 or at least hp_hz + 200")
+    bad_rows = [((49, 2500), hp), ((4001, 0), hp), ((100, 499), lp), ((100, 7801), lp), ((400, 599), gap), ((4001, 499), hp)]
+    plane_stage(pkg, L, "mi_vband", pkg.VBAND_ROW_DTYPE, (100, 2500), bad_rows, VBAND_GEOMETRY, VBAND_STATE, 2040,
+                b"no HIP device: the voice band stage runs on the GPU only")
+
+
+def test_limiter_stage(pkg, L):
+    pregain, ceiling = b"limiter stage: pregain must be finite and within 2^-10 .. 2^10", b"limiter stage: ceiling must be finite and within 0.0625 .. 1"
+    bad_rows = [((0.0009765624, 0.5), pregain), ((1024.0001, 0.5), pregain), ((float("nan"), 0.5), pregain), ((float("inf"), 0.5), pregain),
+                ((1.0, 0.0624), ceiling), ((1.0, 1.0000001), ceiling), ((1.0, float("nan")), ceiling), ((0.0, 2.0), pregain)]
+    plane_stage(pkg, L, "mi_limit", pkg.LIMIT_ROW_DTYPE, (1.0, 0.5), bad_rows, LIMIT_GEOMETRY, LIMIT_STATE, 4344,
+                b"no HIP device: the limiter stage runs on the GPU only")
 
 
 def test_mixer(pkg, L):
