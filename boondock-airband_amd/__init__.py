@@ -519,13 +519,28 @@ class _Handle:
             pass
 
 
-class _PostStage(_Handle):
-    """The handle of a post-stage with a state blob and per-launch timing: the calls `_prefix`_* over its `_launches` launches."""
+class _TimedStage(_Handle):
+    """The handle of a stage with per-launch timing: the calls `_prefix`_* over its `_launches` launches."""
     _prefix = None
     _launches = 0
 
     def _call(self, name, *args):
         _check(getattr(lib(), f"{self._prefix}_{name}")(self._h, *args))
+
+    def set_timing(self, on=True):
+        self._call("set_timing", 1 if on else 0)
+
+    def last_launch_ms(self):
+        """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy;
+        the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
+        ms = (C.c_float * self._launches)()
+        self._call("last_launch_ms", C.cast(ms, C.c_void_p))
+        return tuple(ms)
+
+
+class _PostStage(_TimedStage):
+    """... with a state blob."""
 
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
@@ -540,16 +555,6 @@ class _PostStage(_Handle):
         """The state blob back in (*_set_state): bytes as state() gave them, or an array of the stage's *_STATE_DTYPE."""
         buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
         self._call("set_state", _ptr(buf), buf.size)
-
-    def set_timing(self, on=True):
-        self._call("set_timing", 1 if on else 0)
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy"""
-        ms = (C.c_float * self._launches)()
-        self._call("last_launch_ms", C.cast(ms, C.c_void_p))
-        return tuple(ms)
 
 
 class Plan(_Handle):
@@ -1446,10 +1451,10 @@ def tones_vote_host(records, min_windows=0, min_share_permille=0):
     return out
 
 
-class Survey(_Handle):
+class Survey(_TimedStage):
     """mi_survey: per-bin mean and peak magnitude of every cell of windows_per_cell consecutive windows (0 = WAVE_BATCH), over the full
     FFT of the windows stage 1 runs -- the pass that comes before a channel plan.  Stateless between calls; no state blob."""
-    _destroy = "mi_survey_destroy"
+    _destroy, _prefix, _launches = "mi_survey_destroy", "mi_survey", 2
 
     def __init__(self, dev, nstreams=1, max_cells=1, windows_per_cell=0, gpu=0):
         self.nstreams, self.max_cells = nstreams, max_cells
@@ -1471,15 +1476,6 @@ class Survey(_Handle):
         """Raw device pointers (ints): d_mean and d_peak float32 [nstreams][ncells][fft_size]; asynchronous on hip_stream."""
         _check(lib().mi_survey_process_device(self._h, d_iq, stream_stride, ncells, d_mean, d_peak, hip_stream))
 
-    def set_timing(self, on=True):
-        _check(lib().mi_survey_set_timing(self._h, 1 if on else 0))
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of the two launches of the last call made with set_timing(True): the windows, the fold"""
-        ms = (C.c_float * 2)()
-        _check(lib().mi_survey_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
-        return tuple(ms)
-
 
 def survey_bin_range(dev, bin):
     """mi_survey_bin_range: (lo_hz, hi_hz), a closed range of integer frequencies inside the band that the plan's bin rule maps to
@@ -1496,11 +1492,11 @@ def _occ_cfg(cfg):
     return C.byref(cfg if isinstance(cfg, OccCfg) else OccCfg(int(cfg[0]), float(cfg[1]), int(cfg[2])))
 
 
-class Occupancy(_Handle):
+class Occupancy(_TimedStage):
     """mi_occupancy: the channel finder -- from the survey's planes to one OCC_BIN_DTYPE record per (stream, bin) and to channel
     candidates (OCC_CAND_DTYPE), the maximal runs of occupied bins in frequency order.  cfg: (floor_permille, ratio, min_cells), 0 = the
     default 250 / 3.0 / 1; max_candidates: capacity of the candidate buffer, 0 = nstreams * fft_size / 2.  Stateless between calls."""
-    _destroy = "mi_occupancy_destroy"
+    _destroy, _prefix, _launches = "mi_occupancy_destroy", "mi_occupancy", 4
 
     def __init__(self, dev, nstreams=1, max_cells=1, cfg=None, max_candidates=0, gpu=0):
         self.nstreams, self.max_cells = nstreams, max_cells
@@ -1530,15 +1526,6 @@ class Occupancy(_Handle):
         count = np.zeros(2, np.uint32)
         _check(lib().mi_occupancy_download(self._h, hip_stream, _ptr(bins), _ptr(cands), _ptr(first), _ptr(count)))
         return bins, cands[:int(count[1])], first, count
-
-    def set_timing(self, on=True):
-        _check(lib().mi_occupancy_set_timing(self._h, 1 if on else 0))
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of the four launches of the last call made with set_timing(True): bin records, run starts, scan, candidates"""
-        ms = (C.c_float * 4)()
-        _check(lib().mi_occupancy_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
-        return tuple(ms)
 
 
 def occupancy_plan_host(dev, mean, peak, cfg=None, enabled=None, max_candidates=0, bins=None, cands=None):
@@ -1571,11 +1558,11 @@ def _probe_targets(targets):
     return np.array([(int(s), int(b)) for s, b in targets], PROBE_TARGET_DTYPE)
 
 
-class Probe(_Handle):
+class Probe(_TimedStage):
     """mi_probe: the channel probe -- for a list of targets (stream, bin), one PROBE_CELL_DTYPE record per (target, cell) with the
     float64 sums of the bin's envelope and of z_w * conj(z_(w-1)) over the cell's windows.  The windows are the survey's.  Stateless
     between calls; the target list stays until it is replaced."""
-    _destroy = "mi_probe_destroy"
+    _destroy, _prefix, _launches = "mi_probe_destroy", "mi_probe", 2
 
     def __init__(self, dev, nstreams=1, max_cells=1, windows_per_cell=0, max_targets=1, gpu=0):
         self.nstreams, self.max_cells, self.max_targets = nstreams, max_cells, max_targets
@@ -1604,15 +1591,6 @@ class Probe(_Handle):
         cells = np.zeros(self._last or (0, 0), PROBE_CELL_DTYPE)
         _check(lib().mi_probe_download(self._h, hip_stream, _ptr(cells)))
         return cells
-
-    def set_timing(self, on=True):
-        _check(lib().mi_probe_set_timing(self._h, 1 if on else 0))
-
-    def last_launch_ms(self):
-        """(diagnostic) ms of the two launches of the last call made with set_timing(True): the windows, the reduction"""
-        ms = (C.c_float * 2)()
-        _check(lib().mi_probe_last_launch_ms(self._h, C.cast(ms, C.c_void_p)))
-        return tuple(ms)
 
 
 def probe_targets_from_candidates(cands):

@@ -12,10 +12,15 @@
 // channel bins leave the chip: magnitude (and re/im for channels that need raw I/Q), staged per tile
 // in LDS and written as contiguous rows of the [stream][channel][time] planes stage 2 reads.
 //
+// The span load, level table and lane setup are iq_front.hpp's, which the band survey and the channel probe share.  The pruned kernel
+// k_channelize9p calls them; k_channelize holds the same text written out, because with the calls its fft 2048 instance left its
+// timing band -- a change to load_span, load_levels or fft_lane is made here as well.  Both take the LDS sizes,
+// the launcher and the instance ladders from there.
+//
 // Compile with -ffp-contract=off: products and sums must round separately except where fma is spelled.
 #include <hip/hip_runtime.h>
 
-#include "fft_radix8.hpp"  // FftGeom, Pass<L, K>, pass0, later_passes, fetch_sample: shared with survey.hip
+#include "iq_front.hpp"
 #include "kernels.hpp"
 
 namespace mi {
@@ -25,7 +30,7 @@ template <int L, int SFMT>
 __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_channelize(const ChannelizeArgs a) {
     using Gm = FftGeom<L>;
     constexpr int N = Gm::N, TPF = Gm::TPF, F = Gm::F, TW = Gm::TW, XN = Gm::XN, BLOCK = Gm::BLOCK;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));  // bytes per complex sample
+    constexpr int BPS2 = iq_bps2(SFMT);  // bytes per complex sample
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
@@ -33,14 +38,14 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_channelize(const Channeli
     const unsigned w0 = blockIdx.x * TW;
     const int nw = min(static_cast<unsigned>(TW), a.nfft - w0);
 
-    const unsigned span_alloc = (static_cast<unsigned>(TW - 1) * a.hop_bytes + N * BPS2 + 16 + 15) & ~15u;
+    const unsigned span_bytes = span_alloc<L>(BPS2, a.hop_bytes);
     unsigned char* span = lds;
-    float* lut = reinterpret_cast<float*>(lds + span_alloc);
-    float2* xch_all = reinterpret_cast<float2*>(lds + span_alloc + 1024);
+    float* lut = reinterpret_cast<float*>(lds + span_bytes);
+    float2* xch_all = reinterpret_cast<float2*>(lds + span_bytes + 1024);
     float* out_mag = reinterpret_cast<float*>(xch_all + F * XN);
     float2* out_iq = reinterpret_cast<float2*>(out_mag + a.nch * TW);
 
-    // ---- HBM -> LDS: the byte span of this tile, each byte read once, 16 B per lane ----
+    // ---- HBM -> LDS: the byte span of this tile, each byte read once, 16 B per lane (load_span and load_levels, written out) ----
     const unsigned char* gbase = a.iq + static_cast<size_t>(stream) * a.stream_stride;
     const long long b0 = static_cast<long long>(w0) * a.hop_bytes;
     const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(gbase + b0) & 15);
@@ -67,10 +72,11 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_channelize(const Channeli
             lut[i] = a.levels[i];
     }
 
-    // ---- per-lane constants: window coefficients of the 8 samples this lane converts, twiddles ----
+    // ---- per-lane constants: window coefficients of the 8 samples this lane converts, twiddles (fft_lane, written out) ----
     const int f = tid / TPF;
     const int tau = tid - f * TPF;
     float2* xch = xch_all + f * XN;
+    const float2* tw = reinterpret_cast<const float2*>(a.tw);
     const int nrev = (L > 3) ? static_cast<int>(__brev(static_cast<unsigned>(tau)) >> (32 - (L - 3))) : 0;
     int nidx[8];
     float wreg[8];
@@ -80,7 +86,6 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_channelize(const Channeli
         nidx[r] = rev3 * TPF + nrev;  // natural sample index = bitrev_L(8 tau + r)
         wreg[r] = a.window[nidx[r]];
     }
-    const float2* tw = reinterpret_cast<const float2*>(a.tw);
     const float2 w8 = tw[N / 8], w83 = tw[3 * N / 8];
     float2 twr[Gm::NPASS][7];
     load_all_tw<L, 1>(tau, tw, twr);
@@ -157,7 +162,7 @@ constexpr int kGW = 2;
 template <int SFMT>
 __global__ __launch_bounds__(256, 4) void k_channelize9p(const ChannelizeArgs a) {
     constexpr int L = 9, N = 512, TW = FftGeom<9>::TW, BLOCK = 256, NWAVE = 4;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
+    constexpr int BPS2 = iq_bps2(SFMT);
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
@@ -170,56 +175,24 @@ __global__ __launch_bounds__(256, 4) void k_channelize9p(const ChannelizeArgs a)
     const int b1len = b0len;
     const int wlen = kGW * (b0len + b2len);  // float2 per wave
 
-    const unsigned span_alloc = (static_cast<unsigned>(TW - 1) * a.hop_bytes + N * BPS2 + 16 + 15) & ~15u;
+    const unsigned span_bytes = span_alloc<L>(BPS2, a.hop_bytes);
     unsigned char* span = lds;
-    float* lut = reinterpret_cast<float*>(lds + span_alloc);
-    float2* xw = reinterpret_cast<float2*>(lds + span_alloc + 1024) + wave * wlen;
-    float* out_mag = reinterpret_cast<float*>(reinterpret_cast<float2*>(lds + span_alloc + 1024) + NWAVE * wlen);
+    float* lut = reinterpret_cast<float*>(lds + span_bytes);
+    float2* xw = reinterpret_cast<float2*>(lds + span_bytes + 1024) + wave * wlen;
+    float* out_mag = reinterpret_cast<float*>(reinterpret_cast<float2*>(lds + span_bytes + 1024) + NWAVE * wlen);
     float2* out_iq = reinterpret_cast<float2*>(out_mag + a.nch * TW);
     float2* b0 = xw;
     float2* b1 = b0;
     float2* b2 = b0 + kGW * b0len;
 
-    // ---- HBM -> LDS: the byte span of this tile, each byte read once, 16 B per lane ----
+    // ---- HBM -> LDS: the byte span of this tile ----
     const unsigned char* gbase = a.iq + static_cast<size_t>(stream) * a.stream_stride;
-    const long long byte0 = static_cast<long long>(w0) * a.hop_bytes;
-    const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(gbase + byte0) & 15);
-    const unsigned need = static_cast<unsigned>(nw - 1) * a.hop_bytes + N * BPS2;
-    const unsigned nchunks = (mis + need + 15) >> 4;
-    for (unsigned c = tid; c < nchunks; c += BLOCK) {
-        const long long off = byte0 - mis + 16ll * c;
-        uint4 v;
-        if (off >= 0 && off + 16 <= static_cast<long long>(a.valid_bytes)) {
-            v = *reinterpret_cast<const uint4*>(gbase + off);
-        } else {
-            unsigned char tmp[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const long long o = off + i;
-                tmp[i] = (o >= 0 && o < static_cast<long long>(a.valid_bytes)) ? gbase[o] : 0;
-            }
-            v = *reinterpret_cast<uint4*>(tmp);
-        }
-        *reinterpret_cast<uint4*>(span + 16 * c) = v;
-    }
-    if constexpr (SFMT == MI_SFMT_U8 || SFMT == MI_SFMT_S8) {
-        for (int i = tid; i < 256; i += BLOCK)
-            lut[i] = a.levels[i];
-    }
+    const unsigned mis = load_span<BLOCK>(span, gbase, static_cast<long long>(w0) * a.hop_bytes, nw, a.hop_bytes, N * BPS2, a.valid_bytes, tid);
+    load_levels<SFMT, BLOCK>(lut, a.levels, tid);
 
     // ---- per-lane constants ----
     const int tau = lane;  // pass 0: lane = block of 8 at stage 3
-    const int nrev = static_cast<int>(__brev(static_cast<unsigned>(tau)) >> (32 - (L - 3)));
-    int nidx[8];
-    float wreg[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int rev3 = ((r & 1) << 2) | (r & 2) | ((r >> 2) & 1);
-        nidx[r] = rev3 * (N / 8) + nrev;  // natural sample index = bitrev_9(8 tau + r)
-        wreg[r] = a.window[nidx[r]];
-    }
-    const float2* tw = reinterpret_cast<const float2*>(a.tw);
-    const float2 w8 = tw[N / 8], w83 = tw[3 * N / 8];
+    const FftLane ln = fft_lane<L>(tau, a.window, reinterpret_cast<const float2*>(a.tw));
     // the lane's item class in pass 1 / pass 2: 7 twiddles and 8 output slots each
     const int j1 = lane & ((1 << sh3) - 1), j2 = lane & ((1 << sh6) - 1);
     float2 t1[7], t2[7];
@@ -251,8 +224,8 @@ __global__ __launch_bounds__(256, 4) void k_channelize9p(const ChannelizeArgs a)
             float2 x[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r)
-                x[r] = fetch_sample<SFMT>(span, wbyte + nidx[r] * BPS2, lut, a.conv_scale, wreg[r]);
-            pass0(x, w8, w83);
+                x[r] = fetch_sample<SFMT>(span, wbyte + ln.nidx[r] * BPS2, lut, a.conv_scale, ln.wreg[r]);
+            pass0(x, ln.w8, ln.w83);
             float2* d = b0 + g * b0len + (tau & 7) * rs1 + (tau >> 3) * m3;  // block tau = 8 hi + ri of pass 1
 #pragma unroll
             for (int r = 0; r < 8; ++r)
@@ -341,52 +314,17 @@ __global__ __launch_bounds__(256, 4) void k_channelize9p(const ChannelizeArgs a)
 template <int SFMT>
 hipError_t launch_9p(const ChannelizeArgs& a, int nstreams, hipStream_t s) {
     using Gm = FftGeom<9>;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
-    const unsigned span_alloc = (static_cast<unsigned>(Gm::TW - 1) * a.hop_bytes + Gm::N * BPS2 + 16 + 15) & ~15u;
     const size_t wlen = static_cast<size_t>(kGW) * (8 * a.prune.rs1 + ((a.prune.m9 + 1) & ~1));
-    const size_t lds = span_alloc + 1024 + 4 * wlen * 8 + static_cast<size_t>(a.nch) * Gm::TW * 4 + static_cast<size_t>(a.n_iq_rows) * Gm::TW * 8;
-    if (lds > 160 * 1024)
-        return hipErrorInvalidValue;
-    auto kern = k_channelize9p<SFMT>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess)
-            return e;
-    }
-    const dim3 grid((a.nfft + Gm::TW - 1) / Gm::TW, nstreams);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-    return hipGetLastError();
+    const size_t lds = span_alloc<9>(iq_bps2(SFMT), a.hop_bytes) + 1024 + 4 * wlen * 8 + static_cast<size_t>(a.nch) * Gm::TW * 4 +
+                       static_cast<size_t>(a.n_iq_rows) * Gm::TW * 8;
+    return launch_lds(k_channelize9p<SFMT>, dim3((a.nfft + Gm::TW - 1) / Gm::TW, nstreams), dim3(256), lds, s, a);
 }
 
 template <int L, int SFMT>
 hipError_t launch_one(const ChannelizeArgs& a, int nstreams, hipStream_t s) {
     using Gm = FftGeom<L>;
-    constexpr int BPS2 = (SFMT == MI_SFMT_S16 ? 4 : (SFMT == MI_SFMT_F32 ? 8 : 2));
-    const unsigned span_alloc = (static_cast<unsigned>(Gm::TW - 1) * a.hop_bytes + Gm::N * BPS2 + 16 + 15) & ~15u;
-    const size_t lds = span_alloc + 1024 + static_cast<size_t>(Gm::F) * Gm::XN * 8 + static_cast<size_t>(a.nch) * Gm::TW * 4 +
-                       static_cast<size_t>(a.n_iq_rows) * Gm::TW * 8;
-    if (lds > 160 * 1024)
-        return hipErrorInvalidValue;
-    auto kern = k_channelize<L, SFMT>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess)
-            return e;
-    }
-    const dim3 grid((a.nfft + Gm::TW - 1) / Gm::TW, nstreams);
-    hipLaunchKernelGGL(kern, grid, dim3(Gm::BLOCK), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_fmt(const ChannelizeArgs& a, int sfmt, int nstreams, hipStream_t s) {
-    switch (sfmt) {
-        case MI_SFMT_U8: return a.conv_arith ? launch_one<L, kSfmtU8Arith>(a, nstreams, s) : launch_one<L, MI_SFMT_U8>(a, nstreams, s);
-        case MI_SFMT_S8: return launch_one<L, MI_SFMT_S8>(a, nstreams, s);
-        case MI_SFMT_S16: return launch_one<L, MI_SFMT_S16>(a, nstreams, s);
-        case MI_SFMT_F32: return launch_one<L, MI_SFMT_F32>(a, nstreams, s);
-    }
-    return hipErrorInvalidValue;
+    const size_t lds = tile_lds_bytes<L>(iq_bps2(SFMT), a.hop_bytes) + static_cast<size_t>(a.nch) * Gm::TW * 4 + static_cast<size_t>(a.n_iq_rows) * Gm::TW * 8;
+    return launch_lds(k_channelize<L, SFMT>, dim3((a.nfft + Gm::TW - 1) / Gm::TW, nstreams), dim3(Gm::BLOCK), lds, s, a);
 }
 
 }  // namespace
@@ -399,24 +337,9 @@ hipError_t launch_channelize(const ChannelizeArgs& a, int log2n, int sfmt, int n
     // the pruned graphs have no complete spectrum: AFC launches (they want one) take the full kernel
     if (a.l64.enabled && a.l64_chan && !a.afc_spec && !a.st && l64_supported(log2n, a.hop_bytes, sfmt == MI_SFMT_S16 ? 2 : (sfmt == MI_SFMT_F32 ? 4 : 1)))
         return launch_channelize_l64(a, log2n, sfmt, nstreams, s);
-    if (log2n == 9 && a.prune.enabled && a.prune_t1 && a.prune_t2 && a.prune_rank && !a.afc_spec && !a.st) {
-        switch (sfmt) {
-            case MI_SFMT_U8: return a.conv_arith ? launch_9p<kSfmtU8Arith>(a, nstreams, s) : launch_9p<MI_SFMT_U8>(a, nstreams, s);
-            case MI_SFMT_S8: return launch_9p<MI_SFMT_S8>(a, nstreams, s);
-            case MI_SFMT_S16: return launch_9p<MI_SFMT_S16>(a, nstreams, s);
-            case MI_SFMT_F32: return launch_9p<MI_SFMT_F32>(a, nstreams, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (log2n) {
-        case 8: return launch_fmt<8>(a, sfmt, nstreams, s);
-        case 9: return launch_fmt<9>(a, sfmt, nstreams, s);
-        case 10: return launch_fmt<10>(a, sfmt, nstreams, s);
-        case 11: return launch_fmt<11>(a, sfmt, nstreams, s);
-        case 12: return launch_fmt<12>(a, sfmt, nstreams, s);
-        case 13: return launch_fmt<13>(a, sfmt, nstreams, s);
-    }
-    return hipErrorInvalidValue;
+    if (log2n == 9 && a.prune.enabled && a.prune_t1 && a.prune_t2 && a.prune_rank && !a.afc_spec && !a.st)
+        return dispatch_sfmt(sfmt, a.conv_arith != 0, hipErrorInvalidValue, [&](auto f) { return launch_9p<f()>(a, nstreams, s); });
+    return dispatch_fft(log2n, sfmt, a.conv_arith != 0, hipErrorInvalidValue, [&](auto l, auto f) { return launch_one<l(), f()>(a, nstreams, s); });
 }
 
 }  // namespace mi

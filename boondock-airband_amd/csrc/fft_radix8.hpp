@@ -1,6 +1,8 @@
-// fft_radix8.hpp -- the device pieces channelize.hip (stage 1), survey.hip (the band survey) and probe.hip (the channel probe) share: the geometry of an N-point
-// FFT done by N/8 lanes, the butterflies of the documented FFT spec taken three radix-2 DIT stages at a time, the LDS
-// exchange between passes, and the sample conversion x window.  Internal linkage: every .hip that includes it gets its own copy.
+// fft_radix8.hpp -- the arithmetic channelize.hip (stage 1), survey.hip (the band survey) and probe.hip (the channel probe) share: the
+// geometry of an N-point FFT done by N/8 lanes, the butterflies of the documented FFT spec taken three radix-2 DIT stages
+// at a time, the LDS exchange between passes, and the sample conversion x window.  What stands in front of it -- the span load, the
+// level table, the lane setup -- and the launch are in iq_front.hpp, which includes this file.  Internal linkage: every .hip that
+// includes it gets its own copy.
 //
 // Compile with -ffp-contract=off: products and sums must round separately except where fma is spelled.
 #pragma once

@@ -1,12 +1,14 @@
 // poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
-// share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage) with the
-// bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in and out,
-// the checks of a plane-in / plane-out call), the row scan's launcher and the blob layouts.  The device side of a stage that carries
-// samples from call to call -- the lead's load and the tails kernel -- is in carry.hpp.
+// share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
+// with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
+// and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
+// stage), the row scan's launcher and the blob layouts.  The device side of a stage that carries samples from call to call -- the
+// lead's load and the tails kernel -- is in carry.hpp; that of a stage that reads raw I/Q is in iq_front.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -324,6 +326,114 @@ int limit_rows(const mi_limit_row* row_cfg, size_t rows, std::vector<mi_limit_ro
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is
 // used.  MI_OK, or the plan's refusal with its message set.
 int device_plan(const mi_device_cfg& dev, Plan& p);
+
+// An I/Q front stage: a stage in front of the demodulator that reads raw I/Q as stage 1 does, cells of wpc windows of it (the band
+// survey, the channel probe).  What its handle keeps of the plan, and the bodies its entry points share; `stage` as above.
+struct IqFront : Stage {
+    using Stage::Stage;
+    int nstreams = 0;
+    int max_cells = 0;
+    uint32_t wpc = 0;  // windows per cell
+    int log2n = 0, fft_size = 0, sfmt = 0, sample_bytes = 0;  // sample_bytes: one complex sample
+    bool conv_arith = false;
+    float conv_scale = 0.0f;
+    size_t hop_bytes = 0;
+    DevBuf<float> d_window, d_tw, d_levels;
+};
+
+// The head of a create call, up to the refusal of a geometry whose workgroup would need more than lds_limit bytes by lds_bytes(log2n,
+// sfmt, hop_bytes), the function the stage's launcher sizes its launch with.  MI_OK with the plan, or the refusal.
+template <class H>
+int iq_front_plan(const char* stage, const mi_device_cfg* dev, H** out, int nstreams, int max_cells, int windows_per_cell,
+                  size_t (*lds_bytes)(int, int, unsigned), size_t lds_limit, Plan& plan) {
+    if (!dev || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (nstreams < 1 || nstreams > 65535 || max_cells < 1 || max_cells >= (1 << 24) || windows_per_cell < 0 || windows_per_cell > (1 << 20))
+        return fail(MI_ERR_INVALID, std::string(stage) + " needs 1 <= nstreams < 2^16, 1 <= max_cells < 2^24 and 0 <= windows_per_cell <= 2^20");
+    if (const int rc = device_plan(*dev, plan))
+        return rc;
+    if (plan.hop_bytes == 0 || plan.hop_bytes > (1u << 20))
+        return fail(MI_ERR_INVALID, std::string(stage) + ": the hop (sample_rate / 16000 samples) is out of range");
+    if (const size_t lds = lds_bytes(plan.log2n, plan.dev.sfmt, static_cast<unsigned>(plan.hop_bytes)); lds > lds_limit)
+        return fail(MI_ERR_INVALID, std::string(stage) + ": a workgroup would need " + std::to_string(lds) + " bytes of LDS at this fft_size, sample format and hop (" +
+                                        std::to_string(plan.hop_bytes) + " bytes), over the limit of " + std::to_string(lds_limit) +
+                                        " (160 KiB): lower the sample rate");
+    return MI_OK;
+}
+
+// ... and behind the stage's own checks: the device, then the handle with what it keeps of the plan.  MI_OK with *h, or the refusal.
+template <class H>
+int iq_front_new(const char* stage, const Plan& plan, int nstreams, int max_cells, int windows_per_cell, int gpu, H** h) {
+    if (const int rc = check_gpu(gpu, ("no HIP device: the " + std::string(stage) + " runs on the GPU only").c_str()))
+        return rc;
+    H* s = new (std::nothrow) H();
+    if (!s)
+        return fail(MI_ERR_NOMEM, "host allocation failed");
+    s->gpu = gpu;
+    s->nstreams = nstreams;
+    s->max_cells = max_cells;
+    s->wpc = static_cast<uint32_t>(windows_per_cell ? windows_per_cell : MI_WAVE_BATCH);
+    s->log2n = plan.log2n;
+    s->fft_size = plan.fft_size;
+    s->sfmt = plan.dev.sfmt;
+    s->sample_bytes = 2 * plan.bytes_per_sample;
+    s->conv_arith = plan.conv_arith;
+    s->conv_scale = plan.conv_scale;
+    s->hop_bytes = plan.hop_bytes;
+    *h = s;
+    return MI_OK;
+}
+
+// the plan's window, twiddles and level table into the handle's device arrays
+inline hipError_t iq_front_upload(IqFront* s, const Plan& plan) {
+    if (const hipError_t e = dalloc_copy(s->d_window, plan.window); e != hipSuccess)
+        return e;
+    if (const hipError_t e = dalloc_copy(s->d_tw, plan.tw); e != hipSuccess)
+        return e;
+    return dalloc_copy(s->d_levels, plan.levels);
+}
+
+// bytes of I/Q a call over ncells cells reads per stream
+inline size_t iq_bytes_needed(const IqFront* s, int ncells) {
+    if (!s || ncells < 1)
+        return 0;
+    return (static_cast<size_t>(ncells) * s->wpc - 1) * s->hop_bytes + static_cast<size_t>(s->sample_bytes) * static_cast<size_t>(s->fft_size);
+}
+
+// The checks of a call's ncells and I/Q, with the stage's check of its output's alignment where it stands between them.
+inline int iq_call_ok(const IqFront* s, const void* d_iq, size_t stream_stride_bytes, int ncells, bool out_aligned, const char* out_text) {
+    if (ncells < 1 || ncells > s->max_cells)
+        return fail(MI_ERR_INVALID, "ncells outside 1 .. max_cells");
+    if (!out_aligned)
+        return fail(MI_ERR_INVALID, std::string(s->timing.stage) + ": " + out_text);
+    if (!aligned(d_iq, static_cast<uintptr_t>(s->sample_bytes)) || stream_stride_bytes % static_cast<size_t>(s->sample_bytes) != 0)
+        return fail(MI_ERR_INVALID, std::string(s->timing.stage) + ": d_iq and the stream stride must be aligned to one complex sample");
+    return MI_OK;
+}
+
+// What every kernel of an I/Q front stage is told about the call's I/Q and the plan's tables; a stage's own arguments extend it.
+struct IqArgs {
+    const unsigned char* iq;  // stream s at iq + s*stream_stride
+    size_t stream_stride;
+    size_t valid_bytes;       // readable bytes per stream starting at its base
+    uint32_t hop_bytes;
+    const float* window;
+    const float* tw;
+    const float* levels;
+    float conv_scale;
+};
+
+inline void iq_args(IqArgs& a, const IqFront* s, const void* d_iq, size_t stream_stride_bytes, int ncells) {
+    a.iq = static_cast<const unsigned char*>(d_iq);
+    a.stream_stride = stream_stride_bytes;
+    a.valid_bytes = iq_bytes_needed(s, ncells);
+    a.hop_bytes = static_cast<uint32_t>(s->hop_bytes);
+    a.conv_scale = s->conv_scale;
+    a.window = s->d_window;
+    a.tw = s->d_tw;
+    a.levels = s->d_levels;
+}
 
 static_assert(sizeof(mi_occ_bin) == 32 && sizeof(mi_occ_candidate) == 40, "the channel finder's record layouts are ABI");
 static_assert(sizeof(mi_probe_target) == 8 && sizeof(mi_probe_cell) == 40, "the channel probe's record layouts are ABI");

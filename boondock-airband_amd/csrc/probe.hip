@@ -5,12 +5,14 @@
 //
 // A post-stage of its own like the band survey (survey.hip): its own handle, two launches on the caller's stream, no atomics.
 //   k_probe         one workgroup = one tile of consecutive windows of one stream that has targets.  The windows are the survey's and
-//                   stage 1's: the same span load, conversion x window and radix-8 passes (fft_radix8.hpp), so a bin's value has
-//                   the bits of the oracle's ao_fft_forward.  Behind the last pass, where k_survey takes all bins, lane tau of an
-//                   FFT takes the bins of the stream's targets tau, tau + N/8, ... (a stream has at most N) from the natural-order
-//                   spectrum in the exchange slot and stores {re, im} at z[target][window], the scratch plane in the handle.  Tiles
-//                   cut the call's windows, not the cells: the plane makes a window's predecessor a plain load, whatever tile or
-//                   cell it lies in.  A tile is walked TW windows of span at a time, as in k_survey.
+//                   stage 1's: their level table and lane setup by their own text (iq_front.hpp), the same conversion x window
+//                   and radix-8 passes (fft_radix8.hpp), so a bin's value has the bits of the oracle's ao_fft_forward.  The span
+//                   load is iq_front.hpp's load_span written out here: called as the function, the N = 8192 instances spill 16
+//                   bytes more.  Behind the last pass, where k_survey takes all bins, lane tau of an FFT
+//                   takes the bins of the stream's targets tau, tau + N/8, ... (a stream has at most N) from the natural-order
+//                   spectrum in the exchange slot and stores {re, im} at z[target][window], the scratch plane in the handle.
+//                   Tiles cut the call's windows, not the cells: the plane makes a window's predecessor a plain load, whatever
+//                   tile or cell it lies in.  A tile is walked TW windows of span at a time, as in k_survey.
 //   k_probe_reduce  one workgroup of 256 lanes = one (target, cell).
 // Order of the four float64 sums of a (target, cell) (fixed, so two runs give the same bytes): lane t adds the terms of the cell's
 // windows t, t + 256, t + 512, ... in turn; the 256 lanes' sums are then added by the halving tree -- lane t takes lane t + d for
@@ -19,13 +21,10 @@
 // Compile with -ffp-contract=off (the FFT spec; the float64 terms are sums of exact products and do not depend on it).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "../../include/mi_airband.h"
-#include "fft_radix8.hpp"
+#include "iq_front.hpp"
 #include "poststage.hpp"
 
 namespace mi {
@@ -39,19 +38,11 @@ struct ProbeStream {
 }  // namespace
 }  // namespace mi
 
-struct mi_probe : mi::Stage {
-    mi_probe() : Stage("channel probe", 2) {}
-    int nstreams = 0;
-    int max_cells = 0;
+struct mi_probe : mi::IqFront {
+    mi_probe() : IqFront("channel probe", 2) {}
     int max_targets = 0;
-    uint32_t wpc = 0;           // windows per cell
-    int log2n = 0, fft_size = 0, sfmt = 0, sample_bytes = 0;  // sample_bytes: one complex sample
-    bool conv_arith = false;
-    float conv_scale = 0.0f;
-    size_t hop_bytes = 0;
     int ntargets = 0;  // 0 until mi_probe_set_targets
     int nactive = 0;   // streams that have a target
-    mi::DevBuf<float> d_window, d_tw, d_levels;
     mi::DevBuf<mi_probe_target> d_targets;  // [max_targets], the first ntargets
     mi::DevBuf<mi::ProbeStream> d_active;   // [nstreams], the first nactive
     mi::DevBuf<float2> d_z;                 // [max_targets][max_cells * wpc], the scratch plane
@@ -65,52 +56,17 @@ namespace {
 
 constexpr int kProbeTilePieces = 2;  // a tile is this many TW-window pieces: enough workgroups for one stream, lane setup paid once per tile
 constexpr int kReduceBlock = 256;
-constexpr size_t kProbeLdsLimit = 160 * 1024;  // what one workgroup may ask for on gfx950: the CU's whole LDS
 
-// bytes per complex sample of a kernel instance's format
-constexpr int probe_bps2(int sfmt) {
-    return sfmt == MI_SFMT_S16 ? 4 : (sfmt == MI_SFMT_F32 ? 8 : 2);
-}
-
-// The span of one TW-window piece in LDS: its bytes, up to 15 in front of them (the piece starts at a 16-byte line) and a line's
-// rounding.  k_probe lays its LDS out with it and probe_lds_bytes sizes the launch with it.
-template <int L>
-__host__ __device__ constexpr unsigned probe_span_alloc(int bps2, unsigned hop_bytes) {
-    return (static_cast<unsigned>(FftGeom<L>::TW - 1) * hop_bytes + static_cast<unsigned>(FftGeom<L>::N * bps2) + 16 + 15) & ~15u;
-}
-
-template <int L>
-constexpr size_t probe_lds_bytes_of(int bps2, unsigned hop_bytes) {
-    return static_cast<size_t>(probe_span_alloc<L>(bps2, hop_bytes)) + 1024 + static_cast<size_t>(FftGeom<L>::F) * FftGeom<L>::XN * 8;
-}
-
-// The dynamic LDS a k_probe workgroup needs: span + level table + F exchange slots.  mi_probe_create refuses a geometry whose need
-// exceeds kProbeLdsLimit and launch_probe_one launches with it: one function, so the two cannot drift.  hop_bytes <= 2^20
-// (mi_probe_create), so nothing here wraps.  0: no such kernel instance.
+// The dynamic LDS a k_probe workgroup needs: the tile walk's.  mi_probe_create refuses a geometry whose need exceeds kLdsLimit and
+// launch_probe launches with it: one function, so the two cannot drift.  hop_bytes <= 2^20 (mi_probe_create), so nothing here
+// wraps.  0: no such kernel instance.
 size_t probe_lds_bytes(int log2n, int sfmt, unsigned hop_bytes) {
-    const int bps2 = probe_bps2(sfmt);
-    switch (log2n) {
-        case 8: return probe_lds_bytes_of<8>(bps2, hop_bytes);
-        case 9: return probe_lds_bytes_of<9>(bps2, hop_bytes);
-        case 10: return probe_lds_bytes_of<10>(bps2, hop_bytes);
-        case 11: return probe_lds_bytes_of<11>(bps2, hop_bytes);
-        case 12: return probe_lds_bytes_of<12>(bps2, hop_bytes);
-        case 13: return probe_lds_bytes_of<13>(bps2, hop_bytes);
-    }
-    return 0;
+    return dispatch_log2n(log2n, size_t{0}, [&](auto l) { return tile_lds_bytes<l()>(iq_bps2(sfmt), hop_bytes); });
 }
 
-struct ProbeArgs {
-    const unsigned char* iq;  // stream s at iq + s*stream_stride
-    size_t stream_stride;
-    size_t valid_bytes;       // readable bytes per stream starting at its base
-    uint32_t hop_bytes;
+struct ProbeArgs : IqArgs {
     uint32_t nwindows;        // of the call, per stream
     uint32_t tile_windows;    // kProbeTilePieces * TW, set by the launcher
-    const float* window;
-    const float* tw;
-    const float* levels;
-    float conv_scale;
     const ProbeStream* active;        // [gridDim.z]
     const mi_probe_target* targets;
     float2* z;                        // [targets][zstride]
@@ -121,7 +77,7 @@ template <int L, int SFMT>
 __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) {
     using Gm = FftGeom<L>;
     constexpr int N = Gm::N, TPF = Gm::TPF, F = Gm::F, TW = Gm::TW, XN = Gm::XN, BLOCK = Gm::BLOCK;
-    constexpr int BPS2 = probe_bps2(SFMT);  // bytes per complex sample
+    constexpr int BPS2 = iq_bps2(SFMT);  // bytes per complex sample
     constexpr bool kTwInRegs = L <= 11;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -130,30 +86,18 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) 
     const unsigned wfirst = blockIdx.x * a.tile_windows;                         // first window of the tile, counted from the stream's base
     const int nt = static_cast<int>(min(a.tile_windows, a.nwindows - wfirst));   // its windows: the last tile of the call may be short
 
-    const unsigned span_alloc = probe_span_alloc<L>(BPS2, a.hop_bytes);
+    const unsigned span_bytes = span_alloc<L>(BPS2, a.hop_bytes);
     unsigned char* span = lds;
-    float* lut = reinterpret_cast<float*>(lds + span_alloc);
-    float2* xch_all = reinterpret_cast<float2*>(lds + span_alloc + 1024);
-    if constexpr (SFMT == MI_SFMT_U8 || SFMT == MI_SFMT_S8) {
-        for (int i = tid; i < 256; i += BLOCK)
-            lut[i] = a.levels[i];
-    }
+    float* lut = reinterpret_cast<float*>(lds + span_bytes);
+    float2* xch_all = reinterpret_cast<float2*>(lds + span_bytes + 1024);
+    load_levels<SFMT, BLOCK>(lut, a.levels, tid);
 
     // ---- per-lane constants: window coefficients of the 8 samples this lane converts, twiddles ----
     const int f = tid / TPF;
     const int tau = tid - f * TPF;
     float2* xch = xch_all + f * XN;
-    const int nrev = (L > 3) ? static_cast<int>(__brev(static_cast<unsigned>(tau)) >> (32 - (L - 3))) : 0;
-    int nidx[8];
-    float wreg[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int rev3 = ((r & 1) << 2) | (r & 2) | ((r >> 2) & 1);
-        nidx[r] = rev3 * TPF + nrev;  // natural sample index = bitrev_L(8 tau + r)
-        wreg[r] = a.window[nidx[r]];
-    }
     const float2* tw = reinterpret_cast<const float2*>(a.tw);
-    const float2 w8 = tw[N / 8], w83 = tw[3 * N / 8];
+    const FftLane ln = fft_lane<L>(tau, a.window, tw);
     [[maybe_unused]] float2 twr[kTwInRegs ? Gm::NPASS : 1][7];
     if constexpr (kTwInRegs)
         load_all_tw<L, 1>(tau, tw, twr);
@@ -167,7 +111,7 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) 
         const int nw = min(TW, nt - s0);
         if (s0)
             __syncthreads();  // every FFT of the piece before has converted its samples
-        // ---- HBM -> LDS: the byte span of this piece, each byte read once, 16 B per lane ----
+        // ---- HBM -> LDS: the byte span of this piece, each byte read once, 16 B per lane (load_span, written out) ----
         const long long b0 = (static_cast<long long>(wfirst) + s0) * static_cast<long long>(a.hop_bytes);
         const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(gbase + b0) & 15);
         const unsigned need = static_cast<unsigned>(nw - 1) * a.hop_bytes + N * BPS2;
@@ -198,8 +142,8 @@ __global__ __launch_bounds__(FftGeom<L>::BLOCK) void k_probe(const ProbeArgs a) 
             const int wbyte = static_cast<int>(mis) + (active ? wi : 0) * static_cast<int>(a.hop_bytes);
 #pragma unroll
             for (int r = 0; r < 8; ++r)
-                x[r] = fetch_sample<SFMT>(span, wbyte + nidx[r] * BPS2, lut, a.conv_scale, wreg[r]);
-            pass0(x, w8, w83);
+                x[r] = fetch_sample<SFMT>(span, wbyte + ln.nidx[r] * BPS2, lut, a.conv_scale, ln.wreg[r]);
+            pass0(x, ln.w8, ln.w83);
 #pragma unroll
             for (int r = 0; r < 8; ++r)
                 xch[xpad(tau * 8 + r)] = x[r];
@@ -261,46 +205,13 @@ __global__ __launch_bounds__(kReduceBlock) void k_probe_reduce(const float2* __r
     }
 }
 
-template <int L, int SFMT>
-hipError_t launch_probe_one(ProbeArgs a, int nactive, hipStream_t s) {
-    using Gm = FftGeom<L>;
-    a.tile_windows = kProbeTilePieces * Gm::TW;
-    const unsigned tiles = (a.nwindows + a.tile_windows - 1) / a.tile_windows;
-    const size_t lds = probe_lds_bytes(L, SFMT, a.hop_bytes);
-    if (lds > kProbeLdsLimit)  // (mi_probe_create has refused such a geometry)
-        return hipErrorInvalidValue;
-    auto kern = k_probe<L, SFMT>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess)
-            return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles, 1, nactive), dim3(Gm::BLOCK), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_probe_fmt(const ProbeArgs& a, int sfmt, bool conv_arith, int nactive, hipStream_t s) {
-    switch (sfmt) {
-        case MI_SFMT_U8:
-            return conv_arith ? launch_probe_one<L, kSfmtU8Arith>(a, nactive, s) : launch_probe_one<L, MI_SFMT_U8>(a, nactive, s);
-        case MI_SFMT_S8: return launch_probe_one<L, MI_SFMT_S8>(a, nactive, s);
-        case MI_SFMT_S16: return launch_probe_one<L, MI_SFMT_S16>(a, nactive, s);
-        case MI_SFMT_F32: return launch_probe_one<L, MI_SFMT_F32>(a, nactive, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_probe(const ProbeArgs& a, int log2n, int sfmt, bool conv_arith, int nactive, hipStream_t s) {
-    switch (log2n) {
-        case 8: return launch_probe_fmt<8>(a, sfmt, conv_arith, nactive, s);
-        case 9: return launch_probe_fmt<9>(a, sfmt, conv_arith, nactive, s);
-        case 10: return launch_probe_fmt<10>(a, sfmt, conv_arith, nactive, s);
-        case 11: return launch_probe_fmt<11>(a, sfmt, conv_arith, nactive, s);
-        case 12: return launch_probe_fmt<12>(a, sfmt, conv_arith, nactive, s);
-        case 13: return launch_probe_fmt<13>(a, sfmt, conv_arith, nactive, s);
-    }
-    return hipErrorInvalidValue;
+hipError_t launch_probe(ProbeArgs a, int log2n, int sfmt, bool conv_arith, int nactive, hipStream_t s) {
+    return dispatch_fft(log2n, sfmt, conv_arith, hipErrorInvalidValue, [&](auto l, auto f) {
+        using Gm = FftGeom<l()>;
+        a.tile_windows = kProbeTilePieces * Gm::TW;
+        const unsigned tiles = (a.nwindows + a.tile_windows - 1) / a.tile_windows;
+        return launch_lds(k_probe<l(), f()>, dim3(tiles, 1, nactive), dim3(Gm::BLOCK), probe_lds_bytes(l(), f(), a.hop_bytes), s, a);
+    });
 }
 
 }  // namespace
@@ -312,46 +223,21 @@ using mi::fail;
 extern "C" {
 
 int mi_probe_create(const mi_device_cfg* dev, int nstreams, int max_cells, int windows_per_cell, int max_targets, int gpu, mi_probe** out) {
-    if (!dev || !out)
-        return fail(MI_ERR_INVALID, "NULL argument");
-    *out = nullptr;
-    if (nstreams < 1 || nstreams > 65535 || max_cells < 1 || max_cells >= (1 << 24) || windows_per_cell < 0 || windows_per_cell > (1 << 20))
-        return fail(MI_ERR_INVALID, "channel probe needs 1 <= nstreams < 2^16, 1 <= max_cells < 2^24 and 0 <= windows_per_cell <= 2^20");
     mi::Plan plan;
-    if (const int rc = mi::device_plan(*dev, plan))
+    if (const int rc = mi::iq_front_plan("channel probe", dev, out, nstreams, max_cells, windows_per_cell, mi::probe_lds_bytes, mi::kLdsLimit, plan))
         return rc;
-    if (plan.hop_bytes == 0 || plan.hop_bytes > (1u << 20))
-        return fail(MI_ERR_INVALID, "channel probe: the hop (sample_rate / 16000 samples) is out of range");
-    if (const size_t lds = mi::probe_lds_bytes(plan.log2n, plan.dev.sfmt, static_cast<unsigned>(plan.hop_bytes)); lds > mi::kProbeLdsLimit)
-        return fail(MI_ERR_INVALID, "channel probe: a workgroup would need " + std::to_string(lds) + " bytes of LDS at this fft_size, sample format and hop (" +
-                                        std::to_string(plan.hop_bytes) + " bytes), over the limit of " + std::to_string(mi::kProbeLdsLimit) +
-                                        " (160 KiB): lower the sample rate");
     const uint64_t wpc = static_cast<uint64_t>(windows_per_cell ? windows_per_cell : MI_WAVE_BATCH);
     if (max_targets < 1 || static_cast<int64_t>(max_targets) > static_cast<int64_t>(nstreams) * plan.fft_size ||
         static_cast<uint64_t>(max_targets) * static_cast<uint64_t>(max_cells) >= (uint64_t{1} << 31))
         return fail(MI_ERR_INVALID, "channel probe needs 1 <= max_targets <= nstreams * fft_size and max_targets * max_cells < 2^31");
     if (static_cast<uint64_t>(max_cells) * wpc >= (uint64_t{1} << 32))
         return fail(MI_ERR_INVALID, "channel probe: max_cells * windows_per_cell does not fit the 32-bit window count");
-    if (const int rc = mi::check_gpu(gpu, "no HIP device: the channel probe runs on the GPU only"))
+    mi_probe* p = nullptr;
+    if (const int rc = mi::iq_front_new("channel probe", plan, nstreams, max_cells, windows_per_cell, gpu, &p))
         return rc;
-    mi_probe* p = new (std::nothrow) mi_probe();
-    if (!p)
-        return fail(MI_ERR_NOMEM, "host allocation failed");
-    p->gpu = gpu;
-    p->nstreams = nstreams;
-    p->max_cells = max_cells;
     p->max_targets = max_targets;
-    p->wpc = static_cast<uint32_t>(wpc);
-    p->log2n = plan.log2n;
-    p->fft_size = plan.fft_size;
-    p->sfmt = plan.dev.sfmt;
-    p->sample_bytes = 2 * plan.bytes_per_sample;
-    p->conv_arith = plan.conv_arith;
-    p->conv_scale = plan.conv_scale;
-    p->hop_bytes = plan.hop_bytes;
     const size_t zlen = static_cast<size_t>(max_targets) * static_cast<size_t>(max_cells) * p->wpc;
-    if (hipSetDevice(gpu) != hipSuccess || dalloc_copy(p->d_window, plan.window) != hipSuccess || dalloc_copy(p->d_tw, plan.tw) != hipSuccess ||
-        dalloc_copy(p->d_levels, plan.levels) != hipSuccess || dalloc(p->d_targets, static_cast<size_t>(max_targets)) != hipSuccess ||
+    if (hipSetDevice(gpu) != hipSuccess || iq_front_upload(p, plan) != hipSuccess || dalloc(p->d_targets, static_cast<size_t>(max_targets)) != hipSuccess ||
         dalloc(p->d_active, static_cast<size_t>(nstreams)) != hipSuccess || dalloc(p->d_z, zlen) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         delete p;
@@ -393,9 +279,7 @@ int mi_probe_set_targets(mi_probe* p, const mi_probe_target* targets, int ntarge
 }
 
 size_t mi_probe_bytes_needed(const mi_probe* p, int ncells) {
-    if (!p || ncells < 1)
-        return 0;
-    return (static_cast<size_t>(ncells) * p->wpc - 1) * p->hop_bytes + static_cast<size_t>(p->sample_bytes) * static_cast<size_t>(p->fft_size);
+    return mi::iq_bytes_needed(p, ncells);
 }
 
 int mi_probe_process_device(mi_probe* p, const void* d_iq, size_t stream_stride_bytes, int ncells, mi_probe_cell* d_cells, void* hip_stream) {
@@ -403,25 +287,14 @@ int mi_probe_process_device(mi_probe* p, const void* d_iq, size_t stream_stride_
         return fail(MI_ERR_INVALID, "NULL argument");
     if (p->ntargets < 1)
         return fail(MI_ERR_INVALID, "channel probe: no target list set (mi_probe_set_targets)");
-    if (ncells < 1 || ncells > p->max_cells)
-        return fail(MI_ERR_INVALID, "ncells outside 1 .. max_cells");
-    if (!aligned(d_cells, 8))
-        return fail(MI_ERR_INVALID, "channel probe: d_cells must be 8-byte aligned");
-    if (!aligned(d_iq, static_cast<uintptr_t>(p->sample_bytes)) || stream_stride_bytes % static_cast<size_t>(p->sample_bytes) != 0)
-        return fail(MI_ERR_INVALID, "channel probe: d_iq and the stream stride must be aligned to one complex sample");
+    if (const int rc = mi::iq_call_ok(p, d_iq, stream_stride_bytes, ncells, aligned(d_cells, 8), "d_cells must be 8-byte aligned"))
+        return rc;
     if (hipSetDevice(p->gpu) != hipSuccess)
         return fail(MI_ERR_HIP, "hipSetDevice failed");
     hipStream_t q = static_cast<hipStream_t>(hip_stream);
     mi::ProbeArgs a{};
-    a.iq = static_cast<const unsigned char*>(d_iq);
-    a.stream_stride = stream_stride_bytes;
-    a.valid_bytes = mi_probe_bytes_needed(p, ncells);
-    a.hop_bytes = static_cast<uint32_t>(p->hop_bytes);
+    mi::iq_args(a, p, d_iq, stream_stride_bytes, ncells);
     a.nwindows = static_cast<uint32_t>(ncells) * p->wpc;
-    a.window = p->d_window;
-    a.tw = p->d_tw;
-    a.levels = p->d_levels;
-    a.conv_scale = p->conv_scale;
     a.active = p->d_active;
     a.targets = p->d_targets;
     a.z = p->d_z;
