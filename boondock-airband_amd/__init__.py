@@ -171,6 +171,16 @@ LIMIT_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in LimitRow._fields_])  # 
 LIMIT_STATE_DTYPE = np.dtype([("x", "<f4", (LIMIT_HISTORY,))])  # one row of the limiter stage's state blob, MI_LIMIT_STATE_ROW_BYTES = 4344
 
 
+class DenoiseRow(C.Structure):  # mi_denoise_row
+    _fields_ = [("reduction_db", C.c_float), ("over", C.c_float)]
+
+
+DENOISE_HOP, DENOISE_FRAME, DENOISE_FFT, DENOISE_BINS, DENOISE_DEPTH = 250, 500, 512, 257, 8  # MI_DENOISE_*
+DENOISE_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in DenoiseRow._fields_])  # the same 8 bytes as a numpy record
+# one row of the noise reduction stage's state blob, MI_DENOISE_STATE_ROW_BYTES = 9196
+DENOISE_STATE_DTYPE = np.dtype([("x", "<f4", (DENOISE_FRAME,)), ("m", "<f4", (DENOISE_DEPTH - 1, DENOISE_BINS))])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -254,6 +264,8 @@ ABI_SYMBOLS = [
     "mi_vband_get_state", "mi_vband_set_state", "mi_vband_set_timing", "mi_vband_last_launch_ms", "mi_vband_taps", "mi_vband_plan_host",
     "mi_limit_default_row", "mi_limit_create", "mi_limit_destroy", "mi_limit_set_rows", "mi_limit_process_device", "mi_limit_state_size",
     "mi_limit_get_state", "mi_limit_set_state", "mi_limit_set_timing", "mi_limit_last_launch_ms", "mi_limit_plan_host", "mi_limit_pregain_host",
+    "mi_denoise_default_row", "mi_denoise_create", "mi_denoise_destroy", "mi_denoise_set_rows", "mi_denoise_process_device", "mi_denoise_state_size",
+    "mi_denoise_get_state", "mi_denoise_set_state", "mi_denoise_set_timing", "mi_denoise_last_launch_ms", "mi_denoise_window", "mi_denoise_plan_host",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -395,6 +407,21 @@ def lib():
         L.mi_vband_last_launch_ms.argtypes = [vp, vp]
         L.mi_vband_taps.argtypes = [C.c_uint32, C.c_uint32, vp]
         L.mi_vband_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
+        L.mi_denoise_default_row.argtypes = []
+        L.mi_denoise_default_row.restype = DenoiseRow
+        L.mi_denoise_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.mi_denoise_destroy.argtypes = [vp]
+        L.mi_denoise_destroy.restype = None
+        L.mi_denoise_set_rows.argtypes = [vp, vp, vp]
+        L.mi_denoise_process_device.argtypes = [vp, vp, sz, C.c_int, vp, sz, vp]
+        L.mi_denoise_state_size.argtypes = [vp]
+        L.mi_denoise_state_size.restype = sz
+        L.mi_denoise_get_state.argtypes = [vp, vp, sz]
+        L.mi_denoise_set_state.argtypes = [vp, vp, sz]
+        L.mi_denoise_set_timing.argtypes = [vp, C.c_int]
+        L.mi_denoise_last_launch_ms.argtypes = [vp, vp]
+        L.mi_denoise_window.argtypes = [vp]
+        L.mi_denoise_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
         L.mi_limit_default_row.argtypes = []
         L.mi_limit_default_row.restype = LimitRow
         L.mi_limit_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -532,7 +559,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -545,7 +572,7 @@ class _PostStage(_TimedStage):
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
-        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1220,7 +1247,7 @@ def _row_settings(rows_cfg, rows, dtype, scalar, default):
 
 
 class _PlaneStage(_PostStage):
-    """A post-stage that reads a plane [rows][row_stride] and writes one of the same layout under per-row settings (Vband, Limit):
+    """A post-stage that reads a plane [rows][row_stride] and writes one of the same layout under per-row settings (Vband, Limit, Denoise):
     `_rows_of`(rows_cfg, rows) gives the settings as the library takes them.  A subclass adds process_device under its own argument names."""
     _launches = 2
     _rows_of = None
@@ -1342,6 +1369,57 @@ def limit_pregain_host(records, row, ceiling=None, percentile=0):
     _check(lib().mi_limit_pregain_host(_ptr(records) if records.size else None, records.size, int(row), float(ceiling), int(percentile), C.byref(pregain),
                                        C.byref(used)))
     return np.float32(pregain.value), used.value
+
+
+def denoise_default_row():
+    """mi_denoise_default_row: (reduction_db, over) = (12.0, 4.5)"""
+    r = lib().mi_denoise_default_row()
+    return r.reduction_db, r.over
+
+
+def _denoise_rows(rows_cfg, rows):
+    """None (the default row everywhere), one (reduction_db, over) pair for every row, or a pair per row -> [rows] of DENOISE_ROW_DTYPE"""
+    return _row_settings(rows_cfg, rows, DENOISE_ROW_DTYPE, np.float32, denoise_default_row)
+
+
+def denoise_fresh_state(rows):
+    """the blob of a new handle: zeros in the carried samples, +Inf in the seven carried minima"""
+    s = np.zeros(rows, DENOISE_STATE_DTYPE)
+    s["m"] = np.inf
+    return s.view(np.uint8).reshape(-1)
+
+
+class Denoise(_PlaneStage):
+    """mi_denoise: the noise reduction stage -- a spectral gate per row over a plane of audio: 512-point spectra of 500-sample frames
+    at a hop of 250, a noise floor per bin from the minima of the last eight batches, every bin turned down that does not stand above
+    `over` times the floor, by `reduction_db` at the most, and the overlap-add of the inverse transforms, written as a plane of the same
+    layout (delayed by 250 samples, clamped to [-1, 1]) that the voice band stage, the limiter, the gate, the splitter, the PCM stage
+    and the mixer take in its place.  row_enabled: truth value per row (a disabled row's output is not written and its state stays);
+    rows_cfg: (reduction_db, over) for every row or one pair per row, None = the defaults 12 / 4.5; either one 0 gives a pure delay.
+    state() gives rows * 9196 bytes, .view(DENOISE_STATE_DTYPE): the 500 input samples and the seven minima a row carries into its
+    next call."""
+    _destroy, _prefix, _rows_of, _launches = "mi_denoise_destroy", "mi_denoise", _denoise_rows, 3
+
+    def process_device(self, d_in, row_stride, nbatches, d_out, out_stride, hip_stream=None):
+        """Raw device pointers (ints), the strides in floats; d_out [rows][out_stride] must not overlap d_in; asynchronous on
+        hip_stream."""
+        self._call("process_device", d_in, row_stride, nbatches, d_out, out_stride, hip_stream)
+
+
+def denoise_plan_host(row_enabled, plane, rows_cfg=None, state=None, nbatches=None, out=None):
+    """mi_denoise_plan_host: the noise reduction stage's plane from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    rows_cfg as for Denoise; state: the blob (rows * 9196 bytes) or None (denoise_fresh_state); nbatches: batches of the call, default
+    row_stride // WAVE_BATCH; out: float32 [rows][out_stride] to write into (a disabled row's floats stay), default zeros
+    [rows][nbatches * WAVE_BATCH].  Returns (out, state after the call)."""
+    state = denoise_fresh_state(len(_flags(row_enabled))) if state is None else state
+    return _plane_plan_host(lib().mi_denoise_plan_host, _denoise_rows, DENOISE_STATE_DTYPE, row_enabled, plane, rows_cfg, state, nbatches, out)
+
+
+def denoise_window():
+    """mi_denoise_window: the 500 float32 coefficients of the stage's sine window"""
+    w = np.zeros(DENOISE_FRAME, np.float32)
+    _check(lib().mi_denoise_window(_ptr(w)))
+    return w
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

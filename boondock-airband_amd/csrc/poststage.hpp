@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -321,6 +321,29 @@ static_assert(sizeof(LimitRowState) == MI_LIMIT_STATE_ROW_BYTES && MI_LIMIT_HIST
 // everywhere) checked, or the first refusal.  (poststage_host.cpp)
 int limit_row_ok(const mi_limit_row& r);
 int limit_rows(const mi_limit_row* row_cfg, size_t rows, std::vector<mi_limit_row>& out);
+
+// The noise reduction stage (include/mi_airband.h "noise reduction stage").  One row of its state: the checkpoint blob is an array of
+// these, and denoise.hip keeps the same array in device memory.
+struct DenoiseRowState {
+    float x[MI_DENOISE_FRAME];                           // the last 500 input samples of the row's last batch, oldest first
+    float m[MI_DENOISE_DEPTH - 1][MI_DENOISE_BINS];      // M of the row's last seven batches, oldest first; +Inf at first
+};
+static_assert(sizeof(DenoiseRowState) == MI_DENOISE_STATE_ROW_BYTES && sizeof(mi_denoise_row) == 8 && MI_DENOISE_FRAME == 2 * MI_DENOISE_HOP &&
+                  kWaveBatch % MI_DENOISE_HOP == 0 && MI_DENOISE_FRAME <= MI_DENOISE_FFT && MI_DENOISE_FFT == 1 << MI_DENOISE_FFT_LOG &&
+                  MI_DENOISE_BINS == MI_DENOISE_FFT / 2 + 1 && MI_DENOISE_FRAME % 4 == 0,
+              "the noise reduction stage's blob and settings layouts are ABI");
+// A row's settings as the kernels take them.
+struct DenoiseGains {
+    float g_min;  // (float)10^(-reduction_db / 20)
+    float over;
+};
+// What both halves of the noise reduction stage share (poststage_host.cpp).  denoise_rows: the rows' settings (NULL = the default row
+// everywhere) checked and converted, or the first refusal with its message set.  denoise_window: w[500].  spec_twiddles: the plan's
+// twiddle table at fft_size_log log2n, 2^(log2n - 1) x {re, im}.  denoise_fresh: a blob's first bytes, zeros and +Inf.
+int denoise_rows(const mi_denoise_row* row_cfg, size_t rows, std::vector<DenoiseGains>& out);
+void denoise_window(float* w);
+int spec_twiddles(int log2n, std::vector<float>& tw);
+void denoise_fresh(DenoiseRowState* state, size_t rows);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

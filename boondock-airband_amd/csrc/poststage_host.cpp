@@ -4,8 +4,9 @@
 // too: mi_survey_bin_range, the plan's bin rule read backwards; the channel finder's twin, mi_occupancy_plan_host; and the channel probe's host half
 // (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; the PCM
 // stage's twin mi_pcm_plan_host with its taps and WAV headers; the audio spectrum stage's twin mi_aspec_plan_host with its window,
-// band and the notch vote; the voice band stage's twin mi_vband_plan_host with its settings, taps and classes; and the peak limiter
-// stage's twin mi_limit_plan_host with its settings and the pregain helper.
+// band and the notch vote; the voice band stage's twin mi_vband_plan_host with its settings, taps and classes; the peak limiter
+// stage's twin mi_limit_plan_host with its settings and the pregain helper; and the noise reduction stage's twin mi_denoise_plan_host
+// with its settings and window.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -820,11 +821,12 @@ void aspec_window(float* w) {
         w[i] = w[kWaveBatch - 1 - i] = static_cast<float>(0.5 - 0.5 * std::cos(2.0 * pi * i / (kWaveBatch - 1)));
 }
 
-int aspec_twiddles(std::vector<float>& tw) {
+// the plan's twiddle table at fft_size_log log2n, 2^(log2n - 1) x {re, im}
+int spec_twiddles(int log2n, std::vector<float>& tw) {
     mi_device_cfg dev{};
     dev.sample_rate = 2560000;
     dev.centerfreq = 120000000;
-    dev.fft_size_log = MI_ASPEC_FFT_LOG;
+    dev.fft_size_log = log2n;
     dev.sfmt = MI_SFMT_U8;
     dev.fullscale = 127.5f;
     dev.tau = -1;
@@ -835,22 +837,26 @@ int aspec_twiddles(std::vector<float>& tw) {
     return MI_OK;
 }
 
+int aspec_twiddles(std::vector<float>& tw) {
+    return spec_twiddles(MI_ASPEC_FFT_LOG, tw);
+}
+
 namespace {
 
-// X = the FFT spec at N = 2048, in place over z[2048][2]: bit reversal, then stages s = 1 .. 11 of butterflies (a, b) -> (a + t, a - t)
+// X = the FFT spec at N = 2^log2n, in place over z[N][2]: bit reversal, then stages s = 1 .. log2n of butterflies (a, b) -> (a + t, a - t)
 // with t = w b, w = tw[j N / 2^s]; t = b for w = 1, (b.im, -b.re) for w = -j, else the two explicit fma.
-void aspec_fft(const float* tw, float* z) {
-    constexpr uint32_t n = MI_ASPEC_FFT;
+void spec_fft(const float* tw, float* z, int log2n) {
+    const uint32_t n = 1u << log2n;
     for (uint32_t i = 0; i < n; ++i) {
         uint32_t r = 0;
-        for (int b = 0; b < MI_ASPEC_FFT_LOG; ++b)
-            r |= ((i >> b) & 1u) << (MI_ASPEC_FFT_LOG - 1 - b);
+        for (int b = 0; b < log2n; ++b)
+            r |= ((i >> b) & 1u) << (log2n - 1 - b);
         if (r > i) {
             std::swap(z[2 * i], z[2 * r]);
             std::swap(z[2 * i + 1], z[2 * r + 1]);
         }
     }
-    for (int s = 1; s <= MI_ASPEC_FFT_LOG; ++s) {
+    for (int s = 1; s <= log2n; ++s) {
         const uint32_t half = 1u << (s - 1), step = n >> s;
         for (uint32_t base = 0; base < n; base += 2 * half)
             for (uint32_t j = 0; j < half; ++j) {
@@ -956,7 +962,7 @@ extern "C" int mi_aspec_plan_host(const mi_aspec_cfg* cfg, int rows, int nbatche
             std::fill(z.begin(), z.end(), 0.0f);
             for (int i = 0; i < mi::kWaveBatch; ++i)
                 z[2 * static_cast<size_t>(i)] = x[i] * w[static_cast<size_t>(i)];
-            mi::aspec_fft(tw.data(), z.data());
+            mi::spec_fft(tw.data(), z.data(), MI_ASPEC_FFT_LOG);
             for (size_t j = 0; j < MI_ASPEC_BINS; ++j) {
                 const float rr = z[2 * j] * z[2 * j], ii = z[2 * j + 1] * z[2 * j + 1];
                 pw[j] = rr + ii;
@@ -1248,5 +1254,152 @@ extern "C" int mi_limit_pregain_host(const mi_tx_record* records, size_t n, uint
     std::sort(peaks.begin(), peaks.end());
     const float peak = peaks[static_cast<size_t>((static_cast<uint64_t>(peaks.size()) - 1) * percentile / 100)];
     *pregain = std::fmin(std::fmax(ceiling / peak, 0.0009765625f), 1024.0f);
+    return MI_OK;
+}
+
+// ---- noise reduction stage, host side (include/mi_airband.h "noise reduction stage"): the settings' check, the window, and the twin
+// of denoise.hip -- one block at a time as the device goes: its nine frames through spec_fft, M of the block, m over the eight rows
+// that end with it, the gains, the conjugate transforms and the overlap-add.
+namespace mi {
+
+int denoise_rows(const mi_denoise_row* row_cfg, size_t rows, std::vector<DenoiseGains>& out) {
+    out.resize(rows);
+    for (size_t r = 0; r < rows; ++r) {
+        const mi_denoise_row s = row_cfg ? row_cfg[r] : mi_denoise_default_row();
+        if (!(s.reduction_db >= 0.0f && s.reduction_db <= 40.0f))
+            return fail(MI_ERR_INVALID, "noise reduction stage: reduction_db must be within 0 .. 40");
+        if (!(s.over >= 0.0f && s.over <= 64.0f))
+            return fail(MI_ERR_INVALID, "noise reduction stage: over must be within 0 .. 64");
+        out[r] = DenoiseGains{static_cast<float>(std::pow(10.0, -static_cast<double>(s.reduction_db) / 20.0)), s.over};
+    }
+    return MI_OK;
+}
+
+// The lower half comes from the formula; the upper half is its mirror image, so that the symmetry holds bit for bit whatever sin()
+// does with the two arguments.
+void denoise_window(float* w) {
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < MI_DENOISE_HOP; ++i)
+        w[i] = w[MI_DENOISE_FRAME - 1 - i] = static_cast<float>(std::sin(pi * (i + 0.5) / MI_DENOISE_FRAME));
+}
+
+void denoise_fresh(DenoiseRowState* state, size_t rows) {
+    for (size_t r = 0; r < rows; ++r) {
+        std::fill(state[r].x, state[r].x + MI_DENOISE_FRAME, 0.0f);
+        std::fill(&state[r].m[0][0], &state[r].m[0][0] + (MI_DENOISE_DEPTH - 1) * MI_DENOISE_BINS, INFINITY);
+    }
+}
+
+}  // namespace mi
+
+extern "C" mi_denoise_row mi_denoise_default_row(void) {
+    return mi_denoise_row{12.0f, 4.5f};
+}
+
+extern "C" int mi_denoise_window(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::denoise_window(out);
+    return MI_OK;
+}
+
+extern "C" int mi_denoise_plan_host(const mi_denoise_row* row_cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* in, size_t row_stride,
+                                    void* state_inout, float* out, size_t out_stride) {
+    if (!row_enabled || !in || !state_inout || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1)
+        return fail(MI_ERR_INVALID, "denoise plan needs rows >= 1 and nbatches >= 1");
+    std::vector<mi::DenoiseGains> cfg;
+    if (const int rc = mi::denoise_rows(row_cfg, static_cast<size_t>(rows), cfg))
+        return rc;
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch || out_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    if (mi::planes_overlap(in, row_stride, out, out_stride, static_cast<size_t>(rows), static_cast<size_t>(nbatches)))
+        return fail(MI_ERR_INVALID, "the output overlaps the input plane");
+    constexpr int kHop = MI_DENOISE_HOP, kFrame = MI_DENOISE_FRAME, kN = MI_DENOISE_FFT, kBins = MI_DENOISE_BINS, kDepth = MI_DENOISE_DEPTH;
+    constexpr int kFrames = mi::kWaveBatch / kHop + 1;  // 9 frames make a block
+    std::vector<float> tw, w(kFrame);
+    if (const int rc = mi::spec_twiddles(MI_DENOISE_FFT_LOG, tw))
+        return rc;
+    mi::denoise_window(w.data());
+    std::vector<mi::DenoiseRowState> blob(static_cast<size_t>(rows));  // (the caller's bytes may not be aligned)
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::DenoiseRowState));
+    std::vector<float> x(kFrame + mi::kWaveBatch), X(static_cast<size_t>(kFrames) * 2 * kN), P(static_cast<size_t>(kFrames) * kBins),
+        S(static_cast<size_t>(kFrames) * kBins), z(2 * kN), v(static_cast<size_t>(kFrames) * kFrame), noise(kBins);
+    std::vector<float> floors;  // M of the seven batches before the call, then of the call's
+    bool silent[kFrames];
+    for (int r = 0; r < rows; ++r) {
+        if (!row_enabled[r])
+            continue;
+        const float g_min = cfg[static_cast<size_t>(r)].g_min, over = cfg[static_cast<size_t>(r)].over;
+        mi::DenoiseRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = in + static_cast<size_t>(r) * row_stride;
+        floors.assign(&st.m[0][0], &st.m[0][0] + (kDepth - 1) * kBins);
+        floors.resize(static_cast<size_t>(kDepth - 1 + nbatches) * kBins);
+        for (int b = 0; b < nbatches; ++b) {
+            // x[500 + n] = sample n of the block, x[0 .. 499] = the 500 before it; frame j of the block begins at x[250 j]
+            const float* const blk = row + static_cast<size_t>(b) * mi::kWaveBatch;
+            std::memcpy(x.data(), b ? blk - kFrame : st.x, kFrame * sizeof(float));
+            std::memcpy(x.data() + kFrame, blk, mi::kWaveBatch * sizeof(float));
+            for (int j = 0; j < kFrames; ++j) {
+                float* const Xj = X.data() + static_cast<size_t>(j) * 2 * kN;
+                std::fill(Xj, Xj + 2 * kN, 0.0f);
+                silent[j] = true;
+                for (int i = 0; i < kFrame; ++i) {
+                    const float s = x[static_cast<size_t>(kHop * j + i)];
+                    silent[j] = silent[j] && s == 0.0f;
+                    Xj[2 * i] = s * w[static_cast<size_t>(i)];
+                }
+                mi::spec_fft(tw.data(), Xj, MI_DENOISE_FFT_LOG);
+                for (int k = 0; k < kBins; ++k) {
+                    const float rr = Xj[2 * k] * Xj[2 * k], ii = Xj[2 * k + 1] * Xj[2 * k + 1];
+                    P[static_cast<size_t>(j) * kBins + k] = rr + ii;
+                }
+            }
+            float* const M = floors.data() + static_cast<size_t>(kDepth - 1 + b) * kBins;
+            std::fill(M, M + kBins, INFINITY);
+            for (int j = 1; j < kFrames; ++j) {
+                const float* const p0 = P.data() + static_cast<size_t>(j - 1) * kBins;
+                const float* const p1 = p0 + kBins;
+                for (int k = 0; k < kBins; ++k) {
+                    const int lo = k ? k - 1 : 1, hi = k < kBins - 1 ? k + 1 : kBins - 2;
+                    const float t0 = (p0[lo] + p0[k]) + p0[hi], t1 = (p1[lo] + p1[k]) + p1[hi];
+                    const float s = t0 + t1;
+                    S[static_cast<size_t>(j) * kBins + k] = s;
+                    if (!silent[j - 1] && !silent[j])
+                        M[k] = std::fmin(M[k], s);
+                }
+            }
+            std::memcpy(S.data(), S.data() + kBins, kBins * sizeof(float));  // the block's first frame takes S of the frame behind it
+            for (int k = 0; k < kBins; ++k) {
+                float m = INFINITY;
+                for (int d = 0; d < kDepth; ++d)
+                    m = std::fmin(m, floors[static_cast<size_t>(b + d) * kBins + k]);
+                noise[static_cast<size_t>(k)] = std::isinf(m) ? 0.0f : over * m;
+            }
+            for (int j = 0; j < kFrames; ++j) {
+                const float* const Xj = X.data() + static_cast<size_t>(j) * 2 * kN;
+                for (int k = 0; k < kN; ++k) {
+                    const int kk = k <= kN / 2 ? k : kN - k;
+                    const float n = noise[static_cast<size_t>(kk)], s = S[static_cast<size_t>(j) * kBins + kk];
+                    const float g = n >= s ? g_min : std::fmax(g_min, 1.0f - n / s);
+                    z[2 * static_cast<size_t>(k)] = g * Xj[2 * k];
+                    z[2 * static_cast<size_t>(k) + 1] = -(g * Xj[2 * k + 1]);
+                }
+                mi::spec_fft(tw.data(), z.data(), MI_DENOISE_FFT_LOG);
+                for (int i = 0; i < kFrame; ++i)
+                    v[static_cast<size_t>(j) * kFrame + i] = (z[2 * static_cast<size_t>(i)] * (1.0f / kN)) * w[static_cast<size_t>(i)];
+            }
+            float* const dst = out + static_cast<size_t>(r) * out_stride + static_cast<size_t>(b) * mi::kWaveBatch;
+            for (int n = 0; n < mi::kWaveBatch; ++n) {
+                const int q = n / kHop, i = n - q * kHop;  // the older frame q of the block, the newer one q + 1
+                const float y = v[static_cast<size_t>(q) * kFrame + kHop + i] + v[static_cast<size_t>(q + 1) * kFrame + i];
+                dst[n] = std::fmin(std::fmax(y, -1.0f), 1.0f);
+            }
+        }
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - kFrame, kFrame * sizeof(float));
+        std::memcpy(&st.m[0][0], floors.data() + static_cast<size_t>(nbatches) * kBins, (kDepth - 1) * kBins * sizeof(float));
+    }
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::DenoiseRowState));
     return MI_OK;
 }

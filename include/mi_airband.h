@@ -1201,6 +1201,97 @@ int mi_limit_plan_host(const mi_limit_row* row_cfg /* [rows], NULL = defaults */
  * percentile over 100.  Tried on synthetic signals only. */
 int mi_limit_pregain_host(const mi_tx_record* records, size_t n, uint32_t row, float ceiling, uint32_t percentile, float* pregain, uint32_t* used);
 
+/* ---------------- noise reduction stage: spectral gate per row, on the device ----------------
+ * Nothing else behind the demodulator lowers the broadband hiss under an open AM transmission: the squelch chooses between a whole
+ * batch and silence, and the reference hands waveout to LAME as it is (output.cpp:147-171).  This stage estimates the noise floor of
+ * a row per frequency bin from the minima of its own recent short-time spectra and turns every bin down that does not stand above
+ * it.  A post-stage like the voice band stage: it reads a plane [rows][row_stride] of float32 audio and writes a plane d_out
+ * [rows][out_stride] of the same layout, which the voice band stage, the limiter, the gate, the splitter, the PCM stage and the mixer
+ * take in its place.  Every batch of every enabled row is handled: there is no index and no download entry.  There is no recursion
+ * in time -- minima over a window stand where running averages would --, so every (row, batch) block is computed on its own.
+ *
+ * Stream model.  As for the voice band stage: a row's audio is one running sequence x over all batches of all calls the row was
+ * enabled in; samples before the handle's first call are 0.
+ * Frames are aligned to batches: hop H = MI_DENOISE_HOP = 250 (eight per batch), length MI_DENOISE_FRAME = 500, transform length
+ * MI_DENOISE_FFT = 512, bins k = 0 .. 256 (MI_DENOISE_BINS = 257, 31.25 Hz each).  Frame f covers x[250 (f - 1) .. 250 (f + 1)): with
+ * b the batch, frames 8b .. 8b + 7 begin in the 250 samples before each eighth of batch b and frame 8b - 1 is the last 500 samples
+ * before it.
+ * Window w (mi_denoise_window): w[i] = (float) sin(pi (i + 0.5) / 500), evaluated in float64 for i <= 249; w[499 - i] = w[i], so that w
+ * is symmetric bit for bit.  u[i] = x[250 (f - 1) + i] * w[i] for i < 500, twelve zeros behind them.  The same window is used for
+ * synthesis: w[i]^2 + w[i + 250]^2 = 1, so gains of 1 give back x delayed by 250 samples, up to rounding.
+ * Per frame.  X = the FFT spec of DESIGN.md 2 at log2n 9 of (u, 0.0f).  P[k] = re * re + im * im for k = 0 .. 256, three float32
+ * operations.  A frame is SILENT when all 500 of its samples x compare equal to zero.  With T_f[k] = (P_f[k - 1] + P_f[k]) + P_f[k + 1]
+ * in that order, the bin index mirrored at the ends (k - 1 at k = 0 is bin 1, k + 1 at k = 256 is bin 255), the smoothed power is
+ *   S_f[k] = T_{f-1}[k] + T_f[k]
+ * and frame f COUNTS when neither f - 1 nor f is silent.
+ * Noise estimate, per row and batch b.  M_b[k] = the minimum of S_f[k] over the counting frames f = 8b .. 8b + 7, +Inf when none
+ * counts.  m[k] = the minimum of M_{b-7} .. M_b: MI_DENOISE_DEPTH = 8 batches, one second of history with the current batch.
+ * N_b[k] = over * m[k], and 0.0f where m[k] is +Inf: with no evidence the stage is transparent.
+ * Gain.  A block -- the nine frames f = 8b - 1 .. 8b + 7 that batch b's outputs are made of -- uses the noise estimate of its own batch
+ * for all nine, and nothing outside x[2000 b - 500 .. 2000 b + 2000): its first frame 8b - 1 has no frame in front of it there and
+ * takes the smoothed power of the frame behind it, S_{8b}, which covers its span as well.  Per frame and bin, with S that power:
+ *   g[k] = g_min                                    where N_b[k] >= S[k]
+ *   g[k] = fmaxf(g_min, 1.0f - N_b[k] / S[k])       otherwise (the correctly rounded IEEE division, then one subtraction)
+ * g_min = (float) 10^(-reduction_db / 20), computed in float64 on the host.  Frame 8b - 1 gets the gains of batch b here, for the
+ * half of it that batch b's outputs hold, and it got those of batch b - 1 as frame 8 (b - 1) + 7 of the block before, for the other
+ * half: both halves are well defined because each block uses only its own gains, and no block waits for another.
+ * Synthesis.  Y[k] = g[min(k, 512 - k)] * X[k] for all 512 bins, two float32 products.  z = Re(FFT(conj(Y))) * (1.0f / 512): the same
+ * forward graph on (Y.re, -Y.im), the scale an exact power of two.  v_f[i] = z[i] * w[i] for i < 500.  Sample n of the row's sequence
+ * lies in segment s = n div 250:  y[n] = v_s[i + 250] + v_{s+1}[i]  with i = n mod 250, one float32 addition.  The plane holds
+ *   out[n] = fminf(fmaxf(y[n - 250], -1.0f), 1.0f)
+ * A batch's outputs depend on x from 500 samples before the batch to its end.  NaN and Inf are unspecified, as everywhere behind the
+ * demodulator.
+ * Delay.  250 samples (15.6 ms) against the demodulator's flags; a caller keeps a transmission's last samples with the gate's open
+ * trail (MI_GATE_OPEN_TRAIL), as for the voice band stage.
+ * Row settings.  mi_denoise_row { reduction_db, over } per row, refused unless 0 <= reduction_db <= 40 and 0 <= over <= 64 (NaN is
+ * refused) -- those of a disabled row too.  reduction_db = 0 or over = 0 gives a pure delay, up to rounding, which keeps rows aligned
+ * for the mixer.
+ * State: per row the last 500 input samples of the last batch of the last call the row was enabled in, oldest first, zeros at first;
+ * then M of the last seven batches, oldest first, 7 x 257 float32, +Inf at first.  The blob is rows * MI_DENOISE_STATE_ROW_BYTES bytes,
+ * little-endian.  A disabled row's output row is not written and its state keeps its bytes.
+ * The defaults were tried on synthetic signals only (tools/denoise_classes.py).
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned or overlapping
+ * buffers, nbatches outside 1 .. max_batches. */
+enum { MI_DENOISE_HOP = 250, MI_DENOISE_FRAME = 500, MI_DENOISE_FFT_LOG = 9, MI_DENOISE_FFT = 512, MI_DENOISE_BINS = 257, MI_DENOISE_DEPTH = 8,
+       MI_DENOISE_STATE_ROW_BYTES = 9196 };
+typedef struct { float reduction_db; float over; } mi_denoise_row;
+typedef struct mi_denoise mi_denoise;
+
+/* { 12.0f, 4.5f }.  over: mean(S) / mean(m) on seeded white Gaussian noise (20 s; sigma 0.003, 0.03, 0.3: 4.26, 4.29, 4.25, mean
+ * 4.27), rounded up to the next 0.5 so that the estimate sits slightly above the floor and residual "musical" noise stays down
+ * (tools/denoise_classes.py through the host twin, on the CPU).  At this row white noise comes out 9.2 dB lower after a second, and
+ * so does whatever else stands still for a second: a steady 1 kHz tone 10 dB above the noise in its bin loses 12.0 dB. */
+mi_denoise_row mi_denoise_default_row(void);
+/* row_cfg [rows] (NULL = the default row everywhere); row_enabled [rows] as for mi_vband_create; rows and max_batches within the
+ * gate's limits (1 <= rows < 2^20, rows * max_batches < 2^24).  The handle owns the scratch for M of a call's batches,
+ * [rows][max_batches][257] float32. */
+int mi_denoise_create(const mi_denoise_row* row_cfg /* [rows] */, const uint8_t* row_enabled, int rows, int max_batches, int gpu, mi_denoise** out);
+void mi_denoise_destroy(mi_denoise* d);
+/* Other settings (row_cfg [rows], NULL = keep) and / or other rows (row_enabled [rows], NULL = keep) from the next call on; at least
+ * one of the two.  All state stays.  Completes the work queued on the device first. */
+int mi_denoise_set_rows(mi_denoise* d, const mi_denoise_row* row_cfg, const uint8_t* row_enabled);
+/* One call over nbatches (1 .. max_batches) batches: d_in [rows][row_stride] and d_out [rows][out_stride], both 16-byte aligned with
+ * strides that are multiples of 4 floats and at least nbatches * 2000; the two planes must not overlap (the call is refused when
+ * they do).  Asynchronous on `hip_stream`, no host synchronisation; three kernels without atomics -- M of every block into the
+ * scratch, then the gains and the synthesis, then the enabled rows' last 500 input samples and last seven M into the carried state
+ * -- so every byte is the same on every run and equals mi_denoise_plan_host's. */
+int mi_denoise_process_device(mi_denoise* d, const float* d_in, size_t row_stride, int nbatches, float* d_out, size_t out_stride, void* hip_stream);
+/* Checkpoint / resume, rows * MI_DENOISE_STATE_ROW_BYTES bytes in the layout above (mi_denoise_plan_host reads and writes the same
+ * bytes).  Both complete queued work first. */
+size_t mi_denoise_state_size(const mi_denoise* d);
+int mi_denoise_get_state(mi_denoise* d, void* buf, size_t len);
+int mi_denoise_set_state(mi_denoise* d, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[3] = {floor, apply, tails}.  tools/denoise_rate.py. */
+int mi_denoise_set_timing(mi_denoise* d, int on);
+int mi_denoise_last_launch_ms(mi_denoise* d, float* ms /* [3] */);
+/* The 500 window coefficients w[0 .. 499].  Host only. */
+int mi_denoise_window(float* out /* [MI_DENOISE_FRAME] */);
+/* The host twin: no GPU and no HIP call; the same bytes and the same state blob.  in [rows][row_stride], out [rows][out_stride] (no
+ * alignment asked, no overlap allowed); state_inout rows * MI_DENOISE_STATE_ROW_BYTES bytes, read and updated (a fresh blob: zeros
+ * in the samples, +Inf in M). */
+int mi_denoise_plan_host(const mi_denoise_row* row_cfg /* [rows], NULL = defaults */, const uint8_t* row_enabled, int rows, int nbatches,
+                         const float* in, size_t row_stride, void* state_inout, float* out, size_t out_stride);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
