@@ -181,6 +181,25 @@ DENOISE_ROW_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in DenoiseRow._fields_])
 DENOISE_STATE_DTYPE = np.dtype([("x", "<f4", (DENOISE_FRAME,)), ("m", "<f4", (DENOISE_DEPTH - 1, DENOISE_BINS))])
 
 
+class SelcalCfg(C.Structure):  # mi_selcal_cfg: 0 = MI_SELCAL_16 and the default of every setting
+    _fields_ = [("mode", C.c_uint32), ("ntones", C.c_uint32), ("freq", C.c_float * 32), ("min_energy", C.c_float), ("min_tonality", C.c_float),
+                ("max_twist", C.c_float), ("min_separation", C.c_float), ("min_run", C.c_uint32), ("max_run", C.c_uint32), ("max_gap", C.c_uint32),
+                ("zero", C.c_uint32)]
+
+
+SELCAL_16, SELCAL_32, SELCAL_CUSTOM = 0, 1, 2  # MI_SELCAL_*
+SELCAL_WINDOW, SELCAL_HOP, SELCAL_HISTORY, SELCAL_MAX_TONES = 2000, 1000, 1002, 32
+SELCAL_NONE, SELCAL_NONE8 = 0, 0xFF  # no pair; no third tone in a table of two
+SELCAL_IDLE, SELCAL_FIRST, SELCAL_OVER, SELCAL_GAP, SELCAL_SECOND, SELCAL_DONE = range(6)
+# mi_selcal_window_record (24 bytes), mi_selcal_code (32 bytes), and one row of the SELCAL stage's state blob, MI_SELCAL_STATE_ROW_BYTES = 4048
+SELCAL_WINDOW_DTYPE = np.dtype([("best", "u1"), ("second", "u1"), ("third", "u1"), ("zero", "u1"), ("p_best", "<f4"), ("p_second", "<f4"),
+                                ("p_third", "<f4"), ("energy", "<f4"), ("pair", "<u4")])
+SELCAL_CODE_DTYPE = np.dtype([("row", "<u4"), ("seq", "<u4"), ("tone", "u1", (4,)), ("first_window", "<u4"), ("last_window", "<u4"), ("run1", "<u4"),
+                              ("gap", "<u4"), ("batch", "<u4")])
+SELCAL_STATE_DTYPE = np.dtype([("x", "<f4", (SELCAL_HISTORY,)), ("window", "<u4"), ("seq", "<u4"), ("phase", "<u4"), ("pair1", "<u4"), ("pair2", "<u4"),
+                               ("run1", "<u4"), ("run2", "<u4"), ("gap", "<u4"), ("first_window", "<u4"), ("zero", "<u4")])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -266,6 +285,9 @@ ABI_SYMBOLS = [
     "mi_limit_get_state", "mi_limit_set_state", "mi_limit_set_timing", "mi_limit_last_launch_ms", "mi_limit_plan_host", "mi_limit_pregain_host",
     "mi_denoise_default_row", "mi_denoise_create", "mi_denoise_destroy", "mi_denoise_set_rows", "mi_denoise_process_device", "mi_denoise_state_size",
     "mi_denoise_get_state", "mi_denoise_set_state", "mi_denoise_set_timing", "mi_denoise_last_launch_ms", "mi_denoise_window", "mi_denoise_plan_host",
+    "mi_selcal_create", "mi_selcal_destroy", "mi_selcal_set_rows", "mi_selcal_process_device", "mi_selcal_download", "mi_selcal_state_size",
+    "mi_selcal_get_state", "mi_selcal_set_state", "mi_selcal_set_timing", "mi_selcal_last_launch_ms", "mi_selcal_plan_host", "mi_selcal_table",
+    "mi_selcal_settings", "mi_selcal_window", "mi_selcal_code_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -422,6 +444,23 @@ def lib():
         L.mi_denoise_last_launch_ms.argtypes = [vp, vp]
         L.mi_denoise_window.argtypes = [vp]
         L.mi_denoise_plan_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz, vp, vp, sz]
+        L.mi_selcal_create.argtypes = [C.POINTER(SelcalCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_selcal_destroy.argtypes = [vp]
+        L.mi_selcal_destroy.restype = None
+        L.mi_selcal_set_rows.argtypes = [vp, vp]
+        L.mi_selcal_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp]
+        L.mi_selcal_download.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mi_selcal_state_size.argtypes = [vp]
+        L.mi_selcal_state_size.restype = sz
+        L.mi_selcal_get_state.argtypes = [vp, vp, sz]
+        L.mi_selcal_set_state.argtypes = [vp, vp, sz]
+        L.mi_selcal_set_timing.argtypes = [vp, C.c_int]
+        L.mi_selcal_last_launch_ms.argtypes = [vp, vp]
+        L.mi_selcal_plan_host.argtypes = [C.POINTER(SelcalCfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp, vp]
+        L.mi_selcal_table.argtypes = [C.POINTER(SelcalCfg), C.POINTER(C.c_uint32), vp, vp, vp]
+        L.mi_selcal_settings.argtypes = [C.POINTER(SelcalCfg), C.POINTER(SelcalCfg), C.POINTER(C.c_float)]
+        L.mi_selcal_window.argtypes = [vp]
+        L.mi_selcal_code_text.argtypes = [C.c_uint32, vp, vp]
         L.mi_limit_default_row.argtypes = []
         L.mi_limit_default_row.restype = LimitRow
         L.mi_limit_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -559,7 +598,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -572,7 +611,8 @@ class _PostStage(_TimedStage):
     def state(self):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
-        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
+        .view(SELCAL_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1420,6 +1460,121 @@ def denoise_window():
     w = np.zeros(DENOISE_FRAME, np.float32)
     _check(lib().mi_denoise_window(_ptr(w)))
     return w
+
+
+def selcal_cfg(mode=SELCAL_16, freq=None, min_energy=0.0, min_tonality=0.0, max_twist=0.0, min_separation=0.0, min_run=0, max_run=0, max_gap=0):
+    """mi_selcal_cfg: a table mode (freq: the 2 .. 32 tones of SELCAL_CUSTOM in Hz) and the settings, 0 = the default; a SelcalCfg or
+    None (all defaults) passes through"""
+    if isinstance(mode, SelcalCfg):
+        return mode
+    c = SelcalCfg()
+    c.mode = int(mode or 0)
+    if freq is not None:
+        c.ntones = len(freq)
+        for i, f in enumerate(list(freq)[:SELCAL_MAX_TONES]):
+            c.freq[i] = f
+    c.min_energy, c.min_tonality, c.max_twist, c.min_separation = min_energy, min_tonality, max_twist, min_separation
+    c.min_run, c.max_run, c.max_gap = min_run, max_run, max_gap
+    return c
+
+
+def selcal_settings(cfg=None):
+    """mi_selcal_settings: (the settings with every default filled in, as a SelcalCfg; the constant c of the tonality condition)"""
+    out, c = SelcalCfg(), C.c_float()
+    _check(lib().mi_selcal_settings(C.byref(selcal_cfg(cfg)), C.byref(out), C.byref(c)))
+    return out, np.float32(c.value)
+
+
+def selcal_max_codes(nbatches, cfg=None):
+    """the most codes one row can emit in a call of nbatches batches"""
+    return 1 + (2 * nbatches - 1) // (2 * selcal_settings(cfg)[0].min_run)
+
+
+def selcal_table(cfg=None):
+    """mi_selcal_table: (freq [n], coeff [n], letters, a str of n) of the tone table of cfg (None = SELCAL_16)"""
+    n = C.c_uint32()
+    freq, coeff, letter = np.zeros(SELCAL_MAX_TONES, np.float32), np.zeros(SELCAL_MAX_TONES, np.float32), np.zeros(SELCAL_MAX_TONES, np.uint8)
+    _check(lib().mi_selcal_table(C.byref(selcal_cfg(cfg)), C.byref(n), _ptr(freq), _ptr(coeff), _ptr(letter)))
+    return freq[:n.value], coeff[:n.value], bytes(letter[:n.value]).decode()
+
+
+def selcal_window():
+    """mi_selcal_window: the 2000 float32 coefficients of the stage's Hann window"""
+    w = np.zeros(SELCAL_WINDOW, np.float32)
+    _check(lib().mi_selcal_window(_ptr(w)))
+    return w
+
+
+def selcal_code_text(tones, mode=SELCAL_16):
+    """mi_selcal_code_text: "AB-CD" from a code record's four tone indices"""
+    t = np.ascontiguousarray(tones, dtype=np.uint8)
+    assert t.size == 4
+    out = np.zeros(6, np.uint8)
+    _check(lib().mi_selcal_code_text(int(mode), _ptr(t), _ptr(out)))
+    return bytes(out[:5]).decode()
+
+
+class Selcal(_PostStage):
+    """mi_selcal: the SELCAL decoder stage -- per row, which aircraft was called: a Goertzel bank over the SELCAL tone table per window of
+    2000 samples at a hop of 1000, the decision whether a window names a pair of tones, and a decoder over the windows that emits one
+    code record per call (two pulses of two tones).  It reads a plane of audio (the demodulator's, or what the noise reduction, the
+    voice band stage, the limiter or a mixer wrote) and needs no flags.  row_enabled: truth value per row; cfg: selcal_cfg(...) or
+    None; max_codes: capacity of the code buffer, 0 = rows * selcal_max_codes(max_batches).  state() gives rows * 4048 bytes, whose
+    fields .view(SELCAL_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_selcal_destroy", "mi_selcal", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_codes=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = selcal_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_selcal_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_codes, gpu, C.byref(self._h)))
+        most = self.rows * selcal_max_codes(max_batches, self.cfg)
+        self.max_codes = min(max_codes, most) if max_codes else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_selcal_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_codes, d_row_first_code, d_count, d_windows=None, hip_stream=None):
+        """Raw device pointers (ints; d_windows may be None), the stride in floats; asynchronous on hip_stream."""
+        self._nwin = 2 * nbatches if d_windows is not None else 0
+        _check(lib().mi_selcal_process_device(self._h, d_plane, row_stride, nbatches, d_windows, d_codes, d_row_first_code, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (codes [k] of SELCAL_CODE_DTYPE, windows [rows][2 * nbatches] of
+        SELCAL_WINDOW_DTYPE or None where the call stored none, row_first_code [rows + 1], count [2]) with k = count[1]."""
+        codes = np.zeros(self.max_codes, SELCAL_CODE_DTYPE)
+        nwin = getattr(self, "_nwin", 0)
+        windows = np.zeros((self.rows, nwin), SELCAL_WINDOW_DTYPE) if nwin else None
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_selcal_download(self._h, hip_stream, _ptr(codes), None if windows is None else _ptr(windows), _ptr(row_first), _ptr(count)))
+        return codes[:int(count[1])], windows, row_first, count
+
+
+def selcal_plan_host(row_enabled, plane, cfg=None, state=None, max_codes=0, nbatches=None, want_windows=True):
+    """mi_selcal_plan_host: the SELCAL stage's windows and codes from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 4048 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_codes: 0 = every code of the call.  Returns (codes [count[1]], windows [rows][2 * nbatches] or None, row_first_code
+    [rows + 1], count [2], state after the call)."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = selcal_cfg(cfg)
+    state = np.zeros(rows * SELCAL_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * SELCAL_STATE_DTYPE.itemsize
+    cap = max_codes or max(1, rows * selcal_max_codes(max(nb, 1), c))
+    codes = np.zeros(cap, SELCAL_CODE_DTYPE)
+    windows = np.zeros((rows, 2 * max(nb, 0)), SELCAL_WINDOW_DTYPE) if want_windows else None
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_selcal_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), None if windows is None else _ptr(windows),
+                                     _ptr(codes), cap, _ptr(row_first), _ptr(count)))
+    return codes[:int(count[1])], windows, row_first, count, state
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

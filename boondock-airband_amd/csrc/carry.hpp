@@ -1,4 +1,4 @@
-// carry.hpp -- the device side of a stage that carries samples from call to call (pcm.hip, vband.hip, limit.hip): a row's state is
+// carry.hpp -- the device side of a stage that carries samples from call to call (pcm.hip, vband.hip, limit.hip, selcal.hip): a row's state is
 // the last kHistory input samples of its last call, oldest first, and a block is staged behind a LEAD of kLead = kHistory + 2 floats --
 // two that no output reaches, then the history -- so that the lead is whole float4 of the row's previous batch wherever there is one.
 // (k_limit stages its lead with the text of load_lead4 written out: DESIGN.md section 6.)
@@ -33,7 +33,7 @@ __device__ __forceinline__ float4 load_lead4(const float* blk, const RowState& c
 template <int kHistory, class RowState>
 __global__ __launch_bounds__(256) void k_carry_tails(const uint8_t* __restrict__ enabled, const float* __restrict__ wave, const size_t row_stride,
                                                      const uint32_t rows, const uint32_t nbatches, RowState* __restrict__ state) {
-    static_assert(sizeof(RowState) == kHistory * sizeof(float) && kHistory <= kWaveBatch, "the blob is the history");
+    static_assert(sizeof(RowState::x) == kHistory * sizeof(float) && kHistory <= kWaveBatch, "the blob begins with the history");
     if constexpr (kHistory <= 64) {
         const uint32_t row = blockIdx.x * kRowsPerGroup + (threadIdx.x >> 6), j = threadIdx.x & 63;
         if (row >= rows || j >= kHistory || !enabled[row])

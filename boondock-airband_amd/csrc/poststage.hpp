@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <string>
@@ -52,7 +53,7 @@ struct LaunchTiming {
     const char* stage;  // leads the error texts
     int launches;
     bool on = false;
-    Event ev[5];
+    Event ev[6];
     LaunchTiming(const char* stage_, int launches_) : stage(stage_), launches(launches_) {}
     void stamp(int i, hipStream_t q) {
         if (on)
@@ -344,6 +345,121 @@ int denoise_rows(const mi_denoise_row* row_cfg, size_t rows, std::vector<Denoise
 void denoise_window(float* w);
 int spec_twiddles(int log2n, std::vector<float>& tw);
 void denoise_fresh(DenoiseRowState* state, size_t rows);
+
+// The SELCAL decoder stage (include/mi_airband.h "SELCAL decoder stage").  One row of its state: the checkpoint blob is an array of
+// these, and selcal.hip keeps the same array in device memory.
+struct SelcalRowState {
+    float x[MI_SELCAL_HISTORY];  // the last 1002 input samples of the row's last batch, oldest first (the two oldest are never read)
+    uint32_t window;             // windows seen since creation / set_state
+    uint32_t seq;                // codes emitted
+    uint32_t phase;              // MI_SELCAL_IDLE .. MI_SELCAL_DONE
+    uint32_t pair1, pair2;       // lo | hi << 8, MI_SELCAL_NONE where the phase has none
+    uint32_t run1, run2, gap;
+    uint32_t first_window;
+    uint32_t zero;
+};
+static_assert(sizeof(SelcalRowState) == MI_SELCAL_STATE_ROW_BYTES && offsetof(SelcalRowState, window) == MI_SELCAL_HISTORY * 4 &&
+                  sizeof(mi_selcal_window_record) == 24 && sizeof(mi_selcal_code) == 32 && sizeof(mi_selcal_cfg) == 168 &&
+                  (MI_SELCAL_HISTORY + 2) % 4 == 0 && MI_SELCAL_HISTORY >= MI_SELCAL_HOP && MI_SELCAL_WINDOW == kWaveBatch &&
+                  MI_SELCAL_WINDOW == 2 * MI_SELCAL_HOP && MI_SELCAL_STATE_ROW_BYTES % 8 == 0,
+              "the SELCAL stage's blob, record and settings layouts are ABI");
+// The settings with every default filled in and what follows from them, as both halves take them.
+struct SelcalPlan {
+    uint32_t ntones;
+    float freq[MI_SELCAL_MAX_TONES], coeff[MI_SELCAL_MAX_TONES];
+    char letter[MI_SELCAL_MAX_TONES];
+    float min_energy, tc, max_twist, min_separation;  // tc = min_tonality * c
+    uint32_t min_run, max_run, max_gap;
+    mi_selcal_cfg filled;  // the settings as the caller would have written them
+    float c;
+};
+// The decoder's part of a row's state, as the walk carries it in registers.
+struct SelcalDecoder {
+    uint32_t phase, pair1, pair2, run1, run2, gap, first_window;
+};
+// One window through the decoder table of the header: `pair` is what the window named (MI_SELCAL_NONE: none), n its number.
+// True when the window emits a code (d then holds what the record takes).  Host and device run this text.
+__host__ __device__ inline bool selcal_step(SelcalDecoder& d, const uint32_t pair, const uint32_t n, const uint32_t min_run, const uint32_t max_run,
+                                            const uint32_t max_gap) {
+    const bool some = pair != MI_SELCAL_NONE;
+    bool from_idle = false;
+    switch (d.phase) {
+    case MI_SELCAL_FIRST:
+        if (some && pair == d.pair1) {
+            if (++d.run1 > max_run) {
+                d.phase = MI_SELCAL_OVER;
+                d.run1 = max_run + 1;
+            }
+        } else if (d.run1 >= min_run) {
+            if (some) {
+                d.phase = MI_SELCAL_SECOND;
+                d.pair2 = pair;
+                d.run2 = 1;
+            } else {
+                d.phase = MI_SELCAL_GAP;
+                d.gap = 1;
+            }
+        } else {
+            from_idle = true;  // (a pair Q restarts FIRST, no pair ends in IDLE)
+        }
+        break;
+    case MI_SELCAL_OVER:
+        from_idle = !(some && pair == d.pair1);
+        break;
+    case MI_SELCAL_GAP:
+        if (!some) {
+            from_idle = ++d.gap > max_gap;
+        } else if (pair == d.pair1) {
+            d.run1 += d.gap + 1;
+            d.gap = 0;
+            d.phase = MI_SELCAL_FIRST;
+            if (d.run1 > max_run) {
+                d.phase = MI_SELCAL_OVER;
+                d.run1 = max_run + 1;
+            }
+        } else {
+            d.phase = MI_SELCAL_SECOND;
+            d.pair2 = pair;
+            d.run2 = 1;
+        }
+        break;
+    case MI_SELCAL_SECOND:
+        if (some && pair == d.pair2) {
+            if (++d.run2 == min_run) {
+                d.phase = MI_SELCAL_DONE;
+                return true;
+            }
+        } else {
+            from_idle = true;
+        }
+        break;
+    case MI_SELCAL_DONE:
+        from_idle = !(some && pair == d.pair2);
+        break;
+    default:
+        from_idle = true;
+        break;
+    }
+    if (from_idle) {
+        d = SelcalDecoder{MI_SELCAL_IDLE, MI_SELCAL_NONE, MI_SELCAL_NONE, 0u, 0u, 0u, 0u};
+        if (some) {
+            d.phase = MI_SELCAL_FIRST;
+            d.pair1 = pair;
+            d.run1 = 1;
+            d.first_window = n;
+        }
+    }
+    return false;
+}
+// the most codes one row can emit in a call: the first needs one window of the call, each further one 2 * min_run
+inline uint32_t selcal_max_codes(uint32_t min_run, uint64_t nbatches) {
+    return static_cast<uint32_t>(1 + (2 * nbatches - 1) / (2ull * min_run));
+}
+// What both halves of the SELCAL stage share (poststage_host.cpp).  selcal_plan: MI_OK with the plan, or the settings' refusal with
+// its message set.  selcal_window: w[2000].  selcal_state_ok: NULL, or what is impossible about a blob's decoder state.
+int selcal_plan(const mi_selcal_cfg* cfg, SelcalPlan* out);
+void selcal_window(float* w);
+const char* selcal_state_ok(const SelcalRowState* state, size_t rows, const SelcalPlan& plan);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

@@ -5,8 +5,8 @@
 // (target list, features, classification); the CTCSS tone finder's twin mi_tones_plan_host with its tone table and vote; the PCM
 // stage's twin mi_pcm_plan_host with its taps and WAV headers; the audio spectrum stage's twin mi_aspec_plan_host with its window,
 // band and the notch vote; the voice band stage's twin mi_vband_plan_host with its settings, taps and classes; the peak limiter
-// stage's twin mi_limit_plan_host with its settings and the pregain helper; and the noise reduction stage's twin mi_denoise_plan_host
-// with its settings and window.
+// stage's twin mi_limit_plan_host with its settings and the pregain helper; the noise reduction stage's twin mi_denoise_plan_host
+// with its settings and window; and the SELCAL decoder stage's twin mi_selcal_plan_host with its tables, settings, window and code text.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1401,5 +1401,307 @@ extern "C" int mi_denoise_plan_host(const mi_denoise_row* row_cfg, const uint8_t
         std::memcpy(&st.m[0][0], floors.data() + static_cast<size_t>(nbatches) * kBins, (kDepth - 1) * kBins * sizeof(float));
     }
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::DenoiseRowState));
+    return MI_OK;
+}
+
+// ---- SELCAL decoder stage, host side (include/mi_airband.h "SELCAL decoder stage"): the tone tables, the settings' check, the window,
+// the blob's check, and the twin of selcal.hip -- one row, one window and one tone at a time, then the decoder over the row's windows.
+namespace mi {
+
+namespace {
+
+// ascending frequency; the classic sixteen are the even positions.  The odd ones (SELCAL 32) are written from memory: see the header.
+constexpr float kSelcalHz[MI_SELCAL_MAX_TONES] = {312.6f,  329.2f,  346.7f,  365.2f,  384.6f,  405.0f,  426.6f,  449.3f,  473.2f,  498.3f,  524.8f,
+                                                  552.7f,  582.1f,  613.1f,  645.7f,  680.0f,  716.1f,  754.2f,  794.3f,  836.6f,  881.0f,  927.9f,
+                                                  977.2f,  1029.2f, 1083.9f, 1141.6f, 1202.3f, 1266.2f, 1333.5f, 1404.4f, 1479.1f, 1557.8f};
+constexpr char kSelcalLetter[MI_SELCAL_MAX_TONES + 1] = "ATBUCVDWEXFYGZH1J2K3L4M5P6Q7R8S9";
+
+bool in_range(float v, float lo, float hi) {
+    return std::isfinite(v) && v >= lo && v <= hi;
+}
+
+}  // namespace
+
+void selcal_window(float* w) {
+    aspec_window(w);  // the same 2000-point Hann window, symmetric bit for bit
+}
+
+int selcal_plan(const mi_selcal_cfg* cfg, SelcalPlan* out) {
+    mi_selcal_cfg c{};
+    if (cfg)
+        c = *cfg;
+    SelcalPlan p{};
+    if (c.mode == MI_SELCAL_16 || c.mode == MI_SELCAL_32) {
+        const int step = c.mode == MI_SELCAL_16 ? 2 : 1;
+        p.ntones = MI_SELCAL_MAX_TONES / step;
+        for (uint32_t t = 0; t < p.ntones; ++t) {
+            p.freq[t] = kSelcalHz[t * step];
+            p.letter[t] = kSelcalLetter[t * step];
+        }
+        c.ntones = p.ntones;
+        std::memcpy(c.freq, p.freq, sizeof(p.freq));
+    } else if (c.mode == MI_SELCAL_CUSTOM) {
+        if (c.ntones < 2 || c.ntones > MI_SELCAL_MAX_TONES)
+            return fail(MI_ERR_INVALID, "SELCAL stage: a custom table needs 2 .. 32 tones");
+        for (uint32_t t = 0; t < c.ntones; ++t) {
+            if (!in_range(c.freq[t], 250.0f, 2000.0f))
+                return fail(MI_ERR_INVALID, "SELCAL stage: a custom tone must lie within 250 .. 2000 Hz");
+            if (t && !(c.freq[t] - c.freq[t - 1] >= 16.0f))
+                return fail(MI_ERR_INVALID, "SELCAL stage: custom tones must ascend, at least 16 Hz apart");
+            p.freq[t] = c.freq[t];
+            p.letter[t] = '?';
+        }
+        for (uint32_t t = c.ntones; t < MI_SELCAL_MAX_TONES; ++t)
+            c.freq[t] = 0.0f;
+        p.ntones = c.ntones;
+    } else {
+        return fail(MI_ERR_INVALID, "SELCAL stage: mode must be MI_SELCAL_16, MI_SELCAL_32 or MI_SELCAL_CUSTOM");
+    }
+    const double pi = 3.14159265358979323846;
+    for (uint32_t t = 0; t < p.ntones; ++t)
+        p.coeff[t] = static_cast<float>(2.0 * std::cos(2.0 * pi * static_cast<double>(p.freq[t]) / kWaveRate));
+    c.min_energy = c.min_energy == 0.0f ? 1e-3f : c.min_energy;
+    c.min_tonality = c.min_tonality == 0.0f ? 0.5f : c.min_tonality;
+    c.max_twist = c.max_twist == 0.0f ? 8.0f : c.max_twist;
+    c.min_separation = c.min_separation == 0.0f ? 4.0f : c.min_separation;
+    c.min_run = c.min_run ? c.min_run : 8;
+    c.max_run = c.max_run ? c.max_run : (c.min_run > 22 ? c.min_run : 22);
+    c.max_gap = c.max_gap ? c.max_gap : 8;
+    if (!in_range(c.min_energy, 1e-12f, 1e6f))
+        return fail(MI_ERR_INVALID, "SELCAL stage: min_energy must be finite and within 1e-12 .. 1e6 (0 = the default)");
+    if (!in_range(c.min_tonality, 0.01f, 1.0f))
+        return fail(MI_ERR_INVALID, "SELCAL stage: min_tonality must be within 0.01 .. 1 (0 = the default)");
+    if (!in_range(c.max_twist, 1.0f, 1000.0f))
+        return fail(MI_ERR_INVALID, "SELCAL stage: max_twist must be within 1 .. 1000 (0 = the default)");
+    if (!in_range(c.min_separation, 1.0f, 1000.0f))
+        return fail(MI_ERR_INVALID, "SELCAL stage: min_separation must be within 1 .. 1000 (0 = the default)");
+    if (c.min_run < 2 || c.min_run > 64)
+        return fail(MI_ERR_INVALID, "SELCAL stage: min_run must be within 2 .. 64 windows (0 = the default)");
+    if (c.max_run < c.min_run || c.max_run > 1024)
+        return fail(MI_ERR_INVALID, "SELCAL stage: max_run must be within min_run .. 1024 windows (0 = the default)");
+    if (c.max_gap < 1 || c.max_gap > 64)
+        return fail(MI_ERR_INVALID, "SELCAL stage: max_gap must be within 1 .. 64 windows (0 = the default)");
+    if (c.zero)
+        return fail(MI_ERR_INVALID, "SELCAL stage: the settings' zero field must be 0");
+    float w[MI_SELCAL_WINDOW];
+    selcal_window(w);
+    double sw = 0.0, sw2 = 0.0;
+    for (int j = 0; j < MI_SELCAL_WINDOW; ++j) {
+        sw += static_cast<double>(w[j]);
+        sw2 += static_cast<double>(w[j]) * static_cast<double>(w[j]);
+    }
+    p.c = static_cast<float>(sw * sw / (2.0 * sw2));
+    p.min_energy = c.min_energy;
+    p.tc = c.min_tonality * p.c;
+    p.max_twist = c.max_twist;
+    p.min_separation = c.min_separation;
+    p.min_run = c.min_run;
+    p.max_run = c.max_run;
+    p.max_gap = c.max_gap;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+const char* selcal_state_ok(const SelcalRowState* state, size_t rows, const SelcalPlan& plan) {
+    const auto pair_ok = [&](uint32_t p) { return p <= 0xFFFFu && (p & 0xFFu) < (p >> 8) && (p >> 8) < plan.ntones; };
+    for (size_t r = 0; r < rows; ++r) {
+        const SelcalRowState& s = state[r];
+        if (s.zero)
+            return "the zero field is not 0";
+        bool ok = false;
+        switch (s.phase) {
+        case MI_SELCAL_IDLE:
+            ok = s.pair1 == MI_SELCAL_NONE && s.pair2 == MI_SELCAL_NONE && !s.run1 && !s.run2 && !s.gap && !s.first_window;
+            break;
+        case MI_SELCAL_FIRST:
+            ok = pair_ok(s.pair1) && s.pair2 == MI_SELCAL_NONE && s.run1 >= 1 && s.run1 <= plan.max_run && !s.run2 && !s.gap;
+            break;
+        case MI_SELCAL_OVER:
+            ok = pair_ok(s.pair1) && s.pair2 == MI_SELCAL_NONE && s.run1 == plan.max_run + 1 && !s.run2 && !s.gap;
+            break;
+        case MI_SELCAL_GAP:
+            ok = pair_ok(s.pair1) && s.pair2 == MI_SELCAL_NONE && s.run1 >= plan.min_run && s.run1 <= plan.max_run && !s.run2 && s.gap >= 1 &&
+                 s.gap <= plan.max_gap;
+            break;
+        case MI_SELCAL_SECOND:
+        case MI_SELCAL_DONE:
+            ok = pair_ok(s.pair1) && pair_ok(s.pair2) && s.pair1 != s.pair2 && s.run1 >= plan.min_run && s.run1 <= plan.max_run && s.gap <= plan.max_gap &&
+                 (s.phase == MI_SELCAL_DONE ? s.run2 == plan.min_run : s.run2 >= 1 && s.run2 < plan.min_run);
+            break;
+        default:
+            return "an unknown decoder phase";
+        }
+        if (!ok)
+            return "an impossible decoder state (pairs, runs or gap that the phase cannot have)";
+    }
+    return nullptr;
+}
+
+namespace {
+
+// items 0 .. 4 of the header over the 2000 samples at x
+mi_selcal_window_record selcal_window_record(const float* x, const float* w, const SelcalPlan& plan) {
+    float y[MI_SELCAL_WINDOW], s[64], p[MI_SELCAL_MAX_TONES];
+    for (int j = 0; j < MI_SELCAL_WINDOW; ++j)
+        y[j] = x[j] * w[j];
+    for (int l = 0; l < 64; ++l) {
+        s[l] = y[l] * y[l];
+        for (int j = l + 64; j < MI_SELCAL_WINDOW; j += 64)
+            s[l] = s[l] + y[j] * y[j];
+    }
+    for (int h = 32; h >= 1; h /= 2)
+        for (int l = 0; l < h; ++l)
+            s[l] = s[l] + s[l + h];
+    const float E = s[0];
+    const int nt = static_cast<int>(plan.ntones);
+    for (int t = 0; t < nt; ++t) {
+        p[t] = 0.0f;
+        if (E == 0.0f)  // a silent window: the powers are zero by definition
+            continue;
+        const float c = plan.coeff[t];
+        float q1 = 0.0f, q2 = 0.0f;
+        for (int j = 0; j < MI_SELCAL_WINDOW; ++j) {
+            const float q0 = c * q1 - q2 + y[j];
+            q2 = q1;
+            q1 = q0;
+        }
+        p[t] = q1 * q1 + q2 * q2 - q1 * q2 * c;
+    }
+    int i0 = 0, i1 = -1, i2 = -1;
+    for (int t = 1; t < nt; ++t) {
+        if (p[t] > p[i0]) {
+            i2 = i1;
+            i1 = i0;
+            i0 = t;
+        } else if (i1 < 0 || p[t] > p[i1]) {
+            i2 = i1;
+            i1 = t;
+        } else if (i2 < 0 || p[t] > p[i2]) {
+            i2 = t;
+        }
+    }
+    const float pb = p[i0], ps = p[i1], pt = i2 < 0 ? 0.0f : p[i2];
+    const bool named = E >= plan.min_energy && pb + ps >= plan.tc * E && pb <= plan.max_twist * ps && ps >= plan.min_separation * pt;
+    const uint32_t lo = static_cast<uint32_t>(i0 < i1 ? i0 : i1), hi = static_cast<uint32_t>(i0 < i1 ? i1 : i0);
+    return mi_selcal_window_record{static_cast<uint8_t>(i0), static_cast<uint8_t>(i1), static_cast<uint8_t>(i2 < 0 ? MI_SELCAL_NONE8 : i2), 0, pb, ps, pt, E,
+                                   named ? lo | hi << 8 : MI_SELCAL_NONE};
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" int mi_selcal_table(const mi_selcal_cfg* cfg, uint32_t* ntones, float* freq, float* coeff, char* letter) {
+    mi_selcal_cfg c{};
+    if (cfg) {
+        c.mode = cfg->mode;
+        c.ntones = cfg->ntones;
+        std::memcpy(c.freq, cfg->freq, sizeof(c.freq));
+    }
+    mi::SelcalPlan p;
+    if (const int rc = mi::selcal_plan(&c, &p))
+        return rc;
+    if (ntones)
+        *ntones = p.ntones;
+    for (uint32_t t = 0; t < p.ntones; ++t) {
+        if (freq)
+            freq[t] = p.freq[t];
+        if (coeff)
+            coeff[t] = p.coeff[t];
+        if (letter)
+            letter[t] = p.letter[t];
+    }
+    return MI_OK;
+}
+
+extern "C" int mi_selcal_settings(const mi_selcal_cfg* cfg, mi_selcal_cfg* out, float* c) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::SelcalPlan p;
+    if (const int rc = mi::selcal_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    if (c)
+        *c = p.c;
+    return MI_OK;
+}
+
+extern "C" int mi_selcal_window(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::selcal_window(out);
+    return MI_OK;
+}
+
+extern "C" int mi_selcal_code_text(uint32_t mode, const uint8_t* tones, char* out) {
+    if (!tones || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (mode != MI_SELCAL_16 && mode != MI_SELCAL_32 && mode != MI_SELCAL_CUSTOM)
+        return fail(MI_ERR_INVALID, "SELCAL stage: mode must be MI_SELCAL_16, MI_SELCAL_32 or MI_SELCAL_CUSTOM");
+    const uint32_t n = mode == MI_SELCAL_16 ? 16 : 32, step = mode == MI_SELCAL_16 ? 2 : 1;
+    for (int i = 0; i < 4; ++i) {
+        if (tones[i] >= n)
+            return fail(MI_ERR_INVALID, "SELCAL stage: a tone index beyond the mode's table");
+        out[i + (i >= 2)] = mode == MI_SELCAL_CUSTOM ? '?' : mi::kSelcalLetter[tones[i] * step];
+    }
+    out[2] = '-';
+    out[5] = '\0';
+    return MI_OK;
+}
+
+extern "C" int mi_selcal_plan_host(const mi_selcal_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                   void* state_inout, mi_selcal_window_record* windows, mi_selcal_code* codes, size_t max_codes, uint32_t* row_first_code,
+                                   uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !codes || !row_first_code || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_codes < 1)
+        return fail(MI_ERR_INVALID, "SELCAL plan needs rows >= 1, nbatches >= 1 and max_codes >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::SelcalPlan plan;
+    if (const int rc = mi::selcal_plan(cfg, &plan))
+        return rc;
+    if (static_cast<uint64_t>(rows) * mi::selcal_max_codes(plan.min_run, static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "SELCAL plan: the codes of the call do not fit the 32-bit count");
+    std::vector<mi::SelcalRowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::SelcalRowState));
+    if (const char* const why = mi::selcal_state_ok(blob.data(), blob.size(), plan))
+        return fail(MI_ERR_INVALID, std::string("SELCAL plan: malformed state blob: ") + why);
+    std::vector<float> w(MI_SELCAL_WINDOW), x(MI_SELCAL_HOP + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    mi::selcal_window(w.data());
+    const uint32_t nwin = 2u * static_cast<uint32_t>(nbatches);
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first_code[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::SelcalRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        // x = the last 1000 carried samples, then the call's
+        std::memcpy(x.data(), st.x + (MI_SELCAL_HISTORY - MI_SELCAL_HOP), MI_SELCAL_HOP * sizeof(float));
+        std::memcpy(x.data() + MI_SELCAL_HOP, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::SelcalDecoder d{st.phase, st.pair1, st.pair2, st.run1, st.run2, st.gap, st.first_window};
+        for (uint32_t i = 0; i < nwin; ++i) {
+            const mi_selcal_window_record rec = mi::selcal_window_record(x.data() + static_cast<size_t>(i) * MI_SELCAL_HOP, w.data(), plan);
+            if (windows)
+                windows[static_cast<size_t>(r) * nwin + i] = rec;
+            const uint32_t n = st.window + i;
+            if (mi::selcal_step(d, rec.pair, n, plan.min_run, plan.max_run, plan.max_gap)) {
+                if (k < max_codes)
+                    codes[k] = mi_selcal_code{static_cast<uint32_t>(r), st.seq, {static_cast<uint8_t>(d.pair1 & 0xFF), static_cast<uint8_t>(d.pair1 >> 8),
+                                              static_cast<uint8_t>(d.pair2 & 0xFF), static_cast<uint8_t>(d.pair2 >> 8)},
+                                              d.first_window, n, d.run1, d.gap, i / 2};
+                ++k;
+                st.seq += 1;
+            }
+        }
+        st.window += nwin;
+        st.phase = d.phase, st.pair1 = d.pair1, st.pair2 = d.pair2, st.run1 = d.run1, st.run2 = d.run2, st.gap = d.gap, st.first_window = d.first_window;
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_SELCAL_HISTORY, MI_SELCAL_HISTORY * sizeof(float));
+    }
+    row_first_code[rows] = k;
+    count[0] = k;
+    count[1] = k < max_codes ? k : static_cast<uint32_t>(max_codes);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::SelcalRowState));
     return MI_OK;
 }

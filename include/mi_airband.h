@@ -1292,6 +1292,183 @@ int mi_denoise_window(float* out /* [MI_DENOISE_FRAME] */);
 int mi_denoise_plan_host(const mi_denoise_row* row_cfg /* [rows], NULL = defaults */, const uint8_t* row_enabled, int rows, int nbatches,
                          const float* in, size_t row_stride, void* state_inout, float* out, size_t out_stride);
 
+/* ---------------- SELCAL decoder stage: tone-pair codes per row, on the device ----------------
+ * SELCAL is the selective calling of the aeronautical bands: a call is two pulses of about 1 s, about 0.2 s apart, each pulse two
+ * simultaneous audio tones out of a table of 16 (32 with the SELCAL 32 extension); the letters of the four tones are the code
+ * ("AB-CD").  The reference leaves the chirps in the recording; mi_tones_* answers "which CTCSS tone?" and mi_aspec_* "which steady
+ * whistle?", and neither sees two tones at once, a pulse's length or a sequence of pulses.  This stage answers "which aircraft was
+ * called?": one code record per call, with row and time.  A post-stage in the tone finder's mould: it reads a plane
+ * [rows][row_stride] of float32 audio -- the demodulator's d_waveout, or what the noise reduction, the voice band stage, the limiter
+ * or a mixer wrote in its place -- and writes records.  It takes no d_axc: a closed batch is zeros and decides itself (item 0 below).
+ *
+ * Tone tables (mi_selcal_table).  Tones are indexed in ascending frequency; coeff[t] = (float)(2 cos(2 pi f_t / 16000)), evaluated
+ * in float64 from the float32 literal.
+ *   MI_SELCAL_16 (the default), the classic table:
+ *     A 312.6  B 346.7  C 384.6  D 426.6  E 473.2  F 524.8  G 582.1  H 645.7  J 716.1  K 794.3  L 881.0  M 977.2  P 1083.9  Q 1202.3
+ *     R 1333.5  S 1479.1
+ *   MI_SELCAL_32, those sixteen and the sixteen that sit between them and above S, 32 tones in ascending frequency (A T B U C V ..):
+ *     T 329.2  U 365.2  V 405.0  W 449.3  X 498.3  Y 552.7  Z 613.1  1 680.0  2 754.2  3 836.6  4 927.9  5 1029.2  6 1141.6  7 1266.2
+ *     8 1404.4  9 1557.8
+ *     These sixteen are written from memory of the extension: no document available when this was written could confirm them, and
+ *     they have not been checked against a published table or an off-air call.  What is checked is that all 32 literals lie within
+ *     0.15 Hz of 312.6 * 10^(0.0225 k), k = 0 .. 31 the position in ascending frequency (the classic tones are the even k); at
+ *     analysis bins of 8 Hz an error of 0.1 Hz is harmless.
+ *   MI_SELCAL_CUSTOM: cfg.ntones = 2 .. 32 frequencies cfg.freq[], strictly ascending, within 250 .. 2000 Hz, at least 16 Hz apart
+ *     (NaN is refused); every letter is '?'.
+ *
+ * Stream model.  As for the voice band stage: a row's audio is one running sequence x over all batches of all calls the row was
+ * enabled in; samples before the handle's first call are 0.
+ * Windows are MI_SELCAL_WINDOW = 2000 samples at a hop of 1000: two per (row, batch), numbered per row from creation / set_state.
+ * With b the call's batch and n0 the row's window counter when the call began, window n0 + 2b covers the last 1000 samples before
+ * the batch and the batch's first 1000, window n0 + 2b + 1 the batch's samples 0 .. 1999.  The handle carries MI_SELCAL_HISTORY = 1002
+ * samples per row, of which the two oldest are never read: the lead in front of a block (carry.hpp) is history + 2 floats and must be
+ * whole float4.  The history length is ABI.
+ * Per window, everything float32, every operation rounded on its own, no fused multiply-add:
+ *   0. y[j] = x[j] * w[j], j = 0 .. 1999.  w (mi_selcal_window) is the 2000-point Hann window 0.5 - 0.5 cos(2 pi j / 1999), evaluated
+ *      in float64 for j <= 999 and cast; w[1999 - j] = w[j], so that w is symmetric bit for bit.
+ *   1. E, the window's energy: s_l = the sequential sum, j ascending over j = l (mod 64), of y[j] * y[j], starting from the first
+ *      product, for l = 0 .. 63; then the butterfly s_l + s_{l+32} for l < 32, then + 16, 8, 4, 2, 1 in the same way; E is element 0.
+ *      If E == 0.0f the window is SILENT: p[t] = +0.0f for every tone BY DEFINITION, and the recurrence of item 2 is not part of its
+ *      definition.  Why: E == 0 says every product y[j] * y[j] rounded to zero, |y[j]| < 2^-75.  Where every y[j] is +-0 -- a closed
+ *      batch, digital silence, -0.0f throughout -- the recurrence gives +0.0f everywhere anyway.  Where some are tiny but not zero it
+ *      would give powers below 10^-36, which would carry no information and could never name a pair (min_energy > 0); fixing them at
+ *      zero lets the device skip 2000 steps for every closed batch, and no byte depends on whether it did.
+ *   2. For every tone t of the table: q1 = q2 = 0; for j = 0 .. 1999 in order: q0 = coeff[t] * q1 - q2 + y[j]; q2 = q1; q1 = q0 (a
+ *      product, a subtraction, an addition).  p[t] = q1 * q1 + q2 * q2 - q1 * q2 * coeff[t], evaluated left to right:
+ *      ((q1 * q1) + (q2 * q2)) - ((q1 * q2) * coeff[t]).
+ *   3. best, second, third: the indices of the three largest p, in that order, a tie going to the lowest index (the first three of a
+ *      stable descending sort).  A table of two tones has no third: third = MI_SELCAL_NONE8 and its power +0.0f.
+ *   4. The window NAMES the pair {best, second} iff all four hold, and names no pair otherwise:
+ *        E >= min_energy
+ *        p[best] + p[second] >= tc * E              tc = min_tonality * c, one float32 product made on the host
+ *        p[best] <= max_twist * p[second]
+ *        p[second] >= min_separation * p[third]
+ *      c = (float)((sum w)^2 / (2 sum w^2)), the sums in float64 over the float32 window: what two pure tones of equal level give
+ *      for (p[best] + p[second]) / E, about N / 3 = 666.  The pair is stored lower index first, as lo | hi << 8; MI_SELCAL_NONE (0) = no pair.
+ * The four thresholds are settings (mi_selcal_cfg, 0 = the default): min_energy 1e-3 (refused unless finite and 1e-12 ..
+ * 1e6), min_tonality 0.5 (0.01 .. 1), max_twist 8.0 (1 .. 1000), min_separation 4.0 (1 .. 1000).  They are a caller's settings,
+ * not tolerances, fixed from tools/selcal_classes.py and tried on synthetic signals only: no off-air SELCAL call
+ * has been through this stage.
+ *
+ * Decoder.  Per row, sequentially over the row's windows in order, its state carried in the handle.  Settings in windows: min_run
+ * (default 8, 2 .. 64), max_run (default 22, min_run .. 1024), max_gap (default 8, 1 .. 64).  "A pair" is what item 4 named.
+ *   state    window seen                        action
+ *   IDLE     a pair P                           -> FIRST with P, run1 = 1, first_window = this window
+ *   IDLE     no pair                            stay
+ *   FIRST    the same pair                      run1++; if run1 > max_run the pulse is overlong: -> OVER
+ *   FIRST    another pair Q, run1 >= min_run    -> SECOND with Q, run2 = 1, gap = 0
+ *   FIRST    another pair Q, run1 < min_run     restart FIRST with Q (run1 = 1, first_window = this window)
+ *   FIRST    no pair, run1 >= min_run           -> GAP, gap = 1
+ *   FIRST    no pair, run1 < min_run            -> IDLE
+ *   OVER     the same pair                      stay
+ *   OVER     anything else                      handle the window as from IDLE
+ *   GAP      no pair                            gap++; if gap > max_gap -> IDLE
+ *   GAP      the first pair again               a dropout: -> FIRST with run1 += gap + 1 (then overlong as above if run1 > max_run)
+ *   GAP      another pair Q                     -> SECOND with Q, run2 = 1 (gap stays)
+ *   SECOND   the same pair                      run2++; when run2 == min_run emit one code record, then -> DONE
+ *   SECOND   anything else                      handle the window as from IDLE
+ *   DONE     the second pair                    stay
+ *   DONE     anything else                      handle the window as from IDLE
+ * Decided where the table of the stage's specification left a choice, with tests/selcal_model.py the tie-breaker: an overlong
+ * pulse is a state of its own (OVER), and the window that ends it is handled as from IDLE, so a pair that follows it directly begins a
+ * new FIRST; a dropout that makes run1 exceed max_run is overlong too; min_run >= 2, so that SECOND never emits on entry; a dropout
+ * inside the second pulse before the code is emitted loses the call (SECOND has no GAP); "the same pair" compares both indices.
+ * A code record holds row, seq (the row's code number since creation / set_state), the four tone indices -- first pulse lower,
+ * higher, second pulse lower, higher --, first_window and last_window (the row's numbers of the first window of the first pulse
+ * and of the emitting window), run1 and gap as they stood, and batch, the call-relative batch of the emitting window.  With both
+ * pulses clean the emitting window is the min_run-th of the second pulse.  Window numbers and seq wrap at 2^32.
+ * State: per row MI_SELCAL_STATE_ROW_BYTES bytes, little-endian: float32 x[1002], the last 1002 input samples of the last batch of
+ * the last call the row was enabled in, oldest first, zeros at first; then uint32 window (windows seen), seq (codes emitted), phase
+ * (MI_SELCAL_IDLE ..), pair1, pair2 (lo | hi << 8, MI_SELCAL_NONE where the phase has none), run1, run2, gap, first_window, zero.
+ * A disabled row writes nothing and every byte of its state stays.  NaN and Inf are unspecified, as everywhere behind the
+ * demodulator.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_SELCAL_16 = 0, MI_SELCAL_32 = 1, MI_SELCAL_CUSTOM = 2 };
+enum { MI_SELCAL_WINDOW = 2000, MI_SELCAL_HOP = 1000, MI_SELCAL_HISTORY = 1002, MI_SELCAL_MAX_TONES = 32, MI_SELCAL_STATE_ROW_BYTES = 4048,
+       MI_SELCAL_NONE8 = 0xFF };
+enum { MI_SELCAL_IDLE = 0, MI_SELCAL_FIRST = 1, MI_SELCAL_OVER = 2, MI_SELCAL_GAP = 3, MI_SELCAL_SECOND = 4, MI_SELCAL_DONE = 5 };
+#define MI_SELCAL_NONE 0u /* no pair: a pair has hi >= 1 and so is never 0; a blob of zeros is a fresh state */
+typedef struct {
+    uint32_t mode;                  /* MI_SELCAL_16 / _32 / _CUSTOM */
+    uint32_t ntones;                /* MI_SELCAL_CUSTOM: 2 .. 32; otherwise ignored */
+    float freq[32];                 /* MI_SELCAL_CUSTOM: Hz, ascending; otherwise ignored */
+    float min_energy, min_tonality, max_twist, min_separation; /* 0 = the default */
+    uint32_t min_run, max_run, max_gap;                        /* windows; 0 = the default */
+    uint32_t zero;
+} mi_selcal_cfg;                    /* 168 bytes */
+typedef struct {
+    uint8_t best, second, third, zero; /* indices into the tone table; third = MI_SELCAL_NONE8 in a table of two */
+    float p_best, p_second, p_third;
+    float energy;                   /* E */
+    uint32_t pair;                  /* lo | hi << 8, or MI_SELCAL_NONE */
+} mi_selcal_window_record;          /* 24 bytes */
+typedef struct {
+    uint32_t row, seq;              /* seq: the row's code number since creation / set_state, 0-based */
+    uint8_t tone[4];                /* first pulse lower, higher; second pulse lower, higher */
+    uint32_t first_window, last_window; /* the row's window numbers: first of the first pulse, the emitting one */
+    uint32_t run1, gap;             /* windows of the first pulse (dropouts counted in), windows without a pair between the pulses */
+    uint32_t batch;                 /* call-relative batch of the emitting window */
+} mi_selcal_code;                   /* 32 bytes */
+typedef struct mi_selcal mi_selcal;
+
+/* cfg NULL = MI_SELCAL_16 with every default.  row_enabled [rows] as for mi_tones_create; rows and max_batches within the gate's
+ * limits (1 <= rows < 2^20, rows * max_batches < 2^24).  max_codes: capacity of the caller's code buffer, 0 = rows * the most codes
+ * a row can emit in max_batches batches, 1 + (2 * max_batches - 1) / (2 * min_run).  The handle owns the scratch for a call's
+ * window decisions and codes. */
+int mi_selcal_create(const mi_selcal_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_codes, int gpu, mi_selcal** out);
+void mi_selcal_destroy(mi_selcal* s);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_selcal_set_rows(mi_selcal* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_windows         [rows][2 * nbatches]  window records, window 2b and 2b + 1 of batch b, or NULL (not wanted); 8-byte aligned.
+ *                                           A disabled row's are not written.
+ *   d_codes           [max_codes]           rows ascending, seq ascending within a row (8-byte aligned)
+ *   d_row_first_code  [rows + 1]            exclusive prefix of the rows' code counts
+ *   d_count           [2]                   number of codes, and min(that, max_codes) = the number stored
+ * Nothing is written at or beyond max_codes.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without atomics
+ * -- bank (one wave per (row, batch): the two windows' records and decisions), walk (one lane per row: the decoder over the call's
+ * decisions, its codes into the handle's scratch, the row's count and new decoder state), scan, store (the codes to their places),
+ * tails (the enabled rows' last 1002 samples into the carried state) -- so every byte is the same on every run and equals
+ * mi_selcal_plan_host's. */
+int mi_selcal_process_device(mi_selcal* s, const float* d_plane, size_t row_stride, int nbatches, mi_selcal_window_record* d_windows,
+                             mi_selcal_code* d_codes, uint32_t* d_row_first_code, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_selcal_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] codes (and the rows * 2 * nbatches window records, if the call had a d_windows and windows is not NULL;
+ * with windows not NULL after a call without d_windows it is refused).  codes, windows and row_first_code may each be NULL.  The one
+ * place that synchronises. */
+int mi_selcal_download(mi_selcal* s, void* hip_stream, mi_selcal_code* codes, mi_selcal_window_record* windows, uint32_t* row_first_code,
+                       uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_SELCAL_STATE_ROW_BYTES bytes in the layout above (mi_selcal_plan_host reads and writes the same
+ * bytes).  set_state refuses an impossible decoder state: a phase beyond MI_SELCAL_DONE, a pair the phase needs that is not two
+ * ascending indices into the table, a pair or counter the phase has none of that is not MI_SELCAL_NONE / 0, run1 outside 1 .. max_run
+ * (OVER: max_run + 1), run2 outside 1 .. min_run - 1 (DONE: min_run), gap over max_gap, pair2 equal to pair1, zero not 0.  Both
+ * complete queued work first. */
+size_t mi_selcal_state_size(const mi_selcal* s);
+int mi_selcal_get_state(mi_selcal* s, void* buf, size_t len);
+int mi_selcal_set_state(mi_selcal* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bank, walk, scan, store, tails}.  tools/selcal_rate.py. */
+int mi_selcal_set_timing(mi_selcal* s, int on);
+int mi_selcal_last_launch_ms(mi_selcal* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same windows, codes and state blob byte for byte.  plane [rows][row_stride] (no
+ * alignment asked); state_inout rows * MI_SELCAL_STATE_ROW_BYTES bytes, read and updated; windows [rows][2 * nbatches] or NULL;
+ * codes holds max_codes entries (max_codes >= 1), of which min(count[0], max_codes) = count[1] are written. */
+int mi_selcal_plan_host(const mi_selcal_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                        void* state_inout, mi_selcal_window_record* windows, mi_selcal_code* codes, size_t max_codes, uint32_t* row_first_code,
+                        uint32_t* count /* [2] */);
+/* The tone table of cfg (NULL = MI_SELCAL_16; only mode, ntones and freq are read): *ntones, freq[t], coeff[t] and letter[t] for
+ * t < *ntones.  Each output may be NULL.  Refuses what mi_selcal_create would refuse of the table. */
+int mi_selcal_table(const mi_selcal_cfg* cfg, uint32_t* ntones, float* freq /* [32] */, float* coeff /* [32] */, char* letter /* [32] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in, or the refusal mi_selcal_create would give; *c = the
+ * constant of item 4 (may be NULL). */
+int mi_selcal_settings(const mi_selcal_cfg* cfg, mi_selcal_cfg* out, float* c);
+/* The 2000 window coefficients.  Host only. */
+int mi_selcal_window(float* out /* [MI_SELCAL_WINDOW] */);
+/* "AB-CD" from a code record's four tone indices under `mode`'s letters ("??-??" under MI_SELCAL_CUSTOM), NUL-terminated.  Refuses
+ * an unknown mode and an index beyond the mode's table (32 under MI_SELCAL_CUSTOM). */
+int mi_selcal_code_text(uint32_t mode, const uint8_t* tones /* [4] */, char* out /* [6] */);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
