@@ -200,6 +200,27 @@ SELCAL_STATE_DTYPE = np.dtype([("x", "<f4", (SELCAL_HISTORY,)), ("window", "<u4"
                                ("run1", "<u4"), ("run2", "<u4"), ("gap", "<u4"), ("first_window", "<u4"), ("zero", "<u4")])
 
 
+class AcarsCfg(C.Structure):  # mi_acars_cfg: 0 = the default of every setting
+    _fields_ = [("sync_errors", C.c_uint32), ("keep_bad", C.c_uint32), ("min_quality", C.c_float), ("hold_timing", C.c_uint32)]
+
+
+class AcarsText(C.Structure):  # mi_acars_text
+    _fields_ = [("mode", C.c_char * 2), ("address", C.c_char * 8), ("ack", C.c_char * 2), ("label", C.c_char * 3), ("block_id", C.c_char * 2),
+                ("text", C.c_char * 231)]
+
+
+ACARS_HISTORY, ACARS_HYPOTHESES, ACARS_BITS, ACARS_BIT_WORDS, ACARS_SYNC_BITS, ACARS_HEAD_BYTES, ACARS_MAX_BYTES, ACARS_RAW_BYTES = 6, 20, 300, 10, 39, 12, 240, 248
+ACARS_IDLE, ACARS_FRAME = 0, 1  # MI_ACARS_*
+ACARS_SYNC_EXACT = 0x80000000  # mi_acars_cfg.sync_errors: no mismatch allowed
+# mi_acars_frame (272 bytes) and one row of the ACARS stage's state blob, MI_ACARS_STATE_ROW_BYTES = 496
+ACARS_FRAME_DTYPE = np.dtype([("row", "<u4"), ("batch", "<u4"), ("third", "<u4"), ("tau_sync", "u1"), ("tau_end", "u1"), ("sync_errors", "u1"),
+                              ("crc_ok", "u1"), ("nbytes", "<u2"), ("parity_errors", "u1"), ("end", "u1"), ("end_batch", "<u4"),
+                              ("bytes", "u1", (ACARS_RAW_BYTES,))])
+ACARS_STATE_DTYPE = np.dtype([("x", "<f4", (ACARS_HISTORY,)), ("batch", "<u4"), ("phase", "<u4"), ("hist", "<u8", (ACARS_HYPOTHESES,))] +
+                             [(n, "<u4") for n in ("u", "prev", "nbits", "cur", "nbytes", "tail", "crc", "parity_errors", "start_batch", "start_third",
+                                                   "tau_sync", "mismatches", "end", "zero")] + [("bytes", "u1", (ACARS_RAW_BYTES,))])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -288,6 +309,9 @@ ABI_SYMBOLS = [
     "mi_selcal_create", "mi_selcal_destroy", "mi_selcal_set_rows", "mi_selcal_process_device", "mi_selcal_download", "mi_selcal_state_size",
     "mi_selcal_get_state", "mi_selcal_set_state", "mi_selcal_set_timing", "mi_selcal_last_launch_ms", "mi_selcal_plan_host", "mi_selcal_table",
     "mi_selcal_settings", "mi_selcal_window", "mi_selcal_code_text",
+    "mi_acars_create", "mi_acars_destroy", "mi_acars_set_rows", "mi_acars_process_device", "mi_acars_download", "mi_acars_state_size",
+    "mi_acars_get_state", "mi_acars_set_state", "mi_acars_set_timing", "mi_acars_last_launch_ms", "mi_acars_plan_host", "mi_acars_settings",
+    "mi_acars_templates", "mi_acars_crc", "mi_acars_frame_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -461,6 +485,24 @@ def lib():
         L.mi_selcal_settings.argtypes = [C.POINTER(SelcalCfg), C.POINTER(SelcalCfg), C.POINTER(C.c_float)]
         L.mi_selcal_window.argtypes = [vp]
         L.mi_selcal_code_text.argtypes = [C.c_uint32, vp, vp]
+        L.mi_acars_create.argtypes = [C.POINTER(AcarsCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_acars_destroy.argtypes = [vp]
+        L.mi_acars_destroy.restype = None
+        L.mi_acars_set_rows.argtypes = [vp, vp]
+        L.mi_acars_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.mi_acars_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mi_acars_state_size.argtypes = [vp]
+        L.mi_acars_state_size.restype = sz
+        L.mi_acars_get_state.argtypes = [vp, vp, sz]
+        L.mi_acars_set_state.argtypes = [vp, vp, sz]
+        L.mi_acars_set_timing.argtypes = [vp, C.c_int]
+        L.mi_acars_last_launch_ms.argtypes = [vp, vp]
+        L.mi_acars_plan_host.argtypes = [C.POINTER(AcarsCfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+        L.mi_acars_settings.argtypes = [C.POINTER(AcarsCfg), C.POINTER(AcarsCfg)]
+        L.mi_acars_templates.argtypes = [vp, vp]
+        L.mi_acars_crc.argtypes = [vp, sz]
+        L.mi_acars_crc.restype = C.c_uint32
+        L.mi_acars_frame_text.argtypes = [vp, C.POINTER(AcarsText)]
         L.mi_limit_default_row.argtypes = []
         L.mi_limit_default_row.restype = LimitRow
         L.mi_limit_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -598,7 +640,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -612,7 +654,7 @@ class _PostStage(_TimedStage):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
         .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
-        .view(SELCAL_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1575,6 +1617,111 @@ def selcal_plan_host(row_enabled, plane, cfg=None, state=None, max_codes=0, nbat
     _check(lib().mi_selcal_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), None if windows is None else _ptr(windows),
                                      _ptr(codes), cap, _ptr(row_first), _ptr(count)))
     return codes[:int(count[1])], windows, row_first, count, state
+
+
+def acars_cfg(sync_errors=0, keep_bad=False, min_quality=0.0, hold_timing=False):
+    """mi_acars_cfg, field for field as the C struct takes it: sync_errors 1 .. 4 mismatches a sync may have, 0 (or None) = the
+    default, 2, and ACARS_SYNC_EXACT for none; keep_bad: frames whose checksum fails are records too; min_quality: floor on Q of a
+    sync's batch; hold_timing: no timing moves.  An AcarsCfg passes through."""
+    if isinstance(sync_errors, AcarsCfg):
+        return sync_errors
+    c = AcarsCfg()
+    c.sync_errors = int(sync_errors or 0)
+    c.keep_bad, c.min_quality, c.hold_timing = int(keep_bad), min_quality, int(hold_timing)
+    return c
+
+
+def acars_settings(cfg=None):
+    """mi_acars_settings: the settings with every default filled in, as an AcarsCfg"""
+    out = AcarsCfg()
+    _check(lib().mi_acars_settings(C.byref(acars_cfg(cfg)), C.byref(out)))
+    return out
+
+
+def acars_max_frames(nbatches):
+    """the most frames one row can end in a call of nbatches batches"""
+    return 1 + ACARS_BITS * nbatches // 119
+
+
+def acars_templates():
+    """mi_acars_templates: (h1 [20], h2 [20]), the half cycle of 1200 Hz and the full cycle of 2400 Hz over a bit's 20 thirds"""
+    h1, h2 = np.zeros(20, np.float32), np.zeros(20, np.float32)
+    _check(lib().mi_acars_templates(_ptr(h1), _ptr(h2)))
+    return h1, h2
+
+
+def acars_crc(data):
+    """mi_acars_crc: CRC-16/KERMIT of bytes"""
+    b = np.frombuffer(bytes(data), np.uint8)
+    return int(lib().mi_acars_crc(_ptr(b) if b.size else None, b.size))
+
+
+def acars_frame_text(frame):
+    """mi_acars_frame_text: a record's printable fields, parity stripped, as a dict of str: mode, address, ack, label, block_id, text"""
+    f = np.array(frame, ACARS_FRAME_DTYPE).reshape(1)
+    out = AcarsText()
+    _check(lib().mi_acars_frame_text(_ptr(f), C.byref(out)))
+    return {n: getattr(out, n).decode("ascii") for n, _ in AcarsText._fields_}
+
+
+class Acars(_PostStage):
+    """mi_acars: the ACARS decoder stage -- per row, the blocks its 2400 bit/s MSK bursts carried: a bank of coherent bit detectors
+    under 20 timing hypotheses per batch, a sync compare on every hypothesis while the row is idle, and a walker that reads the frame's
+    bytes, checks parity and the BCS and follows the timing.  It reads a plane of audio as Selcal does and needs no flags.
+    row_enabled: truth value per row; cfg: acars_cfg(...) or None; max_frames: capacity of the frame buffer, 0 = rows *
+    acars_max_frames(max_batches).  state() gives rows * 496 bytes, whose fields .view(ACARS_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_acars_destroy", "mi_acars", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_frames=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = acars_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_acars_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_frames, gpu, C.byref(self._h)))
+        most = self.rows * acars_max_frames(max_batches)
+        self.max_frames = min(max_frames, most) if max_frames else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_acars_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_frames, d_row_first_frame, d_count, d_bits=None, d_q=None, hip_stream=None):
+        """Raw device pointers (ints; d_bits and d_q may be None), the stride in floats; asynchronous on hip_stream."""
+        _check(lib().mi_acars_process_device(self._h, d_plane, row_stride, nbatches, d_bits, d_q, d_frames, d_row_first_frame, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (frames [k] of ACARS_FRAME_DTYPE, row_first_frame [rows + 1],
+        count [2]) with k = count[1]."""
+        frames = np.zeros(self.max_frames, ACARS_FRAME_DTYPE)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_acars_download(self._h, hip_stream, _ptr(frames), _ptr(row_first), _ptr(count)))
+        return frames[:int(count[1])], row_first, count
+
+
+def acars_plan_host(row_enabled, plane, cfg=None, state=None, max_frames=0, nbatches=None):
+    """mi_acars_plan_host: the ACARS stage's bits, Q and frames from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 496 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_frames: 0 = every frame of the call.  Returns (frames [count[1]], bits [rows][nbatches][20][10], q [rows][nbatches][20],
+    row_first_frame [rows + 1], count [2], state after the call).  A disabled row's bits and q stay zero."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = acars_cfg(cfg)
+    state = np.zeros(rows * ACARS_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * ACARS_STATE_DTYPE.itemsize
+    cap = max_frames or max(1, rows * acars_max_frames(max(nb, 1)))
+    frames = np.zeros(cap, ACARS_FRAME_DTYPE)
+    bits = np.zeros((rows, max(nb, 0), ACARS_HYPOTHESES, ACARS_BIT_WORDS), np.uint32)
+    q = np.zeros((rows, max(nb, 0), ACARS_HYPOTHESES), np.float32)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_acars_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(q), _ptr(frames), cap,
+                                    _ptr(row_first), _ptr(count)))
+    return frames[:int(count[1])], bits, q, row_first, count, state
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -460,6 +460,157 @@ inline uint32_t selcal_max_codes(uint32_t min_run, uint64_t nbatches) {
 int selcal_plan(const mi_selcal_cfg* cfg, SelcalPlan* out);
 void selcal_window(float* w);
 const char* selcal_state_ok(const SelcalRowState* state, size_t rows, const SelcalPlan& plan);
+
+// The ACARS decoder stage (include/mi_airband.h "ACARS decoder stage").  One row of its state: the checkpoint blob is an array of
+// these, and acars.hip keeps the same array in device memory.
+struct AcarsRowState {
+    float x[MI_ACARS_HISTORY];              // the last 6 input samples of the row's last batch, oldest first
+    uint32_t batch;                         // batches seen since creation / set_state
+    uint32_t phase;                         // MI_ACARS_IDLE / MI_ACARS_FRAME
+    uint64_t hist[MI_ACARS_HYPOTHESES];     // per hypothesis the last 38 change bits, the newest in bit 0
+    uint32_t u, prev, nbits, cur, nbytes, tail, crc, parity_errors, start_batch, start_third, tau_sync, mismatches, end, zero;
+    uint8_t bytes[MI_ACARS_RAW_BYTES];
+};
+static_assert(sizeof(AcarsRowState) == MI_ACARS_STATE_ROW_BYTES && offsetof(AcarsRowState, hist) == 32 && offsetof(AcarsRowState, u) == 192 &&
+                  offsetof(AcarsRowState, bytes) == 248 && sizeof(mi_acars_frame) == 272 && offsetof(mi_acars_frame, bytes) == 24 &&
+                  sizeof(mi_acars_cfg) == 16 && sizeof(mi_acars_text) == 248 && (MI_ACARS_HISTORY + 2) % 4 == 0 &&
+                  MI_ACARS_MAX_BYTES + 2 <= MI_ACARS_RAW_BYTES && MI_ACARS_RAW_BYTES % 8 == 0 && 20 * MI_ACARS_BITS == 3 * kWaveBatch &&
+                  MI_ACARS_BIT_WORDS * 32 >= MI_ACARS_BITS,
+              "the ACARS stage's blob, record and settings layouts are ABI");
+// The settings with every default filled in, as both halves take them.
+struct AcarsPlan {
+    uint32_t sync_errors;  // the number itself, 0 .. 4
+    uint32_t keep_bad, hold_timing;
+    float min_quality;
+    mi_acars_cfg filled;   // the settings as the caller would have written them
+};
+// The walker's part of a row's state, as the walk carries it in registers; the bytes so far stay in memory beside it.
+struct AcarsWalker {
+    uint32_t phase, u, prev, nbits, cur, nbytes, tail, crc, parity_errors, start_batch, start_third, tau_sync, mismatches, end;
+};
+constexpr uint64_t kAcarsMask39 = (1ull << MI_ACARS_SYNC_BITS) - 1, kAcarsMask38 = kAcarsMask39 >> 1;
+// the 39 change bits inside '+' '*' SYN SYN SOH, sent least significant bit first, the newest in bit 0
+constexpr uint64_t acars_sync_pattern() {
+    const uint8_t s[5] = {0xAB, 0x2A, 0x16, 0x16, 0x01};
+    uint64_t p = 0;
+    int prev = s[0] & 1;
+    for (int i = 1; i < 40; ++i) {
+        const int b = (s[i / 8] >> (i % 8)) & 1;
+        p = p << 1 | static_cast<uint64_t>(b ^ prev);
+        prev = b;
+    }
+    return p;
+}
+constexpr uint64_t kAcarsSync = acars_sync_pattern();
+// the most frames one row can end in a call: the first may end in the call's first slot, each further one takes 39 slots of sync
+// and at least 119 of its 120 bits (a timing move can take two in one slot)
+inline uint32_t acars_max_frames(uint64_t nbatches) {
+    return static_cast<uint32_t>(1 + MI_ACARS_BITS * nbatches / 119);
+}
+__host__ __device__ inline uint32_t acars_crc_byte(uint32_t crc, const uint32_t byte) {
+    crc ^= byte;
+    for (int i = 0; i < 8; ++i)
+        crc = crc & 1u ? crc >> 1 ^ 0x8408u : crc >> 1;
+    return crc;
+}
+// Slot j of hypothesis tau over what is staged for a block -- s[kLead + n] is the block's sample n, kLead = MI_ACARS_HISTORY + 2 --:
+// the change bit, and the quality into *q.  Host and device run this text.
+__host__ __device__ inline uint32_t acars_bit(const float* s, const float* h1, const float* h2, const int tau, const int j, float* q) {
+    const int t0 = tau + 20 * (j - (tau > 0));           // -19 .. 5980
+    const int n0 = (t0 + 23) / 3 - 7;                    // ceil(t0 / 3)
+    const int rho0 = 3 * n0 - t0;                        // 0 .. 2
+    const float* const x = s + (MI_ACARS_HISTORY + 2) + n0;
+    float r1 = x[0] * h1[rho0], r2 = x[0] * h2[rho0];
+#pragma unroll
+    for (int i = 1; i < 6; ++i) {
+        r1 = r1 + x[i] * h1[rho0 + 3 * i];
+        r2 = r2 + x[i] * h2[rho0 + 3 * i];
+    }
+    if (rho0 <= 1) {
+        r1 = r1 + x[6] * h1[rho0 + 18];
+        r2 = r2 + x[6] * h2[rho0 + 18];
+    }
+    const float a1 = r1 * r1, a2 = r2 * r2;
+    *q = a1 > a2 ? a1 : a2;
+    return fabsf(r1) >= fabsf(r2) ? 1u : 0u;
+}
+// What one change bit on the walker's hypothesis does to a frame.
+enum { kAcarsNone = 0, kAcarsDone = 1, kAcarsDropped = 2 };
+// One change bit c through the walker of the header, the frame's bytes so far at `bytes` (MI_ACARS_RAW_BYTES of them).  kAcarsDone:
+// the frame is whole -- w and bytes hold what the record takes, w.crc == 0 being crc_ok -- and the caller calls acars_idle behind the
+// record.  kAcarsDropped: no ETX / ETB in 240 bytes; the row is idle.  Host and device run this text.
+__host__ __device__ inline void acars_idle(AcarsWalker& w, uint8_t* bytes) {
+    for (uint32_t i = 0; i < w.nbytes + w.tail && i < MI_ACARS_RAW_BYTES; ++i)
+        bytes[i] = 0;
+    w = AcarsWalker{};
+}
+__host__ __device__ inline int acars_step(AcarsWalker& w, uint8_t* bytes, const uint32_t c) {
+    w.prev ^= c;
+    w.cur |= w.prev << w.nbits;
+    if (++w.nbits < 8)
+        return kAcarsNone;
+    const uint32_t byte = w.cur;
+    w.cur = 0;
+    w.nbits = 0;
+    w.crc = acars_crc_byte(w.crc, byte);
+    if (w.tail) {
+        bytes[w.nbytes + w.tail - 1] = static_cast<uint8_t>(byte);
+        return ++w.tail == 3 ? kAcarsDone : kAcarsNone;
+    }
+    bytes[w.nbytes++] = static_cast<uint8_t>(byte);
+    uint32_t ones = byte;
+    ones ^= ones >> 4;
+    ones ^= ones >> 2;
+    ones ^= ones >> 1;
+    w.parity_errors += (ones & 1u) ^ 1u;
+    const uint32_t ch = byte & 0x7Fu;
+    if (w.nbytes > MI_ACARS_HEAD_BYTES && (ch == 0x03u || ch == 0x17u)) {
+        w.end = ch;
+        w.tail = 1;
+    } else if (w.nbytes == MI_ACARS_MAX_BYTES) {
+        acars_idle(w, bytes);
+        return kAcarsDropped;
+    }
+    return kAcarsNone;
+}
+// The hypothesis a sync opens the frame on: mism[tau] = the mismatches of tau's 39 bits, q[tau] = Q of the slot's batch; -1: no hit.
+__host__ __device__ inline int acars_pick(const uint32_t* mism, const float* q, const uint32_t sync_errors, const float min_quality) {
+    int best = -1;
+    for (int t = 0; t < MI_ACARS_HYPOTHESES; ++t) {
+        if (mism[t] > sync_errors || !(q[t] >= min_quality))
+            continue;
+        if (best < 0 || mism[t] < mism[best] || (mism[t] == mism[best] && q[t] > q[best]))
+            best = t;
+    }
+    return best;
+}
+// A frame opens on hypothesis u at a hit in slot j of the row's batch number `batch`.
+__host__ __device__ inline void acars_open(AcarsWalker& w, const int u, const uint32_t mismatches, const uint32_t batch, const int j) {
+    w = AcarsWalker{};
+    w.phase = MI_ACARS_FRAME;
+    w.u = w.tau_sync = static_cast<uint32_t>(u);
+    w.mismatches = mismatches;
+    const int t = u + 20 * (j + 1 - (u > 0));  // where slot j + 1 begins
+    w.start_batch = t >= 3 * kWaveBatch ? batch + 1 : batch;
+    w.start_third = static_cast<uint32_t>(t >= 3 * kWaveBatch ? t - 3 * kWaveBatch : t);
+}
+// The timing move at a batch's first slot inside a frame, from the new batch's Q.
+enum { kAcarsInStep = 0, kAcarsSkip = 1, kAcarsReplay = 2 };
+__host__ __device__ inline int acars_retime(AcarsWalker& w, const float* q) {
+    const uint32_t u = w.u, um = (u + 19) % 20, up = (u + 1) % 20;
+    uint32_t v = u;
+    if (q[um] > q[v])
+        v = um;
+    if (q[up] > q[v])
+        v = up;
+    w.u = v;
+    return u == 0 && v == 1 ? kAcarsSkip : u == 1 && v == 0 ? kAcarsReplay : kAcarsInStep;
+}
+// What both halves of the ACARS stage share (poststage_host.cpp).  acars_plan: MI_OK with the plan, or the settings' refusal with its
+// message set.  acars_templates: h1[20], h2[20].  acars_state_ok: NULL, or what is impossible about a blob.
+int acars_plan(const mi_acars_cfg* cfg, AcarsPlan* out);
+void acars_templates(float* h1, float* h2);
+const char* acars_state_ok(const AcarsRowState* state, size_t rows);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

@@ -1705,3 +1705,259 @@ extern "C" int mi_selcal_plan_host(const mi_selcal_cfg* cfg, const uint8_t* row_
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::SelcalRowState));
     return MI_OK;
 }
+
+// ---- ACARS decoder stage, host side (include/mi_airband.h "ACARS decoder stage"): the settings' check, the templates, the blob's
+// check, the record and its text, and the twin of acars.hip -- one row, one batch, one hypothesis and one slot at a time, then the
+// walker over the batch's slots.  The bit, the walker's step, the sync's choice and the timing move are poststage.hpp's.
+namespace mi {
+
+int acars_plan(const mi_acars_cfg* cfg, AcarsPlan* out) {
+    mi_acars_cfg c{};
+    if (cfg)
+        c = *cfg;
+    if (c.sync_errors == 0)
+        c.sync_errors = 2;
+    if (c.sync_errors != MI_ACARS_SYNC_EXACT && c.sync_errors > 4)
+        return fail(MI_ERR_INVALID, "ACARS stage: sync_errors must be within 1 .. 4 or MI_ACARS_SYNC_EXACT (0 = the default)");
+    if (c.keep_bad > 1)
+        return fail(MI_ERR_INVALID, "ACARS stage: keep_bad must be 0 or 1");
+    if (!std::isfinite(c.min_quality) || c.min_quality < 0.0f)
+        return fail(MI_ERR_INVALID, "ACARS stage: min_quality must be finite and not negative (0 = the default)");
+    if (c.hold_timing > 1)
+        return fail(MI_ERR_INVALID, "ACARS stage: hold_timing must be 0 or 1");
+    c.min_quality = c.min_quality + 0.0f;  // (-0.0f is the default too)
+    AcarsPlan p{};
+    p.sync_errors = c.sync_errors == MI_ACARS_SYNC_EXACT ? 0u : c.sync_errors;
+    p.keep_bad = c.keep_bad;
+    p.hold_timing = c.hold_timing;
+    p.min_quality = c.min_quality;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+void acars_templates(float* h1, float* h2) {
+    const double pi = 3.14159265358979323846;
+    for (int r = 0; r < 20; ++r) {
+        h1[r] = static_cast<float>(std::sin(pi * r / 20.0));
+        h2[r] = static_cast<float>(std::sin(2.0 * pi * r / 20.0));
+    }
+}
+
+const char* acars_state_ok(const AcarsRowState* state, size_t rows) {
+    for (size_t r = 0; r < rows; ++r) {
+        const AcarsRowState& s = state[r];
+        if (s.zero)
+            return "the zero field is not 0";
+        for (int t = 0; t < MI_ACARS_HYPOTHESES; ++t)
+            if (s.hist[t] & ~kAcarsMask38)
+                return "a hypothesis holds more than 38 change bits";
+        if (s.phase > MI_ACARS_FRAME)
+            return "an unknown walker phase";
+        uint32_t used = 0;
+        if (s.phase == MI_ACARS_IDLE) {
+            if (s.u | s.prev | s.nbits | s.cur | s.nbytes | s.tail | s.crc | s.parity_errors | s.start_batch | s.start_third | s.tau_sync | s.mismatches | s.end)
+                return "an impossible walker state (an idle row with a walker field set)";
+        } else {
+            bool ok = s.u < 20 && s.tau_sync < 20 && s.prev <= 1 && s.nbits <= 7 && s.cur < (1u << s.nbits) && s.tail <= 2 && s.mismatches <= 4 &&
+                      s.start_third < 3u * kWaveBatch;
+            if (ok && s.tail == 0)
+                ok = s.nbytes < MI_ACARS_MAX_BYTES && s.end == 0;
+            else if (ok)
+                ok = s.nbytes > MI_ACARS_HEAD_BYTES && s.nbytes <= MI_ACARS_MAX_BYTES && (s.end == 0x03 || s.end == 0x17) &&
+                     (s.bytes[s.nbytes - 1] & 0x7Fu) == s.end;
+            if (!ok)
+                return "an impossible walker state (counters, end or timing that a frame cannot have)";
+            used = s.nbytes + (s.tail ? s.tail - 1 : 0);
+            uint32_t crc = 0, bad = 0;
+            for (uint32_t i = 0; i < used; ++i) {
+                crc = acars_crc_byte(crc, s.bytes[i]);
+                if (i >= s.nbytes)
+                    continue;
+                bad += (__builtin_popcount(s.bytes[i]) & 1) ^ 1;
+                const uint32_t ch = s.bytes[i] & 0x7Fu;
+                if (i >= MI_ACARS_HEAD_BYTES && i + 1 < s.nbytes + (s.tail ? 0u : 1u) && (ch == 0x03 || ch == 0x17))
+                    return "an impossible walker state (a frame that goes on behind its ETX / ETB)";
+            }
+            if (crc != s.crc || bad != s.parity_errors)
+                return "an impossible walker state (a crc or parity count that the bytes do not give)";
+        }
+        for (uint32_t i = used; i < MI_ACARS_RAW_BYTES; ++i)
+            if (s.bytes[i])
+                return "an impossible walker state (a byte set behind the ones taken)";
+    }
+    return nullptr;
+}
+
+namespace {
+
+mi_acars_frame acars_frame(const AcarsWalker& w, const uint8_t* bytes, uint32_t row, uint32_t end_batch) {
+    mi_acars_frame f{};
+    f.row = row;
+    f.batch = w.start_batch;
+    f.third = w.start_third;
+    f.tau_sync = static_cast<uint8_t>(w.tau_sync);
+    f.tau_end = static_cast<uint8_t>(w.u);
+    f.sync_errors = static_cast<uint8_t>(w.mismatches);
+    f.crc_ok = w.crc == 0;
+    f.nbytes = static_cast<uint16_t>(w.nbytes);
+    f.parity_errors = static_cast<uint8_t>(w.parity_errors);
+    f.end = static_cast<uint8_t>(w.end);
+    f.end_batch = end_batch;
+    std::memcpy(f.bytes, bytes, MI_ACARS_RAW_BYTES);
+    return f;
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" int mi_acars_settings(const mi_acars_cfg* cfg, mi_acars_cfg* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::AcarsPlan p;
+    if (const int rc = mi::acars_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    return MI_OK;
+}
+
+extern "C" int mi_acars_templates(float* h1, float* h2) {
+    if (!h1 || !h2)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::acars_templates(h1, h2);
+    return MI_OK;
+}
+
+extern "C" uint32_t mi_acars_crc(const uint8_t* bytes, size_t n) {
+    if (!bytes && n)
+        return 0xFFFFFFFFu;
+    uint32_t crc = 0;
+    for (size_t i = 0; i < n; ++i)
+        crc = mi::acars_crc_byte(crc, bytes[i]);
+    return crc;
+}
+
+extern "C" int mi_acars_frame_text(const mi_acars_frame* f, mi_acars_text* out) {
+    if (!f || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (f->nbytes <= MI_ACARS_HEAD_BYTES || f->nbytes > MI_ACARS_MAX_BYTES)
+        return fail(MI_ERR_INVALID, "ACARS stage: a frame's nbytes must be within 13 .. 240");
+    std::memset(out, 0, sizeof(*out));
+    const auto put = [&](char* dst, int first, int n) {
+        for (int i = 0; i < n; ++i) {
+            const int ch = f->bytes[first + i] & 0x7F;
+            dst[i] = ch >= 0x20 && ch <= 0x7E ? static_cast<char>(ch) : '.';
+        }
+    };
+    put(out->mode, 0, 1);
+    put(out->address, 1, 7);
+    put(out->ack, 8, 1);
+    put(out->label, 9, 2);
+    put(out->block_id, 11, 1);
+    put(out->text, MI_ACARS_HEAD_BYTES, f->nbytes - MI_ACARS_HEAD_BYTES - 1);
+    return MI_OK;
+}
+
+extern "C" int mi_acars_plan_host(const mi_acars_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                  void* state_inout, uint32_t* bits, float* q, mi_acars_frame* frames, size_t max_frames, uint32_t* row_first_frame,
+                                  uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !frames || !row_first_frame || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_frames < 1)
+        return fail(MI_ERR_INVALID, "ACARS plan needs rows >= 1, nbatches >= 1 and max_frames >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::AcarsPlan plan;
+    if (const int rc = mi::acars_plan(cfg, &plan))
+        return rc;
+    if (static_cast<uint64_t>(rows) * mi::acars_max_frames(static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "ACARS plan: the frames of the call do not fit the 32-bit count");
+    std::vector<mi::AcarsRowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::AcarsRowState));
+    if (const char* const why = mi::acars_state_ok(blob.data(), blob.size()))
+        return fail(MI_ERR_INVALID, std::string("ACARS plan: malformed state blob: ") + why);
+    constexpr int kLead = MI_ACARS_HISTORY + 2, kTau = MI_ACARS_HYPOTHESES, kBits = MI_ACARS_BITS, kWords = MI_ACARS_BIT_WORDS;
+    float h1[20], h2[20];
+    mi::acars_templates(h1, h2);
+    std::vector<float> s(kLead + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first_frame[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::AcarsRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        s[0] = s[1] = 0.0f;
+        std::memcpy(s.data() + 2, st.x, sizeof(st.x));
+        std::memcpy(s.data() + kLead, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::AcarsWalker w{st.phase, st.u, st.prev, st.nbits, st.cur, st.nbytes, st.tail, st.crc, st.parity_errors, st.start_batch, st.start_third,
+                          st.tau_sync, st.mismatches, st.end};
+        const auto event = [&](int ev, int b) {  // what a step's answer does
+            if (ev == mi::kAcarsDone) {
+                if (w.crc == 0 || plan.keep_bad) {
+                    if (k < max_frames)
+                        frames[k] = mi::acars_frame(w, st.bytes, static_cast<uint32_t>(r), static_cast<uint32_t>(b));
+                    ++k;
+                }
+                mi::acars_idle(w, st.bytes);
+            }
+        };
+        for (int b = 0; b < nbatches; ++b) {
+            const float* const blk = s.data() + static_cast<size_t>(b) * mi::kWaveBatch;  // staged: blk[kLead + n] is the batch's sample n
+            uint32_t word[kTau][kWords] = {};
+            float Q[kTau], qs[kBits];
+            for (int t = 0; t < kTau; ++t) {
+                for (int j = 0; j < kBits; ++j)
+                    word[t][j / 32] |= mi::acars_bit(blk, h1, h2, t, j, &qs[j]) << (j % 32);
+                float lane[64];
+                for (int l = 0; l < 64; ++l) {
+                    lane[l] = qs[l];
+                    for (int j = l + 64; j < kBits; j += 64)
+                        lane[l] = lane[l] + qs[j];
+                }
+                for (int h = 32; h >= 1; h /= 2)
+                    for (int l = 0; l < h; ++l)
+                        lane[l] = lane[l] + lane[l + h];
+                Q[t] = lane[0];
+            }
+            const size_t blk_i = static_cast<size_t>(r) * static_cast<size_t>(nbatches) + static_cast<size_t>(b);
+            if (bits)
+                std::memcpy(bits + blk_i * kTau * kWords, word, sizeof(word));
+            if (q)
+                std::memcpy(q + blk_i * kTau, Q, sizeof(Q));
+            int skip = 0;
+            if (w.phase == MI_ACARS_FRAME && !plan.hold_timing) {
+                const int move = mi::acars_retime(w, Q);
+                skip = move == mi::kAcarsSkip;
+                if (move == mi::kAcarsReplay)
+                    event(mi::acars_step(w, st.bytes, static_cast<uint32_t>(st.hist[0] & 1u)), b);
+            }
+            for (int j = 0; j < kBits; ++j) {
+                uint32_t mism[kTau];
+                for (int t = 0; t < kTau; ++t) {
+                    const uint64_t h39 = st.hist[t] << 1 | (word[t][j / 32] >> (j % 32) & 1u);
+                    mism[t] = static_cast<uint32_t>(__builtin_popcountll(h39 ^ mi::kAcarsSync));
+                    st.hist[t] = h39 & mi::kAcarsMask38;
+                }
+                if (w.phase == MI_ACARS_FRAME) {
+                    if (skip)
+                        skip = 0;
+                    else
+                        event(mi::acars_step(w, st.bytes, word[w.u][j / 32] >> (j % 32) & 1u), b);
+                } else if (const int u = mi::acars_pick(mism, Q, plan.sync_errors, plan.min_quality); u >= 0) {
+                    mi::acars_open(w, u, mism[u], st.batch + static_cast<uint32_t>(b), j);
+                }
+            }
+        }
+        st.batch += static_cast<uint32_t>(nbatches);
+        st.phase = w.phase, st.u = w.u, st.prev = w.prev, st.nbits = w.nbits, st.cur = w.cur, st.nbytes = w.nbytes, st.tail = w.tail, st.crc = w.crc;
+        st.parity_errors = w.parity_errors, st.start_batch = w.start_batch, st.start_third = w.start_third, st.tau_sync = w.tau_sync;
+        st.mismatches = w.mismatches, st.end = w.end;
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_ACARS_HISTORY, sizeof(st.x));
+    }
+    row_first_frame[rows] = k;
+    count[0] = k;
+    count[1] = k < max_frames ? k : static_cast<uint32_t>(max_frames);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::AcarsRowState));
+    return MI_OK;
+}

@@ -1469,6 +1469,145 @@ int mi_selcal_window(float* out /* [MI_SELCAL_WINDOW] */);
  * an unknown mode and an index beyond the mode's table (32 under MI_SELCAL_CUSTOM). */
 int mi_selcal_code_text(uint32_t mode, const uint8_t* tones /* [4] */, char* out /* [6] */);
 
+/* ---------------- ACARS decoder stage: MSK frames per row, on the device ----------------
+ * ACARS runs on plain AM airband channels at 2400 bit/s as MSK in the audio: a bit that differs from the previous one is half a
+ * cycle of 1200 Hz, a bit that repeats it a full cycle of 2400 Hz, the tones locked in phase to the bit clock.  The reference leaves
+ * the bursts in the recording.  This stage reads a plane [rows][row_stride] of float32 audio as mi_selcal_* does, needs no flags, and
+ * writes one record per received block (a FRAME here).  Coherent detection bit by bit: it rests on that phase lock, keeps no phase
+ * memory from bit to bit, and so gives away part of what a full MSK receiver has (DESIGN.md 5o has the measured sensitivity).
+ * NOT CHECKED: no off-air ACARS has been through the stage.  The framing constants, the parity convention, the checksum's coverage
+ * and the phase lock are written from memory of the air format and pinned only to the modulator of tests/acars_model.py.  No error
+ * correction, no reassembly of multi-block messages, no decoding of labels.
+ *
+ * Stream model.  As for the SELCAL stage: a row's audio is one running sequence over all batches of all calls the row was enabled
+ * in; samples before the handle's first call are 0.
+ * Timing grid.  16000 / 2400 = 20 / 3 samples a bit, so time is counted in THIRDS of a sample; sample n sits at third 3 n.  Under
+ * hypothesis tau = 0 .. 19, bit k covers the thirds [tau + 20 k, tau + 20 k + 20), k counted from the row's first sample, and sample n
+ * contributes to it when rho = 3 n - (tau + 20 k) lies in 0 .. 19: seven samples where the first rho is 0 or 1, else six.  tau + 20 is
+ * tau one bit later, exactly.  A batch is 6000 thirds; the bits of a (row, batch) are those whose last sample lies in the batch,
+ * exactly 300 per hypothesis.  They are numbered by SLOT j = 0 .. 299: slot j of hypothesis tau is the bit that begins at third
+ * tau + 20 (j - [tau > 0]) of the batch, so slot 0 of tau >= 1 begins at third tau - 20, before the batch.  The earliest sample any
+ * bit of a batch reads is the sixth before it (tau = 1 .. 2), so the handle carries MI_ACARS_HISTORY = 6 samples per row: the
+ * smallest H for which the lead H + 2 (carry.hpp) is whole float4.  In one slot, hypothesis tau begins a third after tau - 1 for
+ * tau = 2 .. 19, and 0 a third after 19; hypothesis 1 begins a third after hypothesis 0 OF THE SLOT BEFORE.
+ * Bit bank, per (row, batch, tau, slot); float32, every operation rounded on its own, no fused multiply-add.  Templates
+ * (mi_acars_templates) h1[rho] = (float)sin(pi rho / 20), h2[rho] = (float)sin(2 pi rho / 20), rho = 0 .. 19, evaluated in double and
+ * rounded once.  r1 = sum x[n] * h1[rho], r2 = sum x[n] * h2[rho] over the bit's samples in ascending n, each sum beginning with its
+ * first product.  CHANGE bit c = 1 if |r1| >= |r2| (1200 Hz: the bit differs from the one before), else 0; quality q = max(r1 * r1,
+ * r2 * r2).  Q[tau] of the block: s_l = the sequential sum over the slots j = l (mod 64) in ascending j of q, beginning with the
+ * first, l = 0 .. 63; then s_l + s_{l + 32} for l < 32, then + 16, 8, 4, 2, 1 in the same way; Q is element 0 (the order of the SELCAL
+ * stage's energy).  Packed: 10 words per (row, batch, tau), slot j in bit j % 32 of word j / 32, the upper 20 bits of word 9 zero.
+ * A block whose 2000 samples and 6 carried samples are all +-0 gives c = 1 and Q = +0.0f everywhere (|0| >= |0|); the device writes
+ * that without the sums.
+ * Sync.  Characters are 7 bits and odd parity in bit 7, sent least significant bit first.  The pattern is the 39 change bits inside the
+ * 40 bits of '+' '*' SYN SYN SOH (0xAB 0x2A 0x16 0x16 0x01 with parity); only changes are matched, so polarity never enters.  Every
+ * hypothesis keeps its last 39 change bits.  While a row is IDLE, at every slot in order, a hypothesis HITS when its 39 bits differ
+ * from the pattern in at most sync_errors places and Q[tau] of the slot's batch >= min_quality.  The first slot with a hit opens a
+ * frame on the hitting hypothesis with the fewest mismatches, then the largest Q of that batch, then the lowest tau.  The bit
+ * before the frame's first is SOH's last, 0: b_k = b_{k-1} xor c_k from there.  One frame at a time per row; hits inside a frame
+ * are ignored.
+ * Walker.  From the slot after the hit, the chosen hypothesis u's bits, 8 to a byte, least significant first: Mode, Address[7], Ack,
+ * Label[2], Block id (12 bytes), then bytes up to and including the first whose low 7 bits are ETX (0x03) or ETB (0x17), then the
+ * two bytes of the BCS.  The BCS is CRC-16/KERMIT (reflected polynomial 0x8408, initial value 0, mi_acars_crc) over the raw bytes,
+ * parity bits included, from Mode through ETX / ETB, sent low byte first: the CRC over those bytes and the BCS is 0, which is
+ * crc_ok.  parity_errors counts the bytes from Mode through ETX / ETB with an even number of ones.  When byte MI_ACARS_MAX_BYTES =
+ * 240 behind SOH arrives and neither it nor one before it (from the 13th on) was ETX / ETB, the frame is dropped without a record
+ * and the row goes idle.  A finished frame is a record if crc_ok or the setting keep_bad is 1; the row goes idle either way.
+ * Timing moves.  At the first slot of every batch that begins inside a frame (unless hold_timing is 1), with Q of the new batch:
+ * v = u; if Q[u - 1] > Q[v] then v = u - 1; if Q[u + 1] > Q[v] then v = u + 1 (indices mod 20; a tie keeps u, a tie between the
+ * neighbours that beats u goes to u - 1); u = v, one third earlier or later.  By the grid's identity the walker stays in step except
+ * between 0 and 1: moving 0 -> 1 it passes over slot 0 of the new batch (hypothesis 1's slot 1 is the bit a third later), moving
+ * 1 -> 0 it first takes hypothesis 0's last bit of the batch before, out of the carried 38, then slot 0.
+ * Settings (mi_acars_cfg, 0 = the default): sync_errors 1 .. 4, default 2, MI_ACARS_SYNC_EXACT for none (0 is taken by "the
+ * default"); keep_bad 0 / 1; min_quality finite and >= 0, default 0 (no floor was justified by the measurement);
+ * hold_timing 0 / 1 (a diagnostic: tools/acars_classes.py measures what the moves buy).
+ * Record: row; batch and third, where the first bit behind SOH begins (the row's batch number since creation / set_state, wrapping
+ * at 2^32, and the third within it, 0 .. 5999); tau_sync and tau_end, u at the hit and at the end; sync_errors, the hit's
+ * mismatches; crc_ok; nbytes, Mode through ETX / ETB; parity_errors; end, 0x03 or 0x17; end_batch, the call's batch in which the
+ * frame ended; bytes, the nbytes raw bytes and the two of the BCS behind them, zeros to the end.
+ * State: per row MI_ACARS_STATE_ROW_BYTES = 496 bytes, little-endian, a blob of zeros being a fresh state: float32 x[6], the last 6
+ * input samples, oldest first; uint32 batch (batches seen), phase (MI_ACARS_IDLE / MI_ACARS_FRAME); uint64 hist[20], per hypothesis
+ * the last 38 change bits, the newest in bit 0; then uint32 u, prev (the last bit's value), nbits and cur (the bits of the running
+ * byte), nbytes, tail (0 up to ETX / ETB; behind it 1 + the BCS bytes taken), crc (running), parity_errors, start_batch, start_third,
+ * tau_sync, mismatches, end, zero; then bytes[248] as the record has them so far.  An idle row's fields from u on are all zero.
+ * A disabled row writes nothing and every byte of its state stays.  NaN and Inf are unspecified.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_ACARS_HISTORY = 6, MI_ACARS_HYPOTHESES = 20, MI_ACARS_BITS = 300, MI_ACARS_BIT_WORDS = 10, MI_ACARS_SYNC_BITS = 39, MI_ACARS_HEAD_BYTES = 12,
+       MI_ACARS_MAX_BYTES = 240, MI_ACARS_RAW_BYTES = 248, MI_ACARS_STATE_ROW_BYTES = 496 };
+enum { MI_ACARS_IDLE = 0, MI_ACARS_FRAME = 1 };
+#define MI_ACARS_SYNC_EXACT 0x80000000u /* sync_errors: no mismatch allowed */
+typedef struct {
+    uint32_t sync_errors;           /* 0 = 2; 1 .. 4; MI_ACARS_SYNC_EXACT */
+    uint32_t keep_bad;              /* 1: frames whose checksum fails are records too */
+    float min_quality;              /* floor on Q[tau] of the batch of a sync hit */
+    uint32_t hold_timing;           /* 1: no timing moves */
+} mi_acars_cfg;                     /* 16 bytes */
+typedef struct {
+    uint32_t row;
+    uint32_t batch, third;          /* where the first bit behind SOH begins */
+    uint8_t tau_sync, tau_end, sync_errors, crc_ok;
+    uint16_t nbytes;                /* Mode through ETX / ETB, 13 .. 240 */
+    uint8_t parity_errors;
+    uint8_t end;                    /* 0x03 (ETX) or 0x17 (ETB) */
+    uint32_t end_batch;             /* call-relative */
+    uint8_t bytes[248];             /* raw: nbytes, then the BCS low, high; then zeros */
+} mi_acars_frame;                   /* 272 bytes */
+typedef struct {                    /* the printable fields of a frame, parity stripped, NUL-terminated; a character outside 0x20 .. 0x7E is '.' */
+    char mode[2], address[8], ack[2], label[3], block_id[2], text[231];
+} mi_acars_text;                    /* 248 bytes */
+typedef struct mi_acars mi_acars;
+
+/* cfg NULL = every default.  row_enabled, rows and max_batches as for mi_selcal_create.  max_frames: capacity of the caller's frame
+ * buffer, 0 = rows * the most frames a row can end in max_batches batches, 1 + 300 * max_batches / 119.  The handle owns the scratch
+ * for a call's change bits, Q and frames. */
+int mi_acars_create(const mi_acars_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_frames, int gpu, mi_acars** out);
+void mi_acars_destroy(mi_acars* s);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_acars_set_rows(mi_acars* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_bits             [rows][nbatches][20][10]  the packed change bits, or NULL (the handle's scratch); 4-byte aligned.
+ *   d_q                [rows][nbatches][20]      Q, or NULL (the handle's scratch).  A disabled row's are not written.
+ *   d_frames           [max_frames]              rows ascending, time order within a row (8-byte aligned)
+ *   d_row_first_frame  [rows + 1]                exclusive prefix of the rows' frame counts
+ *   d_count            [2]                       number of frames, and min(that, max_frames) = the number stored
+ * Nothing is written at or beyond max_frames.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without atomics
+ * -- bits (one workgroup per (row, batch)), walk (one wave per row, a lane per hypothesis), scan, store, tails -- so every byte is
+ * the same on every run and equals mi_acars_plan_host's. */
+int mi_acars_process_device(mi_acars* s, const float* d_plane, size_t row_stride, int nbatches, uint32_t* d_bits, float* d_q, mi_acars_frame* d_frames,
+                            uint32_t* d_row_first_frame, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_acars_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] frames.  frames and row_first_frame may each be NULL.  The one place that synchronises. */
+int mi_acars_download(mi_acars* s, void* hip_stream, mi_acars_frame* frames, uint32_t* row_first_frame, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_ACARS_STATE_ROW_BYTES bytes in the layout above (mi_acars_plan_host reads and writes the same
+ * bytes).  set_state refuses an impossible state: history bits beyond the 38, an unknown phase, an idle row with a walker field or
+ * byte set, and inside a frame u or tau_sync beyond 19, prev beyond 1, nbits beyond 7, cur beyond its nbits bits, tail beyond 2,
+ * nbytes the frame cannot have (beyond 239 before ETX / ETB, under 13 behind it), an end that is not the byte it names, mismatches
+ * beyond 4, start_third beyond 5999, a crc or parity_errors that the bytes do not give, a byte set behind the ones taken, zero
+ * not 0.  Both complete queued work first. */
+size_t mi_acars_state_size(const mi_acars* s);
+int mi_acars_get_state(mi_acars* s, void* buf, size_t len);
+int mi_acars_set_state(mi_acars* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bits, walk, scan, store, tails}.  tools/acars_rate.py. */
+int mi_acars_set_timing(mi_acars* s, int on);
+int mi_acars_last_launch_ms(mi_acars* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same bits, Q, frames and state blob byte for byte.  plane [rows][row_stride] (no
+ * alignment asked); state_inout rows * MI_ACARS_STATE_ROW_BYTES bytes, read and updated; bits [rows][nbatches][20][10] and
+ * q [rows][nbatches][20], each or NULL; frames holds max_frames entries (max_frames >= 1), of which min(count[0], max_frames) =
+ * count[1] are written. */
+int mi_acars_plan_host(const mi_acars_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                       void* state_inout, uint32_t* bits, float* q, mi_acars_frame* frames, size_t max_frames, uint32_t* row_first_frame,
+                       uint32_t* count /* [2] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in, or the refusal mi_acars_create would give. */
+int mi_acars_settings(const mi_acars_cfg* cfg, mi_acars_cfg* out);
+/* The two templates.  Host only. */
+int mi_acars_templates(float* h1 /* [20] */, float* h2 /* [20] */);
+/* CRC-16/KERMIT of n bytes (NULL with n = 0 is fine; NULL otherwise gives 0xFFFFFFFF, which no CRC is). */
+uint32_t mi_acars_crc(const uint8_t* bytes, size_t n);
+/* The printable fields of a record.  Refuses an nbytes outside 13 .. 240. */
+int mi_acars_frame_text(const mi_acars_frame* f, mi_acars_text* out);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
