@@ -221,6 +221,30 @@ ACARS_STATE_DTYPE = np.dtype([("x", "<f4", (ACARS_HISTORY,)), ("batch", "<u4"), 
                                                    "tau_sync", "mismatches", "end", "zero")] + [("bytes", "u1", (ACARS_RAW_BYTES,))])
 
 
+class SameCfg(C.Structure):  # mi_same_cfg: 0 = the default of every setting
+    _fields_ = [("sync_errors", C.c_uint32), ("max_bad", C.c_uint32), ("gap_batches", C.c_uint32), ("min_quality", C.c_float), ("space_gain", C.c_float),
+                ("hold_timing", C.c_uint32)]
+
+
+class SameText(C.Structure):  # mi_same_text
+    _fields_ = [("originator", C.c_char * 4), ("event", C.c_char * 4), ("purge", C.c_char * 5), ("issue", C.c_char * 8), ("station", C.c_char * 9),
+                ("pad", C.c_char * 2), ("nlocations", C.c_uint32), ("locations", (C.c_char * 7) * 31), ("pad2", C.c_char * 3)]
+
+
+SAME_HISTORY, SAME_HYPOTHESES, SAME_BIT_UNITS, SAME_BATCH_UNITS, SAME_BIT_WORDS, SAME_MAX_BITS, SAME_MAX_BYTES, SAME_RAW_BYTES, SAME_DEAF = 30, 16, 768, 50000, 4, 66, 268, 272, 64
+SAME_IDLE, SAME_BURST = 0, 1  # MI_SAME_*
+SAME_HEADER, SAME_EOM = 0, 1
+SAME_SYNC_EXACT = 0x80000000  # mi_same_cfg.sync_errors: no mismatch allowed
+SAME_WALKER_FIELDS = ("phase", "u", "kind", "nbits", "cur", "nbytes", "nbad", "plus", "dashes", "deaf", "start_batch", "start_unit", "an", "akind", "alen0",
+                      "alen1", "atrunc0", "atrunc1", "aidle", "astart_batch", "astart_unit")
+# mi_same_message (304 bytes) and one row of the SAME stage's state blob, MI_SAME_STATE_ROW_BYTES = 1160
+SAME_MESSAGE_DTYPE = np.dtype([("row", "<u4"), ("kind", "<u4"), ("batch", "<u4"), ("unit", "<u4"), ("end_batch", "<u4"), ("nbursts", "u1"), ("voted", "u1"),
+                               ("truncated", "u1"), ("fields_ok", "u1"), ("nbytes", "<u2"), ("agree", "<u2"), ("zero", "<u4"),
+                               ("bytes", "u1", (SAME_RAW_BYTES,))])
+SAME_STATE_DTYPE = np.dtype([("x", "<f4", (SAME_HISTORY,)), ("batch", "<u4"), ("grid", "<u4"), ("hist", "<u8", (SAME_HYPOTHESES,))] +
+                            [(n, "<u4") for n in SAME_WALKER_FIELDS + ("zero",)] + [("bytes", "u1", (3, SAME_RAW_BYTES))])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -312,6 +336,9 @@ ABI_SYMBOLS = [
     "mi_acars_create", "mi_acars_destroy", "mi_acars_set_rows", "mi_acars_process_device", "mi_acars_download", "mi_acars_state_size",
     "mi_acars_get_state", "mi_acars_set_state", "mi_acars_set_timing", "mi_acars_last_launch_ms", "mi_acars_plan_host", "mi_acars_settings",
     "mi_acars_templates", "mi_acars_crc", "mi_acars_frame_text",
+    "mi_same_create", "mi_same_destroy", "mi_same_set_rows", "mi_same_process_device", "mi_same_download", "mi_same_state_size",
+    "mi_same_get_state", "mi_same_set_state", "mi_same_set_timing", "mi_same_last_launch_ms", "mi_same_plan_host", "mi_same_settings",
+    "mi_same_templates", "mi_same_message_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -503,6 +530,22 @@ def lib():
         L.mi_acars_crc.argtypes = [vp, sz]
         L.mi_acars_crc.restype = C.c_uint32
         L.mi_acars_frame_text.argtypes = [vp, C.POINTER(AcarsText)]
+        L.mi_same_create.argtypes = [C.POINTER(SameCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_same_destroy.argtypes = [vp]
+        L.mi_same_destroy.restype = None
+        L.mi_same_set_rows.argtypes = [vp, vp]
+        L.mi_same_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.mi_same_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mi_same_state_size.argtypes = [vp]
+        L.mi_same_state_size.restype = sz
+        L.mi_same_get_state.argtypes = [vp, vp, sz]
+        L.mi_same_set_state.argtypes = [vp, vp, sz]
+        L.mi_same_set_timing.argtypes = [vp, C.c_int]
+        L.mi_same_last_launch_ms.argtypes = [vp, vp]
+        L.mi_same_plan_host.argtypes = [C.POINTER(SameCfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+        L.mi_same_settings.argtypes = [C.POINTER(SameCfg), C.POINTER(SameCfg)]
+        L.mi_same_templates.argtypes = [vp]
+        L.mi_same_message_text.argtypes = [vp, C.POINTER(SameText)]
         L.mi_limit_default_row.argtypes = []
         L.mi_limit_default_row.restype = LimitRow
         L.mi_limit_create.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -640,7 +683,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails; the SAME stage's bits, walk, scan, store and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -654,7 +697,7 @@ class _PostStage(_TimedStage):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
         .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
-        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1722,6 +1765,109 @@ def acars_plan_host(row_enabled, plane, cfg=None, state=None, max_frames=0, nbat
     _check(lib().mi_acars_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(q), _ptr(frames), cap,
                                     _ptr(row_first), _ptr(count)))
     return frames[:int(count[1])], bits, q, row_first, count, state
+
+
+def same_cfg(sync_errors=0, max_bad=0, gap_batches=0, min_quality=0.0, space_gain=0.0, hold_timing=False):
+    """mi_same_cfg, field for field as the C struct takes it: sync_errors 1 .. 4 mismatches a sync may have, 0 (or None) = the
+    default, 4, and SAME_SYNC_EXACT for none; max_bad: the consecutive bad bytes that end a burst (0 = 4); gap_batches: batches behind
+    the last burst that close a message (0 = 20); min_quality: floor on Q of a sync's batch; space_gain: weight of the space power in
+    the bit decision (0 = 1); hold_timing: no timing moves.  A SameCfg passes through."""
+    if isinstance(sync_errors, SameCfg):
+        return sync_errors
+    c = SameCfg()
+    c.sync_errors, c.max_bad, c.gap_batches = int(sync_errors or 0), int(max_bad), int(gap_batches)
+    c.min_quality, c.space_gain, c.hold_timing = min_quality, space_gain, int(hold_timing)
+    return c
+
+
+def same_settings(cfg=None):
+    """mi_same_settings: the settings with every default filled in, as a SameCfg"""
+    out = SameCfg()
+    _check(lib().mi_same_settings(C.byref(same_cfg(cfg)), C.byref(out)))
+    return out
+
+
+def same_max_messages(nbatches):
+    """the most messages one row can close in a call of nbatches batches (MI_SAME_MAX_MESSAGES)"""
+    return 2 * (2 + 66 * nbatches // 65) + 1
+
+
+def same_templates():
+    """mi_same_templates: [4][768], cos and sin of 4 cycles a bit (mark), cos and sin of 3 (space)"""
+    t = np.zeros((4, SAME_BIT_UNITS), np.float32)
+    _check(lib().mi_same_templates(_ptr(t)))
+    return t
+
+
+def same_message_text(message):
+    """mi_same_message_text: a header record's fields as a dict: originator, event, locations (list of str), purge, issue, station"""
+    m = np.array(message, SAME_MESSAGE_DTYPE).reshape(1)
+    out = SameText()
+    _check(lib().mi_same_message_text(_ptr(m), C.byref(out)))
+    d = {n: getattr(out, n).decode("ascii") for n in ("originator", "event", "purge", "issue", "station")}
+    d["locations"] = [out.locations[i].value.decode("ascii") for i in range(out.nlocations)]
+    return d
+
+
+class Same(_PostStage):
+    """mi_same: the SAME decoder stage -- per row, the weather-alert headers and end-of-message marks its 520.83 bit/s AFSK bursts
+    carried: a bank of mark / space detectors under 16 timing hypotheses per batch, a sync compare on every hypothesis while the row
+    is idle, a walker that reads the burst's bytes and follows the timing, and an assembler that votes three bursts into a message.
+    It reads a plane of audio as Acars does and needs no flags.  row_enabled: truth value per row; cfg: same_cfg(...) or None;
+    max_messages: capacity of the message buffer, 0 = rows * same_max_messages(max_batches).  state() gives rows * 1160 bytes, whose
+    fields .view(SAME_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_same_destroy", "mi_same", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_messages=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = same_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_same_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_messages, gpu, C.byref(self._h)))
+        most = self.rows * same_max_messages(max_batches)
+        self.max_messages = min(max_messages, most) if max_messages else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_same_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_messages, d_row_first_message, d_count, d_bits=None, d_q=None, hip_stream=None):
+        """Raw device pointers (ints; d_bits and d_q may be None), the stride in floats; asynchronous on hip_stream."""
+        _check(lib().mi_same_process_device(self._h, d_plane, row_stride, nbatches, d_bits, d_q, d_messages, d_row_first_message, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (messages [k] of SAME_MESSAGE_DTYPE, row_first_message
+        [rows + 1], count [2]) with k = count[1]."""
+        messages = np.zeros(self.max_messages, SAME_MESSAGE_DTYPE)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_same_download(self._h, hip_stream, _ptr(messages), _ptr(row_first), _ptr(count)))
+        return messages[:int(count[1])], row_first, count
+
+
+def same_plan_host(row_enabled, plane, cfg=None, state=None, max_messages=0, nbatches=None):
+    """mi_same_plan_host: the SAME stage's bits, Q and messages from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 1160 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_messages: 0 = every message of the call.  Returns (messages [count[1]], bits [rows][nbatches][16][4], q [rows][nbatches][16],
+    row_first_message [rows + 1], count [2], state after the call).  A disabled row's bits and q stay zero."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = same_cfg(cfg)
+    state = np.zeros(rows * SAME_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * SAME_STATE_DTYPE.itemsize
+    cap = max_messages or max(1, rows * same_max_messages(max(nb, 1)))
+    messages = np.zeros(cap, SAME_MESSAGE_DTYPE)
+    bits = np.zeros((rows, max(nb, 0), SAME_HYPOTHESES, SAME_BIT_WORDS), np.uint32)
+    q = np.zeros((rows, max(nb, 0), SAME_HYPOTHESES), np.float32)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_same_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(q), _ptr(messages), cap,
+                                   _ptr(row_first), _ptr(count)))
+    return messages[:int(count[1])], bits, q, row_first, count, state
 
 
 def _aspec_cfg(lo_hz=0, hi_hz=0):

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -611,6 +611,287 @@ __host__ __device__ inline int acars_retime(AcarsWalker& w, const float* q) {
 int acars_plan(const mi_acars_cfg* cfg, AcarsPlan* out);
 void acars_templates(float* h1, float* h2);
 const char* acars_state_ok(const AcarsRowState* state, size_t rows);
+
+// The SAME decoder stage (include/mi_airband.h "SAME decoder stage").  The walker's and the assembler's part of a row's state, as the
+// walk carries it in registers; the running burst's bytes and the two stored bursts stay in memory beside it.
+struct SameWalker {
+    uint32_t phase, u, kind, nbits, cur, nbytes, nbad, plus, dashes, deaf, start_batch, start_unit;  // the burst's
+    uint32_t an, akind, alen0, alen1, atrunc0, atrunc1, aidle, astart_batch, astart_unit;            // the assembler's
+};
+constexpr int kSameWalkerWords = sizeof(SameWalker) / 4;
+// One row of the state: the checkpoint blob is an array of these, and same.hip keeps the same array in device memory.
+struct SameRowState {
+    float x[MI_SAME_HISTORY];              // the last 30 input samples of the row's last batch, oldest first
+    uint32_t batch;                        // batches seen since creation / set_state
+    uint32_t grid;                         // (50 000 * batches seen) mod 768
+    uint64_t hist[MI_SAME_HYPOTHESES];     // per hypothesis the last 64 bits, the newest in bit 0
+    SameWalker w;
+    uint32_t zero;
+    uint8_t bytes[3][MI_SAME_RAW_BYTES];   // the running burst, then the assembler's two
+};
+static_assert(sizeof(SameRowState) == MI_SAME_STATE_ROW_BYTES && offsetof(SameRowState, hist) == 128 && offsetof(SameRowState, w) == 256 &&
+                  offsetof(SameRowState, bytes) == 344 && kSameWalkerWords == 21 && sizeof(mi_same_message) == 304 &&
+                  offsetof(mi_same_message, bytes) == 32 && sizeof(mi_same_cfg) == 24 && sizeof(mi_same_text) == 256 &&
+                  (MI_SAME_HISTORY + 2) % 4 == 0 && MI_SAME_MAX_BYTES <= MI_SAME_RAW_BYTES && MI_SAME_RAW_BYTES % 8 == 0 &&
+                  25 * kWaveBatch == MI_SAME_BATCH_UNITS && MI_SAME_BIT_WORDS * 32 >= MI_SAME_MAX_BITS + 32,
+              "the SAME stage's blob, record and settings layouts are ABI");
+// The settings with every default filled in, as both halves take them.
+struct SamePlan {
+    uint32_t sync_errors;  // the number itself, 0 .. 4
+    uint32_t max_bad, gap_batches, hold_timing;
+    float min_quality, space_gain;
+    mi_same_cfg filled;    // the settings as the caller would have written them
+};
+constexpr int kSameTemplate = MI_SAME_BIT_UNITS;  // entries of one template
+constexpr uint64_t same_pattern(const char c0, const char c1, const char c2, const char c3) {
+    const uint8_t s[8] = {0xAB, 0xAB, 0xAB, 0xAB, static_cast<uint8_t>(c0), static_cast<uint8_t>(c1), static_cast<uint8_t>(c2), static_cast<uint8_t>(c3)};
+    uint64_t p = 0;
+    for (int i = 0; i < 64; ++i)
+        p = p << 1 | static_cast<uint64_t>((s[i / 8] >> (i % 8)) & 1);
+    return p;
+}
+constexpr uint64_t kSameHeaderSync = same_pattern('Z', 'C', 'Z', 'C'), kSameEomSync = same_pattern('N', 'N', 'N', 'N');
+inline uint32_t same_max_messages(uint64_t nbatches) {
+    return static_cast<uint32_t>(2 * (2 + 66 * nbatches / 65) + 1);
+}
+// The grid of a batch whose state field is `grid`: the hypotheses below same_ahead had their bit of the batch's first index in the
+// batch before; same_first is where hypothesis tau's first bit of the batch begins, -767 .. 0; same_count how many it has.
+__host__ __device__ inline int same_ahead(const uint32_t grid) {
+    const int a = static_cast<int>(grid) / 48 + 1;
+    return a == MI_SAME_HYPOTHESES ? 0 : a;
+}
+__host__ __device__ inline int same_first(const uint32_t grid, const int tau) {
+    const int c = (48 * tau + MI_SAME_BIT_UNITS - static_cast<int>(grid)) % MI_SAME_BIT_UNITS;
+    return c ? c - MI_SAME_BIT_UNITS : 0;
+}
+__host__ __device__ inline int same_count(const int r0) {
+    return (MI_SAME_BATCH_UNITS - MI_SAME_BIT_UNITS - r0) / MI_SAME_BIT_UNITS + 1;
+}
+// The bit that begins at unit r (-767 .. 49 232) of the block staged at s -- s[32 + n] is the block's sample n --, T the four
+// templates: the bit, and its quality into *q.  Host and device run this text.
+__host__ __device__ inline uint32_t same_bit(const float* s, const float* T, const int r, const float space_gain, float* q) {
+    const int n0 = (r + 824) / 25 - 32;  // ceil(r / 25)
+    int rho = 25 * n0 - r;               // 0 .. 24
+    const bool more = rho + 750 < MI_SAME_BIT_UNITS;
+    const float* const x = s + (MI_SAME_HISTORY + 2) + n0;
+    float s0 = x[0] * T[rho], s1 = x[0] * T[kSameTemplate + rho], s2 = x[0] * T[2 * kSameTemplate + rho], s3 = x[0] * T[3 * kSameTemplate + rho];
+    for (int i = 1; i < 30; ++i) {
+        rho += 25;
+        s0 = s0 + x[i] * T[rho];
+        s1 = s1 + x[i] * T[kSameTemplate + rho];
+        s2 = s2 + x[i] * T[2 * kSameTemplate + rho];
+        s3 = s3 + x[i] * T[3 * kSameTemplate + rho];
+    }
+    if (more) {
+        rho += 25;
+        s0 = s0 + x[30] * T[rho];
+        s1 = s1 + x[30] * T[kSameTemplate + rho];
+        s2 = s2 + x[30] * T[2 * kSameTemplate + rho];
+        s3 = s3 + x[30] * T[3 * kSameTemplate + rho];
+    }
+    const float pm = s0 * s0 + s1 * s1, ps = s2 * s2 + s3 * s3;
+    *q = pm > ps ? pm : ps;
+    return pm >= space_gain * ps ? 1u : 0u;
+}
+// mk[tau] = mismatches | kind << 8 of tau's 64 bits against the nearer pattern
+__host__ __device__ inline uint32_t same_mismatch(const uint64_t hist) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t mh = static_cast<uint32_t>(__popcll(hist ^ kSameHeaderSync)), me = static_cast<uint32_t>(__popcll(hist ^ kSameEomSync));
+#else
+    const uint32_t mh = static_cast<uint32_t>(__builtin_popcountll(hist ^ kSameHeaderSync)), me = static_cast<uint32_t>(__builtin_popcountll(hist ^ kSameEomSync));
+#endif
+    return me < mh ? me | MI_SAME_EOM << 8 : mh;
+}
+// The hypothesis a sync opens the burst on; -1: no hit.
+__host__ __device__ inline int same_pick(const uint32_t* mk, const float* q, const uint32_t sync_errors, const float min_quality) {
+    int best = -1;
+    for (int t = 0; t < MI_SAME_HYPOTHESES; ++t) {
+        const uint32_t m = mk[t] & 0xFFu;
+        if (m > sync_errors || !(q[t] >= min_quality))
+            continue;
+        if (best < 0 || m < (mk[best] & 0xFFu) || (m == (mk[best] & 0xFFu) && q[t] > q[best]))
+            best = t;
+    }
+    return best;
+}
+// Whether n bytes of a message of `kind` match the grammar of the header.
+__host__ __device__ inline uint32_t same_fields_ok(const uint8_t* b, const uint32_t n, const uint32_t kind) {
+    const auto cap = [](uint8_t c) { return c >= 'A' && c <= 'Z'; };
+    const auto dig = [](uint8_t c) { return c >= '0' && c <= '9'; };
+    if (kind == MI_SAME_EOM)
+        return n == 4 && b[0] == 'N' && b[1] == 'N' && b[2] == 'N' && b[3] == 'N';
+    // "ZCZC-ORG-EEE" 12, a location 7, "+TTTT-JJJHHMM-LLLLLLLL-" 23
+    if (n < 12 + 7 + 23 || (n - 12 - 23) % 7 != 0 || (n - 12 - 23) / 7 > 31)
+        return 0;
+    if (b[0] != 'Z' || b[1] != 'C' || b[2] != 'Z' || b[3] != 'C' || b[4] != '-' || b[8] != '-')
+        return 0;
+    for (int i = 0; i < 3; ++i)
+        if (!cap(b[5 + i]) || !cap(b[9 + i]))
+            return 0;
+    uint32_t i = 12;
+    for (; i < n - 23; i += 7) {
+        if (b[i] != '-')
+            return 0;
+        for (int d = 1; d < 7; ++d)
+            if (!dig(b[i + d]))
+                return 0;
+    }
+    if (b[i] != '+' || b[i + 5] != '-' || b[i + 13] != '-' || b[i + 22] != '-')
+        return 0;
+    for (int d = 0; d < 4; ++d)
+        if (!dig(b[i + 1 + d]))
+            return 0;
+    for (int d = 0; d < 7; ++d)
+        if (!dig(b[i + 6 + d]))
+            return 0;
+    for (int d = 0; d < 8; ++d)
+        if (b[i + 14 + d] < 0x20 || b[i + 14 + d] > 0x7E || b[i + 14 + d] == '-')
+            return 0;
+    return 1;
+}
+// The assembler's n bursts become the record *m, closed in the call's batch b; the third burst, where n = 3, is the running one
+// (len2 bytes, flag trunc2).  The assembler is empty behind it.  bytes: the row's [3][272].
+__host__ __device__ inline void same_close(SameWalker& w, uint8_t* bytes, const uint32_t row, const uint32_t b, const uint32_t n, const uint32_t len2,
+                                           const uint32_t trunc2, mi_same_message* m) {
+    uint8_t *const b0 = bytes + MI_SAME_RAW_BYTES, *const b1 = bytes + 2 * MI_SAME_RAW_BYTES;
+    const uint8_t* const b2 = bytes;
+    uint32_t len = w.alen0, trunc = w.atrunc0, agree = 0;
+    if (n == 3) {
+        const uint32_t lo = w.alen0 < w.alen1 ? w.alen0 : w.alen1, hi = w.alen0 < w.alen1 ? w.alen1 : w.alen0;
+        len = len2 < lo ? lo : len2 > hi ? hi : len2;  // the median
+        trunc = w.atrunc0 + w.atrunc1 + trunc2 >= 2;
+    }
+    for (uint32_t i = 0; i < MI_SAME_RAW_BYTES; ++i) {
+        uint8_t v = 0;
+        if (i < len) {
+            const uint8_t a = b0[i], c = b1[i], d = b2[i];
+            v = n == 3 ? static_cast<uint8_t>((a & c) | (a & d) | (c & d)) : a;
+            agree += n == 1 || (a == c && (n == 2 || c == d));
+        }
+        m->bytes[i] = v;
+    }
+    m->row = row;
+    m->kind = w.akind;
+    m->batch = w.astart_batch;
+    m->unit = w.astart_unit;
+    m->end_batch = b;
+    m->nbursts = static_cast<uint8_t>(n);
+    m->voted = n == 3;
+    m->truncated = static_cast<uint8_t>(trunc);
+    m->nbytes = static_cast<uint16_t>(len);
+    m->agree = static_cast<uint16_t>(agree);
+    m->zero = 0;
+    m->fields_ok = static_cast<uint8_t>(same_fields_ok(m->bytes, len, w.akind));
+    for (uint32_t i = 0; i < w.alen0; ++i)
+        b0[i] = 0;
+    for (uint32_t i = 0; i < w.alen1; ++i)
+        b1[i] = 0;
+    w.an = w.akind = w.alen0 = w.alen1 = w.atrunc0 = w.atrunc1 = w.aidle = w.astart_batch = w.astart_unit = 0;
+}
+// The running burst ends (trunc: as truncated) in the call's batch b: it goes to the assembler, the row is idle and deaf.  True when
+// that closed a message into *m.
+__host__ __device__ inline bool same_burst_end(SameWalker& w, uint8_t* bytes, const uint32_t trunc, const uint32_t row, const uint32_t b, mi_same_message* m) {
+    bool closed = false;
+    if (w.an == 0) {
+        w.akind = w.kind;
+        w.astart_batch = w.start_batch;
+        w.astart_unit = w.start_unit;
+    }
+    if (w.an == 2) {
+        same_close(w, bytes, row, b, 3, w.nbytes, trunc, m);
+        closed = true;
+    } else {
+        uint8_t* const dst = bytes + (1 + w.an) * MI_SAME_RAW_BYTES;
+        for (uint32_t i = 0; i < w.nbytes; ++i)
+            dst[i] = bytes[i];
+        (w.an ? w.alen1 : w.alen0) = w.nbytes;
+        (w.an ? w.atrunc1 : w.atrunc0) = trunc;
+        ++w.an;
+        w.aidle = 0;
+    }
+    for (uint32_t i = 0; i < w.nbytes; ++i)
+        bytes[i] = 0;
+    w.phase = MI_SAME_IDLE;
+    w.u = w.kind = w.nbits = w.cur = w.nbytes = w.nbad = w.plus = w.dashes = w.start_batch = w.start_unit = 0;
+    w.deaf = MI_SAME_DEAF;
+    return closed;
+}
+// A burst of `kind` opens on hypothesis u at a hit on the bit that begins at unit r of the row's batch number `batch`, the call's b.
+// True when that closed a message of the other kind into *m.  (The caller ends an EOM burst at once.)
+__host__ __device__ inline bool same_open(SameWalker& w, uint8_t* bytes, const int u, const uint32_t kind, const uint32_t batch, const int r, const uint32_t row,
+                                          const uint32_t b, mi_same_message* m) {
+    bool closed = false;
+    if (w.an && w.akind != kind) {
+        same_close(w, bytes, row, b, w.an, 0, 0, m);
+        closed = true;
+    }
+    w.phase = MI_SAME_BURST;
+    w.u = static_cast<uint32_t>(u);
+    w.kind = kind;
+    w.nbits = w.cur = w.nbad = w.plus = w.dashes = w.deaf = 0;
+    w.nbytes = 4;
+    bytes[0] = bytes[2] = kind == MI_SAME_EOM ? 'N' : 'Z';
+    bytes[1] = bytes[3] = kind == MI_SAME_EOM ? 'N' : 'C';
+    const int zs = r - 31 * MI_SAME_BIT_UNITS;  // the hit's bit is the pattern's last: 'Z' / 'N' began 31 bits before it
+    w.start_batch = zs < 0 ? batch - 1u : batch;
+    w.start_unit = static_cast<uint32_t>(zs < 0 ? zs + MI_SAME_BATCH_UNITS : zs);
+    return closed;
+}
+// One bit c of the chosen hypothesis through a ZCZC burst.  True when the burst ends, *trunc saying how.
+__host__ __device__ inline bool same_step(SameWalker& w, uint8_t* bytes, const uint32_t c, const uint32_t max_bad, uint32_t* trunc) {
+    w.cur |= c << w.nbits;
+    if (++w.nbits < 8)
+        return false;
+    const uint32_t byte = w.cur;
+    w.cur = 0;
+    w.nbits = 0;
+    bytes[w.nbytes++] = static_cast<uint8_t>(byte);
+    if ((byte & 0x80u) || byte < 0x20u) {
+        if (++w.nbad == max_bad) {
+            for (uint32_t i = 0; i < max_bad; ++i)
+                bytes[--w.nbytes] = 0;
+            *trunc = 1;
+            return true;
+        }
+    } else {
+        w.nbad = 0;
+        if (!w.plus) {
+            w.plus = byte == '+';
+        } else if (byte == '-' && ++w.dashes == 3) {
+            *trunc = 0;
+            return true;
+        }
+    }
+    if (w.nbytes == MI_SAME_MAX_BYTES) {
+        *trunc = 1;
+        return true;
+    }
+    return false;
+}
+// The gap rule at a batch's first index.  True when it closed a message into *m.
+__host__ __device__ inline bool same_gap(SameWalker& w, uint8_t* bytes, const uint32_t gap_batches, const uint32_t row, const uint32_t b, mi_same_message* m) {
+    if (w.phase != MI_SAME_IDLE || !w.an || ++w.aidle < gap_batches)
+        return false;
+    same_close(w, bytes, row, b, w.an, 0, 0, m);
+    return true;
+}
+// The timing move at a batch's first index inside a burst, from the new batch's Q.
+enum { kSameInStep = 0, kSameSkip = 1, kSameReplay = 2 };
+__host__ __device__ inline int same_retime(SameWalker& w, const float* q) {
+    const uint32_t u = w.u, um = (u + 15) % 16, up = (u + 1) % 16;
+    uint32_t v = u;
+    if (q[um] > q[v])
+        v = um;
+    if (q[up] > q[v])
+        v = up;
+    w.u = v;
+    return u == 15 && v == 0 ? kSameSkip : u == 0 && v == 15 ? kSameReplay : kSameInStep;
+}
+// What both halves of the SAME stage share (poststage_host.cpp).  same_plan: MI_OK with the plan, or the settings' refusal with its
+// message set.  same_templates: T[4][768].  same_state_ok: NULL, or what is impossible about a blob.
+int same_plan(const mi_same_cfg* cfg, SamePlan* out);
+void same_templates(float* T);
+const char* same_state_ok(const SameRowState* state, size_t rows, const SamePlan& plan);
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

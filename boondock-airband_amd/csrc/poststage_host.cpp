@@ -1961,3 +1961,264 @@ extern "C" int mi_acars_plan_host(const mi_acars_cfg* cfg, const uint8_t* row_en
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::AcarsRowState));
     return MI_OK;
 }
+
+// ---- SAME decoder stage, host side (include/mi_airband.h "SAME decoder stage"): the settings' check, the templates, the blob's
+// check, a header's text, and the twin of same.hip -- one row, one batch, one hypothesis and one bit at a time, then the walker over
+// the batch's indices.  The bit, the walker's step, the sync's choice, the assembler and the timing move are poststage.hpp's.
+namespace mi {
+
+int same_plan(const mi_same_cfg* cfg, SamePlan* out) {
+    mi_same_cfg c{};
+    if (cfg)
+        c = *cfg;
+    if (c.sync_errors == 0)
+        c.sync_errors = 4;
+    if (c.sync_errors != MI_SAME_SYNC_EXACT && c.sync_errors > 4)
+        return fail(MI_ERR_INVALID, "SAME stage: sync_errors must be within 1 .. 4 or MI_SAME_SYNC_EXACT (0 = the default)");
+    if (c.max_bad == 0)
+        c.max_bad = 4;
+    if (c.max_bad > 16)
+        return fail(MI_ERR_INVALID, "SAME stage: max_bad must be within 1 .. 16 (0 = the default)");
+    if (c.gap_batches == 0)
+        c.gap_batches = 20;
+    if (c.gap_batches > 1000)
+        return fail(MI_ERR_INVALID, "SAME stage: gap_batches must be within 1 .. 1000 (0 = the default)");
+    if (!std::isfinite(c.min_quality) || c.min_quality < 0.0f)
+        return fail(MI_ERR_INVALID, "SAME stage: min_quality must be finite and not negative (0 = the default)");
+    if (!std::isfinite(c.space_gain) || c.space_gain < 0.0f)
+        return fail(MI_ERR_INVALID, "SAME stage: space_gain must be finite and above 0 (0 = the default)");
+    if (c.hold_timing > 1)
+        return fail(MI_ERR_INVALID, "SAME stage: hold_timing must be 0 or 1");
+    c.min_quality = c.min_quality + 0.0f;  // (-0.0f is the default too)
+    if (c.space_gain == 0.0f)
+        c.space_gain = 1.0f;
+    SamePlan p{};
+    p.sync_errors = c.sync_errors == MI_SAME_SYNC_EXACT ? 0u : c.sync_errors;
+    p.max_bad = c.max_bad;
+    p.gap_batches = c.gap_batches;
+    p.hold_timing = c.hold_timing;
+    p.min_quality = c.min_quality;
+    p.space_gain = c.space_gain;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+void same_templates(float* T) {
+    const double pi = 3.14159265358979323846;
+    for (int r = 0; r < kSameTemplate; ++r) {
+        T[r] = static_cast<float>(std::cos(2.0 * pi * 4.0 * r / 768.0));
+        T[kSameTemplate + r] = static_cast<float>(std::sin(2.0 * pi * 4.0 * r / 768.0));
+        T[2 * kSameTemplate + r] = static_cast<float>(std::cos(2.0 * pi * 3.0 * r / 768.0));
+        T[3 * kSameTemplate + r] = static_cast<float>(std::sin(2.0 * pi * 3.0 * r / 768.0));
+    }
+}
+
+const char* same_state_ok(const SameRowState* state, size_t rows, const SamePlan& plan) {
+    for (size_t r = 0; r < rows; ++r) {
+        const SameRowState& s = state[r];
+        const SameWalker& w = s.w;
+        if (s.zero)
+            return "the zero field is not 0";
+        if (s.grid >= MI_SAME_BIT_UNITS || s.grid % 16 != 0)
+            return "a grid that is no multiple of 16 below 768";
+        if (w.phase > MI_SAME_BURST)
+            return "an unknown walker phase";
+        if (w.phase == MI_SAME_IDLE) {
+            if (w.u | w.kind | w.nbits | w.cur | w.nbytes | w.nbad | w.plus | w.dashes | w.start_batch | w.start_unit)
+                return "an impossible walker state (an idle row with a burst field set)";
+            if (w.deaf > MI_SAME_DEAF)
+                return "an impossible walker state (deaf beyond 64)";
+        } else {
+            if (w.kind != MI_SAME_HEADER || w.u > 15 || w.nbits > 7 || w.cur >= (1u << w.nbits) || w.nbytes < 4 || w.nbytes >= MI_SAME_MAX_BYTES || w.deaf ||
+                w.start_unit >= MI_SAME_BATCH_UNITS || std::memcmp(s.bytes[0], "ZCZC", 4) != 0 || (w.an && w.akind != MI_SAME_HEADER))
+                return "an impossible walker state (counters, kind or timing that a burst cannot have)";
+            SameWalker t{};
+            t.nbytes = 4;
+            uint8_t copy[MI_SAME_RAW_BYTES] = {'Z', 'C', 'Z', 'C'};
+            uint32_t trunc = 0;
+            for (uint32_t i = 4; i < w.nbytes; ++i)
+                for (int bit = 0; bit < 8; ++bit)
+                    if (same_step(t, copy, s.bytes[0][i] >> bit & 1u, plan.max_bad, &trunc))
+                        return "an impossible walker state (bytes that would have ended the burst)";
+            if (t.nbad != w.nbad || t.plus != w.plus || t.dashes != w.dashes)
+                return "an impossible walker state (nbad, plus or dashes that the bytes do not give)";
+        }
+        if (w.an > 2 || w.akind > MI_SAME_EOM || w.atrunc0 > 1 || w.atrunc1 > 1 || w.astart_unit >= MI_SAME_BATCH_UNITS || w.aidle >= plan.gap_batches)
+            return "an impossible assembler state (count, kind, flag, aidle or unit out of range)";
+        const uint32_t len[3] = {w.phase == MI_SAME_BURST ? w.nbytes : 0u, w.an >= 1 ? w.alen0 : 0u, w.an >= 2 ? w.alen1 : 0u};
+        if ((w.an < 1 && (w.alen0 | w.atrunc0 | w.akind | w.aidle | w.astart_batch | w.astart_unit)) || (w.an < 2 && (w.alen1 | w.atrunc1)))
+            return "an impossible assembler state (a field set that its bursts do not use)";
+        for (uint32_t i = 1; i <= w.an; ++i)
+            if (len[i] < 4 || len[i] > MI_SAME_MAX_BYTES || (w.akind == MI_SAME_EOM && len[i] != 4))
+                return "an impossible assembler state (a burst's length)";
+        for (int k = 0; k < 3; ++k)
+            for (uint32_t i = len[k]; i < MI_SAME_RAW_BYTES; ++i)
+                if (s.bytes[k][i])
+                    return "an impossible state (a byte set behind a burst's length)";
+    }
+    return nullptr;
+}
+
+}  // namespace mi
+
+extern "C" int mi_same_settings(const mi_same_cfg* cfg, mi_same_cfg* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::SamePlan p;
+    if (const int rc = mi::same_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    return MI_OK;
+}
+
+extern "C" int mi_same_templates(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::same_templates(out);
+    return MI_OK;
+}
+
+extern "C" int mi_same_message_text(const mi_same_message* m, mi_same_text* out) {
+    if (!m || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (m->kind != MI_SAME_HEADER || m->nbytes > MI_SAME_MAX_BYTES || !mi::same_fields_ok(m->bytes, m->nbytes, MI_SAME_HEADER))
+        return fail(MI_ERR_INVALID, "SAME stage: not a header whose fields are in order");
+    std::memset(out, 0, sizeof(*out));
+    const uint8_t* const b = m->bytes;
+    std::memcpy(out->originator, b + 5, 3);
+    std::memcpy(out->event, b + 9, 3);
+    const uint32_t nloc = (m->nbytes - 35u) / 7u;
+    out->nlocations = nloc;
+    for (uint32_t i = 0; i < nloc; ++i)
+        std::memcpy(out->locations[i], b + 13 + 7 * i, 6);
+    const uint8_t* const t = b + 12 + 7 * nloc;  // '+'
+    std::memcpy(out->purge, t + 1, 4);
+    std::memcpy(out->issue, t + 6, 7);
+    std::memcpy(out->station, t + 14, 8);
+    return MI_OK;
+}
+
+extern "C" int mi_same_plan_host(const mi_same_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                 void* state_inout, uint32_t* bits, float* q, mi_same_message* messages, size_t max_messages, uint32_t* row_first_message,
+                                 uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !messages || !row_first_message || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_messages < 1)
+        return fail(MI_ERR_INVALID, "SAME plan needs rows >= 1, nbatches >= 1 and max_messages >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::SamePlan plan;
+    if (const int rc = mi::same_plan(cfg, &plan))
+        return rc;
+    if (static_cast<uint64_t>(rows) * (2 * (2 + 66 * static_cast<uint64_t>(nbatches) / 65) + 1) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "SAME plan: the messages of the call do not fit the 32-bit count");
+    std::vector<mi::SameRowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::SameRowState));
+    if (const char* const why = mi::same_state_ok(blob.data(), blob.size(), plan))
+        return fail(MI_ERR_INVALID, std::string("SAME plan: malformed state blob: ") + why);
+    constexpr int kLead = MI_SAME_HISTORY + 2, kTau = MI_SAME_HYPOTHESES, kWords = MI_SAME_BIT_WORDS;
+    std::vector<float> T(4 * mi::kSameTemplate);
+    mi::same_templates(T.data());
+    std::vector<float> s(kLead + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    uint32_t k = 0;
+    mi_same_message m;
+    for (int r = 0; r < rows; ++r) {
+        row_first_message[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::SameRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        s[0] = s[1] = 0.0f;
+        std::memcpy(s.data() + 2, st.x, sizeof(st.x));
+        std::memcpy(s.data() + kLead, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::SameWalker& w = st.w;
+        uint8_t* const bytes = st.bytes[0];
+        const auto record = [&](bool closed) {
+            if (!closed)
+                return;
+            if (k < max_messages)
+                messages[k] = m;
+            ++k;
+        };
+        const auto step = [&](uint32_t c, int b) {  // one bit of the chosen hypothesis inside a burst
+            uint32_t trunc = 0;
+            if (mi::same_step(w, bytes, c, plan.max_bad, &trunc))
+                record(mi::same_burst_end(w, bytes, trunc, static_cast<uint32_t>(r), static_cast<uint32_t>(b), &m));
+        };
+        for (int b = 0; b < nbatches; ++b) {
+            const float* const blk = s.data() + static_cast<size_t>(b) * mi::kWaveBatch;  // staged: blk[kLead + n] is the batch's sample n
+            uint32_t word[kTau][kWords] = {};
+            int r0[kTau], cnt[kTau];
+            float Q[kTau], qs[MI_SAME_MAX_BITS];
+            for (int t = 0; t < kTau; ++t) {
+                r0[t] = mi::same_first(st.grid, t);
+                cnt[t] = mi::same_count(r0[t]);
+                for (int j = 0; j < cnt[t]; ++j)
+                    word[t][j / 32] |= mi::same_bit(blk, T.data(), r0[t] + MI_SAME_BIT_UNITS * j, plan.space_gain, &qs[j]) << (j % 32);
+                word[t][3] = static_cast<uint32_t>(cnt[t]);
+                float lane[64];
+                for (int l = 0; l < 64; ++l)
+                    lane[l] = l + 64 < cnt[t] ? qs[l] + qs[l + 64] : qs[l];
+                for (int h = 32; h >= 1; h /= 2)
+                    for (int l = 0; l < h; ++l)
+                        lane[l] = lane[l] + lane[l + h];
+                Q[t] = lane[0];
+            }
+            const size_t blk_i = static_cast<size_t>(r) * static_cast<size_t>(nbatches) + static_cast<size_t>(b);
+            if (bits)
+                std::memcpy(bits + blk_i * kTau * kWords, word, sizeof(word));
+            if (q)
+                std::memcpy(q + blk_i * kTau, Q, sizeof(Q));
+            const int ahead = mi::same_ahead(st.grid);
+            record(mi::same_gap(w, bytes, plan.gap_batches, static_cast<uint32_t>(r), static_cast<uint32_t>(b), &m));
+            int skip = 0;
+            if (w.phase == MI_SAME_BURST && !plan.hold_timing) {
+                const int move = mi::same_retime(w, Q);
+                skip = move == mi::kSameSkip;
+                if (move == mi::kSameReplay)
+                    step(static_cast<uint32_t>(st.hist[15] & 1u), b);
+            }
+            for (int i = 0; i < cnt[15]; ++i) {
+                uint32_t mk[kTau], c[kTau];
+                for (int t = 0; t < kTau; ++t) {
+                    const int j = i - (t < ahead);
+                    if (j >= 0) {
+                        c[t] = word[t][j / 32] >> (j % 32) & 1u;
+                        st.hist[t] = st.hist[t] << 1 | c[t];
+                    } else {
+                        c[t] = static_cast<uint32_t>(st.hist[t] & 1u);
+                    }
+                    mk[t] = mi::same_mismatch(st.hist[t]);
+                }
+                if (w.phase == MI_SAME_BURST) {
+                    if (skip)
+                        skip = 0;
+                    else
+                        step(c[w.u], b);
+                } else if (w.deaf) {
+                    --w.deaf;
+                } else if (const int u = mi::same_pick(mk, Q, plan.sync_errors, plan.min_quality); u >= 0) {
+                    const uint32_t kind = mk[u] >> 8;
+                    record(mi::same_open(w, bytes, u, kind, st.batch + static_cast<uint32_t>(b), r0[u] + MI_SAME_BIT_UNITS * (i - (u < ahead)),
+                                         static_cast<uint32_t>(r), static_cast<uint32_t>(b), &m));
+                    if (kind == MI_SAME_EOM)
+                        record(mi::same_burst_end(w, bytes, 0, static_cast<uint32_t>(r), static_cast<uint32_t>(b), &m));
+                }
+            }
+            const uint32_t next = (st.grid + 80u) % MI_SAME_BIT_UNITS;
+            for (int t = 0; t < mi::same_ahead(next); ++t) {  // the bit that waits for the next batch's first index
+                const int j = cnt[t] - 1;
+                st.hist[t] = st.hist[t] << 1 | (word[t][j / 32] >> (j % 32) & 1u);
+            }
+            st.grid = next;
+        }
+        st.batch += static_cast<uint32_t>(nbatches);
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_SAME_HISTORY, sizeof(st.x));
+    }
+    row_first_message[rows] = k;
+    count[0] = k;
+    count[1] = k < max_messages ? k : static_cast<uint32_t>(max_messages);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::SameRowState));
+    return MI_OK;
+}

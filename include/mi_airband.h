@@ -1608,6 +1608,156 @@ uint32_t mi_acars_crc(const uint8_t* bytes, size_t n);
 /* The printable fields of a record.  Refuses an nbytes outside 13 .. 240. */
 int mi_acars_frame_text(const mi_acars_frame* f, mi_acars_text* out);
 
+/* ---------------- SAME decoder stage: weather-alert headers per row, on the device ----------------
+ * On NFM weather-radio channels an alert is announced in the audio by SAME (Specific Area Message Encoding) bursts: 520.83 bit/s AFSK,
+ * a preamble of 0xAB bytes, then "ZCZC-ORG-EEE-PSSCCC(-PSSCCC..)+TTTT-JJJHHMM-LLLLLLLL-", sent three times about a second apart; behind
+ * the voice message "NNNN" is sent three times.  This stage reads a plane [rows][row_stride] of float32 audio as mi_acars_* does,
+ * needs no flags, and writes one record per received MESSAGE (up to three bursts of one kind, voted).
+ * NOT CHECKED: no off-air SAME has been through the stage.  The format is restated from memory of 47 CFR 11.31 and pinned only to the
+ * modulator of tests/same_model.py.  The 1050 Hz warning tone is mi_aspec_*'s to find; no event-code dictionary.
+ *
+ * Stream model.  As for the ACARS stage: a row's audio is one running sequence over all batches of all calls the row was enabled in;
+ * samples before the handle's first call are 0.
+ * Tones.  A bit lasts 16000 * 6 / 3125 = 30.72 samples; mark (1) is 4 cycles per bit (2083.3 Hz), space (0) 3 cycles (1562.5 Hz).
+ * Bytes go least significant bit first, 8 bits, bit 7 zero, no parity.
+ * Timing grid.  Time is counted in UNITS of 1/25 sample: sample n sits at unit 25 n, a bit is 768 units, a batch 50 000.  Hypotheses
+ * tau = 0 .. 15 lie 48 units apart: bit k of tau covers the units [48 tau + 768 k, + 768), k counted from the row's first sample, and
+ * tau + 16 is tau one bit later exactly.  50 000 = 65 * 768 + 80, so the grid moves 80 units a batch against the batch edge and
+ * repeats every 48 batches; the state carries grid = (50 000 * batches seen) mod 768 itself (a multiple of 16), so a wrapping batch
+ * counter changes nothing.  The bits of a (row, batch) are those whose last sample lies in the batch: with c = (48 tau - grid) mod 768
+ * the first begins at unit r0 = c - 768 of the batch (r0 = 0 where c = 0), the others 768 apart up to unit 49 232: 65 or 66 per
+ * hypothesis, bit j beginning at r = r0 + 768 j.  The earliest sample a batch's bits read is the 30th before it: MI_SAME_HISTORY = 30
+ * carried samples per row, a lead of 32 (carry.hpp).
+ * Bit bank, per (row, batch, tau, j); float32, every operation rounded on its own, no fused multiply-add.  Templates
+ * (mi_same_templates) of 768 entries each, evaluated in double and rounded once: T0 = cos, T1 = sin of 2 pi 4 rho / 768, T2 = cos,
+ * T3 = sin of 2 pi 3 rho / 768.  A bit's samples are n = ceil(r / 25) .. floor((r + 767) / 25), 30 or 31 of them, rho = 25 n - r;
+ * the four sums S0 .. S3 of x[n] * T[rho] run in ascending n, each beginning with its first product.  Pm = S0 * S0 + S1 * S1,
+ * Ps = S2 * S2 + S3 * S3; the bit is 1 if Pm >= space_gain * Ps; q = max(Pm, Ps).  Q[tau] of the block in the ACARS stage's order:
+ * s_l = q_l (+ q_{l + 64} where there is one), l = 0 .. 63; then s_l + s_{l + 32} for l < 32, then + 16, 8, 4, 2, 1; Q is element 0.
+ * Packed: 4 words per (row, batch, tau): bit j in bit j % 32 of word j / 32, the bits of word 2 from the count on zero, and the
+ * count (65 or 66) in word 3.  A block whose 2000 samples and 30 carried samples are all +-0 holds every bit 1 (0 >= space_gain * 0),
+ * its counts, and Q = +0.0f everywhere; the device writes that without the sums.
+ * Sync.  Every hypothesis keeps its last 64 bits, the newest in bit 0 (zeros before the row's first bit).  The patterns are the 64
+ * bits of AB AB AB AB 'Z' 'C' 'Z' 'C' (MI_SAME_HEADER) and of AB AB AB AB 'N' 'N' 'N' 'N' (MI_SAME_EOM); they differ in 10 places, so
+ * with at most 4 mismatches allowed a history hits at most one.  Decisions are taken per bit index k in ascending order over the 16
+ * bits (tau, k).  BOOKKEEPING AT A BATCH EDGE: the bits (tau, k) of one k begin 48 units apart, so a batch edge cuts one k in two:
+ * the hypotheses tau <= grid / 48 (grid of the later batch; none where grid >= 720) have their bit in the earlier batch.  That k is
+ * decided in the LATER batch: the earlier batch shifts those hypotheses' bit into their histories, where it waits, and decides
+ * cnt(15) indices; Q in every decision is Q of the batch that decides.  An IDLE row that is not deaf opens a burst at the first k
+ * where a hypothesis differs from a pattern in at most sync_errors places and Q[tau] >= min_quality; among the hitting hypotheses the
+ * fewest mismatches, then the largest Q, then the lowest tau.  A row is DEAF for the 64 indices behind a burst's end: the next sync
+ * has to arrive whole behind the burst.
+ * Burst.  The record's bytes begin with the pattern's own "ZCZC" / "NNNN".  An NNNN burst ends at once.  Behind ZCZC the chosen
+ * hypothesis u's bits are read 8 to a byte from index k + 1 on.  The burst ends with the third '-' behind the first '+'; as TRUNCATED
+ * at MI_SAME_MAX_BYTES = 268 bytes counted from 'Z'; and as truncated at the max_bad-th consecutive byte with bit 7 set or under
+ * 0x20, those max_bad bytes being dropped.  Timing moves by the ACARS rule at the first index of every batch that begins inside a
+ * burst (unless hold_timing): v = u; if Q[u - 1] > Q[v] then v = u - 1; if Q[u + 1] > Q[v] then v = u + 1 (indices mod 16); u = v.
+ * Moving 15 -> 0 the walker passes over the batch's first index; moving 0 -> 15 it first takes hypothesis 15's newest carried bit.
+ * Message.  A row's assembler keeps the ended bursts of one kind.  The third burst closes the message: nbytes is the median of the
+ * three lengths (the length two of them share, where two do), every byte the bitwise two-of-three majority of the bursts' bytes,
+ * a burst shorter than the place counting as zeros there, truncated the majority of the three flags, voted = 1.  A message also
+ * closes when a burst of the other kind opens, and at the first index of the gap_batches-th batch that begins since the last burst
+ * ended with the row outside a burst: then it is the FIRST burst, voted = 0, nbursts 1 or 2.  agree counts the places below nbytes at
+ * which all nbursts bursts hold the same byte.  fields_ok: an EOM is "NNNN"; a header matches the grammar above with ORG and EEE
+ * three capitals, 1 to 31 locations of six digits, TTTT four digits, JJJHHMM seven digits and a station of eight printable characters
+ * other than '-'.  batch / unit: where the first burst's 'Z' or 'N' begins (the row's batch number since creation / set_state,
+ * wrapping at 2^32, and the unit within it); end_batch: the call's batch that closed the message.
+ * The most messages a row closes in a call of n batches: every close but those of the gap rule belongs to one burst, bursts open at
+ * least 65 indices apart, a batch decides at most 66 indices, so at most B = 2 + 66 n / 65 bursts touch the call and each refills the
+ * assembler once for the gap rule: 2 B + 1 = MI_SAME_MAX_MESSAGES(n).
+ * Settings (mi_same_cfg, 0 = the default): sync_errors 1 .. 4, default 4, MI_SAME_SYNC_EXACT for none; max_bad 1 .. 16, default 4;
+ * gap_batches 1 .. 1000, default 20 (2.5 s); min_quality finite and >= 0, default 0; space_gain finite and > 0, default 1 (DESIGN.md
+ * 5p: the de-emphasis tilt measured behind the demodulator asks for no other); hold_timing 0 / 1.
+ * State: per row MI_SAME_STATE_ROW_BYTES = 1160 bytes, little-endian, a blob of zeros being a fresh state: float32 x[30]; uint32 batch,
+ * grid; uint64 hist[16]; uint32 phase (MI_SAME_IDLE / MI_SAME_BURST), u, kind, nbits, cur, nbytes, nbad, plus, dashes, deaf,
+ * start_batch, start_unit (the burst's); an, akind, alen[2], atrunc[2], aidle, astart_batch, astart_unit (the assembler's), zero;
+ * then bytes[3][272]: the running burst and the assembler's two stored ones, zeros behind their lengths.
+ * A disabled row writes nothing and every byte of its state stays.  NaN and Inf are unspecified.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_SAME_HISTORY = 30, MI_SAME_HYPOTHESES = 16, MI_SAME_BIT_UNITS = 768, MI_SAME_BATCH_UNITS = 50000, MI_SAME_BIT_WORDS = 4, MI_SAME_MAX_BITS = 66,
+       MI_SAME_SYNC_BITS = 64, MI_SAME_MAX_BYTES = 268, MI_SAME_RAW_BYTES = 272, MI_SAME_DEAF = 64, MI_SAME_STATE_ROW_BYTES = 1160 };
+enum { MI_SAME_IDLE = 0, MI_SAME_BURST = 1 };
+enum { MI_SAME_HEADER = 0, MI_SAME_EOM = 1 };
+#define MI_SAME_SYNC_EXACT 0x80000000u /* sync_errors: no mismatch allowed */
+#define MI_SAME_MAX_MESSAGES(nbatches) (2u * (2u + 66u * (nbatches) / 65u) + 1u)
+typedef struct {
+    uint32_t sync_errors;           /* 0 = 4; 1 .. 4; MI_SAME_SYNC_EXACT */
+    uint32_t max_bad;               /* 0 = 4; 1 .. 16 */
+    uint32_t gap_batches;           /* 0 = 20; 1 .. 1000 */
+    float min_quality;              /* floor on Q[tau] of the batch that decides a sync hit */
+    float space_gain;               /* 0 = 1 */
+    uint32_t hold_timing;           /* 1: no timing moves */
+} mi_same_cfg;                      /* 24 bytes */
+typedef struct {
+    uint32_t row;
+    uint32_t kind;                  /* MI_SAME_HEADER / MI_SAME_EOM */
+    uint32_t batch, unit;           /* where the first burst's 'Z' / 'N' begins */
+    uint32_t end_batch;             /* call-relative */
+    uint8_t nbursts, voted, truncated, fields_ok;
+    uint16_t nbytes, agree;
+    uint32_t zero;
+    uint8_t bytes[272];             /* nbytes from 'Z' / 'N' on, then zeros */
+} mi_same_message;                  /* 304 bytes */
+typedef struct {                    /* a header's fields, NUL-terminated */
+    char originator[4], event[4], purge[5], issue[8], station[9], pad[2];
+    uint32_t nlocations;
+    char locations[31][7];
+    char pad2[3];
+} mi_same_text;                     /* 256 bytes */
+typedef struct mi_same mi_same;
+
+/* cfg NULL = every default.  row_enabled, rows and max_batches as for mi_acars_create.  max_messages: capacity of the caller's
+ * message buffer, 0 = rows * MI_SAME_MAX_MESSAGES(max_batches).  The handle owns the scratch for a call's bits, Q and messages; the
+ * messages' part is sized by the bound whatever max_messages says, rows * MI_SAME_MAX_MESSAGES(max_batches) * 304 bytes -- 23 MB at
+ * 2048 rows x 16 batches, 600 bytes per (row, batch) in the limit, so gigabytes near rows * max_batches = 2^24 -- though audio closes
+ * a message every few seconds at most: size max_batches by the calls made, not by the longest imaginable. */
+int mi_same_create(const mi_same_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_messages, int gpu, mi_same** out);
+void mi_same_destroy(mi_same* s);
+int mi_same_set_rows(mi_same* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_bits               [rows][nbatches][16][4]  the packed bits and counts, or NULL (the handle's scratch); 4-byte aligned.
+ *   d_q                  [rows][nbatches][16]     Q, or NULL (the handle's scratch).  A disabled row's are not written.
+ *   d_messages           [max_messages]           rows ascending, time order within a row (8-byte aligned)
+ *   d_row_first_message  [rows + 1]               exclusive prefix of the rows' message counts
+ *   d_count              [2]                      number of messages, and min(that, max_messages) = the number stored
+ * Nothing is written at or beyond max_messages.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without atomics
+ * -- bits (one workgroup per (row, batch)), walk (one wave per row, a lane per hypothesis), scan, store, tails -- so every byte is
+ * the same on every run and equals mi_same_plan_host's. */
+int mi_same_process_device(mi_same* s, const float* d_plane, size_t row_stride, int nbatches, uint32_t* d_bits, float* d_q, mi_same_message* d_messages,
+                           uint32_t* d_row_first_message, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_same_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] messages.  messages and row_first_message may each be NULL.  The one place that synchronises. */
+int mi_same_download(mi_same* s, void* hip_stream, mi_same_message* messages, uint32_t* row_first_message, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_SAME_STATE_ROW_BYTES bytes in the layout above (mi_same_plan_host reads and writes the same bytes).
+ * set_state refuses an impossible state: zero not 0; a grid that is no multiple of 16 below 768; an unknown phase; an idle row with a
+ * burst field or a byte of the running burst set, or deaf beyond 64; inside a burst a kind other than MI_SAME_HEADER, u beyond 15,
+ * nbits beyond 7, cur beyond its nbits bits, nbytes outside 4 .. 267, bytes that do not begin with "ZCZC", nbad / plus / dashes that
+ * the bytes do not give or that would have ended the burst, deaf not 0, start_unit beyond 49 999, an assembler of the other kind;
+ * an assembler with more than 2 bursts, an unknown kind, a length outside 4 .. 268 (an EOM's: not 4), a flag beyond 1, aidle at or
+ * beyond gap_batches, astart_unit beyond 49 999, a field or byte set that its bursts do not use; a byte set behind a burst's length.
+ * Both complete queued work first. */
+size_t mi_same_state_size(const mi_same* s);
+int mi_same_get_state(mi_same* s, void* buf, size_t len);
+int mi_same_set_state(mi_same* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bits, walk, scan, store, tails}.  tools/same_rate.py. */
+int mi_same_set_timing(mi_same* s, int on);
+int mi_same_last_launch_ms(mi_same* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same bits, Q, messages and state blob byte for byte.  plane [rows][row_stride] (no
+ * alignment asked); state_inout rows * MI_SAME_STATE_ROW_BYTES bytes, read and updated; bits [rows][nbatches][16][4] and
+ * q [rows][nbatches][16], each or NULL; messages holds max_messages entries (>= 1), of which min(count[0], max_messages) = count[1]
+ * are written. */
+int mi_same_plan_host(const mi_same_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                      void* state_inout, uint32_t* bits, float* q, mi_same_message* messages, size_t max_messages, uint32_t* row_first_message,
+                      uint32_t* count /* [2] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in, or the refusal mi_same_create would give. */
+int mi_same_settings(const mi_same_cfg* cfg, mi_same_cfg* out);
+/* The four templates T0 .. T3.  Host only. */
+int mi_same_templates(float* out /* [4][768] */);
+/* A header record's fields.  Refuses a record that is no header with fields_ok. */
+int mi_same_message_text(const mi_same_message* m, mi_same_text* out);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
