@@ -307,6 +307,24 @@ class ProbeRule(C.Structure):  # mi_probe_rule: 0 = the default
 PROBE_TARGET_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ProbeTarget._fields_])  # the same 8 bytes as a numpy record
 PROBE_CELL_DTYPE = np.dtype([(n, np.dtype(t)) for n, t in ProbeCell._fields_])  # the same 40 bytes
 
+
+class EltCfg(C.Structure):  # mi_elt_cfg: 0 = the default of every setting
+    _fields_ = [("min_energy", C.c_float), ("min_tonality", C.c_float), ("band_lo", C.c_uint32), ("band_hi", C.c_uint32), ("min_span", C.c_uint32),
+                ("min_len", C.c_uint32), ("max_len", C.c_uint32), ("max_step", C.c_uint32), ("max_drop", C.c_uint32), ("max_gap", C.c_uint32),
+                ("min_sweeps", C.c_uint32), ("zero", C.c_uint32)]
+
+
+ELT_FRAME, ELT_HOP, ELT_HISTORY, ELT_FRAMES, ELT_BINS, ELT_BIN0, ELT_NONE8 = 256, 80, 178, 25, 32, 2, 0xFF  # MI_ELT_*
+ELT_ONSET, ELT_END = 1, 2
+ELT_UP, ELT_DOWN = 1, 2
+# mi_elt_frame_record (16 bytes), mi_elt_event (32 bytes), and one row of the ELT stage's state blob, MI_ELT_STATE_ROW_BYTES = 776
+ELT_FRAME_DTYPE = np.dtype([("best", "u1"), ("bin", "u1"), ("zero", "<u2"), ("energy", "<f4"), ("p_best", "<f4"), ("p3", "<f4")])
+ELT_EVENT_DTYPE = np.dtype([("row", "<u4"), ("seq", "<u4"), ("kind", "u1"), ("dir", "u1"), ("bin_from", "u1"), ("bin_to", "u1"), ("frame", "<u4"),
+                            ("first_frame", "<u4"), ("last_end", "<u4"), ("sweeps", "<u4"), ("batch", "<u4")])
+ELT_STATE_DTYPE = np.dtype([("x", "<f4", (ELT_HISTORY,))] +
+                           [(n, "<u4") for n in ("frame", "seq", "open", "start", "first_bin", "last_bin", "last_frame", "dir", "drops", "count", "chain_dir",
+                                                 "chain_first", "last_end", "alarmed", "bin_from", "bin_to")])
+
 ABI_SYMBOLS = [
     "mi_last_error", "mi_device_count", "mi_demod_create", "mi_demod_destroy", "mi_demod_prepare", "mi_set_cache_dir", "mi_jit_counts", "mi_demod_bytes_needed", "mi_demod_bytes_consumed",
     "mi_demod_hop_bytes", "mi_demod_process", "mi_demod_submit", "mi_demod_wait", "mi_host_alloc", "mi_host_free", "mi_demod_process_device", "mi_demod_set_active_streams", "mi_demod_get_active_streams", "mi_demod_get_stats", "mi_demod_state_size",
@@ -339,6 +357,9 @@ ABI_SYMBOLS = [
     "mi_same_create", "mi_same_destroy", "mi_same_set_rows", "mi_same_process_device", "mi_same_download", "mi_same_state_size",
     "mi_same_get_state", "mi_same_set_state", "mi_same_set_timing", "mi_same_last_launch_ms", "mi_same_plan_host", "mi_same_settings",
     "mi_same_templates", "mi_same_message_text",
+    "mi_elt_create", "mi_elt_destroy", "mi_elt_set_rows", "mi_elt_process_device", "mi_elt_download", "mi_elt_state_size", "mi_elt_get_state",
+    "mi_elt_set_state", "mi_elt_set_timing", "mi_elt_last_launch_ms", "mi_elt_plan_host", "mi_elt_settings", "mi_elt_window", "mi_elt_coeffs",
+    "mi_elt_event_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -530,6 +551,23 @@ def lib():
         L.mi_acars_crc.argtypes = [vp, sz]
         L.mi_acars_crc.restype = C.c_uint32
         L.mi_acars_frame_text.argtypes = [vp, C.POINTER(AcarsText)]
+        L.mi_elt_create.argtypes = [C.POINTER(EltCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_elt_destroy.argtypes = [vp]
+        L.mi_elt_destroy.restype = None
+        L.mi_elt_set_rows.argtypes = [vp, vp]
+        L.mi_elt_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp]
+        L.mi_elt_download.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.mi_elt_state_size.argtypes = [vp]
+        L.mi_elt_state_size.restype = sz
+        L.mi_elt_get_state.argtypes = [vp, vp, sz]
+        L.mi_elt_set_state.argtypes = [vp, vp, sz]
+        L.mi_elt_set_timing.argtypes = [vp, C.c_int]
+        L.mi_elt_last_launch_ms.argtypes = [vp, vp]
+        L.mi_elt_plan_host.argtypes = [C.POINTER(EltCfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp, vp]
+        L.mi_elt_settings.argtypes = [C.POINTER(EltCfg), C.POINTER(EltCfg), C.POINTER(C.c_float)]
+        L.mi_elt_window.argtypes = [vp]
+        L.mi_elt_coeffs.argtypes = [vp]
+        L.mi_elt_event_text.argtypes = [vp, vp]
         L.mi_same_create.argtypes = [C.POINTER(SameCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
         L.mi_same_destroy.argtypes = [vp]
         L.mi_same_destroy.restype = None
@@ -683,7 +721,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails; the SAME stage's bits, walk, scan, store and tails;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails; the SAME stage's bits, walk, scan, store and tails; the ELT stage's bank, walk, scan, store and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -697,7 +735,7 @@ class _PostStage(_TimedStage):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
         .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
-        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE); the ELT stage's rows * 776, .view(ELT_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1660,6 +1698,114 @@ def selcal_plan_host(row_enabled, plane, cfg=None, state=None, max_codes=0, nbat
     _check(lib().mi_selcal_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), None if windows is None else _ptr(windows),
                                      _ptr(codes), cap, _ptr(row_first), _ptr(count)))
     return codes[:int(count[1])], windows, row_first, count, state
+
+
+def elt_cfg(min_energy=0.0, min_tonality=0.0, band_lo=0, band_hi=0, min_span=0, min_len=0, max_len=0, max_step=0, max_drop=0, max_gap=0, min_sweeps=0):
+    """mi_elt_cfg: the settings, 0 = the default; an EltCfg or None (all defaults) passes through"""
+    if isinstance(min_energy, EltCfg):
+        return min_energy
+    c = EltCfg()
+    c.min_energy, c.min_tonality = min_energy or 0.0, min_tonality
+    c.band_lo, c.band_hi, c.min_span, c.min_len, c.max_len = band_lo, band_hi, min_span, min_len, max_len
+    c.max_step, c.max_drop, c.max_gap, c.min_sweeps = max_step, max_drop, max_gap, min_sweeps
+    return c
+
+
+def elt_settings(cfg=None):
+    """mi_elt_settings: (the settings with every default filled in, as an EltCfg; the constant c of the tonality condition)"""
+    out, c = EltCfg(), C.c_float()
+    _check(lib().mi_elt_settings(C.byref(elt_cfg(cfg)), C.byref(out), C.byref(c)))
+    return out, np.float32(c.value)
+
+
+def elt_max_events(nbatches, cfg=None):
+    """the most events one row can emit in a call of nbatches batches"""
+    s = elt_settings(cfg)[0]
+    return 2 * (1 + (ELT_FRAMES * nbatches - 1) // (s.min_sweeps * s.min_len)) + 1
+
+
+def elt_window():
+    """mi_elt_window: the 256 float32 coefficients of the stage's Hann window"""
+    w = np.zeros(ELT_FRAME, np.float32)
+    _check(lib().mi_elt_window(_ptr(w)))
+    return w
+
+
+def elt_coeffs():
+    """mi_elt_coeffs: the 32 float32 recurrence coefficients of bins 2 .. 33"""
+    c = np.zeros(ELT_BINS, np.float32)
+    _check(lib().mi_elt_coeffs(_ptr(c)))
+    return c
+
+
+def elt_event_text(event):
+    """mi_elt_event_text: one printable line from an event record (one element of ELT_EVENT_DTYPE)"""
+    e = np.array(event, dtype=ELT_EVENT_DTYPE).reshape(1)
+    out = np.zeros(96, np.uint8)
+    _check(lib().mi_elt_event_text(_ptr(e), _ptr(out)))
+    return bytes(out).split(b"\0")[0].decode()
+
+
+class Elt(_PostStage):
+    """mi_elt: the ELT detector stage -- per row, whether a distress beacon's swept tone is on it and since when: a Goertzel bank over
+    the bins 2 .. 33 of 256-sample frames at a hop of 80, the decision whether a frame is tonal and on which bin, and a walker over the
+    frames that follows sweeps, chains valid ones and emits one ONSET and one END record per beacon.  It reads a plane of audio as
+    Selcal does and needs no flags.  row_enabled: truth value per row; cfg: elt_cfg(...) or None; max_events: capacity of the event
+    buffer, 0 = rows * elt_max_events(max_batches).  state() gives rows * 776 bytes, whose fields .view(ELT_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_elt_destroy", "mi_elt", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_events=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = elt_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_elt_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_events, gpu, C.byref(self._h)))
+        most = self.rows * elt_max_events(max_batches, self.cfg)
+        self.max_events = min(max_events, most) if max_events else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_elt_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_events, d_row_first_event, d_count, d_frames=None, hip_stream=None):
+        """Raw device pointers (ints; d_frames may be None), the stride in floats; asynchronous on hip_stream."""
+        self._nframes = ELT_FRAMES * nbatches if d_frames is not None else 0
+        _check(lib().mi_elt_process_device(self._h, d_plane, row_stride, nbatches, d_frames, d_events, d_row_first_event, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (events [k] of ELT_EVENT_DTYPE, frames [rows][25 * nbatches] of
+        ELT_FRAME_DTYPE or None where the call stored none, row_first_event [rows + 1], count [2]) with k = count[1]."""
+        events = np.zeros(self.max_events, ELT_EVENT_DTYPE)
+        nf = getattr(self, "_nframes", 0)
+        frames = np.zeros((self.rows, nf), ELT_FRAME_DTYPE) if nf else None
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_elt_download(self._h, hip_stream, _ptr(events), None if frames is None else _ptr(frames), _ptr(row_first), _ptr(count)))
+        return events[:int(count[1])], frames, row_first, count
+
+
+def elt_plan_host(row_enabled, plane, cfg=None, state=None, max_events=0, nbatches=None, want_frames=True):
+    """mi_elt_plan_host: the ELT stage's frame records and events from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 776 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_events: 0 = every event of the call.  Returns (events [count[1]], frames [rows][25 * nbatches] or None, row_first_event
+    [rows + 1], count [2], state after the call)."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = elt_cfg(cfg)
+    state = np.zeros(rows * ELT_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * ELT_STATE_DTYPE.itemsize
+    cap = max_events or max(1, rows * elt_max_events(max(nb, 1), c))
+    events = np.zeros(cap, ELT_EVENT_DTYPE)
+    frames = np.zeros((rows, ELT_FRAMES * max(nb, 0)), ELT_FRAME_DTYPE) if want_frames else None
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_elt_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), None if frames is None else _ptr(frames),
+                                  _ptr(events), cap, _ptr(row_first), _ptr(count)))
+    return events[:int(count[1])], frames, row_first, count, state
 
 
 def acars_cfg(sync_errors=0, keep_bad=False, min_quality=0.0, hold_timing=False):

@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, elt.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -892,6 +892,118 @@ __host__ __device__ inline int same_retime(SameWalker& w, const float* q) {
 int same_plan(const mi_same_cfg* cfg, SamePlan* out);
 void same_templates(float* T);
 const char* same_state_ok(const SameRowState* state, size_t rows, const SamePlan& plan);
+
+// The ELT detector stage (include/mi_airband.h "ELT detector stage").  One row of its state: the checkpoint blob is an array of these,
+// and elt.hip keeps the same array in device memory.
+struct EltRowState {
+    float x[MI_ELT_HISTORY];  // the last 178 input samples of the row's last batch, oldest first (the two oldest are never read)
+    uint32_t frame;           // frames seen since creation / set_state
+    uint32_t seq;             // events emitted
+    uint32_t open, start, first_bin, last_bin, last_frame, dir, drops;       // the segment
+    uint32_t count, chain_dir, chain_first, last_end, alarmed, bin_from, bin_to;  // the chain
+};
+static_assert(sizeof(EltRowState) == MI_ELT_STATE_ROW_BYTES && offsetof(EltRowState, frame) == MI_ELT_HISTORY * 4 && sizeof(mi_elt_frame_record) == 16 &&
+                  sizeof(mi_elt_event) == 32 && sizeof(mi_elt_cfg) == 48 && (MI_ELT_HISTORY + 2) % 4 == 0 &&
+                  MI_ELT_HISTORY >= MI_ELT_FRAME - MI_ELT_HOP && MI_ELT_FRAMES * MI_ELT_HOP == kWaveBatch && MI_ELT_STATE_ROW_BYTES % 8 == 0 &&
+                  MI_ELT_BIN0 + MI_ELT_BINS - 1 < MI_ELT_FRAME / 2,
+              "the ELT stage's blob, record and settings layouts are ABI");
+// The settings with every default filled in and what follows from them, as both halves take them.
+struct EltPlan {
+    float min_energy, tc;  // tc = min_tonality * c
+    uint32_t band_lo, band_hi, min_span, min_len, max_len, max_step, max_drop, max_gap, min_sweeps;
+    float coeff[MI_ELT_BINS];
+    mi_elt_cfg filled;  // the settings as the caller would have written them
+    float c;
+};
+// What the walker is told of the settings.
+struct EltRules {
+    uint32_t min_span, min_len, max_len, max_step, max_drop, max_gap, min_sweeps;
+};
+// The walker's part of a row's state, as the walk carries it in registers.
+struct EltWalker {
+    uint32_t open, start, first_bin, last_bin, last_frame, dir, drops, count, chain_dir, chain_first, last_end, alarmed, bin_from, bin_to;
+};
+// One frame through the walker of the header: b is the frame's decision (MI_ELT_NONE8: none), f its number.  emit(kind) is called for
+// every record the frame emits, in order, while w holds what the record takes.  Host and device run this text.
+template <class Emit>
+__host__ __device__ inline void elt_step(EltWalker& w, const EltRules& r, const uint32_t b, const uint32_t f, Emit&& emit) {
+    bool close = false, reopen = false;
+    if (b != MI_ELT_NONE8) {
+        if (!w.open) {
+            reopen = true;
+        } else {
+            const uint32_t up = b > w.last_bin ? b - w.last_bin : 0u, down = w.last_bin > b ? w.last_bin - b : 0u;
+            const uint32_t sd = up ? MI_ELT_UP : down ? MI_ELT_DOWN : 0u;
+            if (up + down <= r.max_step * (1u + w.drops) && (sd == 0u || w.dir == 0u || sd == w.dir)) {
+                if (w.dir == 0u)
+                    w.dir = sd;
+                w.last_bin = b;
+                w.last_frame = f;
+                w.drops = 0u;
+            } else {
+                close = reopen = true;
+            }
+        }
+    } else if (w.open) {
+        close = ++w.drops > r.max_drop;
+    }
+    if (close) {
+        const uint32_t len = w.last_frame - w.start + 1u;
+        const uint32_t span = w.first_bin > w.last_bin ? w.first_bin - w.last_bin : w.last_bin - w.first_bin;
+        if (w.dir != 0u && span >= r.min_span && len >= r.min_len && len <= r.max_len) {
+            if (w.count > 0u && w.start - w.last_end <= r.max_gap && w.dir == w.chain_dir) {
+                ++w.count;
+            } else {
+                if (w.alarmed) {  // a chain begins while an alarmed one stands: that one ends here
+                    emit(MI_ELT_END);
+                    w.alarmed = 0u;
+                }
+                w.count = 1u;
+                w.chain_first = w.start;
+                w.chain_dir = w.dir;
+            }
+            w.last_end = w.last_frame;
+            w.bin_from = w.first_bin;
+            w.bin_to = w.last_bin;
+            if (!w.alarmed && w.count >= r.min_sweeps) {
+                w.alarmed = 1u;
+                emit(MI_ELT_ONSET);
+            }
+        }
+        w.open = w.start = w.first_bin = w.last_bin = w.last_frame = w.dir = w.drops = 0u;
+    }
+    if (reopen) {
+        w.open = 1u;
+        w.start = w.last_frame = f;
+        w.first_bin = w.last_bin = b;
+        w.dir = w.drops = 0u;
+    }
+    if (w.count > 0u) {
+        const bool alive = f - w.last_end <= r.max_gap || (w.open && w.start - w.last_end <= r.max_gap && f - w.start + 1u <= r.max_len);
+        if (!alive) {
+            if (w.alarmed)
+                emit(MI_ELT_END);
+            w.count = w.chain_dir = w.chain_first = w.last_end = w.alarmed = w.bin_from = w.bin_to = 0u;
+        }
+    }
+}
+// an event record's words as both halves write them: {row, seq, kind | dir << 8 | bin_from << 16 | bin_to << 24, frame}, {first_frame,
+// last_end, sweeps, batch}
+__host__ __device__ inline uint32_t elt_event_word2(const EltWalker& w, const uint32_t kind) {
+    return kind | w.chain_dir << 8 | w.bin_from << 16 | w.bin_to << 24;
+}
+// the most events one row can emit in a call (the header has the argument)
+inline uint32_t elt_max_events(uint32_t min_sweeps, uint32_t min_len, uint64_t nbatches) {
+    return static_cast<uint32_t>(2 * (1 + (MI_ELT_FRAMES * nbatches - 1) / (static_cast<uint64_t>(min_sweeps) * min_len)) + 1);
+}
+// What both halves of the ELT stage share (poststage_host.cpp).  elt_plan: MI_OK with the plan, or the settings' refusal with its
+// message set.  elt_window: w[256].  elt_state_ok: NULL, or what is impossible about a blob's walker state.
+int elt_plan(const mi_elt_cfg* cfg, EltPlan* out);
+void elt_window(float* w);
+const char* elt_state_ok(const EltRowState* state, size_t rows, const EltPlan& plan);
+inline EltRules elt_rules(const EltPlan& p) {
+    return EltRules{p.min_span, p.min_len, p.max_len, p.max_step, p.max_drop, p.max_gap, p.min_sweeps};
+}
 
 // The device configuration as the plan sees it (poststage_host.cpp): window, twiddles, level table, hop.  The band survey, the channel
 // finder and the channel probe have no channels; the plan is built for one at the centre frequency and only its device-wide part is

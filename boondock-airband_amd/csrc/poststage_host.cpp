@@ -9,6 +9,7 @@
 // with its settings and window; and the SELCAL decoder stage's twin mi_selcal_plan_host with its tables, settings, window and code text.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include "poststage.hpp"
@@ -2220,5 +2221,265 @@ extern "C" int mi_same_plan_host(const mi_same_cfg* cfg, const uint8_t* row_enab
     count[0] = k;
     count[1] = k < max_messages ? k : static_cast<uint32_t>(max_messages);
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::SameRowState));
+    return MI_OK;
+}
+
+// ---- ELT detector stage, host side (include/mi_airband.h "ELT detector stage"): the settings' check, the window, the coefficients,
+// the blob's check, an event's text, and the twin of elt.hip -- one row and one frame at a time, the 32 recurrences side by side, then
+// the walker over the row's frames.  The walker's step is poststage.hpp's.
+namespace mi {
+
+void elt_window(float* w) {
+    const double pi = 3.14159265358979323846;
+    for (int j = 0; j < MI_ELT_FRAME / 2; ++j)
+        w[j] = w[MI_ELT_FRAME - 1 - j] = static_cast<float>(0.5 - 0.5 * std::cos(2.0 * pi * j / (MI_ELT_FRAME - 1)));
+}
+
+int elt_plan(const mi_elt_cfg* cfg, EltPlan* out) {
+    mi_elt_cfg c{};
+    if (cfg)
+        c = *cfg;
+    c.min_energy = c.min_energy == 0.0f ? 1e-4f : c.min_energy;
+    c.min_tonality = c.min_tonality == 0.0f ? 0.5f : c.min_tonality;
+    c.band_lo = c.band_lo ? c.band_lo : 4;
+    c.band_hi = c.band_hi ? c.band_hi : (c.band_lo > 26 ? c.band_lo : 26);
+    c.min_span = c.min_span ? c.min_span : 10;
+    c.min_len = c.min_len ? c.min_len : 40;
+    c.max_len = c.max_len ? c.max_len : (c.min_len > 120 ? c.min_len : 120);
+    c.max_step = c.max_step ? c.max_step : 3;
+    c.max_drop = c.max_drop ? c.max_drop : 2;
+    c.max_gap = c.max_gap ? c.max_gap : 10;
+    c.min_sweeps = c.min_sweeps ? c.min_sweeps : 6;
+    const uint32_t top = MI_ELT_BIN0 + MI_ELT_BINS - 1;
+    if (!in_range(c.min_energy, 1e-12f, 1e6f))
+        return fail(MI_ERR_INVALID, "ELT stage: min_energy must be finite and within 1e-12 .. 1e6 (0 = the default)");
+    if (!in_range(c.min_tonality, 0.01f, 1.5f))
+        return fail(MI_ERR_INVALID, "ELT stage: min_tonality must be within 0.01 .. 1.5 (0 = the default)");
+    if (c.band_lo < MI_ELT_BIN0 || c.band_lo > top)
+        return fail(MI_ERR_INVALID, "ELT stage: band_lo must be within 2 .. 33 bins (0 = the default)");
+    if (c.band_hi < c.band_lo || c.band_hi > top)
+        return fail(MI_ERR_INVALID, "ELT stage: band_hi must be within band_lo .. 33 bins (0 = the default)");
+    if (c.min_span < 1 || c.min_span > MI_ELT_BINS - 1)
+        return fail(MI_ERR_INVALID, "ELT stage: min_span must be within 1 .. 31 bins (0 = the default)");
+    if (c.min_len < 2 || c.min_len > 4096)
+        return fail(MI_ERR_INVALID, "ELT stage: min_len must be within 2 .. 4096 frames (0 = the default)");
+    if (c.max_len < c.min_len || c.max_len > 65536)
+        return fail(MI_ERR_INVALID, "ELT stage: max_len must be within min_len .. 65536 frames (0 = the default)");
+    if (c.max_step < 1 || c.max_step > MI_ELT_BINS - 1)
+        return fail(MI_ERR_INVALID, "ELT stage: max_step must be within 1 .. 31 bins (0 = the default)");
+    if (c.max_drop < 1 || c.max_drop > 64)
+        return fail(MI_ERR_INVALID, "ELT stage: max_drop must be within 1 .. 64 frames (0 = the default)");
+    if (c.max_gap < 1 || c.max_gap > 1024)
+        return fail(MI_ERR_INVALID, "ELT stage: max_gap must be within 1 .. 1024 frames (0 = the default)");
+    if (c.min_sweeps < 1 || c.min_sweeps > 1024)
+        return fail(MI_ERR_INVALID, "ELT stage: min_sweeps must be within 1 .. 1024 sweeps (0 = the default)");
+    if (c.zero)
+        return fail(MI_ERR_INVALID, "ELT stage: the settings' zero field must be 0");
+    EltPlan p{};
+    float w[MI_ELT_FRAME];
+    elt_window(w);
+    double sw = 0.0, sw2 = 0.0;
+    for (int j = 0; j < MI_ELT_FRAME; ++j) {
+        sw += static_cast<double>(w[j]);
+        sw2 += static_cast<double>(w[j]) * static_cast<double>(w[j]);
+    }
+    p.c = static_cast<float>(sw * sw / (2.0 * sw2));
+    const double pi = 3.14159265358979323846;
+    for (int t = 0; t < MI_ELT_BINS; ++t)
+        p.coeff[t] = static_cast<float>(2.0 * std::cos(2.0 * pi * (t + MI_ELT_BIN0) / MI_ELT_FRAME));
+    p.min_energy = c.min_energy;
+    p.tc = c.min_tonality * p.c;
+    p.band_lo = c.band_lo, p.band_hi = c.band_hi, p.min_span = c.min_span, p.min_len = c.min_len, p.max_len = c.max_len;
+    p.max_step = c.max_step, p.max_drop = c.max_drop, p.max_gap = c.max_gap, p.min_sweeps = c.min_sweeps;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+const char* elt_state_ok(const EltRowState* state, size_t rows, const EltPlan& plan) {
+    const auto bin_ok = [](uint32_t b) { return b >= MI_ELT_BIN0 && b < MI_ELT_BIN0 + MI_ELT_BINS; };
+    const auto dir_of = [](uint32_t from, uint32_t to) { return to > from ? MI_ELT_UP : to < from ? MI_ELT_DOWN : 0; };
+    for (size_t r = 0; r < rows; ++r) {
+        const EltRowState& s = state[r];
+        const uint32_t f = s.frame - 1u;  // the last frame the walker saw
+        if (s.open > 1u || s.alarmed > 1u)
+            return "open or alarmed beyond 1";
+        if (!s.open) {
+            if (s.start || s.first_bin || s.last_bin || s.last_frame || s.dir || s.drops)
+                return "a closed segment with a field set";
+        } else {
+            if (!bin_ok(s.first_bin) || !bin_ok(s.last_bin))
+                return "a segment's bin outside 2 .. 33";
+            if (s.dir > MI_ELT_DOWN || s.dir != static_cast<uint32_t>(dir_of(s.first_bin, s.last_bin)))
+                return "a segment's dir that its bins contradict";
+            if (s.drops > plan.max_drop || f - s.last_frame != s.drops)
+                return "drops over max_drop, or not the frames since last_frame";
+            if (s.last_frame - s.start >= 0x80000000u)
+                return "a segment of 2^31 frames or more";
+        }
+        if (!s.count) {
+            if (s.chain_dir || s.chain_first || s.last_end || s.alarmed || s.bin_from || s.bin_to)
+                return "a cleared chain with a field set";
+        } else {
+            if (!bin_ok(s.bin_from) || !bin_ok(s.bin_to))
+                return "a chain's bin outside 2 .. 33";
+            if (s.chain_dir < MI_ELT_UP || s.chain_dir > MI_ELT_DOWN || s.chain_dir != static_cast<uint32_t>(dir_of(s.bin_from, s.bin_to)))
+                return "a chain's chain_dir that its bins contradict";
+            if ((s.bin_from > s.bin_to ? s.bin_from - s.bin_to : s.bin_to - s.bin_from) < plan.min_span)
+                return "a chain whose last sweep spans less than min_span";
+            if (s.alarmed != (s.count >= plan.min_sweeps ? 1u : 0u))
+                return "alarmed is not (count >= min_sweeps)";
+            if (s.last_end - s.chain_first >= 0x80000000u || f - s.last_end >= 0x80000000u || (s.open && s.start - s.last_end - 1u >= 0x7FFFFFFFu))
+                return "a chain whose frames are out of order";
+            const bool alive = f - s.last_end <= plan.max_gap || (s.open && s.start - s.last_end <= plan.max_gap && f - s.start + 1u <= plan.max_len);
+            if (!alive)
+                return "a chain that would have expired";
+        }
+    }
+    return nullptr;
+}
+
+namespace {
+
+// items 0 .. 4 of the header over the 256 samples at x
+mi_elt_frame_record elt_frame_record(const float* x, const float* w, const EltPlan& plan) {
+    float y[MI_ELT_FRAME], s[64], p[MI_ELT_BINS], q1[MI_ELT_BINS], q2[MI_ELT_BINS];
+    for (int j = 0; j < MI_ELT_FRAME; ++j)
+        y[j] = x[j] * w[j];
+    for (int l = 0; l < 64; ++l) {
+        s[l] = y[l] * y[l];
+        for (int j = l + 64; j < MI_ELT_FRAME; j += 64)
+            s[l] = s[l] + y[j] * y[j];
+    }
+    for (int h = 32; h >= 1; h /= 2)
+        for (int l = 0; l < h; ++l)
+            s[l] = s[l] + s[l + h];
+    const float E = s[0];
+    for (int t = 0; t < MI_ELT_BINS; ++t)
+        p[t] = q1[t] = q2[t] = 0.0f;
+    if (E != 0.0f) {  // (a silent frame: the powers are zero by definition)
+        for (int j = 0; j < MI_ELT_FRAME; ++j)
+            for (int t = 0; t < MI_ELT_BINS; ++t) {
+                const float q0 = plan.coeff[t] * q1[t] - q2[t] + y[j];
+                q2[t] = q1[t];
+                q1[t] = q0;
+            }
+        for (int t = 0; t < MI_ELT_BINS; ++t)
+            p[t] = q1[t] * q1[t] + q2[t] * q2[t] - q1[t] * q2[t] * plan.coeff[t];
+    }
+    int best = 0;
+    for (int t = 1; t < MI_ELT_BINS; ++t)
+        if (p[t] > p[best])
+            best = t;
+    const float below = best > 0 ? p[best - 1] : 0.0f, above = best < MI_ELT_BINS - 1 ? p[best + 1] : 0.0f;
+    const float p3 = below + p[best] + above;
+    const uint32_t bin = static_cast<uint32_t>(best) + MI_ELT_BIN0;
+    const bool tonal = E >= plan.min_energy && p3 >= plan.tc * E && bin >= plan.band_lo && bin <= plan.band_hi;
+    return mi_elt_frame_record{static_cast<uint8_t>(bin), static_cast<uint8_t>(tonal ? bin : MI_ELT_NONE8), 0, E, p[best], p3};
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" int mi_elt_settings(const mi_elt_cfg* cfg, mi_elt_cfg* out, float* c) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::EltPlan p;
+    if (const int rc = mi::elt_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    if (c)
+        *c = p.c;
+    return MI_OK;
+}
+
+extern "C" int mi_elt_window(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::elt_window(out);
+    return MI_OK;
+}
+
+extern "C" int mi_elt_coeffs(float* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::EltPlan p;
+    if (const int rc = mi::elt_plan(nullptr, &p))
+        return rc;
+    std::memcpy(out, p.coeff, sizeof(p.coeff));
+    return MI_OK;
+}
+
+extern "C" int mi_elt_event_text(const mi_elt_event* e, char* out) {
+    if (!e || !out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    const auto bin_ok = [](uint32_t b) { return b >= MI_ELT_BIN0 && b < MI_ELT_BIN0 + MI_ELT_BINS; };
+    if ((e->kind != MI_ELT_ONSET && e->kind != MI_ELT_END) || (e->dir != MI_ELT_UP && e->dir != MI_ELT_DOWN) || !bin_ok(e->bin_from) || !bin_ok(e->bin_to))
+        return fail(MI_ERR_INVALID, "ELT stage: not an event record the stage writes (kind, dir or a bin out of range)");
+    std::snprintf(out, 96, "%s %s %.1f -> %.1f Hz, %u sweeps, %.3f s", e->kind == MI_ELT_ONSET ? "ONSET" : "END", e->dir == MI_ELT_UP ? "up" : "down",
+                  62.5 * e->bin_from, 62.5 * e->bin_to, e->sweeps, 0.005 * static_cast<double>(e->frame - e->first_frame));
+    return MI_OK;
+}
+
+extern "C" int mi_elt_plan_host(const mi_elt_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                void* state_inout, mi_elt_frame_record* frames, mi_elt_event* events, size_t max_events, uint32_t* row_first_event,
+                                uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !events || !row_first_event || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_events < 1)
+        return fail(MI_ERR_INVALID, "ELT plan needs rows >= 1, nbatches >= 1 and max_events >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::EltPlan plan;
+    if (const int rc = mi::elt_plan(cfg, &plan))
+        return rc;
+    if (static_cast<uint64_t>(rows) * mi::elt_max_events(plan.min_sweeps, plan.min_len, static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "ELT plan: the events of the call do not fit the 32-bit count");
+    std::vector<mi::EltRowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::EltRowState));
+    if (const char* const why = mi::elt_state_ok(blob.data(), blob.size(), plan))
+        return fail(MI_ERR_INVALID, std::string("ELT plan: malformed state blob: ") + why);
+    constexpr int kBack = MI_ELT_FRAME - MI_ELT_HOP;  // 176: the samples of a batch's first frame that lie before the batch
+    std::vector<float> x(kBack + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    float w[MI_ELT_FRAME];
+    mi::elt_window(w);
+    const mi::EltRules rules = mi::elt_rules(plan);
+    const uint32_t nframes = MI_ELT_FRAMES * static_cast<uint32_t>(nbatches);
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first_event[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::EltRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        // x = the last 176 carried samples, then the call's
+        std::memcpy(x.data(), st.x + (MI_ELT_HISTORY - kBack), kBack * sizeof(float));
+        std::memcpy(x.data() + kBack, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::EltWalker wk{st.open, st.start, st.first_bin, st.last_bin, st.last_frame, st.dir, st.drops, st.count, st.chain_dir, st.chain_first, st.last_end,
+                         st.alarmed, st.bin_from, st.bin_to};
+        for (uint32_t i = 0; i < nframes; ++i) {
+            const mi_elt_frame_record rec = mi::elt_frame_record(x.data() + static_cast<size_t>(i) * MI_ELT_HOP, w, plan);
+            if (frames)
+                frames[static_cast<size_t>(r) * nframes + i] = rec;
+            const uint32_t f = st.frame + i;
+            mi::elt_step(wk, rules, rec.bin, f, [&](uint32_t kind) {
+                if (k < max_events)
+                    events[k] = mi_elt_event{static_cast<uint32_t>(r), st.seq, static_cast<uint8_t>(kind), static_cast<uint8_t>(wk.chain_dir),
+                                             static_cast<uint8_t>(wk.bin_from), static_cast<uint8_t>(wk.bin_to), f, wk.chain_first, wk.last_end, wk.count,
+                                             i / MI_ELT_FRAMES};
+                ++k;
+                st.seq += 1;
+            });
+        }
+        st.frame += nframes;
+        st.open = wk.open, st.start = wk.start, st.first_bin = wk.first_bin, st.last_bin = wk.last_bin, st.last_frame = wk.last_frame, st.dir = wk.dir;
+        st.drops = wk.drops, st.count = wk.count, st.chain_dir = wk.chain_dir, st.chain_first = wk.chain_first, st.last_end = wk.last_end;
+        st.alarmed = wk.alarmed, st.bin_from = wk.bin_from, st.bin_to = wk.bin_to;
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_ELT_HISTORY, MI_ELT_HISTORY * sizeof(float));
+    }
+    row_first_event[rows] = k;
+    count[0] = k;
+    count[1] = k < max_events ? k : static_cast<uint32_t>(max_events);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::EltRowState));
     return MI_OK;
 }

@@ -1758,6 +1758,182 @@ int mi_same_templates(float* out /* [4][768] */);
 /* A header record's fields.  Refuses a record that is no header with fields_ok. */
 int mi_same_message_text(const mi_same_message* m, mi_same_text* out);
 
+/* ---------------- ELT detector stage: swept-tone beacon alarms per row, on the device ----------------
+ * The homing signal of a distress beacon (ELT / EPIRB / PLB) on 121.5 MHz is an AM carrier whose audio tone sweeps through at least
+ * 700 Hz somewhere inside 300 .. 1600 Hz, normally downward, and repeats 2 to 4 times a second for minutes or hours.  The reference
+ * leaves the wail in the recording; mi_tones_* and mi_selcal_* want steady tones and mi_aspec_* averages 125 ms, which smears a whole
+ * sweep.  This stage answers "which row carries a beacon, and since when?": one ONSET record when a beacon starts, one END record
+ * when it ends.  It reads a plane [rows][row_stride] of float32 audio as mi_selcal_* does and needs no flags.
+ * NOT CHECKED: the signal description above is written from memory of the ELT specifications (TSO-C91a class); no document available
+ * when this was written could confirm it, and no off-air beacon has been through the stage.  Everything is tried on synthetic
+ * signals only (tests/elt_model.py, tools/elt_classes.py).
+ *
+ * Stream model.  As for the SELCAL stage: a row's audio is one running sequence x over all batches of all calls the row was enabled
+ * in; samples before the handle's first call are 0.  A disabled row writes nothing and every byte of its state stays.  NaN and Inf
+ * are unspecified, as everywhere behind the demodulator.
+ * Frames are MI_ELT_FRAME = 256 samples at a hop of MI_ELT_HOP = 80: exactly 25 per (row, batch), numbered per row from creation /
+ * set_state, modulo 2^32.  Frame g = 0 .. 24 of a batch covers the batch's samples 80 g - 176 .. 80 g + 79 (negative: the samples
+ * before the batch).  The handle carries MI_ELT_HISTORY = 178 samples per row, of which the two oldest are never read: the lead in
+ * front of a block (carry.hpp) is history + 2 = 180 floats and must be whole float4.  The history length is ABI.
+ * Per frame, everything float32, every operation rounded on its own, no fused multiply-add:
+ *   0. y[j] = x[j] * w[j], j = 0 .. 255.  w (mi_elt_window) is the 256-point Hann window 0.5 - 0.5 cos(2 pi j / 255), evaluated in
+ *      float64 for j <= 127 and cast; w[255 - j] = w[j], so that w is symmetric bit for bit.
+ *   1. E, the frame's energy: s_l = the sequential sum, j ascending over j = l (mod 64), of y[j] * y[j], starting from the first
+ *      product, for l = 0 .. 63 (four terms each); then the butterfly s_l + s_{l+32} for l < 32, then + 16, 8, 4, 2, 1 in the same
+ *      way; E is element 0.  If E == 0.0f the frame is SILENT: every power is +0.0f BY DEFINITION (so best = 2 and p3 = +0.0f) and
+ *      the recurrence of item 2 is not part of its definition, for the reasons the SELCAL stage gives.
+ *   2. A bank of 32 detectors on the exact bins k = 2 .. 33 of the 256-point transform (62.5 Hz apart, 125 .. 2062.5 Hz):
+ *      coeff[k] = (float)(2 cos(2 pi k / 256)) (mi_elt_coeffs).  q1 = q2 = 0; for j = 0 .. 255 in order: q0 = coeff * q1 - q2 + y[j];
+ *      q2 = q1; q1 = q0 (a product, a subtraction, an addition).  p[k] = ((q1 * q1) + (q2 * q2)) - ((q1 * q2) * coeff).
+ *   3. best = the bin of the largest p, a tie going to the lowest bin.  p3 = (p[best - 1] + p[best]) + p[best + 1], a neighbour
+ *      outside 2 .. 33 counting as +0.0f.
+ *   4. The frame is TONAL with bin `best` iff all three hold, and has no bin (MI_ELT_NONE8) otherwise:
+ *        E >= min_energy
+ *        p3 >= tc * E                               tc = min_tonality * c, one float32 product made on the host
+ *        band_lo <= best <= band_hi
+ *      c = (float)((sum w)^2 / (2 sum w^2)), the sums in float64 over the float32 window: what one pure tone on a bin gives for
+ *      p[best] / E, about 256 / 3 = 85.
+ * Settings (mi_elt_cfg, 0 = the default; refused with MI_ERR_INVALID and "ELT stage: <setting> must be ..." outside the bounds):
+ *   min_energy    1e-4   frame energy; finite and within 1e-12 .. 1e6
+ *   min_tonality  0.5    fraction of c; within 0.01 .. 1.5
+ *   band_lo       4      bins; within 2 .. 33
+ *   band_hi       26     bins; within band_lo .. 33 (the default is band_lo where that is above 26)
+ *   min_span      10     bins between a sweep's first and last bin; within 1 .. 31
+ *   min_len       40     frames; within 2 .. 4096
+ *   max_len       120    frames; within min_len .. 65536 (the default is min_len where that is above 120)
+ *   max_step      3      bins between consecutive tonal frames; within 1 .. 31
+ *   max_drop      2      frames without a bin inside a sweep; within 1 .. 64
+ *   max_gap       10     frames between sweeps; within 1 .. 1024
+ *   min_sweeps    6      sweeps before the alarm; within 1 .. 1024
+ *   zero                 must be 0
+ * They are a caller's settings, not tolerances, fixed from tools/elt_classes.py.
+ *
+ * Walker.  Per row, sequentially over the row's frames in order, its state carried in the handle.  A SEGMENT is a run of frames
+ * that follows one sweep: start, first_bin, last_bin, last_frame (its last tonal frame), dir (0 until the first non-zero step, then
+ * MI_ELT_UP or MI_ELT_DOWN) and drops.  A CHAIN is a run of valid sweeps: count, chain_dir, chain_first (the start of its first
+ * sweep), last_end, alarmed, and bin_from / bin_to, the first and last bin of its last valid sweep.  At frame f with decision b, in
+ * this order:
+ *   1. b is a bin, no segment open: open one at f with first_bin = last_bin = b, last_frame = f, dir = 0, drops = 0.
+ *   2. b is a bin, a segment open: step = b - last_bin.  The step is FOLLOWING iff |step| <= max_step * (1 + drops) and (step is 0, or
+ *      dir is 0, or step has dir's sign).  A following step sets dir (if it was 0 and step != 0), last_bin = b, last_frame = f and
+ *      drops = 0.  Any other step CLOSES the segment (4) and then opens a new one at f with b: what a beacon's retrace does.
+ *   3. b is none, a segment open: drops++; if drops > max_drop, close it (4).  No segment is open afterwards.
+ *   4. Closing.  The segment is a VALID SWEEP iff dir != 0, |first_bin - last_bin| >= min_span and min_len <= last_frame - start + 1
+ *      <= max_len.  A valid sweep continues the chain (count++) iff count > 0, start - last_end <= max_gap and dir == chain_dir;
+ *      otherwise it begins one: count = 1, chain_first = start, chain_dir = dir.  Either way last_end = last_frame, bin_from =
+ *      first_bin, bin_to = last_bin.  When count reaches min_sweeps and the chain is not alarmed, alarmed = 1 and an ONSET record is
+ *      emitted.  A segment that is not valid changes nothing in the chain.
+ *   5. Expiry, judged last at every frame with count > 0.  The chain is ALIVE iff f - last_end <= max_gap, or a segment is open
+ *      with start - last_end <= max_gap and f - start + 1 <= max_len.  Otherwise it expires: if alarmed, an END record is emitted;
+ *      then the chain is cleared (count = 0, alarmed = 0, every chain field 0).
+ * Decided where the rules above leave a choice, with tests/elt_model.py the tie-breaker:
+ *   - A valid sweep that BEGINS a chain while an alarmed one stands (its direction differs: a beacon that flips) first emits the END
+ *     record of the standing chain, with that chain's fields, and clears the alarm; the new chain raises its own ONSET when it has
+ *     min_sweeps sweeps.  So alarmed == (count >= min_sweeps) always, and a row's records alternate ONSET, END, ONSET, ...
+ *   - A chain that begins in the frame that expires another: the closing of item 4 comes first, so the close has already ended the
+ *     old chain as above; item 5 then judges the new chain, which expires at once (silently: it is not alarmed unless min_sweeps is
+ *     1) only where max_drop + 1 > max_gap.
+ *   - Frame numbers, seq and every difference of frame numbers are uint32, modulo 2^32: a wrap inside a sweep or a chain changes
+ *     nothing.  A segment that stays open for 2^31 frames or more (an unbroken tone for four months) has its length taken modulo
+ *     2^32; set_state refuses such a state.
+ *   - A consequence of item 5: a sweep of exactly max_len frames keeps its chain alive only where the retrace follows at once; one
+ *     frame without a bin later f - start + 1 is over max_len while the segment is still open, and the chain expires.
+ *   - Closed or cleared fields are 0 in the state, so one stream has one blob.  max_drop = 0 cannot be asked for (0 = the default).
+ * An event record holds row, seq (the row's event number since creation / set_state), kind (MI_ELT_ONSET / MI_ELT_END), dir
+ * (chain_dir), bin_from and bin_to (of the chain's last valid sweep), frame (the row's number of the frame that emitted it),
+ * first_frame (chain_first), last_end, sweeps (count as it stood; for an ONSET min_sweeps) and batch, the call-relative batch of the
+ * emitting frame.  A frame can emit up to three records (END, ONSET, END: only with min_sweeps = 1); they keep that order.
+ * State: per row MI_ELT_STATE_ROW_BYTES = 776 bytes, little-endian: float32 x[178], the last 178 input samples of the last batch of
+ * the last call the row was enabled in, oldest first, zeros at first; then uint32 frame (frames seen), seq (events emitted), open
+ * (0 / 1), start, first_bin, last_bin, last_frame, dir, drops, count, chain_dir, chain_first, last_end, alarmed, bin_from, bin_to.  A
+ * blob of zeros is a fresh state; there is no padding.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_ELT_FRAME = 256, MI_ELT_HOP = 80, MI_ELT_HISTORY = 178, MI_ELT_FRAMES = 25, MI_ELT_BINS = 32, MI_ELT_BIN0 = 2, MI_ELT_STATE_ROW_BYTES = 776,
+       MI_ELT_NONE8 = 0xFF };
+enum { MI_ELT_ONSET = 1, MI_ELT_END = 2 };
+enum { MI_ELT_UP = 1, MI_ELT_DOWN = 2 };
+typedef struct {
+    float min_energy, min_tonality;                 /* 0 = the default */
+    uint32_t band_lo, band_hi, min_span;            /* bins; 0 = the default */
+    uint32_t min_len, max_len;                      /* frames; 0 = the default */
+    uint32_t max_step, max_drop, max_gap, min_sweeps; /* 0 = the default */
+    uint32_t zero;
+} mi_elt_cfg;                       /* 48 bytes */
+typedef struct {
+    uint8_t best;                   /* the bin of the largest power, 2 .. 33 */
+    uint8_t bin;                    /* the decision: best, or MI_ELT_NONE8 */
+    uint16_t zero;
+    float energy;                   /* E */
+    float p_best, p3;
+} mi_elt_frame_record;              /* 16 bytes */
+typedef struct {
+    uint32_t row, seq;              /* seq: the row's event number since creation / set_state, 0-based */
+    uint8_t kind, dir;              /* MI_ELT_ONSET / MI_ELT_END; MI_ELT_UP / MI_ELT_DOWN */
+    uint8_t bin_from, bin_to;       /* first and last bin of the chain's last valid sweep */
+    uint32_t frame;                 /* the row's number of the emitting frame */
+    uint32_t first_frame, last_end; /* chain_first; last tonal frame of the chain's last valid sweep */
+    uint32_t sweeps;                /* count as it stood */
+    uint32_t batch;                 /* call-relative batch of the emitting frame */
+} mi_elt_event;                     /* 32 bytes */
+typedef struct mi_elt mi_elt;
+
+/* cfg NULL = every default.  row_enabled [rows] as for mi_tones_create; rows and max_batches within the gate's limits (1 <= rows <
+ * 2^20, rows * max_batches < 2^24).  max_events: capacity of the caller's event buffer, 0 = rows * the most events a row can emit in
+ * max_batches batches, 2 * (1 + (25 * max_batches - 1) / (min_sweeps * min_len)) + 1.  Why: a row's records alternate ONSET and END;
+ * an ONSET is emitted where a sweep closes, consecutive closes of valid sweeps lie at least min_len frames apart, and between two
+ * ONSETs min_sweeps sweeps close, so the call's F = 25 * max_batches frames hold at most N = 1 + (F - 1) / (min_sweeps * min_len)
+ * ONSETs (the first in the call's first frame, out of carried state) and at most N + 1 ENDs (the first out of an alarm carried in).
+ * The handle owns the scratch for a call's frame decisions and events. */
+int mi_elt_create(const mi_elt_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_events, int gpu, mi_elt** out);
+void mi_elt_destroy(mi_elt* s);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_elt_set_rows(mi_elt* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_frames           [rows][25 * nbatches]  frame records, or NULL (not wanted); 8-byte aligned.  A disabled row's are not written.
+ *   d_events           [max_events]           rows ascending, seq ascending within a row (8-byte aligned)
+ *   d_row_first_event  [rows + 1]             exclusive prefix of the rows' event counts
+ *   d_count            [2]                    number of events, and min(that, max_events) = the number stored
+ * Nothing is written at or beyond max_events.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without atomics
+ * -- bank (one wave per (row, batch): the 25 frames' records and decisions), walk (one lane per row: the walker over the call's
+ * decisions, its events into the handle's scratch, the row's count and new walker state), scan, store (the events to their places),
+ * tails (the enabled rows' last 178 samples into the carried state) -- so every byte is the same on every run and equals
+ * mi_elt_plan_host's. */
+int mi_elt_process_device(mi_elt* s, const float* d_plane, size_t row_stride, int nbatches, mi_elt_frame_record* d_frames, mi_elt_event* d_events,
+                          uint32_t* d_row_first_event, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_elt_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and copies
+ * exactly count[1] events (and the rows * 25 * nbatches frame records, if the call had a d_frames and frames is not NULL; with
+ * frames not NULL after a call without d_frames it is refused).  events, frames and row_first_event may each be NULL.  The one place
+ * that synchronises. */
+int mi_elt_download(mi_elt* s, void* hip_stream, mi_elt_event* events, mi_elt_frame_record* frames, uint32_t* row_first_event, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_ELT_STATE_ROW_BYTES bytes in the layout above (mi_elt_plan_host reads and writes the same bytes).
+ * set_state refuses a state the walker cannot be in: open or alarmed beyond 1; a closed segment or a cleared chain with a field
+ * set; bins outside 2 .. 33; dir or chain_dir beyond MI_ELT_DOWN; bins that contradict dir; drops over max_drop or not the frames
+ * since last_frame; a segment of 2^31 frames or more; a chain with chain_dir 0, a span under min_span, alarmed != (count >=
+ * min_sweeps), or one that would have expired.  Both complete queued work first. */
+size_t mi_elt_state_size(const mi_elt* s);
+int mi_elt_get_state(mi_elt* s, void* buf, size_t len);
+int mi_elt_set_state(mi_elt* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bank, walk, scan, store, tails}.  tools/elt_rate.py. */
+int mi_elt_set_timing(mi_elt* s, int on);
+int mi_elt_last_launch_ms(mi_elt* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same frame records, events and state blob byte for byte.  plane [rows][row_stride] (no
+ * alignment asked); state_inout rows * MI_ELT_STATE_ROW_BYTES bytes, read and updated; frames [rows][25 * nbatches] or NULL; events
+ * holds max_events entries (max_events >= 1), of which min(count[0], max_events) = count[1] are written. */
+int mi_elt_plan_host(const mi_elt_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride, void* state_inout,
+                     mi_elt_frame_record* frames, mi_elt_event* events, size_t max_events, uint32_t* row_first_event, uint32_t* count /* [2] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in, or the refusal mi_elt_create would give; *c = the constant
+ * of item 4 (may be NULL). */
+int mi_elt_settings(const mi_elt_cfg* cfg, mi_elt_cfg* out, float* c);
+/* The 256 window coefficients; the 32 recurrence coefficients of bins 2 .. 33.  Host only. */
+int mi_elt_window(float* out /* [MI_ELT_FRAME] */);
+int mi_elt_coeffs(float* out /* [MI_ELT_BINS] */);
+/* One printable line from an event record, NUL-terminated, e.g. "ONSET down 1500.0 -> 500.0 Hz, 6 sweeps, 1.435 s": kind, direction,
+ * the frequencies of bin_from and bin_to (62.5 Hz a bin), sweeps, and the seconds from first_frame to frame (0.005 s a frame, the
+ * difference modulo 2^32).  Refuses a kind, a dir or a bin the stage cannot write. */
+int mi_elt_event_text(const mi_elt_event* e, char* out /* [96] */);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
