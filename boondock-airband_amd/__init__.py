@@ -245,6 +245,24 @@ SAME_STATE_DTYPE = np.dtype([("x", "<f4", (SAME_HISTORY,)), ("batch", "<u4"), ("
                             [(n, "<u4") for n in SAME_WALKER_FIELDS + ("zero",)] + [("bytes", "u1", (3, SAME_RAW_BYTES))])
 
 
+class Ax25Cfg(C.Structure):  # mi_ax25_cfg: 0 = the default of every setting
+    _fields_ = [("gain", C.c_float * 3), ("strict", C.c_uint32)]
+
+
+AX25_HISTORY, AX25_HYPOTHESES, AX25_SLICERS, AX25_LANES, AX25_BITS, AX25_BIT_WORDS, AX25_MIN_BYTES, AX25_MAX_BYTES, AX25_RAW_BYTES = 14, 10, 3, 30, 150, 5, 17, 330, 332
+AX25_WAIT, AX25_FRAME = 0, 1  # MI_AX25_*
+AX25_RESIDUE, AX25_FLAG_RESIDUE = 0xF0B8, 0x9F0B
+AX25_STRICT_OFF = 0x80000000  # mi_ax25_cfg.strict: frames whose address field is not well formed are records too
+AX25_TEXT_BYTES = 384
+# mi_ax25_frame (352 bytes) and one row of the packet stage's state blob, MI_AX25_STATE_ROW_BYTES = 10544
+AX25_FRAME_DTYPE = np.dtype([("row", "<u4"), ("batch", "<u4"), ("third", "<u4"), ("end_batch", "<u4"), ("nbytes", "<u2"), ("lane", "u1"), ("naddr", "u1"),
+                             ("bytes", "u1", (AX25_RAW_BYTES,))])
+AX25_STATE_DTYPE = np.dtype([("x", "<f4", (AX25_HISTORY,)), ("batch", "<u8"), ("last_end", "<u8"), ("start", "<u8", (AX25_LANES,)),
+                             ("nbytes", "<u2", (AX25_LANES,)), ("crc", "<u2", (AX25_LANES,)), ("prev", "u1", (AX25_LANES,)), ("ones", "u1", (AX25_LANES,)),
+                             ("phase", "u1", (AX25_LANES,)), ("nbits", "u1", (AX25_LANES,)), ("cur", "u1", (AX25_LANES,)), ("zero", "u1", (2,)),
+                             ("bytes", "u1", (AX25_LANES, AX25_RAW_BYTES))])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -360,6 +378,9 @@ ABI_SYMBOLS = [
     "mi_elt_create", "mi_elt_destroy", "mi_elt_set_rows", "mi_elt_process_device", "mi_elt_download", "mi_elt_state_size", "mi_elt_get_state",
     "mi_elt_set_state", "mi_elt_set_timing", "mi_elt_last_launch_ms", "mi_elt_plan_host", "mi_elt_settings", "mi_elt_window", "mi_elt_coeffs",
     "mi_elt_event_text",
+    "mi_ax25_create", "mi_ax25_destroy", "mi_ax25_set_rows", "mi_ax25_process_device", "mi_ax25_download", "mi_ax25_state_size",
+    "mi_ax25_get_state", "mi_ax25_set_state", "mi_ax25_set_timing", "mi_ax25_last_launch_ms", "mi_ax25_plan_host", "mi_ax25_settings",
+    "mi_ax25_templates", "mi_ax25_crc", "mi_ax25_frame_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -551,6 +572,24 @@ def lib():
         L.mi_acars_crc.argtypes = [vp, sz]
         L.mi_acars_crc.restype = C.c_uint32
         L.mi_acars_frame_text.argtypes = [vp, C.POINTER(AcarsText)]
+        L.mi_ax25_create.argtypes = [C.POINTER(Ax25Cfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_ax25_destroy.argtypes = [vp]
+        L.mi_ax25_destroy.restype = None
+        L.mi_ax25_set_rows.argtypes = [vp, vp]
+        L.mi_ax25_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp]
+        L.mi_ax25_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mi_ax25_state_size.argtypes = [vp]
+        L.mi_ax25_state_size.restype = sz
+        L.mi_ax25_get_state.argtypes = [vp, vp, sz]
+        L.mi_ax25_set_state.argtypes = [vp, vp, sz]
+        L.mi_ax25_set_timing.argtypes = [vp, C.c_int]
+        L.mi_ax25_last_launch_ms.argtypes = [vp, vp]
+        L.mi_ax25_plan_host.argtypes = [C.POINTER(Ax25Cfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, sz, vp, vp]
+        L.mi_ax25_settings.argtypes = [C.POINTER(Ax25Cfg), C.POINTER(Ax25Cfg)]
+        L.mi_ax25_templates.argtypes = [vp]
+        L.mi_ax25_crc.argtypes = [vp, sz]
+        L.mi_ax25_crc.restype = C.c_uint32
+        L.mi_ax25_frame_text.argtypes = [vp, C.c_char_p, sz]
         L.mi_elt_create.argtypes = [C.POINTER(EltCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
         L.mi_elt_destroy.argtypes = [vp]
         L.mi_elt_destroy.restype = None
@@ -735,7 +774,7 @@ class _PostStage(_TimedStage):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
         .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
-        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE); the ELT stage's rows * 776, .view(ELT_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE); the ELT stage's rows * 776, .view(ELT_STATE_DTYPE); the packet stage's rows * 10544, .view(AX25_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -1911,6 +1950,111 @@ def acars_plan_host(row_enabled, plane, cfg=None, state=None, max_frames=0, nbat
     _check(lib().mi_acars_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(q), _ptr(frames), cap,
                                     _ptr(row_first), _ptr(count)))
     return frames[:int(count[1])], bits, q, row_first, count, state
+
+
+def ax25_cfg(gain=None, strict=True):
+    """mi_ax25_cfg, field for field as the C struct takes it: gain: the three slicers' weights of the space power, each 0 (or the
+    whole None) = its default; strict: False = frames whose address field is not well formed are records too.  An Ax25Cfg passes
+    through."""
+    if isinstance(gain, Ax25Cfg):
+        return gain
+    c = Ax25Cfg()
+    for g, v in enumerate(gain or (0.0, 0.0, 0.0)):
+        c.gain[g] = v
+    c.strict = 0 if strict else AX25_STRICT_OFF
+    return c
+
+
+def ax25_settings(cfg=None):
+    """mi_ax25_settings: the settings with every default filled in, as an Ax25Cfg"""
+    out = Ax25Cfg()
+    _check(lib().mi_ax25_settings(C.byref(ax25_cfg(cfg)), C.byref(out)))
+    return out
+
+
+def ax25_max_frames(nbatches):
+    """the most records one row can have in a call of nbatches batches"""
+    return 1 + AX25_BITS * nbatches // 143
+
+
+def ax25_templates():
+    """mi_ax25_templates: [4][40], cos and sin of 1200 Hz, cos and sin of 2200 Hz over a bit's 40 thirds"""
+    t = np.zeros((4, 40), np.float32)
+    _check(lib().mi_ax25_templates(_ptr(t)))
+    return t
+
+
+def ax25_crc(data):
+    """mi_ax25_crc: CRC-16/X.25 of bytes, complemented as it is sent"""
+    b = np.frombuffer(bytes(data), np.uint8)
+    return int(lib().mi_ax25_crc(_ptr(b) if b.size else None, b.size))
+
+
+def ax25_frame_text(frame):
+    """mi_ax25_frame_text: a record's TNC2 line SRC-S>DST-S,DIGI-S*,..:info as a str"""
+    f = np.array(frame, AX25_FRAME_DTYPE).reshape(1)
+    out = C.create_string_buffer(AX25_TEXT_BYTES)
+    _check(lib().mi_ax25_frame_text(_ptr(f), out, AX25_TEXT_BYTES))
+    return out.value.decode("ascii")
+
+
+class Ax25(_PostStage):
+    """mi_ax25: the packet decoder stage -- per row, the AX.25 frames its 1200 bit/s Bell 202 bursts carried: a bank of tone detectors
+    under 10 timing hypotheses and three slicers per batch, and 30 HDLC deframers side by side, whose frames the frame check admits
+    and a rule on their positions keeps to one record each.  It reads a plane of audio as Acars does and needs no flags.
+    row_enabled: truth value per row; cfg: ax25_cfg(...) or None; max_frames: capacity of the frame buffer, 0 = rows *
+    ax25_max_frames(max_batches).  state() gives rows * 10544 bytes, whose fields .view(AX25_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_ax25_destroy", "mi_ax25", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_frames=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = ax25_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_ax25_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_frames, gpu, C.byref(self._h)))
+        most = self.rows * ax25_max_frames(max_batches)
+        self.max_frames = min(max_frames, most) if max_frames else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_ax25_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_frames, d_row_first_frame, d_count, d_bits=None, hip_stream=None):
+        """Raw device pointers (ints; d_bits may be None), the stride in floats; asynchronous on hip_stream."""
+        _check(lib().mi_ax25_process_device(self._h, d_plane, row_stride, nbatches, d_bits, d_frames, d_row_first_frame, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (frames [k] of AX25_FRAME_DTYPE, row_first_frame [rows + 1],
+        count [2]) with k = count[1]."""
+        frames = np.zeros(self.max_frames, AX25_FRAME_DTYPE)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_ax25_download(self._h, hip_stream, _ptr(frames), _ptr(row_first), _ptr(count)))
+        return frames[:int(count[1])], row_first, count
+
+
+def ax25_plan_host(row_enabled, plane, cfg=None, state=None, max_frames=0, nbatches=None):
+    """mi_ax25_plan_host: the packet stage's tone bits and frames from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 10544 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_frames: 0 = every frame of the call.  Returns (frames [count[1]], bits [rows][nbatches][3][10][5], row_first_frame [rows + 1],
+    count [2], state after the call).  A disabled row's bits stay zero."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = ax25_cfg(cfg)
+    state = np.zeros(rows * AX25_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * AX25_STATE_DTYPE.itemsize
+    cap = max_frames or max(1, rows * ax25_max_frames(max(nb, 1)))
+    frames = np.zeros(cap, AX25_FRAME_DTYPE)
+    bits = np.zeros((rows, max(nb, 0), AX25_SLICERS, AX25_HYPOTHESES, AX25_BIT_WORDS), np.uint32)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_ax25_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(frames), cap,
+                                   _ptr(row_first), _ptr(count)))
+    return frames[:int(count[1])], bits, row_first, count, state
 
 
 def same_cfg(sync_errors=0, max_bad=0, gap_batches=0, min_quality=0.0, space_gain=0.0, hold_timing=False):

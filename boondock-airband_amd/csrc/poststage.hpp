@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, elt.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, elt.hip, ax25.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -1124,5 +1124,151 @@ static_assert(sizeof(mi_probe_target) == 8 && sizeof(mi_probe_cell) == 40, "the 
 // The channel finder's settings with the defaults filled in and its view of the device configuration (poststage_host.cpp): MI_OK, or
 // the refusal with its message set.  *log2n: the one field the arithmetic uses.
 int occ_settings(const mi_device_cfg* dev, const mi_occ_cfg* cfg, mi_occ_cfg* out, int* log2n);
+
+// The packet decoder stage (include/mi_airband.h "packet decoder stage").  One row of its state: the checkpoint blob is an array of
+// these, and ax25.hip keeps the same array in device memory.  The lanes' fields lie lane by lane, so a wave's lane l reads field[l].
+struct Ax25RowState {
+    float x[MI_AX25_HISTORY];               // the last 14 input samples of the row's last batch, oldest first
+    uint64_t batch;                         // batches seen since creation / set_state
+    uint64_t last_end;                      // where the closing flag of the row's last record ended, in absolute thirds
+    uint64_t start[MI_AX25_LANES];          // where the lane's frame began
+    uint16_t nbytes[MI_AX25_LANES], crc[MI_AX25_LANES];
+    uint8_t prev[MI_AX25_LANES], ones[MI_AX25_LANES], phase[MI_AX25_LANES], nbits[MI_AX25_LANES], cur[MI_AX25_LANES], zero[2];
+    uint8_t bytes[MI_AX25_LANES][MI_AX25_RAW_BYTES];
+};
+constexpr int kAx25LaneWords = MI_AX25_RAW_BYTES / 4;  // 83 words of frame bytes a lane
+constexpr uint32_t ax25_crc_bit(const uint32_t crc, const uint32_t d) {
+    return (crc ^ d) & 1u ? crc >> 1 ^ 0x8408u : crc >> 1;
+}
+constexpr uint32_t ax25_flag_residue() {
+    uint32_t crc = MI_AX25_RESIDUE;
+    for (int i = 0; i < 6; ++i)
+        crc = ax25_crc_bit(crc, i ? 1u : 0u);
+    return crc;
+}
+static_assert(sizeof(Ax25RowState) == MI_AX25_STATE_ROW_BYTES && offsetof(Ax25RowState, batch) == 56 && offsetof(Ax25RowState, start) == 72 &&
+                  offsetof(Ax25RowState, nbytes) == 312 && offsetof(Ax25RowState, prev) == 432 && offsetof(Ax25RowState, zero) == 582 &&
+                  offsetof(Ax25RowState, bytes) == 584 && sizeof(mi_ax25_frame) == 352 && offsetof(mi_ax25_frame, nbytes) == 16 &&
+                  offsetof(mi_ax25_frame, bytes) == 20 && sizeof(mi_ax25_cfg) == 16 && (MI_AX25_HISTORY + 2) % 4 == 0 &&
+                  MI_AX25_MAX_BYTES <= MI_AX25_RAW_BYTES && MI_AX25_RAW_BYTES % 4 == 0 && MI_AX25_LANES == MI_AX25_SLICERS * MI_AX25_HYPOTHESES &&
+                  40 * MI_AX25_BITS == 3 * kWaveBatch && MI_AX25_BIT_WORDS * 32 >= MI_AX25_BITS && ax25_flag_residue() == MI_AX25_FLAG_RESIDUE,
+              "the packet stage's blob, record and settings layouts are ABI");
+// The settings with every default filled in, as both halves take them.
+struct Ax25Plan {
+    float gain[MI_AX25_SLICERS];
+    uint32_t strict;     // 0 / 1
+    mi_ax25_cfg filled;  // the settings as the caller would have written them
+};
+struct Ax25Gains {
+    float g[MI_AX25_SLICERS];
+};
+// A lane's deframer, as the walk carries it in registers; its bytes so far stay in memory beside it.
+struct Ax25Lane {
+    uint32_t prev, ones, phase, nbits, cur, nbytes, crc;
+    uint64_t start;
+};
+// the most records one row can have in a call (the header argues it)
+inline uint32_t ax25_max_frames(uint64_t nbatches) {
+    return static_cast<uint32_t>(1 + MI_AX25_BITS * nbatches / 143);
+}
+// Where slot j of hypothesis tau ends, in thirds from the batch's first.
+__host__ __device__ inline int ax25_slot_end(const int tau, const int j) {
+    return 4 * tau + 40 * (j + 1 - (tau > 0));
+}
+// Slot j of hypothesis tau over what is staged for a block -- s[kLead + n] is the block's sample n, kLead = MI_AX25_HISTORY + 2 --, T
+// the four templates: the three slicers' tone bits, slicer g's in bit g.  Host and device run this text.
+__host__ __device__ inline uint32_t ax25_bit(const float* s, const float* T, const Ax25Gains& gain, const int tau, const int j) {
+    const int t0 = 4 * tau + 40 * (j - (tau > 0));  // -36 .. 5960
+    const int n0 = (t0 + 41) / 3 - 13;              // ceil(t0 / 3)
+    int rho = 3 * n0 - t0;                          // 0 .. 2
+    const bool more = rho == 0;
+    const float* const x = s + (MI_AX25_HISTORY + 2) + n0;
+    float s0 = x[0] * T[rho], s1 = x[0] * T[40 + rho], s2 = x[0] * T[80 + rho], s3 = x[0] * T[120 + rho];
+#pragma unroll
+    for (int i = 1; i < 13; ++i) {
+        rho += 3;
+        s0 = s0 + x[i] * T[rho];
+        s1 = s1 + x[i] * T[40 + rho];
+        s2 = s2 + x[i] * T[80 + rho];
+        s3 = s3 + x[i] * T[120 + rho];
+    }
+    if (more) {
+        rho += 3;
+        s0 = s0 + x[13] * T[rho];
+        s1 = s1 + x[13] * T[40 + rho];
+        s2 = s2 + x[13] * T[80 + rho];
+        s3 = s3 + x[13] * T[120 + rho];
+    }
+    const float pm = s0 * s0 + s1 * s1, ps = s2 * s2 + s3 * s3;
+    return (pm >= gain.g[0] * ps ? 1u : 0u) | (pm >= gain.g[1] * ps ? 2u : 0u) | (pm >= gain.g[2] * ps ? 4u : 0u);
+}
+// What a slot did to a lane: kAx25Flag -- the slot is a flag's last bit, the caller opens the next frame with ax25_open behind
+// whatever it does about the old one --, with kAx25Cand where the lane's frame is a candidate (whole bytes, at least 17, the check
+// right; the address field and the ordering are the caller's to judge).
+enum { kAx25Flag = 1, kAx25Cand = 2 };
+__host__ __device__ inline void ax25_wait(Ax25Lane& L) {
+    L.phase = MI_AX25_WAIT;
+    L.nbits = L.cur = L.nbytes = L.crc = 0;
+    L.start = 0;
+}
+__host__ __device__ inline void ax25_open(Ax25Lane& L, const uint64_t next) {
+    L.phase = MI_AX25_FRAME;
+    L.nbits = L.cur = L.nbytes = 0;
+    L.crc = 0xFFFFu;
+    L.start = next;
+}
+// One tone bit t through a lane's deframer; store(i, byte) takes byte number i of the frame.  Bytes behind nbytes are whatever an
+// earlier frame left: whoever reads a lane's bytes takes nbytes of them.  Host and device run this text.
+template <class Store>
+__host__ __device__ inline uint32_t ax25_step(Ax25Lane& L, const uint32_t t, Store&& store) {
+    const uint32_t d = t == L.prev ? 1u : 0u, n = L.ones;
+    L.prev = t;
+    L.ones = d ? (n < 7u ? n + 1u : 7u) : 0u;
+    if (n >= 5u) {
+        if (n != 6u)
+            return 0;
+        if (d) {
+            ax25_wait(L);
+            return 0;
+        }
+        return L.phase == MI_AX25_FRAME && L.nbits == 6u && L.nbytes >= MI_AX25_MIN_BYTES && L.crc == MI_AX25_FLAG_RESIDUE ? kAx25Flag | kAx25Cand : kAx25Flag;
+    }
+    if (L.phase != MI_AX25_FRAME)
+        return 0;
+    L.cur |= d << L.nbits;
+    L.crc = ax25_crc_bit(L.crc, d);
+    if (++L.nbits == 8u) {
+        if (L.nbytes == MI_AX25_MAX_BYTES) {
+            ax25_wait(L);
+        } else {
+            store(L.nbytes, L.cur);
+            ++L.nbytes;
+            L.nbits = L.cur = 0;
+        }
+    }
+    return 0;
+}
+// Whether a callsign byte, shifted right by one, is 'A'-'Z', '0'-'9' or a space.
+__host__ __device__ inline bool ax25_call_char(const uint32_t byte) {
+    const uint32_t c = byte >> 1;
+    return (c >= 'A' && c <= 'Z') || (c >= '0' && c <= '9') || c == ' ';
+}
+// The number of addresses of a frame of nbytes bytes whose address field is well formed, else 0.
+inline uint32_t ax25_naddr(const uint8_t* b, const uint32_t nbytes) {
+    uint32_t i = 0;
+    while (i < 70 && i + 3 < nbytes && !(b[i] & 1u))
+        ++i;
+    if (i >= 70 || i + 3 >= nbytes || i % 7 != 6 || i < 13)
+        return 0;
+    for (uint32_t k = 0; k < i; ++k)
+        if (k % 7 != 6 && !ax25_call_char(b[k]))
+            return 0;
+    return (i + 1) / 7;
+}
+// What both halves of the packet stage share (poststage_host.cpp).  ax25_plan: MI_OK with the plan, or the settings' refusal with its
+// message set.  ax25_templates: t[160].  ax25_state_ok: NULL, or what is impossible about a blob.
+int ax25_plan(const mi_ax25_cfg* cfg, Ax25Plan* out);
+void ax25_templates(float* t);
+const char* ax25_state_ok(const Ax25RowState* state, size_t rows);
 
 }  // namespace mi

@@ -2483,3 +2483,249 @@ extern "C" int mi_elt_plan_host(const mi_elt_cfg* cfg, const uint8_t* row_enable
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::EltRowState));
     return MI_OK;
 }
+
+// ---- packet decoder stage, host side (include/mi_airband.h "packet decoder stage"): the settings' check, the templates, the blob's
+// check, the frame check, a record's TNC2 line, and the twin of ax25.hip -- one row, one batch, one hypothesis and one slot at a time,
+// then the 30 deframers over the batch's slots.  The bit, the deframer's step and the address field's check are poststage.hpp's.
+namespace mi {
+
+int ax25_plan(const mi_ax25_cfg* cfg, Ax25Plan* out) {
+    mi_ax25_cfg c{};
+    if (cfg)
+        c = *cfg;
+    const float def[MI_AX25_SLICERS] = {MI_AX25_GAIN0, MI_AX25_GAIN1, MI_AX25_GAIN2};
+    Ax25Plan p{};
+    for (int g = 0; g < MI_AX25_SLICERS; ++g) {
+        if (!std::isfinite(c.gain[g]) || c.gain[g] < 0.0f)
+            return fail(MI_ERR_INVALID, "packet stage: every gain must be finite and positive (0 = the default)");
+        if (c.gain[g] == 0.0f)
+            c.gain[g] = def[g];
+        p.gain[g] = c.gain[g];
+    }
+    if (c.strict > 1 && c.strict != MI_AX25_STRICT_OFF)
+        return fail(MI_ERR_INVALID, "packet stage: strict must be 0, 1 or MI_AX25_STRICT_OFF");
+    if (c.strict == 0)
+        c.strict = 1;
+    p.strict = c.strict == 1;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+void ax25_templates(float* t) {
+    const double pi = 3.14159265358979323846;
+    for (int r = 0; r < 40; ++r) {
+        t[r] = static_cast<float>(std::cos(2.0 * pi * 1200.0 * r / 48000.0));
+        t[40 + r] = static_cast<float>(std::sin(2.0 * pi * 1200.0 * r / 48000.0));
+        t[80 + r] = static_cast<float>(std::cos(2.0 * pi * 2200.0 * r / 48000.0));
+        t[120 + r] = static_cast<float>(std::sin(2.0 * pi * 2200.0 * r / 48000.0));
+    }
+}
+
+const char* ax25_state_ok(const Ax25RowState* state, size_t rows) {
+    for (size_t r = 0; r < rows; ++r) {
+        const Ax25RowState& s = state[r];
+        if (s.zero[0] | s.zero[1])
+            return "the zero field is not 0";
+        if (s.batch >= (1ull << 40))
+            return "a batch count at or beyond 2^40";
+        const uint64_t now = 3ull * kWaveBatch * s.batch;
+        if (s.last_end > now)
+            return "an impossible position (the last record ends behind the row's last batch)";
+        for (int l = 0; l < MI_AX25_LANES; ++l) {
+            if (s.prev[l] > 1 || s.ones[l] > 7 || s.nbits[l] > 7 || s.cur[l] >> s.nbits[l] || s.nbytes[l] > MI_AX25_MAX_BYTES)
+                return "an impossible lane state (a counter beyond its range)";
+            if (s.phase[l] > MI_AX25_FRAME)
+                return "an unknown lane phase";
+            uint32_t used = 0;
+            if (s.phase[l] == MI_AX25_WAIT) {
+                if (s.start[l] | s.nbytes[l] | s.crc[l] | s.nbits[l] | s.cur[l])
+                    return "an impossible lane state (a waiting lane with a frame field set)";
+            } else {
+                // the lane's last slot ended at lane_now, and every collected bit took a slot of 40 thirds behind start
+                const int64_t lane_now = static_cast<int64_t>(now) + ax25_slot_end(l % MI_AX25_HYPOTHESES, -1);
+                if (s.start[l] > now || static_cast<int64_t>(s.start[l]) + 40 * (8 * static_cast<int64_t>(s.nbytes[l]) + s.nbits[l]) > lane_now)
+                    return "an impossible position (a frame begins behind the row's last batch or later than its collected bits allow)";
+                used = s.nbytes[l];
+                uint32_t crc = 0xFFFFu;
+                for (uint32_t i = 0; i < used; ++i)
+                    for (int k = 0; k < 8; ++k)
+                        crc = ax25_crc_bit(crc, s.bytes[l][i] >> k & 1u);
+                for (uint32_t k = 0; k < s.nbits[l]; ++k)
+                    crc = ax25_crc_bit(crc, s.cur[l] >> k & 1u);
+                if (crc != s.crc[l])
+                    return "an impossible lane state (a crc that the bytes do not give)";
+            }
+            for (uint32_t i = used; i < MI_AX25_RAW_BYTES; ++i)
+                if (s.bytes[l][i])
+                    return "an impossible lane state (a byte set behind the ones taken)";
+        }
+    }
+    return nullptr;
+}
+
+}  // namespace mi
+
+extern "C" int mi_ax25_settings(const mi_ax25_cfg* cfg, mi_ax25_cfg* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::Ax25Plan p;
+    if (const int rc = mi::ax25_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    return MI_OK;
+}
+
+extern "C" int mi_ax25_templates(float* t) {
+    if (!t)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::ax25_templates(t);
+    return MI_OK;
+}
+
+extern "C" uint32_t mi_ax25_crc(const uint8_t* bytes, size_t n) {
+    if (!bytes && n)
+        return 0xFFFFFFFFu;
+    uint32_t crc = 0xFFFFu;
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 8; ++k)
+            crc = mi::ax25_crc_bit(crc, bytes[i] >> k & 1u);
+    return crc ^ 0xFFFFu;
+}
+
+extern "C" int mi_ax25_frame_text(const mi_ax25_frame* f, char* text, size_t cap) {
+    if (!f || !text)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (f->nbytes < MI_AX25_MIN_BYTES || f->nbytes > MI_AX25_MAX_BYTES)
+        return fail(MI_ERR_INVALID, "packet stage: a frame's nbytes must be within 17 .. 330");
+    const uint32_t naddr = mi::ax25_naddr(f->bytes, f->nbytes);
+    if (!naddr)
+        return fail(MI_ERR_INVALID, "packet stage: the frame's address field is not well formed");
+    std::string line;
+    const auto call = [&](uint32_t a) {
+        const uint8_t* const b = f->bytes + 7 * a;
+        int len = 6;
+        while (len > 0 && b[len - 1] >> 1 == ' ')
+            --len;
+        for (int i = 0; i < len; ++i)
+            line += static_cast<char>(b[i] >> 1);
+        if (const uint32_t ssid = b[6] >> 1 & 15u)
+            line += "-" + std::to_string(ssid);
+    };
+    call(1);
+    line += '>';
+    call(0);
+    uint32_t last_h = 0;  // the address behind which the '*' goes
+    for (uint32_t a = 2; a < naddr; ++a)
+        if (f->bytes[7 * a + 6] & 0x80u)
+            last_h = a;
+    for (uint32_t a = 2; a < naddr; ++a) {
+        line += ',';
+        call(a);
+        if (a == last_h)
+            line += '*';
+    }
+    line += ':';
+    const uint32_t control = f->bytes[7 * naddr];
+    uint32_t at = 7 * naddr + ((control | 0x10u) == 0x13u ? 2u : 1u);
+    for (; at + 2 < f->nbytes; ++at)
+        line += f->bytes[at] >= 0x20 && f->bytes[at] <= 0x7E ? static_cast<char>(f->bytes[at]) : '.';
+    if (line.size() + 1 > cap)
+        return fail(MI_ERR_INVALID, "packet stage: the text buffer is shorter than the line");
+    std::memcpy(text, line.c_str(), line.size() + 1);
+    return MI_OK;
+}
+
+extern "C" int mi_ax25_plan_host(const mi_ax25_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                 void* state_inout, uint32_t* bits, mi_ax25_frame* frames, size_t max_frames, uint32_t* row_first_frame,
+                                 uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !frames || !row_first_frame || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_frames < 1)
+        return fail(MI_ERR_INVALID, "packet plan needs rows >= 1, nbatches >= 1 and max_frames >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::Ax25Plan plan;
+    if (const int rc = mi::ax25_plan(cfg, &plan))
+        return rc;
+    if (static_cast<uint64_t>(rows) * mi::ax25_max_frames(static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "packet plan: the frames of the call do not fit the 32-bit count");
+    std::vector<mi::Ax25RowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::Ax25RowState));
+    if (const char* const why = mi::ax25_state_ok(blob.data(), blob.size()))
+        return fail(MI_ERR_INVALID, std::string("packet plan: malformed state blob: ") + why);
+    constexpr int kLead = MI_AX25_HISTORY + 2, kTau = MI_AX25_HYPOTHESES, kBits = MI_AX25_BITS, kWords = MI_AX25_BIT_WORDS, kLanes = MI_AX25_LANES;
+    float T[160];
+    mi::ax25_templates(T);
+    const mi::Ax25Gains gain{{plan.gain[0], plan.gain[1], plan.gain[2]}};
+    std::vector<float> s(kLead + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    uint32_t k = 0;
+    for (int r = 0; r < rows; ++r) {
+        row_first_frame[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::Ax25RowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        s[0] = s[1] = 0.0f;
+        std::memcpy(s.data() + 2, st.x, sizeof(st.x));
+        std::memcpy(s.data() + kLead, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::Ax25Lane lane[kLanes];
+        for (int l = 0; l < kLanes; ++l)
+            lane[l] = mi::Ax25Lane{st.prev[l], st.ones[l], st.phase[l], st.nbits[l], st.cur[l], st.nbytes[l], st.crc[l], st.start[l]};
+        for (int b = 0; b < nbatches; ++b) {
+            const float* const blk = s.data() + static_cast<size_t>(b) * mi::kWaveBatch;  // staged: blk[kLead + n] is the batch's sample n
+            uint32_t word[kLanes][kWords] = {};
+            for (int t = 0; t < kTau; ++t)
+                for (int j = 0; j < kBits; ++j) {
+                    const uint32_t m = mi::ax25_bit(blk, T, gain, t, j);
+                    for (int g = 0; g < MI_AX25_SLICERS; ++g)
+                        word[10 * g + t][j / 32] |= (m >> g & 1u) << (j % 32);
+                }
+            if (bits)
+                std::memcpy(bits + (static_cast<size_t>(r) * static_cast<size_t>(nbatches) + static_cast<size_t>(b)) * kLanes * kWords, word, sizeof(word));
+            const uint64_t base = 3ull * mi::kWaveBatch * (st.batch + static_cast<uint64_t>(b));
+            for (int j = 0; j < kBits; ++j)
+                for (int l = 0; l < kLanes; ++l) {
+                    mi::Ax25Lane& L = lane[l];
+                    const uint32_t ev = mi::ax25_step(L, word[l][j / 32] >> (j % 32) & 1u, [&](uint32_t i, uint32_t byte) { st.bytes[l][i] = static_cast<uint8_t>(byte); });
+                    if (!ev)
+                        continue;
+                    const uint64_t end = base + static_cast<uint64_t>(mi::ax25_slot_end(l % kTau, j));
+                    if ((ev & mi::kAx25Cand) && L.start + 40 >= st.last_end) {
+                        const uint32_t naddr = mi::ax25_naddr(st.bytes[l], L.nbytes);
+                        if (naddr || !plan.strict) {
+                            if (k < max_frames) {
+                                mi_ax25_frame f{};
+                                f.row = static_cast<uint32_t>(r);
+                                f.batch = static_cast<uint32_t>(L.start / (3u * mi::kWaveBatch));
+                                f.third = static_cast<uint32_t>(L.start % (3u * mi::kWaveBatch));
+                                f.end_batch = static_cast<uint32_t>(b);
+                                f.nbytes = static_cast<uint16_t>(L.nbytes);
+                                f.lane = static_cast<uint8_t>(l);
+                                f.naddr = static_cast<uint8_t>(naddr);
+                                std::memcpy(f.bytes, st.bytes[l], L.nbytes);
+                                frames[k] = f;
+                            }
+                            ++k;
+                            st.last_end = end;
+                        }
+                    }
+                    mi::ax25_open(L, end);
+                }
+        }
+        st.batch += static_cast<uint64_t>(nbatches);
+        for (int l = 0; l < kLanes; ++l) {
+            const mi::Ax25Lane& L = lane[l];
+            st.prev[l] = static_cast<uint8_t>(L.prev), st.ones[l] = static_cast<uint8_t>(L.ones), st.phase[l] = static_cast<uint8_t>(L.phase);
+            st.nbits[l] = static_cast<uint8_t>(L.nbits), st.cur[l] = static_cast<uint8_t>(L.cur), st.nbytes[l] = static_cast<uint16_t>(L.nbytes);
+            st.crc[l] = static_cast<uint16_t>(L.crc), st.start[l] = L.start;
+            std::memset(st.bytes[l] + L.nbytes, 0, MI_AX25_RAW_BYTES - L.nbytes);  // (what an earlier frame left behind the ones taken)
+        }
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_AX25_HISTORY, sizeof(st.x));
+    }
+    row_first_frame[rows] = k;
+    count[0] = k;
+    count[1] = k < max_frames ? k : static_cast<uint32_t>(max_frames);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::Ax25RowState));
+    return MI_OK;
+}

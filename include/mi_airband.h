@@ -1934,6 +1934,158 @@ int mi_elt_coeffs(float* out /* [MI_ELT_BINS] */);
  * difference modulo 2^32).  Refuses a kind, a dir or a bin the stage cannot write. */
 int mi_elt_event_text(const mi_elt_event* e, char* out /* [96] */);
 
+/* ---------------- packet decoder stage: AX.25 / APRS frames per row, on the device ----------------
+ * 1200 bit/s Bell 202 packet on NFM channels (AX.25 UI frames: APRS on 144.39 / 144.80 MHz, packet on marine and utility channels):
+ * a 1200 Hz tone (MARK) or a 2200 Hz tone (SPACE) per bit, NRZI, HDLC framing.  The reference leaves it in the recording.  This stage
+ * reads a plane [rows][row_stride] of float32 audio as mi_acars_* does, needs no flags, and writes one record per received frame
+ * whose frame check sequence is right.  HDLC opens on an 8-bit flag, not on a long sync, so nothing chooses a hypothesis: a deframer
+ * runs on every one of 30 LANES (three slicers times ten timing hypotheses) all the time, the frame check decides, and a rule on the
+ * frames' positions keeps the copies of one frame down to one record.
+ * NOT CHECKED: the air format is written from memory and pinned only to the modulator of tests/ax25_model.py; no off-air packet has
+ * been through the stage.  No error correction and no bit-flip repair: one wrong bit loses the frame on that lane.
+ *
+ * Stream model.  As for the ACARS stage: a row's audio is one running sequence over all batches of all calls the row was enabled in;
+ * samples before the handle's first call are 0.
+ * Timing grid.  16000 / 1200 = 40 / 3 samples a bit; time is counted in THIRDS of a sample, sample n at third 3 n.  A bit is 40 thirds,
+ * a batch 6000 thirds = exactly 150 bits, so the grid does not move from batch to batch.  Under hypothesis tau = 0 .. 9, bit k covers
+ * the thirds [4 tau + 40 k, 4 tau + 40 k + 40), and sample n contributes to it when rho = 3 n - (4 tau + 40 k) lies in 0 .. 39:
+ * fourteen samples where the first rho is 0, else thirteen.  The bits of a (row, batch) are those whose last sample lies in the batch,
+ * exactly 150 per hypothesis, numbered by SLOT j = 0 .. 149: slot j of hypothesis tau is the bit that begins at third
+ * 4 tau + 40 (j - [tau > 0]) of the batch.  The earliest sample a bit of a batch reads is the twelfth before it (tau = 1); the handle
+ * carries MI_AX25_HISTORY = 14 samples per row, the smallest H >= 13 whose lead H + 2 (carry.hpp) is whole float4.  Positions are
+ * ABSOLUTE THIRDS, 64 bits: 6000 * (the row's batches before the batch) + the third within it.  Slot j of hypothesis tau in the
+ * row's batch B ends -- and slot j + 1 begins -- at 6000 B + 4 tau + 40 (j + 1 - [tau > 0]).
+ * Bit bank, per (row, batch, tau, slot); float32, every operation rounded on its own, no fused multiply-add.  Four templates of 40
+ * entries (mi_ax25_templates): T[0][rho] = cos(2 pi 1200 rho / 48000), T[1] the sine, T[2][rho] = cos(2 pi 2200 rho / 48000), T[3]
+ * the sine, evaluated in double and rounded once.  s_i = sum x[n] * T[i][rho] over the bit's samples in ascending n, each sum
+ * beginning with its first product; pm = s_0 * s_0 + s_1 * s_1, ps = s_2 * s_2 + s_3 * s_3.  THREE slicers share the sums: TONE bit
+ * t_g = 1 (mark) if pm >= gain[g] * ps, g = 0, 1, 2.  Behind an NFM de-emphasis the 2200 Hz tone arrives weaker than the 1200 Hz one,
+ * by an amount that depends on whether the transmitter pre-emphasised: gain[0] = 1 is flat audio, gain[2] the power tilt measured
+ * behind this project's NFM path for a flat-deviation transmitter, gain[1] their geometric mean.  Packed: 5 words per
+ * (row, batch, g, tau), slot j in bit j % 32 of word j / 32, the upper 10 bits of word 4 zero.  A block whose 2000 samples and 14
+ * carried samples are all +-0 gives t = 1 everywhere (0 >= gain * 0); the device writes that without the sums.
+ * Deframers.  Lane l = 10 g + tau, l = 0 .. 29; the lanes are independent.  Per slot a lane takes its tone bit t:
+ *   d = 1 if t equals the lane's previous tone bit, else 0 (NRZI); the previous tone bit becomes t.  n = the lane's ONES count.
+ *   d = 1: ones = min(n + 1, 7).  n <= 4: the 1 is COLLECTED.  n = 5: a sixth one is never data and is not collected.  n = 6: ABORT --
+ *     the lane forgets its frame (every frame field 0) and WAITS for a flag.  n = 7: nothing.
+ *   d = 0: ones = 0.  n <= 4: the 0 is collected.  n = 5: a stuffed bit, dropped.  n = 6: a FLAG (below).  n = 7: nothing.
+ *   Collected (only IN A FRAME, i.e. behind a flag): the bit goes into the running byte, least significant first, and through the
+ *   lane's CRC register (reflected polynomial 0x8408, the register starts a frame at 0xFFFF).  The eighth bit ends a byte: it is byte
+ *   number nbytes of the frame, unless the frame already has MI_AX25_MAX_BYTES = 330 (10 addresses, control, PID, 256 of information,
+ *   2 of the check): then the lane aborts as above.
+ *   A flag's own 0 and first five ones are collected like any bits before the flag is known.  So at a flag a frame holds WHOLE BYTES
+ *   when its running byte has exactly those 6 bits, and its register has taken them too: the frame check CRC-16/X.25 over the whole
+ *   bytes (initial value 0xFFFF, the check sent low byte first and complemented) leaves the residue 0xF0B8, which those six bits
+ *   advance to MI_AX25_FLAG_RESIDUE; the step is one to one, so the register equals it exactly when the residue was right.
+ *   At a flag the lane CLOSES a candidate if it is in a frame that holds whole bytes, at least 17, whose frame check is right, and --
+ *   under `strict` -- whose ADDRESS FIELD is well formed: the first byte with bit 0 set is byte 7 a - 1 for a number of addresses
+ *   a = 2 .. 10, 7 a + 3 <= nbytes (a control byte and the check follow), and every byte i < 7 a with i % 7 != 6 shifted right by one
+ *   is 'A'-'Z', '0'-'9' or a space.  naddr = a, or 0 where the field is not well formed (a record only without strict).
+ *   A flag always opens the next frame, whether or not it closed one: the lane is in a frame with no bits, no bytes, the register
+ *   0xFFFF, and START = the position where the next slot begins.  Frames may share one flag, and flags one 0.
+ * One record per frame.  Slots are taken in order and within a slot the lanes in ascending l.  END of a candidate = the position
+ * where the slot behind its closing flag's last bit begins.  A candidate is a record unless start + 40 < last_end, the end of the
+ * row's last record (0 before the first): its first bit begins more than one bit before that record's closing flag ended.  A record
+ * sets last_end to its end.  That is the duplicate filter -- the other lanes' copies of a frame start at least 17 bytes before its
+ * end -- and the capacity bound: a frame takes 136 bits and its closing flag 8, so the ends of two records on one lane, or on lanes
+ * that saw the flag in the same slot, lie 144 bits apart, and a lane that opened one bit before the last record's end can close 143
+ * bits behind it; ends lie inside the call's 150 n bits, so a row has at most 1 + 150 n / 143 records in n batches.  Frames of 17
+ * bytes sharing their flags on one lane give 1 + (150 n - 1) / 144, which is the same number for n <= 20 (tests reach it).
+ * No timing moves: a lane's grid is fixed; the ten lanes four thirds apart are the tracker (DESIGN.md 5r has the clock offset the
+ * longest frame survives).
+ * Settings (mi_ax25_cfg, 0 = the default): gain[3], each finite and > 0, 0 = its default, MI_AX25_GAIN0 / 1 / 2; strict, 0 = on,
+ * MI_AX25_STRICT_OFF = off (1 = on, said out loud).
+ * Record: row; batch and third, where the first bit behind the opening flag begins (start / 6000 modulo 2^32 and start % 6000);
+ * end_batch, the call's batch in which the closing flag ended; nbytes 17 .. 330, the check's two included; lane; naddr; the raw
+ * bytes, zeros behind them.
+ * State: per row MI_AX25_STATE_ROW_BYTES = 10544 bytes, little-endian, a blob of zeros being a fresh state: float32 x[14], the last
+ * 14 input samples, oldest first; uint64 batch (batches seen, < 2^40); uint64 last_end; then per lane, 30 entries each: uint64 start;
+ * uint16 nbytes; uint16 crc (the register over every collected bit, the running byte's included); uint8 prev (the previous tone
+ * bit); uint8 ones (0 .. 7); uint8 phase (MI_AX25_WAIT / MI_AX25_FRAME); uint8 nbits and uint8 cur (the running byte's bits); then
+ * uint8 zero[2]; then bytes[30][332], a lane's whole bytes so far with zeros behind them.  A waiting lane's start, nbytes, crc, nbits,
+ * cur and bytes are all zero.  A disabled row writes nothing and every byte of its state stays.  NaN and Inf are unspecified.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_AX25_HISTORY = 14, MI_AX25_HYPOTHESES = 10, MI_AX25_SLICERS = 3, MI_AX25_LANES = 30, MI_AX25_BITS = 150, MI_AX25_BIT_WORDS = 5,
+       MI_AX25_MIN_BYTES = 17, MI_AX25_MAX_BYTES = 330, MI_AX25_RAW_BYTES = 332, MI_AX25_STATE_ROW_BYTES = 10544 };
+enum { MI_AX25_WAIT = 0, MI_AX25_FRAME = 1 };
+enum { MI_AX25_RESIDUE = 0xF0B8, MI_AX25_FLAG_RESIDUE = 0x9F0B }; /* the second: the first through the bits 0 1 1 1 1 1 */
+#define MI_AX25_STRICT_OFF 0x80000000u /* strict: frames whose address field is not well formed are records too */
+#define MI_AX25_GAIN0 1.0f
+#define MI_AX25_GAIN1 1.6432f /* sqrt(2.7) */
+#define MI_AX25_GAIN2 2.7f    /* tools/ax25_classes.py: 2.7002, +4.31 dB */
+typedef struct {
+    float gain[3];                  /* weight of the space power in slicer g's decision; 0 = the default */
+    uint32_t strict;                /* 0 or 1 = on; MI_AX25_STRICT_OFF */
+} mi_ax25_cfg;                      /* 16 bytes */
+typedef struct {
+    uint32_t row;
+    uint32_t batch, third;          /* where the first bit behind the opening flag begins */
+    uint32_t end_batch;             /* call-relative */
+    uint16_t nbytes;                /* 17 .. 330, the two of the check included */
+    uint8_t lane;                   /* 10 g + tau */
+    uint8_t naddr;                  /* 2 .. 10; 0: the address field is not well formed */
+    uint8_t bytes[332];             /* raw; zeros behind nbytes */
+} mi_ax25_frame;                    /* 352 bytes */
+typedef struct mi_ax25 mi_ax25;
+
+/* cfg NULL = every default.  row_enabled, rows and max_batches as for mi_acars_create.  max_frames: capacity of the caller's frame
+ * buffer, 0 = rows * the most records a row can have in max_batches batches, 1 + 150 * max_batches / 143.  The handle owns the
+ * scratch for a call's tone bits and frames. */
+int mi_ax25_create(const mi_ax25_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_frames, int gpu, mi_ax25** out);
+void mi_ax25_destroy(mi_ax25* s);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_ax25_set_rows(mi_ax25* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_bits             [rows][nbatches][3][10][5]  the packed tone bits, or NULL (the handle's scratch); 4-byte aligned.  A disabled
+ *                                                  row's are not written.
+ *   d_frames           [max_frames]                rows ascending, time order within a row (8-byte aligned)
+ *   d_row_first_frame  [rows + 1]                  exclusive prefix of the rows' frame counts
+ *   d_count            [2]                         number of frames, and min(that, max_frames) = the number stored
+ * Nothing is written at or beyond max_frames.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without atomics
+ * -- bits (one workgroup per (row, batch)), walk (one wave per row, a lane per deframer), scan, store, tails -- so every byte is the
+ * same on every run and equals mi_ax25_plan_host's. */
+int mi_ax25_process_device(mi_ax25* s, const float* d_plane, size_t row_stride, int nbatches, uint32_t* d_bits, mi_ax25_frame* d_frames,
+                           uint32_t* d_row_first_frame, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_ax25_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] frames.  frames and row_first_frame may each be NULL.  The one place that synchronises. */
+int mi_ax25_download(mi_ax25* s, void* hip_stream, mi_ax25_frame* frames, uint32_t* row_first_frame, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_AX25_STATE_ROW_BYTES bytes in the layout above (mi_ax25_plan_host reads and writes the same bytes).
+ * set_state refuses an impossible state: batch at or beyond 2^40, a position beyond the row's next batch (last_end, or a start in a
+ * frame), a start later than the lane's collected bits allow (start + 40 (8 nbytes + nbits) beyond where the lane's last slot ended:
+ * the capacity bound rests on it), zero not 0, and per lane prev beyond 1, ones beyond 7, an unknown phase, nbits beyond 7, cur beyond its nbits bits, nbytes
+ * beyond 330, a waiting lane with a frame field or a byte set, a crc that the bytes and the running bits do not give, a byte set
+ * behind the ones taken.  Both complete queued work first. */
+size_t mi_ax25_state_size(const mi_ax25* s);
+int mi_ax25_get_state(mi_ax25* s, void* buf, size_t len);
+int mi_ax25_set_state(mi_ax25* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bits, walk, scan, store, tails}.  tools/ax25_rate.py. */
+int mi_ax25_set_timing(mi_ax25* s, int on);
+int mi_ax25_last_launch_ms(mi_ax25* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same bits, frames and state blob byte for byte.  plane [rows][row_stride] (no alignment
+ * asked); state_inout rows * MI_AX25_STATE_ROW_BYTES bytes, read and updated; bits [rows][nbatches][3][10][5] or NULL; frames holds
+ * max_frames entries (max_frames >= 1), of which min(count[0], max_frames) = count[1] are written. */
+int mi_ax25_plan_host(const mi_ax25_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                      void* state_inout, uint32_t* bits, mi_ax25_frame* frames, size_t max_frames, uint32_t* row_first_frame,
+                      uint32_t* count /* [2] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in (strict as 1 or MI_AX25_STRICT_OFF), or the refusal
+ * mi_ax25_create would give. */
+int mi_ax25_settings(const mi_ax25_cfg* cfg, mi_ax25_cfg* out);
+/* The four templates, T[i][rho] at t[40 i + rho].  Host only. */
+int mi_ax25_templates(float* t /* [160] */);
+/* CRC-16/X.25 of n bytes, complemented as it is sent: 0x906E for "123456789" (NULL with n = 0 is fine; NULL otherwise gives
+ * 0xFFFFFFFF, which no CRC is).  A frame's bytes with the check behind them, low byte first, give 0x0F47 = ~0xF0B8. */
+uint32_t mi_ax25_crc(const uint8_t* bytes, size_t n);
+/* The TNC2 line of a record, NUL-terminated, into text[cap]: SRC-S>DST-S,DIGI-S*,..:info -- the destination is the frame's first
+ * address, the source its second; callsigns without their trailing spaces; a zero SSID (bits 1 .. 4 of an address's last byte) is
+ * omitted; '*' behind the last digipeater whose H bit (bit 7 of its last byte) is set; info = the bytes behind control and PID (behind
+ * control alone where the control byte is not 0x03 / 0x13, a UI frame's) up to the check, a byte outside 0x20 .. 0x7E written as '.'.
+ * Refuses nbytes outside 17 .. 330, an address field that is not well formed (what strict refuses), and a cap the line does not fit
+ * (MI_AX25_TEXT_BYTES always fits). */
+enum { MI_AX25_TEXT_BYTES = 384 };
+int mi_ax25_frame_text(const mi_ax25_frame* f, char* text, size_t cap);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
