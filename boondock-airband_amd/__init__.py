@@ -263,6 +263,27 @@ AX25_STATE_DTYPE = np.dtype([("x", "<f4", (AX25_HISTORY,)), ("batch", "<u8"), ("
                              ("bytes", "u1", (AX25_LANES, AX25_RAW_BYTES))])
 
 
+class PocsagCfg(C.Structure):  # mi_pocsag_cfg: 0 = the default of every setting
+    _fields_ = [("baud", C.c_uint32), ("sync_errors", C.c_uint32), ("preamble_errors", C.c_uint32), ("correct", C.c_uint32), ("hold_timing", C.c_uint32)]
+
+
+POCSAG_HISTORY, POCSAG_MAX_HYPOTHESES, POCSAG_MAX_LANES, POCSAG_MAX_WORDS, POCSAG_TEXT_BYTES = 34, 15, 30, 80, 408
+POCSAG_IDLE, POCSAG_TRANSMISSION = 0, 1  # MI_POCSAG_*
+POCSAG_TEXT_AUTO, POCSAG_TEXT_NUMERIC, POCSAG_TEXT_ALPHA = 0, 1, 2
+POCSAG_SYNC, POCSAG_IDLE_WORD = 0x7CD215D8, 0x7A89C197
+POCSAG_SYNC_EXACT = 0x80000000  # mi_pocsag_cfg.sync_errors: no mismatch allowed
+POCSAG_PREAMBLE_EXACT, POCSAG_PREAMBLE_OFF = 0x80000000, 0x80000001  # mi_pocsag_cfg.preamble_errors: none allowed; the condition dropped
+POCSAG_CORRECT_NONE = 0x80000000  # mi_pocsag_cfg.correct: a word is good only as received
+POCSAG_WALKER_FIELDS = ("lane", "inverted", "pos", "cur", "nbits", "gbad", "lane_sync", "mismatches", "wbatch", "wtwelfth", "open")
+# mi_pocsag_message (368 bytes) and one row of the pager stage's state blob, MI_POCSAG_STATE_ROW_BYTES = 800
+POCSAG_MESSAGE_DTYPE = np.dtype([("row", "<u4"), ("batch", "<u4"), ("twelfth", "<u4"), ("end_batch", "<u4"), ("address", "<u4"), ("function", "u1"),
+                                 ("nwords", "u1"), ("nbad", "u1"), ("truncated", "u1"), ("corrected", "<u2"), ("inverted", "u1"), ("sync_errors", "u1"),
+                                 ("lane_sync", "u1"), ("lane_end", "u1"), ("zero", "<u2"), ("bad", "<u4", (3,)), ("zero2", "<u4"),
+                                 ("words", "<u4", (POCSAG_MAX_WORDS,))])
+POCSAG_STATE_DTYPE = np.dtype([("x", "<f4", (POCSAG_HISTORY,)), ("batch", "<u4"), ("phase", "<u4"), ("hist", "<u8", (POCSAG_MAX_LANES,))] +
+                              [(n, "<u4") for n in POCSAG_WALKER_FIELDS + ("zero",)] + [("msg", POCSAG_MESSAGE_DTYPE)])
+
+
 class AspecCfg(C.Structure):  # mi_aspec_cfg: 0 = 60 / 3800
     _fields_ = [("lo_hz", C.c_uint32), ("hi_hz", C.c_uint32)]
 
@@ -381,6 +402,9 @@ ABI_SYMBOLS = [
     "mi_ax25_create", "mi_ax25_destroy", "mi_ax25_set_rows", "mi_ax25_process_device", "mi_ax25_download", "mi_ax25_state_size",
     "mi_ax25_get_state", "mi_ax25_set_state", "mi_ax25_set_timing", "mi_ax25_last_launch_ms", "mi_ax25_plan_host", "mi_ax25_settings",
     "mi_ax25_templates", "mi_ax25_crc", "mi_ax25_frame_text",
+    "mi_pocsag_create", "mi_pocsag_destroy", "mi_pocsag_set_rows", "mi_pocsag_process_device", "mi_pocsag_download", "mi_pocsag_state_size",
+    "mi_pocsag_get_state", "mi_pocsag_set_state", "mi_pocsag_set_timing", "mi_pocsag_last_launch_ms", "mi_pocsag_plan_host", "mi_pocsag_settings",
+    "mi_pocsag_geometry", "mi_pocsag_max_messages", "mi_pocsag_encode", "mi_pocsag_decode", "mi_pocsag_message_text",
     "mi_survey_create", "mi_survey_destroy", "mi_survey_set_streams", "mi_survey_bytes_needed", "mi_survey_process_device", "mi_survey_set_timing",
     "mi_survey_last_launch_ms", "mi_survey_bin_range",
     "mi_occupancy_create", "mi_occupancy_destroy", "mi_occupancy_set_streams", "mi_occupancy_process_device", "mi_occupancy_download",
@@ -590,6 +614,27 @@ def lib():
         L.mi_ax25_crc.argtypes = [vp, sz]
         L.mi_ax25_crc.restype = C.c_uint32
         L.mi_ax25_frame_text.argtypes = [vp, C.c_char_p, sz]
+        L.mi_pocsag_create.argtypes = [C.POINTER(PocsagCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
+        L.mi_pocsag_destroy.argtypes = [vp]
+        L.mi_pocsag_destroy.restype = None
+        L.mi_pocsag_set_rows.argtypes = [vp, vp]
+        L.mi_pocsag_process_device.argtypes = [vp, vp, sz, C.c_int, vp, vp, vp, vp, vp, vp]
+        L.mi_pocsag_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mi_pocsag_state_size.argtypes = [vp]
+        L.mi_pocsag_state_size.restype = sz
+        L.mi_pocsag_get_state.argtypes = [vp, vp, sz]
+        L.mi_pocsag_set_state.argtypes = [vp, vp, sz]
+        L.mi_pocsag_set_timing.argtypes = [vp, C.c_int]
+        L.mi_pocsag_last_launch_ms.argtypes = [vp, vp]
+        L.mi_pocsag_plan_host.argtypes = [C.POINTER(PocsagCfg), vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+        L.mi_pocsag_settings.argtypes = [C.POINTER(PocsagCfg), C.POINTER(PocsagCfg)]
+        L.mi_pocsag_geometry.argtypes = [C.c_uint32, vp, vp, vp]
+        L.mi_pocsag_max_messages.argtypes = [C.c_uint32, C.c_uint64]
+        L.mi_pocsag_max_messages.restype = C.c_uint32
+        L.mi_pocsag_encode.argtypes = [C.c_uint32]
+        L.mi_pocsag_encode.restype = C.c_uint32
+        L.mi_pocsag_decode.argtypes = [C.c_uint32, C.c_uint32, vp, vp]
+        L.mi_pocsag_message_text.argtypes = [vp, C.c_int, C.c_char_p, sz]
         L.mi_elt_create.argtypes = [C.POINTER(EltCfg), vp, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]
         L.mi_elt_destroy.argtypes = [vp]
         L.mi_elt_destroy.restype = None
@@ -760,7 +805,7 @@ class _TimedStage(_Handle):
 
     def last_launch_ms(self):
         """(diagnostic) ms of each launch of the last call made with set_timing(True): the gate's rank pass, scan and block copy;
-        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails; the SAME stage's bits, walk, scan, store and tails; the ELT stage's bank, walk, scan, store and tails;
+        the splitter's walk, scan, block statistics and combine pass; the tone finder's walk, scan and bank; the PCM stage's encoder and tail copy; the audio spectrum stage's blocks and row means; the voice band stage's filter and tail copy; the limiter stage's limiter and tail copy; the noise reduction stage's floor, apply and tails; the SELCAL stage's bank, walk, scan, store and tails; the ACARS stage's bits, walk, scan, store and tails; the SAME stage's bits, walk, scan, store and tails; the ELT stage's bank, walk, scan, store and tails; the packet and the pager stage's bits, walk, scan, store and tails;
         the survey's windows and fold; the channel finder's bin records, run starts, scan and candidates; the probe's windows and reduction"""
         ms = (C.c_float * self._launches)()
         self._call("last_launch_ms", C.cast(ms, C.c_void_p))
@@ -774,7 +819,7 @@ class _PostStage(_TimedStage):
         """The state blob as bytes (*_get_state): the gate's carried flags, one per row; the splitter's rows * 32 bytes, whose
         fields .view(TX_STATE_DTYPE) names; the tone finder's rows * 520 bytes, .view(TONES_STATE_DTYPE); the PCM stage's rows * 248,
         .view(PCM_STATE_DTYPE); the voice band stage's rows * 2040, .view(VBAND_STATE_DTYPE); the limiter stage's rows * 4344, .view(LIMIT_STATE_DTYPE); the noise reduction stage's rows * 9196, .view(DENOISE_STATE_DTYPE); the SELCAL stage's rows * 4048,
-        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE); the ELT stage's rows * 776, .view(ELT_STATE_DTYPE); the packet stage's rows * 10544, .view(AX25_STATE_DTYPE).  The audio spectrum stage has none."""
+        .view(SELCAL_STATE_DTYPE); the ACARS stage's rows * 496, .view(ACARS_STATE_DTYPE); the SAME stage's rows * 1160, .view(SAME_STATE_DTYPE); the ELT stage's rows * 776, .view(ELT_STATE_DTYPE); the packet stage's rows * 10544, .view(AX25_STATE_DTYPE); the pager stage's rows * 800, .view(POCSAG_STATE_DTYPE).  The audio spectrum stage has none."""
         n = getattr(lib(), f"{self._prefix}_state_size")(self._h)
         buf = np.zeros(n, np.uint8)
         self._call("get_state", _ptr(buf), n)
@@ -2055,6 +2100,124 @@ def ax25_plan_host(row_enabled, plane, cfg=None, state=None, max_frames=0, nbatc
     _check(lib().mi_ax25_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(frames), cap,
                                    _ptr(row_first), _ptr(count)))
     return frames[:int(count[1])], bits, row_first, count, state
+
+
+def pocsag_cfg(baud=0, sync_errors=0, preamble_errors=0, correct=0, hold_timing=False):
+    """mi_pocsag_cfg, field for field as the C struct takes it: baud 512, 1200 or 2400, 0 (or None) = 1200; sync_errors 1 .. 4
+    mismatches a sync may have, 0 = the default, 2, and POCSAG_SYNC_EXACT for none; preamble_errors 1 .. 8 mismatches of the 32 bits
+    before it, 0 = the default, 4, POCSAG_PREAMBLE_EXACT for none, POCSAG_PREAMBLE_OFF to drop the condition; correct: the bits a
+    word may have repaired, 1 (0 = the default) or 2, POCSAG_CORRECT_NONE for none; hold_timing: no timing moves.  A PocsagCfg passes
+    through."""
+    if isinstance(baud, PocsagCfg):
+        return baud
+    c = PocsagCfg()
+    c.baud, c.sync_errors, c.preamble_errors, c.correct, c.hold_timing = int(baud or 0), int(sync_errors or 0), int(preamble_errors or 0), int(correct or 0), int(hold_timing)
+    return c
+
+
+def pocsag_settings(cfg=None):
+    """mi_pocsag_settings: the settings with every default filled in, as a PocsagCfg"""
+    out = PocsagCfg()
+    _check(lib().mi_pocsag_settings(C.byref(pocsag_cfg(cfg)), C.byref(out)))
+    return out
+
+
+def pocsag_geometry(baud=0):
+    """mi_pocsag_geometry: (hypotheses H, bits of a batch and hypothesis B, words W) of a baud"""
+    h, b, w = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().mi_pocsag_geometry(int(baud or 0), C.byref(h), C.byref(b), C.byref(w)))
+    return h.value, b.value, w.value
+
+
+def pocsag_max_messages(nbatches, baud=0):
+    """mi_pocsag_max_messages: the most messages one row can close in a call of nbatches batches, 1 + (nbatches (B + 1) - 1) // 32"""
+    pocsag_geometry(baud)  # (the refusal of a baud the stage does not have)
+    return int(lib().mi_pocsag_max_messages(int(baud or 0), int(nbatches)))
+
+
+def pocsag_encode(data21):
+    """mi_pocsag_encode: the codeword of 21 data bits"""
+    return int(lib().mi_pocsag_encode(int(data21)))
+
+
+def pocsag_decode(word, correct=0):
+    """mi_pocsag_decode: (good, the word as stored, e) by the walker's rule for one word under the setting `correct`"""
+    fixed, errors = C.c_uint32(), C.c_uint32()
+    rc = lib().mi_pocsag_decode(int(word), int(correct), C.byref(fixed), C.byref(errors))
+    if rc < 0:
+        _check(rc)
+    return bool(rc), fixed.value, errors.value
+
+
+def pocsag_message_text(message, mode=POCSAG_TEXT_AUTO):
+    """mi_pocsag_message_text: a record's text as a str: POCSAG_TEXT_NUMERIC, POCSAG_TEXT_ALPHA, or by its function (AUTO)"""
+    m = np.array(message, POCSAG_MESSAGE_DTYPE).reshape(1)
+    out = C.create_string_buffer(POCSAG_TEXT_BYTES)
+    _check(lib().mi_pocsag_message_text(_ptr(m), mode, out, POCSAG_TEXT_BYTES))
+    return out.value.decode("ascii")
+
+
+class Pocsag(_PostStage):
+    """mi_pocsag: the pager decoder stage -- per row, the pages its 512 / 1200 / 2400 bit/s POCSAG transmissions carried: a bank of
+    bit sums under H timing hypotheses and two slicers per batch, a sync compare of both polarities on every lane while the row is
+    idle, and a walker that reads the codewords, repairs them by BCH(31,21), assembles the messages and follows the timing.  It reads
+    a plane of audio as Acars does and needs no flags.  row_enabled: truth value per row; cfg: pocsag_cfg(...) or None;
+    max_messages: capacity of the message buffer, 0 = rows * pocsag_max_messages(max_batches, baud).  state() gives rows * 800 bytes,
+    whose fields .view(POCSAG_STATE_DTYPE) names."""
+    _destroy, _prefix, _launches = "mi_pocsag_destroy", "mi_pocsag", 5
+
+    def __init__(self, row_enabled, max_batches=1, cfg=None, max_messages=0, gpu=0):
+        en = _flags(row_enabled)
+        self.cfg = pocsag_cfg(cfg)
+        self.rows, self.max_batches = en.size, max_batches
+        self._h = C.c_void_p()
+        _check(lib().mi_pocsag_create(C.byref(self.cfg), _ptr(en), self.rows, max_batches, max_messages, gpu, C.byref(self._h)))
+        self.hypotheses, self.bits, self.words = pocsag_geometry(self.cfg.baud)
+        most = self.rows * pocsag_max_messages(max_batches, self.cfg.baud)
+        self.max_messages = min(max_messages, most) if max_messages else most
+
+    def set_rows(self, row_enabled):
+        en = _flags(row_enabled)
+        assert en.size == self.rows
+        _check(lib().mi_pocsag_set_rows(self._h, _ptr(en)))
+
+    def process_device(self, d_plane, row_stride, nbatches, d_messages, d_row_first_message, d_count, d_bits=None, d_q=None, hip_stream=None):
+        """Raw device pointers (ints; d_bits and d_q may be None), the stride in floats; asynchronous on hip_stream."""
+        _check(lib().mi_pocsag_process_device(self._h, d_plane, row_stride, nbatches, d_bits, d_q, d_messages, d_row_first_message, d_count, hip_stream))
+
+    def download(self, hip_stream=None):
+        """Results of the last process_device (enqueued on hip_stream): (messages [k] of POCSAG_MESSAGE_DTYPE, row_first_message
+        [rows + 1], count [2]) with k = count[1]."""
+        messages = np.zeros(self.max_messages, POCSAG_MESSAGE_DTYPE)
+        row_first = np.empty(self.rows + 1, np.uint32)
+        count = np.zeros(2, np.uint32)
+        _check(lib().mi_pocsag_download(self._h, hip_stream, _ptr(messages), _ptr(row_first), _ptr(count)))
+        return messages[:int(count[1])], row_first, count
+
+
+def pocsag_plan_host(row_enabled, plane, cfg=None, state=None, max_messages=0, nbatches=None):
+    """mi_pocsag_plan_host: the pager stage's bits, Q and messages from audio on the host, no GPU.  plane: float32 [rows][row_stride];
+    state: the blob (rows * 800 bytes) or None (a fresh one, zeros); nbatches: batches of the call, default row_stride // 2000;
+    max_messages: 0 = every message of the call.  Returns (messages [count[1]], bits [rows][nbatches][2][H][W], q [rows][nbatches][2][H],
+    row_first_message [rows + 1], count [2], state after the call).  A disabled row's bits and q stay zero."""
+    en = _flags(row_enabled)
+    plane = np.ascontiguousarray(plane, dtype=np.float32)
+    assert plane.ndim == 2 and plane.shape[0] == en.size
+    rows = en.size
+    nb = plane.shape[1] // WAVE_BATCH if nbatches is None else nbatches
+    c = pocsag_cfg(cfg)
+    H, _, W = pocsag_geometry(c.baud)
+    state = np.zeros(rows * POCSAG_STATE_DTYPE.itemsize, np.uint8) if state is None else np.array(state, copy=True).view(np.uint8).reshape(-1)
+    assert state.size == rows * POCSAG_STATE_DTYPE.itemsize
+    cap = max_messages or max(1, rows * pocsag_max_messages(max(nb, 1), c.baud))
+    messages = np.zeros(cap, POCSAG_MESSAGE_DTYPE)
+    bits = np.zeros((rows, max(nb, 0), 2, H, W), np.uint32)
+    q = np.zeros((rows, max(nb, 0), 2, H), np.float32)
+    row_first = np.empty(rows + 1, np.uint32)
+    count = np.zeros(2, np.uint32)
+    _check(lib().mi_pocsag_plan_host(C.byref(c), _ptr(en), rows, nb, _ptr(plane), plane.shape[1], _ptr(state), _ptr(bits), _ptr(q), _ptr(messages), cap,
+                                     _ptr(row_first), _ptr(count)))
+    return messages[:int(count[1])], bits, q, row_first, count, state
 
 
 def same_cfg(sync_errors=0, max_bad=0, gap_batches=0, min_quality=0.0, space_gain=0.0, hold_timing=False):

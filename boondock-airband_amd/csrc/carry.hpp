@@ -1,4 +1,4 @@
-// carry.hpp -- the device side of a stage that carries samples from call to call (pcm.hip, vband.hip, limit.hip, selcal.hip, acars.hip, same.hip, elt.hip, ax25.hip): a row's state is
+// carry.hpp -- the device side of a stage that carries samples from call to call (pcm.hip, vband.hip, limit.hip, selcal.hip, acars.hip, same.hip, elt.hip, ax25.hip, pocsag.hip): a row's state is
 // the last kHistory input samples of its last call, oldest first, and a block is staged behind a LEAD of kLead = kHistory + 2 floats --
 // two that no output reaches, then the history -- so that the lead is whole float4 of the row's previous batch wherever there is one.
 // (k_limit stages its lead with the text of load_lead4 written out: DESIGN.md section 6.)

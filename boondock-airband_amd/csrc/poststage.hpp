@@ -1,4 +1,4 @@
-// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, elt.hip, ax25.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
+// poststage.hpp -- what the post-stages (outgate.hip, txsplit.hip, tones.hip, pcm.hip, aspec.hip, vband.hip, limit.hip, denoise.hip, selcal.hip, acars.hip, same.hip, elt.hip, ax25.hip, pocsag.hip, mixer.hip, gather.hip, survey.hip, occupancy.hip, probe.hip) and the host twins (poststage_host.cpp)
 // share on the host side: the error helper, argument checks, launch timing, the handle bases (Stage, BatchStage, RowStage, IqFront)
 // with the bodies of the entry points every handle repeats (geometry, set_rows, set_timing, last_launch_ms, destroy, the state blob in
 // and out, the checks of a plane-in / plane-out call, the create checks, table upload, I/Q checks and kernel arguments of an I/Q front
@@ -1270,5 +1270,212 @@ inline uint32_t ax25_naddr(const uint8_t* b, const uint32_t nbytes) {
 int ax25_plan(const mi_ax25_cfg* cfg, Ax25Plan* out);
 void ax25_templates(float* t);
 const char* ax25_state_ok(const Ax25RowState* state, size_t rows);
+
+// The pager decoder stage (include/mi_airband.h "pager decoder stage").  One row of its state: the checkpoint blob is an array of
+// these, and pocsag.hip keeps the same array in device memory.
+struct PocsagRowState {
+    float x[MI_POCSAG_HISTORY];             // the last 34 input samples of the row's last batch, oldest first
+    uint32_t batch;                         // batches seen since creation / set_state
+    uint32_t phase;                         // MI_POCSAG_IDLE / MI_POCSAG_TRANSMISSION
+    uint64_t hist[MI_POCSAG_MAX_LANES];     // per lane the last 64 bits, the newest in bit 0
+    uint32_t lane, inverted, pos, cur, nbits, gbad, lane_sync, mismatches, wbatch, wtwelfth, open, zero;
+    mi_pocsag_message msg;                  // the open message as the record has it so far
+};
+static_assert(sizeof(PocsagRowState) == MI_POCSAG_STATE_ROW_BYTES && offsetof(PocsagRowState, batch) == 136 && offsetof(PocsagRowState, hist) == 144 &&
+                  offsetof(PocsagRowState, lane) == 384 && offsetof(PocsagRowState, msg) == 432 && sizeof(mi_pocsag_message) == 368 &&
+                  offsetof(mi_pocsag_message, corrected) == 24 && offsetof(mi_pocsag_message, lane_end) == 29 && offsetof(mi_pocsag_message, bad) == 32 &&
+                  offsetof(mi_pocsag_message, words) == 48 && sizeof(mi_pocsag_cfg) == 20 && (MI_POCSAG_HISTORY + 2) % 4 == 0 &&
+                  MI_POCSAG_MAX_LANES == 2 * MI_POCSAG_MAX_HYPOTHESES && MI_POCSAG_MAX_WORDS <= 96,
+              "the pager stage's blob, record and settings layouts are ABI");
+// The grid of a baud: a bit's twelfths, the hypotheses' distance, their number, the bits and the words of a batch and hypothesis.
+struct PocsagGeom {
+    int L, step, H, B, W;
+};
+__host__ __device__ inline PocsagGeom pocsag_geom(const uint32_t baud) {  // (baud: 512, 1200 or 2400)
+    return baud == 512 ? PocsagGeom{375, 25, 15, 64, 2} : baud == 2400 ? PocsagGeom{80, 8, 10, 300, 10} : PocsagGeom{160, 16, 10, 150, 5};
+}
+constexpr int kPocsagTwelfths = 12 * kWaveBatch;
+constexpr uint32_t kPocsagNoHit = 99, kPocsagNoPattern = 1;
+// The settings with every default filled in, as both halves take them.
+struct PocsagPlan {
+    PocsagGeom g;
+    uint32_t sync_errors;      // the number itself, 0 .. 4
+    uint32_t preamble_errors;  // the number itself, 0 .. 8; 32 where the condition is off (no 32 bits are further than 16 from both phases)
+    uint32_t correct;          // the number itself, 0 .. 2
+    uint32_t hold_timing;
+    mi_pocsag_cfg filled;      // the settings as the caller would have written them
+};
+// The walker's part of a row's state, as the walk carries it in registers; the open message stays in memory beside it.
+struct PocsagWalker {
+    uint32_t phase, lane, inverted, pos, cur, nbits, gbad, lane_sync, mismatches, wbatch, wtwelfth, open;
+};
+// the most messages one row can close in a call: the first word can end with the call's first bit, each further one takes 32 of
+// the n B slots and the at most n bits that the moves 1 -> 0 add
+inline uint32_t pocsag_max_messages(const PocsagGeom& g, uint64_t nbatches) {
+    return static_cast<uint32_t>(1 + (nbatches * static_cast<uint64_t>(g.B + 1) - 1) / 32);
+}
+// Where slot j of hypothesis tau begins, in twelfths from the batch's first sample (negative: in the batch before).
+__host__ __device__ inline int pocsag_slot_begin(const PocsagGeom& g, const int tau, const int j) {
+    return tau * g.step + g.L * (j - (tau > 0));
+}
+// Slot j of hypothesis tau over what is staged for a block -- s[kLead + n] is the block's sample n, kLead = MI_POCSAG_HISTORY + 2 --:
+// the sum of the bit's samples, and their number into *k.  Host and device run this text.
+__host__ __device__ inline float pocsag_sum(const float* s, const PocsagGeom& g, const int tau, const int j, int* k) {
+    const int t0 = pocsag_slot_begin(g, tau, j);  // -350 .. 24000 - L
+    const int n0 = (t0 + 371) / 12 - 30;          // ceil(t0 / 12), -29 ..
+    const int n1 = (t0 + g.L + 371) / 12 - 30;    // .. 2000
+    const float* const x = s + (MI_POCSAG_HISTORY + 2) + n0;
+    float a = x[0];
+    for (int i = 1; i < n1 - n0; ++i)
+        a = a + x[i];
+    *k = n1 - n0;
+    return a;
+}
+// The remainder of a word's bits 31 .. 1 under the generator 0x769.
+__host__ __device__ inline uint32_t pocsag_syndrome(const uint32_t word) {
+    uint32_t r = word >> 1;
+    for (int i = 30; i >= 10; --i)
+        if (r >> i & 1u)
+            r ^= 0x769u << (i - 10);
+    return r;
+}
+// One word by the header's rule, table[syndrome] = the error pattern of weight <= 2 in bits 31 .. 1 (kPocsagNoPattern: none): e, the
+// word being good where e <= correct; *fixed = the word repaired (as received where there is no pattern, e = 3).
+__host__ __device__ inline uint32_t pocsag_repair(const uint32_t* table, const uint32_t word, uint32_t* fixed) {
+    const uint32_t pat = table[pocsag_syndrome(word)];
+    if (pat == kPocsagNoPattern) {
+        *fixed = word;
+        return 3u;
+    }
+    uint32_t f = word ^ pat, e = static_cast<uint32_t>(__builtin_popcount(pat));
+    if (__builtin_popcount(f) & 1) {
+        f ^= 1u;
+        ++e;
+    }
+    *fixed = f;
+    return e;
+}
+// A lane's last 64 bits against SYNC, its complement and the preamble: the sync mismatches of a hit, else kPocsagNoHit.
+__host__ __device__ inline uint32_t pocsag_hit(const uint64_t h, const uint32_t sync_errors, const uint32_t preamble_errors, uint32_t* inverted) {
+    uint32_t m = static_cast<uint32_t>(__builtin_popcount(static_cast<uint32_t>(h) ^ MI_POCSAG_SYNC));
+    *inverted = m > 16u;
+    if (m > 16u)
+        m = 32u - m;
+    uint32_t p = static_cast<uint32_t>(__builtin_popcount(static_cast<uint32_t>(h >> 32) ^ 0xAAAAAAAAu));
+    if (p > 16u)
+        p = 32u - p;
+    return m <= sync_errors && p <= preamble_errors ? m : kPocsagNoHit;
+}
+// The lane a sync opens the transmission on: mism[lane] = pocsag_hit's answer, q[lane] = Q of the slot's batch; -1: no hit.
+__host__ __device__ inline int pocsag_pick(const uint32_t* mism, const float* q, const int lanes) {
+    int best = -1;
+    for (int t = 0; t < lanes; ++t) {
+        if (mism[t] == kPocsagNoHit)
+            continue;
+        if (best < 0 || mism[t] < mism[best] || (mism[t] == mism[best] && q[t] > q[best]))
+            best = t;
+    }
+    return best;
+}
+__host__ __device__ inline void pocsag_open(PocsagWalker& w, const int lane, const uint32_t inverted, const uint32_t mismatches) {
+    w = PocsagWalker{};
+    w.phase = MI_POCSAG_TRANSMISSION;
+    w.lane = w.lane_sync = static_cast<uint32_t>(lane);
+    w.inverted = inverted;
+    w.mismatches = mismatches;
+}
+// The timing move at a batch's first slot inside a transmission, from the new batch's Q.
+enum { kPocsagInStep = 0, kPocsagSkip = 1, kPocsagReplay = 2 };
+__host__ __device__ inline int pocsag_retime(PocsagWalker& w, const float* q, const int H) {
+    const uint32_t h = static_cast<uint32_t>(H), base = w.lane / h * h, u = w.lane - base, um = (u + h - 1) % h, up = (u + 1) % h;
+    uint32_t v = u;
+    if (q[base + um] > q[base + v])
+        v = um;
+    if (q[base + up] > q[base + v])
+        v = up;
+    w.lane = base + v;
+    return u == 0 && v == 1 ? kPocsagSkip : u == 1 && v == 0 ? kPocsagReplay : kPocsagInStep;
+}
+// The open message closes: emit() takes the record out of *msg (the caller adds row, end_batch and lane_end), then it is cleared.
+template <class Emit>
+__host__ __device__ inline void pocsag_close(PocsagWalker& w, mi_pocsag_message* msg, Emit& emit) {
+    if (!w.open)
+        return;
+    emit();
+    const uint32_t n = offsetof(mi_pocsag_message, words) / 4 + msg->nwords;
+    for (uint32_t i = 0; i < n; ++i)
+        reinterpret_cast<uint32_t*>(msg)[i] = 0;
+    w.open = 0;
+}
+// The walker's running word is whole: what it does to the group, the open message and the transmission.  Host and device run this
+// text, the device with wave-uniform values and every lane writing the same bytes of *msg.
+template <class Emit>
+__host__ __device__ inline void pocsag_word(PocsagWalker& w, mi_pocsag_message* msg, const uint32_t* table, const uint32_t sync_errors, const uint32_t correct,
+                                            Emit& emit) {
+    const uint32_t word = w.cur;
+    w.cur = w.nbits = 0;
+    if (w.pos == 16) {  // the SYNC behind word 15
+        if (static_cast<uint32_t>(__builtin_popcount(word ^ MI_POCSAG_SYNC)) <= sync_errors) {
+            w.pos = w.gbad = 0;
+        } else {
+            pocsag_close(w, msg, emit);
+            w = PocsagWalker{};
+        }
+        return;
+    }
+    uint32_t fixed;
+    const uint32_t e = pocsag_repair(table, word, &fixed);
+    const bool good = e <= correct;
+    if (good && fixed == MI_POCSAG_IDLE_WORD) {
+        pocsag_close(w, msg, emit);
+    } else if (good && !(fixed >> 31)) {
+        pocsag_close(w, msg, emit);
+        msg->batch = w.wbatch;
+        msg->twelfth = w.wtwelfth;
+        msg->address = (fixed >> 13 & 0x3FFFFu) << 3 | w.pos >> 1;
+        msg->function = static_cast<uint8_t>(fixed >> 11 & 3u);
+        msg->corrected = static_cast<uint16_t>(e);
+        msg->inverted = static_cast<uint8_t>(w.inverted);
+        msg->sync_errors = static_cast<uint8_t>(w.mismatches);
+        msg->lane_sync = static_cast<uint8_t>(w.lane_sync);
+        w.open = 1;
+    } else if (w.open) {
+        const uint32_t i = msg->nwords;
+        if (i == MI_POCSAG_MAX_WORDS) {
+            msg->truncated = 1;
+        } else {
+            msg->words[i] = good ? fixed : word;
+            if (good) {
+                msg->corrected = static_cast<uint16_t>(msg->corrected + e);
+            } else {
+                msg->bad[i / 32] |= 1u << (i % 32);
+                msg->nbad = static_cast<uint8_t>(msg->nbad + 1);
+            }
+            msg->nwords = static_cast<uint8_t>(i + 1);
+        }
+    }
+    w.gbad += good ? 0u : 1u;
+    if (++w.pos == 16 && w.gbad == 16) {
+        pocsag_close(w, msg, emit);
+        w = PocsagWalker{};
+    }
+}
+// One bit, polarity undone, that begins t twelfths from the first sample of the row's batch number `batch`, into the running word.
+template <class Emit>
+__host__ __device__ inline void pocsag_take(PocsagWalker& w, mi_pocsag_message* msg, const uint32_t* table, const uint32_t sync_errors, const uint32_t correct,
+                                            const uint32_t bit, const uint32_t batch, const int t, Emit& emit) {
+    if (w.nbits == 0) {
+        w.wbatch = t < 0 ? batch - 1u : batch;
+        w.wtwelfth = static_cast<uint32_t>(t < 0 ? t + kPocsagTwelfths : t);
+    }
+    w.cur = w.cur << 1 | bit;
+    if (++w.nbits == 32)
+        pocsag_word(w, msg, table, sync_errors, correct, emit);
+}
+// What both halves of the pager stage share (poststage_host.cpp).  pocsag_plan: MI_OK with the plan, or the settings' refusal with
+// its message set.  pocsag_table: t[1024].  pocsag_state_ok: NULL, or what is impossible about a blob on a handle of the plan's baud.
+int pocsag_plan(const mi_pocsag_cfg* cfg, PocsagPlan* out);
+void pocsag_table(uint32_t* t);
+const char* pocsag_state_ok(const PocsagRowState* state, size_t rows, const PocsagPlan& plan);
 
 }  // namespace mi

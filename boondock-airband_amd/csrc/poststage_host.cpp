@@ -2729,3 +2729,329 @@ extern "C" int mi_ax25_plan_host(const mi_ax25_cfg* cfg, const uint8_t* row_enab
     std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::Ax25RowState));
     return MI_OK;
 }
+
+// ---- pager decoder stage, host side (include/mi_airband.h "pager decoder stage"): the settings' check, the syndrome table, the
+// blob's check, the codeword helpers, a message's text, and the twin of pocsag.hip -- one row, one batch, one hypothesis and one
+// slot at a time, then the walker over the batch's slots.  The bit's sum, the sync compare and choice, the word's rule and the timing
+// move are poststage.hpp's.
+namespace mi {
+
+int pocsag_plan(const mi_pocsag_cfg* cfg, PocsagPlan* out) {
+    mi_pocsag_cfg c{};
+    if (cfg)
+        c = *cfg;
+    if (c.baud == 0)
+        c.baud = 1200;
+    if (c.baud != 512 && c.baud != 1200 && c.baud != 2400)
+        return fail(MI_ERR_INVALID, "pager stage: baud must be 512, 1200 or 2400 (0 = the default, 1200)");
+    if (c.sync_errors == 0)
+        c.sync_errors = 2;
+    if (c.sync_errors != MI_POCSAG_SYNC_EXACT && c.sync_errors > 4)
+        return fail(MI_ERR_INVALID, "pager stage: sync_errors must be within 1 .. 4 or MI_POCSAG_SYNC_EXACT (0 = the default)");
+    if (c.preamble_errors == 0)
+        c.preamble_errors = 4;
+    if (c.preamble_errors != MI_POCSAG_PREAMBLE_EXACT && c.preamble_errors != MI_POCSAG_PREAMBLE_OFF && c.preamble_errors > 8)
+        return fail(MI_ERR_INVALID, "pager stage: preamble_errors must be within 1 .. 8, MI_POCSAG_PREAMBLE_EXACT or MI_POCSAG_PREAMBLE_OFF (0 = the default)");
+    if (c.correct == 0)
+        c.correct = 1;
+    if (c.correct != MI_POCSAG_CORRECT_NONE && c.correct > 2)
+        return fail(MI_ERR_INVALID, "pager stage: correct must be 1, 2 or MI_POCSAG_CORRECT_NONE (0 = the default)");
+    if (c.hold_timing > 1)
+        return fail(MI_ERR_INVALID, "pager stage: hold_timing must be 0 or 1");
+    PocsagPlan p{};
+    p.g = pocsag_geom(c.baud);
+    p.sync_errors = c.sync_errors == MI_POCSAG_SYNC_EXACT ? 0u : c.sync_errors;
+    p.preamble_errors = c.preamble_errors == MI_POCSAG_PREAMBLE_EXACT ? 0u : c.preamble_errors == MI_POCSAG_PREAMBLE_OFF ? 32u : c.preamble_errors;
+    p.correct = c.correct == MI_POCSAG_CORRECT_NONE ? 0u : c.correct;
+    p.hold_timing = c.hold_timing;
+    p.filled = c;
+    *out = p;
+    return MI_OK;
+}
+
+void pocsag_table(uint32_t* t) {
+    for (int i = 0; i < 1024; ++i)
+        t[i] = kPocsagNoPattern;
+    t[0] = 0;
+    for (int a = 1; a < 32; ++a) {
+        t[pocsag_syndrome(1u << a)] = 1u << a;
+        for (int b = a + 1; b < 32; ++b)
+            t[pocsag_syndrome(1u << a | 1u << b)] = 1u << a | 1u << b;
+    }
+}
+
+const char* pocsag_state_ok(const PocsagRowState* state, size_t rows, const PocsagPlan& plan) {
+    const uint32_t H = static_cast<uint32_t>(plan.g.H), lanes = 2 * H;
+    for (size_t r = 0; r < rows; ++r) {
+        const PocsagRowState& s = state[r];
+        const mi_pocsag_message& m = s.msg;
+        if (s.zero)
+            return "the zero field is not 0";
+        if (s.phase > MI_POCSAG_TRANSMISSION)
+            return "an unknown walker phase";
+        for (uint32_t l = lanes; l < MI_POCSAG_MAX_LANES; ++l)
+            if (s.hist[l])
+                return "history bits in a lane the baud does not have";
+        bool any = false;  // a byte of the message set
+        for (size_t i = 0; i < sizeof(m); ++i)
+            any = any || reinterpret_cast<const uint8_t*>(&m)[i];
+        if (s.phase == MI_POCSAG_IDLE) {
+            if (s.lane | s.inverted | s.pos | s.cur | s.nbits | s.gbad | s.lane_sync | s.mismatches | s.wbatch | s.wtwelfth | s.open || any)
+                return "an impossible walker state (an idle row with a walker field or a byte of the message set)";
+            continue;
+        }
+        if (s.lane >= lanes || s.lane_sync >= lanes || s.lane / H != s.lane_sync / H)
+            return "an impossible walker state (a lane the baud does not have, or two slicers in one transmission)";
+        if (s.inverted > 1 || s.open > 1 || s.pos > 16 || s.nbits > 31 || s.cur >> s.nbits || s.gbad > s.pos || s.gbad > 15 || s.mismatches > 4 ||
+            s.wtwelfth >= static_cast<uint32_t>(kPocsagTwelfths))
+            return "an impossible walker state (counters, a running word or timing that a transmission cannot have)";
+        if (!s.open) {
+            if (any)
+                return "an impossible walker state (a message set though none is open)";
+            continue;
+        }
+        if (m.row | m.end_batch | m.lane_end | m.zero | m.zero2 || m.address >> 21 || m.function > 3 || m.nwords > MI_POCSAG_MAX_WORDS || m.truncated > 1 ||
+            (m.truncated && m.nwords < MI_POCSAG_MAX_WORDS) || m.twelfth >= static_cast<uint32_t>(kPocsagTwelfths) || m.inverted != s.inverted ||
+            m.lane_sync != s.lane_sync || m.sync_errors != s.mismatches)
+            return "an impossible open message (a field that no message of the transmission has)";
+        uint32_t nbad = 0;
+        for (uint32_t i = 0; i < 96; ++i) {
+            const uint32_t bad = m.bad[i / 32] >> (i % 32) & 1u;
+            if (i >= m.nwords && (bad || (i < MI_POCSAG_MAX_WORDS && m.words[i])))
+                return "an impossible open message (a bad bit or a word behind nwords)";
+            nbad += bad;
+        }
+        if (nbad != m.nbad || m.corrected > 2u * (m.nwords - nbad + 1u))
+            return "an impossible open message (an nbad that the mask does not give, or more repairs than its words can have)";
+    }
+    return nullptr;
+}
+
+namespace {
+
+const uint32_t* pocsag_table_once() {
+    static const std::vector<uint32_t> t = [] {
+        std::vector<uint32_t> v(1024);
+        pocsag_table(v.data());
+        return v;
+    }();
+    return t.data();
+}
+
+}  // namespace
+}  // namespace mi
+
+extern "C" int mi_pocsag_settings(const mi_pocsag_cfg* cfg, mi_pocsag_cfg* out) {
+    if (!out)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    mi::PocsagPlan p;
+    if (const int rc = mi::pocsag_plan(cfg, &p))
+        return rc;
+    *out = p.filled;
+    return MI_OK;
+}
+
+extern "C" int mi_pocsag_geometry(uint32_t baud, int* hypotheses, int* bits, int* words) {
+    mi_pocsag_cfg c{};
+    c.baud = baud;
+    mi::PocsagPlan p;
+    if (const int rc = mi::pocsag_plan(&c, &p))
+        return rc;
+    if (hypotheses)
+        *hypotheses = p.g.H;
+    if (bits)
+        *bits = p.g.B;
+    if (words)
+        *words = p.g.W;
+    return MI_OK;
+}
+
+extern "C" uint32_t mi_pocsag_max_messages(uint32_t baud, uint64_t nbatches) {
+    mi_pocsag_cfg c{};
+    c.baud = baud;
+    mi::PocsagPlan p;
+    if (mi::pocsag_plan(&c, &p))
+        return 0;
+    return mi::pocsag_max_messages(p.g, nbatches);
+}
+
+extern "C" uint32_t mi_pocsag_encode(uint32_t data21) {
+    const uint32_t cw = (data21 & 0x1FFFFFu) << 11;
+    const uint32_t word = cw | mi::pocsag_syndrome(cw) << 1;  // (the remainder of the data times x^10, the check bits still 0)
+    return word | static_cast<uint32_t>(__builtin_popcount(word) & 1);
+}
+
+extern "C" int mi_pocsag_decode(uint32_t word, uint32_t correct, uint32_t* fixed, uint32_t* errors) {
+    mi_pocsag_cfg c{};
+    c.correct = correct;
+    mi::PocsagPlan p;
+    if (const int rc = mi::pocsag_plan(&c, &p))
+        return rc;
+    uint32_t f;
+    const uint32_t e = mi::pocsag_repair(mi::pocsag_table_once(), word, &f);
+    const bool good = e <= p.correct;
+    if (fixed)
+        *fixed = good ? f : word;
+    if (errors)
+        *errors = e;
+    return good ? 1 : 0;
+}
+
+extern "C" int mi_pocsag_message_text(const mi_pocsag_message* m, int mode, char* text, size_t cap) {
+    if (!m || !text)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (m->nwords > MI_POCSAG_MAX_WORDS)
+        return fail(MI_ERR_INVALID, "pager stage: a message's nwords must be within 0 .. 80");
+    if (mode != MI_POCSAG_TEXT_AUTO && mode != MI_POCSAG_TEXT_NUMERIC && mode != MI_POCSAG_TEXT_ALPHA)
+        return fail(MI_ERR_INVALID, "pager stage: the text mode must be MI_POCSAG_TEXT_AUTO, _NUMERIC or _ALPHA");
+    if (mode == MI_POCSAG_TEXT_AUTO)
+        mode = m->function == 0 ? MI_POCSAG_TEXT_NUMERIC : MI_POCSAG_TEXT_ALPHA;
+    const int width = mode == MI_POCSAG_TEXT_NUMERIC ? 4 : 7;
+    const uint32_t nbits = 20u * m->nwords;
+    // payload bit i of the message: bit 30 - i % 20 of word i / 20
+    const auto bit = [&](uint32_t i) { return m->words[i / 20] >> (30 - i % 20) & 1u; };
+    const auto bad = [&](uint32_t i) { return m->bad[i / 20 / 32] >> (i / 20 % 32) & 1u; };
+    std::string s;
+    for (uint32_t i = 0; i + width <= nbits; i += width) {
+        uint32_t v = 0, b = 0;
+        for (int k = 0; k < width; ++k) {
+            v |= bit(i + k) << k;
+            b |= bad(i + k);
+        }
+        s += b ? '?' : width == 4 ? "0123456789*U -)("[v] : v >= 0x20 && v <= 0x7E ? static_cast<char>(v) : '.';
+    }
+    if (width == 7) {  // the fill behind the text: NUL, ETX, EOT
+        while (!s.empty()) {
+            uint32_t v = 0;
+            for (int k = 0; k < 7; ++k)
+                v |= bit(7 * (static_cast<uint32_t>(s.size()) - 1) + k) << k;
+            if (s.back() == '?' || (v != 0x00 && v != 0x03 && v != 0x04))
+                break;
+            s.pop_back();
+        }
+    }
+    if (s.size() + 1 > cap)
+        return fail(MI_ERR_INVALID, "pager stage: the text does not fit the buffer");
+    std::memcpy(text, s.c_str(), s.size() + 1);
+    return MI_OK;
+}
+
+extern "C" int mi_pocsag_plan_host(const mi_pocsag_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                                   void* state_inout, uint32_t* bits, float* q, mi_pocsag_message* messages, size_t max_messages,
+                                   uint32_t* row_first_message, uint32_t* count) {
+    if (!row_enabled || !plane || !state_inout || !messages || !row_first_message || !count)
+        return fail(MI_ERR_INVALID, "NULL argument");
+    if (rows < 1 || nbatches < 1 || max_messages < 1)
+        return fail(MI_ERR_INVALID, "pager plan needs rows >= 1, nbatches >= 1 and max_messages >= 1");
+    if (row_stride < static_cast<size_t>(nbatches) * mi::kWaveBatch)
+        return fail(MI_ERR_INVALID, "a row stride is shorter than the call");
+    mi::PocsagPlan plan;
+    if (const int rc = mi::pocsag_plan(cfg, &plan))
+        return rc;
+    const mi::PocsagGeom g = plan.g;
+    if (static_cast<uint64_t>(rows) * mi::pocsag_max_messages(g, static_cast<uint64_t>(nbatches)) > UINT32_MAX)
+        return fail(MI_ERR_INVALID, "pager plan: the messages of the call do not fit the 32-bit count");
+    std::vector<mi::PocsagRowState> blob(static_cast<size_t>(rows));
+    std::memcpy(blob.data(), state_inout, blob.size() * sizeof(mi::PocsagRowState));
+    if (const char* const why = mi::pocsag_state_ok(blob.data(), blob.size(), plan))
+        return fail(MI_ERR_INVALID, std::string("pager plan: malformed state blob: ") + why);
+    constexpr int kLead = MI_POCSAG_HISTORY + 2;
+    const int lanes = 2 * g.H;
+    const uint32_t* const table = mi::pocsag_table_once();
+    std::vector<float> s(kLead + static_cast<size_t>(nbatches) * mi::kWaveBatch);
+    std::vector<uint32_t> word(static_cast<size_t>(lanes) * g.W);
+    std::vector<float> v0(g.B), v1(g.B);
+    uint32_t k = 0;
+    // a[0 .. n - 1] summed in the order of the header: 64 running sums, then the halving tree
+    const auto tree = [](const float* a, int n) {
+        float lane[64];
+        for (int l = 0; l < 64; ++l) {
+            lane[l] = a[l];
+            for (int j = l + 64; j < n; j += 64)
+                lane[l] = lane[l] + a[j];
+        }
+        for (int h = 32; h >= 1; h /= 2)
+            for (int l = 0; l < h; ++l)
+                lane[l] = lane[l] + lane[l + h];
+        return lane[0];
+    };
+    for (int r = 0; r < rows; ++r) {
+        row_first_message[r] = k;
+        if (!row_enabled[r])
+            continue;
+        mi::PocsagRowState& st = blob[static_cast<size_t>(r)];
+        const float* const row = plane + static_cast<size_t>(r) * row_stride;
+        s[0] = s[1] = 0.0f;
+        std::memcpy(s.data() + 2, st.x, sizeof(st.x));
+        std::memcpy(s.data() + kLead, row, static_cast<size_t>(nbatches) * mi::kWaveBatch * sizeof(float));
+        mi::PocsagWalker w{st.phase, st.lane, st.inverted, st.pos, st.cur, st.nbits, st.gbad, st.lane_sync, st.mismatches, st.wbatch, st.wtwelfth, st.open};
+        int b = 0;
+        const auto emit = [&]() {
+            if (k < max_messages) {
+                mi_pocsag_message m = st.msg;
+                m.row = static_cast<uint32_t>(r);
+                m.end_batch = static_cast<uint32_t>(b);
+                m.lane_end = static_cast<uint8_t>(w.lane);
+                messages[k] = m;
+            }
+            ++k;
+        };
+        for (b = 0; b < nbatches; ++b) {
+            const float* const blk = s.data() + static_cast<size_t>(b) * mi::kWaveBatch;  // staged: blk[kLead + n] is the batch's sample n
+            const float mu = tree(blk + kLead, mi::kWaveBatch) / 2000.0f;
+            std::vector<float> Q(static_cast<size_t>(lanes));
+            std::fill(word.begin(), word.end(), 0u);
+            for (int t = 0; t < g.H; ++t) {
+                for (int j = 0; j < g.B; ++j) {
+                    int n;
+                    const float sum = mi::pocsag_sum(blk, g, t, j, &n);
+                    const float a = sum, c = sum - static_cast<float>(n) * mu;
+                    word[static_cast<size_t>(t) * g.W + j / 32] |= (a < 0.0f ? 1u : 0u) << (j % 32);
+                    word[static_cast<size_t>(g.H + t) * g.W + j / 32] |= (c < 0.0f ? 1u : 0u) << (j % 32);
+                    v0[j] = std::fabs(a);
+                    v1[j] = std::fabs(c);
+                }
+                Q[t] = tree(v0.data(), g.B);
+                Q[g.H + t] = tree(v1.data(), g.B);
+            }
+            const size_t blk_i = static_cast<size_t>(r) * static_cast<size_t>(nbatches) + static_cast<size_t>(b);
+            if (bits)
+                std::memcpy(bits + blk_i * word.size(), word.data(), word.size() * sizeof(uint32_t));
+            if (q)
+                std::memcpy(q + blk_i * lanes, Q.data(), Q.size() * sizeof(float));
+            const uint32_t batch = st.batch + static_cast<uint32_t>(b);
+            int skip = 0;
+            if (w.phase == MI_POCSAG_TRANSMISSION && !plan.hold_timing) {
+                const int move = mi::pocsag_retime(w, Q.data(), g.H);
+                skip = move == mi::kPocsagSkip;
+                if (move == mi::kPocsagReplay)  // hypothesis 0's last bit of the batch before
+                    mi::pocsag_take(w, &st.msg, table, plan.sync_errors, plan.correct, static_cast<uint32_t>(st.hist[w.lane] & 1u) ^ w.inverted, batch, -g.L, emit);
+            }
+            for (int j = 0; j < g.B; ++j) {
+                uint32_t mism[MI_POCSAG_MAX_LANES], inv[MI_POCSAG_MAX_LANES];
+                for (int l = 0; l < lanes; ++l) {
+                    st.hist[l] = st.hist[l] << 1 | (word[static_cast<size_t>(l) * g.W + j / 32] >> (j % 32) & 1u);
+                    mism[l] = mi::pocsag_hit(st.hist[l], plan.sync_errors, plan.preamble_errors, &inv[l]);
+                }
+                if (w.phase == MI_POCSAG_TRANSMISSION) {
+                    if (skip)
+                        skip = 0;
+                    else
+                        mi::pocsag_take(w, &st.msg, table, plan.sync_errors, plan.correct, static_cast<uint32_t>(st.hist[w.lane] & 1u) ^ w.inverted, batch,
+                                        mi::pocsag_slot_begin(g, static_cast<int>(w.lane) % g.H, j), emit);
+                } else if (const int u = mi::pocsag_pick(mism, Q.data(), lanes); u >= 0) {
+                    mi::pocsag_open(w, u, inv[u], mism[u]);
+                }
+            }
+        }
+        st.batch += static_cast<uint32_t>(nbatches);
+        st.phase = w.phase, st.lane = w.lane, st.inverted = w.inverted, st.pos = w.pos, st.cur = w.cur, st.nbits = w.nbits, st.gbad = w.gbad;
+        st.lane_sync = w.lane_sync, st.mismatches = w.mismatches, st.wbatch = w.wbatch, st.wtwelfth = w.wtwelfth, st.open = w.open;
+        std::memcpy(st.x, row + static_cast<size_t>(nbatches) * mi::kWaveBatch - MI_POCSAG_HISTORY, sizeof(st.x));
+    }
+    row_first_message[rows] = k;
+    count[0] = k;
+    count[1] = k < max_messages ? k : static_cast<uint32_t>(max_messages);
+    std::memcpy(state_inout, blob.data(), blob.size() * sizeof(mi::PocsagRowState));
+    return MI_OK;
+}

@@ -2086,6 +2086,187 @@ uint32_t mi_ax25_crc(const uint8_t* bytes, size_t n);
 enum { MI_AX25_TEXT_BYTES = 384 };
 int mi_ax25_frame_text(const mi_ax25_frame* f, char* text, size_t cap);
 
+/* ---------------- pager decoder stage: POCSAG messages per row, on the device ----------------
+ * POCSAG is the 512 / 1200 / 2400 bit/s pager format: direct FSK of the carrier, +-4.5 kHz, which an NFM channel's discriminator
+ * turns into NRZ audio.  The reference leaves it in the recording.  This stage reads a plane [rows][row_stride] of float32 audio as
+ * mi_acars_* does, needs no flags, and writes one record per page (a MESSAGE).  It is the first decoder stage with forward error
+ * correction: BCH(31,21) repair of up to two bits a codeword, by a table of the 497 syndromes of the error patterns of weight <= 2.
+ * NOT CHECKED against off-air traffic: no recorded pager channel has been through the stage.  SYNC, IDLE, the generator and the
+ * character codes are the published ones and were checked for consistency (both words have remainder 0 and even parity; the 497
+ * patterns have 497 distinct syndromes), and the rest is pinned only to the modulator of tests/pocsag_model.py.  No reassembly of
+ * pages sent in parts, no address filter, no FLEX.
+ *
+ * Air format.  A codeword is 32 bits, the first bit sent being bit 31.  Bit 31 is the kind, 0 address and 1 message; then 20 payload
+ * bits; bits 10 .. 1 are the check bits of BCH(31,21), the remainder of bits 31 .. 11 times x^10 under the generator 0x769; bit 0
+ * makes the parity of all 32 even.  SYNC is 0x7CD215D8, IDLE 0x7A89C197.  A transmission is a preamble of at least 576 alternating
+ * bits, then GROUPS (the standard's "batch", a word that is taken here): SYNC and 16 codewords, index c = 0 .. 15.  An address word
+ * carries 18 address bits (30 .. 13) and 2 function bits (12 .. 11); the full address is addr18 << 3 | c >> 1.  The lower radio
+ * frequency is bit 1; receivers differ in the sign of their discriminator, so the stage takes both polarities and says which.
+ * Stream model.  As for the ACARS stage: a row's audio is one running sequence over all batches of all calls the row was enabled
+ * in; samples before the handle's first call are 0.
+ * Timing grid.  Time is counted in TWELFTHS of a sample; sample n sits at twelfth 12 n; a batch is 24000 twelfths.  The baud is a
+ * setting of the handle: a bit is L twelfths, there are H hypotheses a STEP = L / H twelfths apart, B = 24000 / L bits of a batch
+ * and hypothesis in W = ceil(B / 32) words (mi_pocsag_geometry):
+ *     baud 512: L 375, H 15, step 25, B 64, W 2;   1200: L 160, H 10, step 16, B 150, W 5;   2400: L 80, H 10, step 8, B 300, W 10.
+ * Under hypothesis tau = 0 .. H - 1, bit k covers the twelfths [tau step + L k, tau step + L k + L), k counted from the row's first
+ * sample, and sample n belongs to it when 12 n lies in that span (31 or 32 samples at 512 baud, 13 or 14 at 1200, 6 or 7 at 2400).
+ * tau + H is tau one bit later, exactly.  The bits of a (row, batch) are those whose last sample lies in the batch, exactly B per
+ * hypothesis, numbered by SLOT j = 0 .. B - 1: slot j of hypothesis tau is the bit that begins at twelfth tau step + L (j - [tau > 0])
+ * of the batch, so slot 0 of tau >= 1 begins before the batch.  The earliest is tau = 1, at twelfth step - L: -350 at 512 baud, whose
+ * first sample is the 29th before the batch (-348), -144 at 1200 (the 12th), -72 at 2400 (the 6th).  The handle carries
+ * MI_POCSAG_HISTORY = 34 samples per row at every baud -- at least the 29, the lead 34 + 2 (carry.hpp) whole float4, and one size
+ * of blob for every baud.  In one slot, hypothesis tau begins a step after tau - 1 for tau = 2 .. H - 1, and 0 a step after H - 1:
+ * a walker steps between H - 1 and 0 as between any two neighbours.  Hypothesis 1 begins a step after hypothesis 0 OF THE SLOT BEFORE.
+ * Bit bank, per (row, batch, lane, slot), lane = H g + tau for the slicer g = 0, 1; float32, every operation rounded on its own, no
+ * fused multiply-add.  s = the sum of the bit's samples in ascending n, beginning with the first; k = their number.  Slicer 0:
+ * v = s.  Slicer 1: v = s - (float)k * mu, mu = S / 2000.0f, S the sum of the batch's 2000 samples in the order of the ACARS
+ * stage's Q: s_l = the sequential sum over the samples n = l (mod 64) in ascending n, l = 0 .. 63; then s_l + s_{l + 32} for l < 32,
+ * then + 16, 8, 4, 2, 1 in the same way; S is element 0.  (Slicer 1 is for a discriminator with a tuning offset.)  The bit is 1 if
+ * v < 0.  Q[lane] of the block is the sum of |v| over its slots in that same order, slot j in the place of sample n.  Packed: W
+ * words per (row, batch, lane), slot j in bit j % 32 of word j / 32, the bits behind B zero: bits [rows][nbatches][2][H][W] and
+ * q [rows][nbatches][2][H].  A block whose 2000 samples and 34 carried samples are all +-0 gives bits 0 and Q = +0.0f everywhere;
+ * the device writes that without the sums.
+ * Sync.  Every lane keeps its last 64 bits.  While a row is IDLE, at every slot in order, a lane HITS when its newest 32 bits
+ * differ from SYNC in at most sync_errors places (polarity as sent) or from SYNC's complement in at most that many (INVERTED), and
+ * the 32 bits before them differ from 0xAAAAAAAA or from 0x55555555 in at most preamble_errors places.  The first slot with a hit
+ * opens a TRANSMISSION on the hitting lane with the fewest sync mismatches, then the largest Q of that batch, then the lowest
+ * lane.  One transmission at a time per row; hits inside one are ignored.
+ * Walker.  From the slot after the hit the chosen lane's bits, polarity undone, 32 to a word, the first in bit 31; a word's place
+ * (batch, twelfth) is where its first bit begins.  ONE WORD (mi_pocsag_decode): the syndrome of bits 31 .. 1 under 0x769; e = the
+ * weight of the one error pattern of weight <= 2 in those 31 bits with that syndrome (0 for syndrome 0), the word BAD if there is
+ * none; the pattern is undone, and if the parity of the 32 bits is then odd, e + 1 and bit 0 is flipped.  GOOD if e <= correct,
+ * stored corrected; else BAD, stored as received.  Words c = 0 .. 15 of a group: a good IDLE closes the open message; a good
+ * address word closes it and opens one (address, function, the word's place, its e into corrected); a good message word is
+ * appended to the open message with its e added to corrected -- dropped if none is open, and beyond MI_POCSAG_MAX_WORDS = 80
+ * dropped with truncated set --; a bad word is appended with its bit in the mask `bad` and counted in nbad, under the same two
+ * conditions.  Behind word 15 of a group whose 16 words were all bad the transmission ENDS: the open message closes and the row is
+ * idle from the next slot.  Otherwise the next 32 bits must differ from SYNC in at most sync_errors places (no preamble is asked);
+ * then the next group follows, else the transmission ends in the same way.  A closed message is a record; an address word alone
+ * is a record with 0 words (a tone-only page).
+ * Timing moves.  At the first slot of every batch that begins inside a transmission (unless hold_timing is 1), with Q of the new
+ * batch and the lanes of the transmission's slicer g: v = tau; if Q[tau - 1] > Q[v] then v = tau - 1; if Q[tau + 1] > Q[v] then
+ * v = tau + 1 (indices mod H; a tie keeps tau, a tie between the neighbours that beats tau goes to tau - 1); tau = v.  The walker
+ * stays in step except between 0 and 1: moving 0 -> 1 it passes over slot 0 of the new batch, moving 1 -> 0 it first takes
+ * hypothesis 0's last bit of the batch before, out of the lane's history, then slot 0.  The slicer never changes in a transmission.
+ * Settings (mi_pocsag_cfg, 0 = the default): baud 512, 1200 (default) or 2400; sync_errors 1 .. 4, default 2,
+ * MI_POCSAG_SYNC_EXACT for none; preamble_errors 1 .. 8, default 4, MI_POCSAG_PREAMBLE_EXACT for none, MI_POCSAG_PREAMBLE_OFF
+ * drops the condition (a receiver that joins a transmission at a later group); correct 1 (default) or 2, MI_POCSAG_CORRECT_NONE:
+ * at 1 a random word passes as good with probability 33 / 2048, at 2 with 1 / 4; hold_timing 0 / 1.
+ * Record (mi_pocsag_message, 368 bytes): at 0 row; 4 batch and 8 twelfth, the address word's place (the row's batch number since
+ * creation / set_state, wrapping at 2^32, and 0 .. 23999); 12 end_batch, the call's batch in which the message closed; 16 address
+ * (21 bits); 20 function, 21 nwords, 22 nbad, 23 truncated; 24 corrected (the e of the address word and the good words); 26
+ * inverted; 27 sync_errors, the hit's mismatches; 28 lane_sync and 29 lane_end, the lane at the hit and at the close; 30 zero; 32
+ * bad[3], bit i % 32 of bad[i / 32] for word i; 44 zero2; 48 words[80], zeros behind nwords.
+ * State: per row MI_POCSAG_STATE_ROW_BYTES = 800 bytes, little-endian, a blob of zeros being a fresh state: float32 x[34], the last
+ * 34 input samples, oldest first; at 136 uint32 batch (batches seen), 140 phase (MI_POCSAG_IDLE / MI_POCSAG_TRANSMISSION); 144 uint64
+ * hist[30], per lane the last 64 bits, the newest in bit 0 (lanes the baud does not have stay 0); at 384 uint32 lane, inverted, pos
+ * (words of the group taken, 16 = SYNC is next), cur and nbits (the running word), gbad (bad words of the group), lane_sync,
+ * mismatches, wbatch and wtwelfth (the running word's place), open, zero; at 432 the open message as the record has it so far
+ * (row, end_batch and lane_end 0).  An idle row's fields from `lane` on are all zero.  A disabled row writes nothing and every byte
+ * of its state stays.  The baud is not in the blob: one moved between handles of different baud is the caller's error, refused only
+ * where a lane does not exist.  NaN and Inf are unspecified.
+ * Capacity.  A message closes at the end of a 32-bit word, and no two closes share a word.  A call of n batches gives the walker n B
+ * slots and at most n bits more (one 1 -> 0 move a batch), and the first word can end with the first of them, so a row closes at
+ * most 1 + (n (B + 1) - 1) / 32 messages: mi_pocsag_max_messages.
+ * MI_ERR_NO_DEVICE without a GPU (create only); MI_ERR_INVALID for bad arguments, refused settings, misaligned buffers, nbatches
+ * outside 1 .. max_batches. */
+enum { MI_POCSAG_HISTORY = 34, MI_POCSAG_MAX_HYPOTHESES = 15, MI_POCSAG_MAX_LANES = 30, MI_POCSAG_MAX_WORDS = 80, MI_POCSAG_STATE_ROW_BYTES = 800 };
+enum { MI_POCSAG_IDLE = 0, MI_POCSAG_TRANSMISSION = 1 };
+enum { MI_POCSAG_TEXT_AUTO = 0, MI_POCSAG_TEXT_NUMERIC = 1, MI_POCSAG_TEXT_ALPHA = 2 };
+#define MI_POCSAG_SYNC 0x7CD215D8u
+#define MI_POCSAG_IDLE_WORD 0x7A89C197u
+#define MI_POCSAG_SYNC_EXACT 0x80000000u     /* sync_errors: no mismatch allowed */
+#define MI_POCSAG_PREAMBLE_EXACT 0x80000000u /* preamble_errors: no mismatch allowed */
+#define MI_POCSAG_PREAMBLE_OFF 0x80000001u   /* preamble_errors: the 32 bits before SYNC are not looked at */
+#define MI_POCSAG_CORRECT_NONE 0x80000000u   /* correct: a word is good only as received */
+typedef struct {
+    uint32_t baud;                  /* 0 = 1200; 512, 1200, 2400 */
+    uint32_t sync_errors;           /* 0 = 2; 1 .. 4; MI_POCSAG_SYNC_EXACT */
+    uint32_t preamble_errors;       /* 0 = 4; 1 .. 8; MI_POCSAG_PREAMBLE_EXACT; MI_POCSAG_PREAMBLE_OFF */
+    uint32_t correct;               /* 0 = 1; 1, 2; MI_POCSAG_CORRECT_NONE */
+    uint32_t hold_timing;           /* 1: no timing moves */
+} mi_pocsag_cfg;                    /* 20 bytes */
+typedef struct {
+    uint32_t row;
+    uint32_t batch, twelfth;        /* where the address word's first bit begins */
+    uint32_t end_batch;             /* call-relative */
+    uint32_t address;               /* 21 bits */
+    uint8_t function, nwords, nbad, truncated;
+    uint16_t corrected;             /* bits repaired in the address word and the good words */
+    uint8_t inverted, sync_errors;
+    uint8_t lane_sync, lane_end;
+    uint16_t zero;
+    uint32_t bad[3];
+    uint32_t zero2;
+    uint32_t words[80];             /* message words, corrected where good; zeros behind nwords */
+} mi_pocsag_message;                /* 368 bytes */
+typedef struct mi_pocsag mi_pocsag;
+
+/* cfg NULL = every default.  row_enabled, rows and max_batches as for mi_acars_create.  max_messages: capacity of the caller's
+ * message buffer, 0 = rows * mi_pocsag_max_messages(baud, max_batches).  The handle owns the scratch for a call's bits, Q and
+ * messages, and the syndrome table. */
+int mi_pocsag_create(const mi_pocsag_cfg* cfg, const uint8_t* row_enabled, int rows, int max_batches, size_t max_messages, int gpu, mi_pocsag** out);
+void mi_pocsag_destroy(mi_pocsag* s);
+/* Other rows from the next call on; all state stays.  Completes the work queued on the device first. */
+int mi_pocsag_set_rows(mi_pocsag* s, const uint8_t* row_enabled /* [rows] */);
+/* One call over nbatches (1 .. max_batches) batches of the plane d_plane [rows][row_stride]: 16-byte aligned, the stride a multiple
+ * of 4 floats and at least nbatches * 2000.  Outputs in device memory:
+ *   d_bits               [rows][nbatches][2][H][W]  the packed bits, or NULL (the handle's scratch); 4-byte aligned.
+ *   d_q                  [rows][nbatches][2][H]     Q, or NULL (the handle's scratch).  A disabled row's are not written.
+ *   d_messages           [max_messages]             rows ascending, in the order they closed within a row (8-byte aligned)
+ *   d_row_first_message  [rows + 1]                 exclusive prefix of the rows' message counts
+ *   d_count              [2]                        number of messages, and min(that, max_messages) = the number stored
+ * Nothing is written at or beyond max_messages.  Asynchronous on `hip_stream`, no host synchronisation; five kernels without
+ * atomics -- bits (one workgroup per (row, batch)), walk (one wave per row, a lane per lane of the bank), scan, store, tails -- so
+ * every byte is the same on every run and equals mi_pocsag_plan_host's. */
+int mi_pocsag_process_device(mi_pocsag* s, const float* d_plane, size_t row_stride, int nbatches, uint32_t* d_bits, float* d_q,
+                             mi_pocsag_message* d_messages, uint32_t* d_row_first_message, uint32_t* d_count, void* hip_stream);
+/* Results of the last mi_pocsag_process_device, which must have been enqueued on `hip_stream`: waits for it, reads the counts and
+ * copies exactly count[1] messages.  messages and row_first_message may each be NULL.  The one place that synchronises. */
+int mi_pocsag_download(mi_pocsag* s, void* hip_stream, mi_pocsag_message* messages, uint32_t* row_first_message, uint32_t* count /* [2] */);
+/* Checkpoint / resume, rows * MI_POCSAG_STATE_ROW_BYTES bytes in the layout above (mi_pocsag_plan_host reads and writes the same
+ * bytes).  set_state refuses an impossible state: zero not 0; an unknown phase; history bits in a lane the baud does not have; an
+ * idle row with a walker field or a byte of the message set; inside a transmission a lane or lane_sync the baud does not have or
+ * the two on different slicers, inverted or open beyond 1, pos beyond 16, nbits beyond 31, cur beyond its nbits bits, gbad beyond
+ * pos or 16 of 16, mismatches beyond 4, wtwelfth beyond 23999; a message set though none is open; and of an open message a row,
+ * end_batch, lane_end or zero field set, an address beyond 21 bits, a function beyond 3, nwords beyond 80, truncated beyond 1 or
+ * set below 80 words, a twelfth beyond 23999, inverted, lane_sync or sync_errors that are not the transmission's, bad bits or
+ * words behind nwords, an nbad that is not the mask's count, a corrected beyond 2 (nwords - nbad + 1).  Both complete queued work
+ * first. */
+size_t mi_pocsag_state_size(const mi_pocsag* s);
+int mi_pocsag_get_state(mi_pocsag* s, void* buf, size_t len);
+int mi_pocsag_set_state(mi_pocsag* s, const void* buf, size_t len);
+/* (diagnostic) as mi_outgate_set_timing; ms[5] = {bits, walk, scan, store, tails}.  tools/pocsag_rate.py. */
+int mi_pocsag_set_timing(mi_pocsag* s, int on);
+int mi_pocsag_last_launch_ms(mi_pocsag* s, float* ms /* [5] */);
+/* The host twin: no GPU and no HIP call; the same bits, Q, messages and state blob byte for byte.  plane [rows][row_stride] (no
+ * alignment asked); state_inout rows * MI_POCSAG_STATE_ROW_BYTES bytes, read and updated; bits [rows][nbatches][2][H][W] and
+ * q [rows][nbatches][2][H], each or NULL; messages holds max_messages entries (max_messages >= 1), of which
+ * min(count[0], max_messages) = count[1] are written. */
+int mi_pocsag_plan_host(const mi_pocsag_cfg* cfg, const uint8_t* row_enabled, int rows, int nbatches, const float* plane, size_t row_stride,
+                        void* state_inout, uint32_t* bits, float* q, mi_pocsag_message* messages, size_t max_messages,
+                        uint32_t* row_first_message, uint32_t* count /* [2] */);
+/* The settings of cfg (NULL = all defaults) with every default filled in, or the refusal mi_pocsag_create would give. */
+int mi_pocsag_settings(const mi_pocsag_cfg* cfg, mi_pocsag_cfg* out);
+/* H, B and W of a baud (0 = 1200); each pointer may be NULL.  Refuses any other baud.  Host only, as the four below. */
+int mi_pocsag_geometry(uint32_t baud, int* hypotheses, int* bits, int* words);
+/* The most messages one row can close in nbatches batches at a baud; 0 for a refused baud. */
+uint32_t mi_pocsag_max_messages(uint32_t baud, uint64_t nbatches);
+/* The codeword of 21 data bits (bit 20 the kind): check bits and parity appended.  mi_pocsag_encode(MI_POCSAG_SYNC >> 11) is SYNC. */
+uint32_t mi_pocsag_encode(uint32_t data21);
+/* The walker's rule for one word: 1 GOOD, 0 BAD, MI_ERR_INVALID for a refused `correct` (a setting, 0 = the default).  *fixed = the
+ * word as stored, *errors = e (for a bad word whose syndrome has a pattern, what the repair would have taken; where it has
+ * none, 3).  fixed and errors may be NULL. */
+int mi_pocsag_decode(uint32_t word, uint32_t correct, uint32_t* fixed, uint32_t* errors);
+/* A record's text, NUL-terminated, into text[cap].  MI_POCSAG_TEXT_NUMERIC: every word's 20 payload bits (30 .. 11) as five 4-bit
+ * BCD digits, each least significant bit first, "0123456789*U -)(" ; MI_POCSAG_TEXT_ALPHA: the payloads as one bit string, 7-bit
+ * characters least significant bit first, a character outside 0x20 .. 0x7E written '.', trailing bits short of a character and
+ * trailing NUL / ETX / EOT characters left out; a character (or digit) with a bit out of a bad word is '?'.  MI_POCSAG_TEXT_AUTO:
+ * function 0 numeric, any other alpha.  Refuses nwords beyond 80, an unknown mode and a cap the text does not fit
+ * (MI_POCSAG_TEXT_BYTES always fits). */
+enum { MI_POCSAG_TEXT_BYTES = 408 };
+int mi_pocsag_message_text(const mi_pocsag_message* m, int mode, char* text, size_t cap);
+
 /* ---------------- multi-GPU: gather of audio + flags to rank 0 ----------------
  * One process per GPU; device streams are independent (one demod thread per device in the reference,
  * rtl_airband.cpp:1044-1078) and are partitioned stream-major over the ranks; nothing crosses GPUs except this gather, which
